@@ -24,7 +24,13 @@ gr_complex, one MI355X per rank.
 tracked_channels_sustained: channel sweep (12 … 65536 channels on one GPU, the same file and loop)
   → the largest MEASURED channel count that ran at ≥ real time.
 
-Auxiliary lines (never `value`): the generic-rotator closed loop, closed loops at 25 Msps (GPS and
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps and prints the
+result line with the headline alone; `--dump-outputs DIR` also writes the last timed step's epoch
+records (one float64 `DIR/<field>.npy` per field of gnsship_trk_epoch, [rounds, channels]; the file
+and the receiver are seeded, so the same arguments give the same inputs).  Everything below — the
+channel sweep, the auxiliary lines and the CPU baselines — runs only with `--full`.
+
+Auxiliary lines (`--full`; never `value`): the generic-rotator closed loop, closed loops at 25 Msps (GPS and
 the Galileo E1 C4 share), the C5 per-GPU share in closed loop (12 GPS + 12 E1 + 8 B1I engines
 launched together at 50 Msps ibyte with the IF in the NCO), the open-loop batched correlator (round
 1's headline, truth NCOs), PCPS acquisition sweeps (C1-shape, C3, E1), the open-loop C4/C5 legs, and
@@ -67,8 +73,12 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--seconds", type=float, default=1.0, help="IF seconds per step (D)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="CPU baseline time budget (0 = skip)")
-    ap.add_argument("--no-aux", action="store_true", help="headline only (no auxiliary lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the auxiliary lines and the CPU baselines (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's epoch records (what the step's caller receives) as DIR/<field>.npy, float64")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: CPU baseline time budget (0 = skip)")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: headline only (no auxiliary lines)")
     ap.add_argument("--sharded-aux-only", action="store_true", help="of the auxiliary lines, only the multi-rank ones")
     ap.add_argument("--rotator", type=int, default=-1, help="-1 volk's dispatch on this host, 0 generic, 1 AVX")
     ap.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_trk.json"),
@@ -130,12 +140,13 @@ def closed_loop_steps(ctx, rx, dev_ptr, t0_abs, fs, step_s, n_steps, barrier=Non
     passed with a little slack on both sides (the channels' epoch windows straddle the boundaries;
     every channel consumes each sample once); max_rounds is sized to the segment (D ÷ code period +
     4) and every step's epoch records are copied to the host inside the timed region.  Returns
-    (wall, kernel_ms list, records emitted)."""
+    (wall, kernel_ms list, records emitted, the last step's records[:rounds done])."""
     step_n = int(round(step_s * fs))
     slack = 2 * rx.vl
     max_rounds = int(round(step_s / period_s)) + 4
     kms = []
     n_rec = 0
+    last = None
     if barrier:
         barrier()
     t0 = time.perf_counter()
@@ -145,11 +156,12 @@ def closed_loop_steps(ctx, rx, dev_ptr, t0_abs, fs, step_s, n_steps, barrier=Non
         rec, done = rx.run_records(dev_ptr[0] + (lo - dev_ptr[1]) * 8, 0, lo, step_n + 2 * slack, max_rounds)
         ctx.event_record(1)
         n_rec += int(np.count_nonzero(rec[:done]["flags"] & 8))
+        last = rec[:done]
         if timed:
             kms.append(ctx.event_elapsed_ms(0, 1))
     if barrier:
         barrier()
-    return time.perf_counter() - t0, kms, n_rec
+    return time.perf_counter() - t0, kms, n_rec, last
 
 
 def headline(ctx, torch, args, rank, world, device, barrier):
@@ -173,12 +185,21 @@ def headline(ctx, torch, args, rank, world, device, barrier):
     st = rx.trk.states()
     closed_loop_steps(ctx, rx, base, first + pre_n, FS, args.seconds, args.warmup, timed=False)
     t_timed = first + pre_n + int(round(args.warmup * args.seconds * FS))
-    wall, kms, n_rec = closed_loop_steps(ctx, rx, base, t_timed, FS, args.seconds, args.steps, barrier=barrier)
+    wall, kms, n_rec, last = closed_loop_steps(ctx, rx, base, t_timed, FS, args.seconds, args.steps, barrier=barrier)
     st_end = rx.trk.states()
     wall = sharding.max_over_ranks(wall)
     rx.close()
     return dict(rotator=rot, wall=wall, kernel_ms=float(np.mean(kms)), states_pre=st, states_end=st_end, x=x, base=base, sats=sats,
-                first=first, records=n_rec)
+                first=first, records=n_rec, last_records=last)
+
+
+def dump_outputs(path, rec):
+    """--dump-outputs: the last timed step's epoch records, [rounds, channels], one float64 array per
+    field of gnsship_trk_epoch (every field's values are exact in float64)."""
+    os.makedirs(path, exist_ok=True)
+    for name in rec.dtype.names:
+        if name != "pad":
+            np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(rec[name], dtype=np.float64))
 
 
 SWEEP_PRE = 450  # epochs: every channel bit-synchronised (state 4) before a sweep point's timed epochs
@@ -1031,14 +1052,17 @@ def main():
         "roofline": roof,
     }
     result["config"]["fanout"] = COMM["transport"]
-    if not args.no_aux:  # every rank: its PRN shard of the C3 sweep
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, h.pop("last_records"))
+    aux = args.full and not args.no_aux  # the auxiliary lines and CPU baselines: only with --full
+    if aux:  # every rank: its PRN shard of the C3 sweep
         result["acquisition_c3"] = guarded(acq_c3_sharded, ctx, torch, rank, world, device, barrier)
         if rank == 0 and world == 1 and args.cpu_seconds > 0:
             c3 = result["acquisition_c3"]
             c3["cpu_baseline"] = guarded(cpu_acq_c3, min(8.0, args.cpu_seconds))
             if "sweeps_per_s" in c3 and "sweeps_per_s" in c3["cpu_baseline"]:
                 c3["gpu_vs_cpu"] = round(c3["sweeps_per_s"] / c3["cpu_baseline"]["sweeps_per_s"], 1)
-    if rank == 0 and not args.no_aux and not args.sharded_aux_only:
+    if rank == 0 and aux and not args.sharded_aux_only:
         counts = [12, 256, 1024, 4096, 16384, 65536, 98304, 131072, 163840]
         sw = sweep(ctx, h, h["rotator"], counts)
         rt = [r["channels"] for r in sw if r["realtime_factor"] >= 1.0]
@@ -1067,7 +1091,7 @@ def main():
             g = Receiver(ctx, "GPS", FS, VL, [h["sats"][i] for i in range(N_CH)], N_CH, h["first"], 0, code_base=800)
             pre = int(round(PRE_ROLL_S * FS))
             g.run(h["base"][0] + 2 * VL * 8, 0, h["first"], pre + 2 * VL)
-            gw, _, _ = closed_loop_steps(ctx, g, h["base"], h["first"] + pre, FS, args.seconds, min(args.steps, 5))
+            gw, _, _, _ = closed_loop_steps(ctx, g, h["base"], h["first"] + pre, FS, args.seconds, min(args.steps, 5))
             g.close()
             result["closed_loop_generic_rotator"] = {"config": "as value, rotator " + rotator_name(0),
                                                       "if_msamples_per_s": round(min(args.steps, 5) * args.seconds * FS / gw / 1e6, 1),
@@ -1090,7 +1114,7 @@ def main():
             result["c1_receiver"] = guarded(c1_receiver, torch, device, cpu_seconds=1.0 if args.cpu_seconds > 0 else 0.0)
         result["tracking_c4_e1_open_loop"] = guarded(e1_open_loop, ctx, rot=h["rotator"])
         result["tracking_c5_hybrid_open_loop"] = guarded(c5_open_loop, ctx, rot=h["rotator"])
-    if world > 1 and not args.no_aux:
+    if world > 1 and aux:
         result["streaming_broadcast"] = guarded(streaming_broadcast, ctx, torch, rank, world, device, barrier, h)
     del h
     # the line's key figures once more at its end (a reader of the line's tail sees them)

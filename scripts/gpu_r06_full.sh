@@ -9,6 +9,6 @@ if [ -z "$SKIP_TESTS" ]; then
   tail -n 3 $O/tests.log
   [ $rc -ne 0 ] && { grep -E "FAILED|Error" $O/tests.log | head -20; exit 1; }
 fi
-timeout -k 10 900 python3 -u bench.py > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+timeout -k 10 900 python3 -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python3 -c "import json; d=json.load(open('$O/bench.json')); print(json.dumps(d['summary']))"
 exit 0
