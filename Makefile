@@ -56,6 +56,12 @@ $(MIRROR_TEST): tests/cpp/mirror_test.cpp include/gnsship_cpp.hpp include/gnsshi
 	g++ -O2 -std=c++17 -Iinclude tests/cpp/mirror_test.cpp build/gnss_oracle_test.o build/avx_port_test.o -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
 all: $(MIRROR_TEST)
 
+# GPS L5 through the C++ mirror (tests/test_cpp_mirror_l5.py compares its records with the oracle)
+L5_MIRROR_TEST := tests/cpp/l5_mirror_test
+$(L5_MIRROR_TEST): tests/cpp/l5_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
+	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/l5_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
+all: $(L5_MIRROR_TEST)
+
 # Profiling variant (workgroup phase timestamps in corr_batch_kernel; scripts/corr_wg_profile.py)
 PROF_LIB := scripts/libgnsship_prof.so
 PROF_OBJS := $(patsubst $(CSRC)/%.hip,$(PROF_OBJDIR)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(PROF_OBJDIR)/%.cpp.o,$(CPP_SRCS))

@@ -4,6 +4,10 @@
 //  GPS L1 C/A   : G1 = 1 + x^3 + x^10, G2 = 1 + x^2 + x^3 + x^6 + x^8 + x^9 + x^10, PRN code =
 //                 G1 ⊕ G2 delayed by the IS-GPS-200 delay  (reference gps_sdr_signal_replica.cc:25-110)
 //  BeiDou B1I   : 11-stage Gold code, G2 output taps per PRN  (beidou_b1i_signal_replica.cc:26-110)
+//  GPS L5I / L5Q : XA (13 stages, 1 + x^9 + x^10 + x^12 + x^13, short-cycled to 8190) ⊕ XB (13 stages,
+//                 1 + x + x^3 + x^4 + x^6 + x^7 + x^8 + x^12 + x^13) advanced per PRN and component
+//                 (IS-GPS-705 Table 3-Ia; reference gps_l5_signal_replica.cc:24-187); their sampled
+//                 forms index the chips with ceil() in float (:193-298), unlike the L1 generators
 //  sampled forms: the Borre-style upsampling with a float chip clock and the last sample forced
 //                 to the last chip  (gps_sdr_signal_replica.cc:145-185, beidou_b1i_signal_replica.cc:142-180)
 //
@@ -90,6 +94,64 @@ int b1i_chips(int32_t prn, uint32_t chip_shift, int8_t* chips)
     return GNSSHIP_OK;
 }
 
+// IS-GPS-705 XB code advances (chips) of PRN 1..32: row 0 the I5 (data) component, row 1 the Q5 (pilot)
+// component.  tests/test_codes_l5.py recovers each from the fixture chips (the unique shift at which
+// XA ⊕ code equals the XB sequence).
+constexpr int kL5Len = 10230;
+constexpr int16_t kL5XbAdvance[2][32] = {
+    {266, 365, 804, 1138, 1509, 1559, 1756, 2084, 2170, 2303, 2527, 2687, 2930, 3471, 3940, 4132, 4332, 4924, 5343, 5443, 5641, 5816, 5898,
+        5918, 5955, 6243, 6345, 6477, 6518, 6875, 7168, 7187},
+    {1701, 323, 5292, 2020, 5429, 7136, 1041, 5947, 4315, 148, 535, 1939, 5206, 5910, 3595, 5135, 6082, 6990, 3546, 1523, 4548, 4484, 1893,
+        3961, 7106, 5299, 4660, 276, 4389, 3783, 1591, 1601}};
+
+// component: 0 = L5I, 1 = L5Q.  Both share XA and XB (all-ones start); XA returns to all ones after the
+// state 1111111111101 (cell 1 clear), i.e. every 8190 chips.
+int l5_chips(int component, int32_t prn, int8_t* chips)
+{
+    if (prn < 1 || prn > 32) return GNSSHIP_E_INVAL;
+    static uint8_t xa[kL5Len], xb[kL5Len];
+    static const bool ready = [] {
+        // cell i ↔ polynomial stage 13-i: XA taps 9,10,12,13 → cells 4,3,1,0
+        uint32_t s = 0x1FFFu;
+        for (int i = 0; i < kL5Len; i++) {
+            xa[i] = s & 1u;
+            s = s == 0x1FFDu ? 0x1FFFu : (s >> 1) | (static_cast<uint32_t>(__builtin_parity(s & 0x1Bu)) << 12);
+        }
+        // XB taps 1,3,4,6,7,8,12,13 → cells 12,10,9,7,6,5,1,0
+        lfsr_sequence<13>(0x1FFFu, 0x16E3u, kL5Len, xb);
+        return true;
+    }();
+    (void)ready;
+    int d = kL5XbAdvance[component][prn - 1];
+    for (int i = 0; i < kL5Len; i++) {
+        chips[i] = (xa[i] ^ xb[d]) ? -1 : 1;  // 1 − 2·chip
+        d = d + 1 == kL5Len ? 0 : d + 1;
+    }
+    return GNSSHIP_OK;
+}
+
+// The L5 generators' sampling rule (gps_l5_signal_replica.cc:193-226, :262-298): chip index
+// (int)ceil(ts·(i + 1.0F)/tc) − 1 in float, the last sample forced to the last chip.  tc_double_div:
+// L5I forms tc as 1.0 / float (:196), L5Q as 1.0F / float (:278).  An index past the last chip (the
+// reference reads its array unchecked there) is held at the last chip.
+int sample_code_ceil(const int8_t* chips, int code_len, int32_t chip_rate, int32_t fs, bool imag_part, bool tc_double_div, float* dest)
+{
+    if (fs <= 0) return GNSSHIP_E_INVAL;
+    const float tc = tc_double_div ? static_cast<float>(1.0 / static_cast<double>(static_cast<float>(chip_rate)))
+                                   : 1.0F / static_cast<float>(chip_rate);
+    const float ts = 1.0F / static_cast<float>(fs);
+    const auto n = static_cast<int32_t>(static_cast<double>(fs) / (static_cast<double>(chip_rate) / static_cast<double>(code_len)));
+    for (int32_t i = 0; i < n; i++) {
+        int32_t k = static_cast<int32_t>(std::ceil(ts * (static_cast<float>(i) + 1.0F) / tc)) - 1;
+        if (i == n - 1 || k >= code_len) k = code_len - 1;
+        if (k < 0) k = 0;
+        const float v = static_cast<float>(chips[k]);
+        dest[2 * i] = imag_part ? 0.0F : v;
+        dest[2 * i + 1] = imag_part ? v : 0.0F;
+    }
+    return n;
+}
+
 // Borre upsampling (float chip clock), code value placed in re (imag_part=false) or im.
 // tc_double_div: the B1I generator forms the chip period as 1.0 / float (a double division,
 // beidou_b1i_signal_replica.cc:146), the GPS one as 1.0F / float (gps_sdr_signal_replica.cc:150).
@@ -145,6 +207,34 @@ extern "C" int gnsship_beidou_b1i_code_gen_complex_sampled(float* dest, uint32_t
     int8_t c[2046];
     if (int rc = b1i_chips(static_cast<int32_t>(prn), chip_shift, c)) return rc;
     return sample_code(c, 2046, 2046000, fs, false, true, dest);
+}
+
+static int l5_float(float* dest, int component, int32_t prn)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    static thread_local int8_t c[kL5Len];
+    if (int rc = l5_chips(component, prn, c)) return rc;
+    for (int i = 0; i < kL5Len; i++) dest[i] = static_cast<float>(c[i]);
+    return GNSSHIP_OK;
+}
+
+extern "C" int gnsship_gps_l5i_code_gen_float(float* dest, int32_t prn) { return l5_float(dest, 0, prn); }
+extern "C" int gnsship_gps_l5q_code_gen_float(float* dest, int32_t prn) { return l5_float(dest, 1, prn); }
+
+extern "C" int gnsship_gps_l5i_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t fs)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    static thread_local int8_t c[kL5Len];
+    if (int rc = l5_chips(0, static_cast<int32_t>(prn), c)) return rc;
+    return sample_code_ceil(c, kL5Len, 10230000, fs, false, true, dest);
+}
+
+extern "C" int gnsship_gps_l5q_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t fs)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    static thread_local int8_t c[kL5Len];
+    if (int rc = l5_chips(1, static_cast<int32_t>(prn), c)) return rc;
+    return sample_code_ceil(c, kL5Len, 10230000, fs, true, false, dest);
 }
 
 extern "C" int gnsship_code_samples_per_code(int32_t chip_rate, int32_t code_len, int32_t fs)

@@ -197,6 +197,25 @@ bool build_params(const gnsship_trk_conf& c, TrkParams& p)
         g.data_secondary_len = 20;
         set_bits(g.data_secondary_bits, "00000100110101001110");
         break;
+    case GNSSHIP_SYS_GPS_L5:  // :213-237 (L5, pilot); GPS_L5.h:32-46, :167-172; start_tracking :670-678
+        p.code_chip_rate = 10.23e6;
+        p.carrier_freq = 1176.45e6;
+        p.code_period = 0.001;
+        p.code_length_chips = 10230;
+        p.code_samples_per_chip = 1;
+        g.symbols_per_bit = 10;
+        p.veml = 0;
+        p.track_pilot = 1;  // (track_pilot = 0 — d_interchange_iq — is rejected by gnsship_trk_create)
+        p.conf.slope = 1.0F;
+        p.conf.spc = c.early_late_space_chips;
+        p.conf.y_intercept = 1.0F;
+        if (p.conf.extend_correlation_symbols < 1) p.conf.extend_correlation_symbols = 1;  // gps_l5_dll_pll_tracking.cc:49-53
+        g.secondary = 1;
+        g.secondary_len = 20;
+        set_bits(g.secondary_bits, "00000100110101001110");  // NH20 on the pilot (GPS_L5Q_NH_CODE_STR)
+        g.data_secondary_len = 10;
+        set_bits(g.data_secondary_bits, "0000110101");  // NH10 on the data component (GPS_L5I_NH_CODE_STR)
+        break;
     default: return false;
     }
     p.n_taps = p.veml ? 5 : 3;
@@ -349,6 +368,11 @@ extern "C" int gnsship_trk_create(gnsship_ctx* ctx, const gnsship_trk_conf* conf
     gnsship_trk* t = new (std::nothrow) gnsship_trk();
     if (!t) return GNSSHIP_E_NOMEM;
     t->ctx = ctx;
+    if (conf->system == GNSSHIP_SYS_GPS_L5 && !conf->track_pilot) {
+        delete t;
+        return fail(ctx, GNSSHIP_E_INVAL,
+            "gnsship_trk_create: GPS L5 data-only tracking (track_pilot = 0, the reference's interchange_iq) is not supported: track the L5Q pilot");
+    }
     if (!build_params(*conf, t->params)) {
         delete t;
         return fail(ctx, GNSSHIP_E_INVAL, "gnsship_trk_create: unknown system");
@@ -731,7 +755,7 @@ static int trk_enqueue(gnsship_trk* t, const void* src, int fmt, uint64_t buffer
         const char* fast_env = std::getenv("GNSSHIP_TRK_FAST");
         const bool no_fast = fast_env && fast_env[0] == '0';
         const bool lanes = avx && !no_fast && trk_lane_supported(t->params, code_cap, nc, fmt, n_buffer_samples, binary);
-        const bool fast = avx && !lanes && trk_fast_supported(t->params, code_cap, nc);
+        const bool fast = avx && !lanes && trk_fast_supported(t->params, code_cap, nc, binary);
         t->last_engine = GNSSHIP_TRK_ENGINE_NONE;
         if (lanes)
             e = launch_trk_lane(t->params_dev, t->params, t->chans_dev, nc, ctx->codes_dev, n_codes, code_cap, src, fmt, buffer_first_sample,

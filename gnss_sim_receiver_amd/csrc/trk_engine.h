@@ -49,7 +49,7 @@ struct TrkParams {
     float lock_alpha, lock_one_minus_alpha, lock_min_value, lock_offset;
     int32_t lock_init_samples;
     // job layout
-    int32_t jobs_per_channel;  // 1, or 2 with the E1 data prompt
+    int32_t jobs_per_channel;  // 1, or 2 with the data prompt (E1-B, L5I)
     int32_t chunks_per_job;
     // carrier IF fused into the correlator NCO (gnsship_trk_conf::if_hz): 2π·if_hz/fs, and the IF phase
     // per sample as the exact fraction if_mod / fs_int of a cycle (0 ≤ if_mod < fs_int)
@@ -129,12 +129,11 @@ hipError_t launch_trk_step(const TrkParams* params, TrkChannel* chans, int n_cha
 // buffer within one launch (standard correlator only; not high_dyn).  code_cap_floats: LDS floats per
 // code replica (padded_code_quads(max code length) · 4).  LDS bytes of the dynamic region:
 size_t trk_persist_lds_bytes(const TrkParams& p, int code_cap_floats, bool avx);
-// Tap layouts the persistent kernel is instantiated for (3 or 5 taps, the E1 data prompt with 5);
-// others run the round-based loop (generic rotator only).
+// Tap layouts the persistent kernels are instantiated for (3 or 5 taps, the E1 data prompt with 5,
+// the GPS L5 data prompt with 3); others run the round-based loop (generic rotator only).
 inline bool trk_persist_supports(const TrkParams& p)
 {
-    const bool data = p.jobs_per_channel > 1;
-    return (p.n_taps == 3 && !data) || (p.n_taps == 5 && !data) || (p.n_taps == 5 && data);
+    return p.n_taps == 3 || p.n_taps == 5;  // each with and without the data prompt (jobs_per_channel 2)
 }
 constexpr size_t kTrkPersistMaxLds = 150 * 1024;  // of the 160 KiB per CU, beside the static state
 hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes,
@@ -142,7 +141,8 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
     gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool avx, hipStream_t stream);
 // The latency-optimised persistent loop for the AVX rotator (trk_fast.hip): register-resident loop
 // state, flagless phasor slots, lock detectors beside the loop update.
-bool trk_fast_supported(const TrkParams& p, int code_cap_floats, int n_chans);
+// codes_binary: every chip of the channels' codes is ±1 (the GPS L5 tap layout holds its replicas as sign bits).
+bool trk_fast_supported(const TrkParams& p, int code_cap_floats, int n_chans, bool codes_binary);
 bool trk_fast_thru(int n_chans);  // the throughput form (more channels than CUs)
 int trk_device_cus();             // compute units of the current device
 // The throughput form with one 16-lane row per channel (trk_lane.hip): every code ±1 (codes_binary),

@@ -42,7 +42,9 @@
 // round-based loop.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
+#include "code_bits.h"
 #include "corr_device.h"
 #include "trk_engine.h"
 
@@ -492,11 +494,29 @@ __device__ __forceinline__ float fast_replay(float x, float c, float k2, int M, 
     return x;
 }
 
+// A code replica in LDS: floats (the padded replica, pointer at chip 0), or — PACKED — its sign bits
+// (code_bits.h, pointer at the table's word 0) where two float replicas would leave the product ring
+// fewer than kFastMinRingGroups groups (two 10230-chip GPS L5 replicas: 80 KiB as floats, 2.6 KiB as
+// bits).  A ±1 chip from either form is the same float, so the products are the same.
+template <bool PACKED>
+using CodePtr = std::conditional_t<PACKED, const uint32_t*, const float*>;
+template <bool PACKED, bool IN_MARGIN>
+__device__ __forceinline__ float chip_at(CodePtr<PACKED> code, int L, float sn, float sh, float rem)
+{
+    if constexpr (PACKED) return code_chip<IN_MARGIN>(code, L, sn, sh, rem);
+    else return code_at<IN_MARGIN>(code, L, sn, sh, rem);
+}
+// LDS floats of one replica: the padded float replica, or its sign words rounded up to 16 bytes
+__host__ __device__ constexpr int fast_code_stride(bool packed, int code_cap_floats)
+{
+    return packed ? (lane_code_words(code_cap_floats) + 3) / 4 * 4 : code_cap_floats;
+}
+
 // Producer phase A, before the group's phasor slots are ready: the code value of every tap at
 // every sample of this lane's task (the resampler, volk_gnsssdr_32f_xn_resampler_32f_xn.h:63-80), in
 // registers — it depends only on the code NCO, so it runs ahead of the replay.
-template <int NT, bool DATA, bool IN_MARGIN, int G, bool FULL>
-__device__ __forceinline__ void group_codes(const float* __restrict__ code0, const float* __restrict__ code1, int L, int n0, int cnt, float step,
+template <int NT, bool DATA, bool IN_MARGIN, int G, bool FULL, bool PACKED>
+__device__ __forceinline__ void group_codes(CodePtr<PACKED> __restrict__ code0, CodePtr<PACKED> __restrict__ code1, int L, int n0, int cnt, float step,
     float rem, const float (&shifts)[NT], float (&cv)[G][NT + (DATA ? 1 : 0)])
 {
     float fn = static_cast<float>(n0);  // (float)n, exact steps of 16 (n < 2^24)
@@ -506,8 +526,8 @@ __device__ __forceinline__ void group_codes(const float* __restrict__ code0, con
         const bool on = FULL || i < cnt;
         const float sn = __fmul_rn(step, on ? fn : fn0);
 #pragma unroll
-        for (int q = 0; q < NT; q++) cv[i][q] = code_at<IN_MARGIN>(code0, L, sn, shifts[q], rem);
-        if constexpr (DATA) cv[i][NT] = code_at<IN_MARGIN>(code1, L, sn, 0.0f, rem);
+        for (int q = 0; q < NT; q++) cv[i][q] = chip_at<PACKED, IN_MARGIN>(code0, L, sn, shifts[q], rem);
+        if constexpr (DATA) cv[i][NT] = chip_at<PACKED, IN_MARGIN>(code1, L, sn, 0.0f, rem);
         fn += static_cast<float>(kAvxLanes);
     }
 }
@@ -590,8 +610,8 @@ __device__ __forceinline__ void group_phasors(i4v span, f2 z, f2 dz, bool renorm
 // the group, chain, tap and component (ProdLayout).  Group tags count over the run (gbase = epoch ·
 // n_groups): no flag is re-armed.  A ring group is reused once every accumulator wave consumed it.
 // One producer per group; producer pw takes groups pw, pw + NP, ...
-template <int FMT, int NT, bool DATA, bool IN_MARGIN, int G, int W>
-__device__ __forceinline__ void fast_produce(const FJob& job, i4v span, const float* __restrict__ code0, const float* __restrict__ code1, int L,
+template <int FMT, int NT, bool DATA, bool IN_MARGIN, int G, int W, bool PACKED>
+__device__ __forceinline__ void fast_produce(const FJob& job, i4v span, CodePtr<PACKED> __restrict__ code0, CodePtr<PACKED> __restrict__ code1, int L,
     uint64_t* __restrict__ Zs, int rs, float* __restrict__ Pp, int rg, int32_t* ready, const int32_t* acc_groups, int gbase, int lane, int pw, int pe,
     f2 (&xa)[G < 8 ? G : 8], float (&cv)[G][NT + (DATA ? 1 : 0)])
 {
@@ -625,9 +645,9 @@ __device__ __forceinline__ void fast_produce(const FJob& job, i4v span, const fl
 #pragma unroll
         for (int u = 0; u < kB; u++) xa[u] = load_sample<FMT>(span, (n0 + kAvxLanes * u) * SB, 0);  // in flight during phase A and the slot poll
         if (full)
-            group_codes<NT, DATA, IN_MARGIN, G, true>(code0, code1, L, n0, G, step, rem, shifts, cv);
+            group_codes<NT, DATA, IN_MARGIN, G, true, PACKED>(code0, code1, L, n0, G, step, rem, shifts, cv);
         else
-            group_codes<NT, DATA, IN_MARGIN, G, false>(code0, code1, L, n0, cnt, step, rem, shifts, cv);
+            group_codes<NT, DATA, IN_MARGIN, G, false, PACKED>(code0, code1, L, n0, cnt, step, rem, shifts, cv);
 #ifdef GNSSHIP_CORR_PROFILE
         for (int i = 0; i < G; i++)  // phase A's code loads landed (profiling only)
             for (int q = 0; q < NTT; q++) asm volatile("" ::"v"(cv[i][q]));
@@ -755,8 +775,8 @@ __device__ __forceinline__ float avx_chain_sum(float d)
 
 // The N mod 16 tail (:298-308) on wave 1: lane j < tail forms sample 16M + j's products with the
 // serial phasor T[j] (the accumulator adds them in order after the chain combination).
-template <int FMT, int NT, bool DATA, bool IN_MARGIN>
-__device__ __forceinline__ void fast_tail_products(const FJob& job, i4v span, const float* __restrict__ code0, const float* __restrict__ code1, int L,
+template <int FMT, int NT, bool DATA, bool IN_MARGIN, bool PACKED>
+__device__ __forceinline__ void fast_tail_products(const FJob& job, i4v span, CodePtr<PACKED> __restrict__ code0, CodePtr<PACKED> __restrict__ code1, int L,
     const f2* T, int lane, f2 (*tp)[kMaxTaps + 1])
 {
     constexpr int SB = sample_bytes<FMT>();
@@ -767,11 +787,11 @@ __device__ __forceinline__ void fast_tail_products(const FJob& job, i4v span, co
     const float sn = __fmul_rn(job.code_step, static_cast<float>(n));
 #pragma unroll
     for (int q = 0; q < NT; q++) {
-        const float c = code_at<IN_MARGIN>(code0, L, sn, job.shifts[q], job.rem_code);
+        const float c = chip_at<PACKED, IN_MARGIN>(code0, L, sn, job.shifts[q], job.rem_code);
         tp[lane][q] = wo * f2{c, c};
     }
     if constexpr (DATA) {
-        const float c = code_at<IN_MARGIN>(code1, L, sn, 0.0f, job.rem_code);
+        const float c = chip_at<PACKED, IN_MARGIN>(code1, L, sn, 0.0f, job.rem_code);
         tp[lane][NT] = wo * f2{c, c};
     }
 }
@@ -854,7 +874,7 @@ __device__ __forceinline__ f2 derive_chains(float rem, f2 inc, int lane)
     return z;
 }
 
-template <int FMT, int NT, bool DATA, int G, bool THRU, bool SRING, int W>
+template <int FMT, int NT, bool DATA, int G, bool THRU, bool SRING, int W, bool PACKED>
 __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void trk_fast_kernel(const TrkParams* __restrict__ pk, TrkChannel* __restrict__ chans,
     const CodeDesc* __restrict__ codes, int n_codes, const void* __restrict__ samples, uint64_t buf_first, int64_t buf_len, int max_rounds,
     int n_chans, int code_cap_floats, int rs, int rg, gnsship_trk_epoch* __restrict__ rec, gnsship_trk_dump_record* __restrict__ dump,
@@ -878,12 +898,13 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
         int* dst = reinterpret_cast<int*>(&sc);
         for (int i = tid; i < static_cast<int>(sizeof(TrkChannel) / 4); i += kFThreads) dst[i] = src[i];
     }
-    // dynamic LDS: phasor slots (rs tasks) | code replica(s) | ring: sample products (rg groups) |
+    // dynamic LDS: phasor slots (rs tasks) | code replica(s): floats, or sign words when PACKED | ring: sample products (rg groups) |
     // ring: code values | ring flags
     uint64_t* Zs = reinterpret_cast<uint64_t*>(lds);  // first: the replay's slot stores address it through M0[15:0]
     float* code0 = reinterpret_cast<float*>(Zs + static_cast<size_t>(rs) * kAvxLanes);
-    float* code1 = code0 + code_cap_floats;
-    float* Pp = code0 + (DATA ? 2 : 1) * code_cap_floats;
+    const int code_stride = fast_code_stride(PACKED, code_cap_floats);
+    float* code1 = code0 + code_stride;
+    float* Pp = code0 + (DATA ? 2 : 1) * code_stride;
     int32_t* ready = reinterpret_cast<int32_t*>(Pp + static_cast<size_t>(rg) * ProdLayout<NTT, G>::kGroup);
     for (int i = tid; i < rs * kAvxLanes; i += kFThreads) Zs[i] = kSlotEmpty;
     for (int i = tid; i < 2 * rg; i += kFThreads) ready[i] = 0;
@@ -1037,12 +1058,23 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
     if (g_trkf_prof && lane == 0)  // row 0's slots 72-77: HW_ID | role << 32 of every wave
         g_fprof_lds[72 + wave] = static_cast<uint32_t>(__builtin_amdgcn_s_getreg(4 | (31 << 11))) | (static_cast<unsigned long long>(role) << 32);
 #endif
-    stage_code_f(code0, codes[sc.code_id], kFThreads);
-    if constexpr (DATA) stage_code_f(code1, codes[sc.data_code_id], kFThreads);
+    if constexpr (PACKED) {
+        stage_code_bits(reinterpret_cast<uint32_t*>(code0), codes[sc.code_id], code_stride, lane, wave, kFWaves);
+        if constexpr (DATA) stage_code_bits(reinterpret_cast<uint32_t*>(code1), codes[sc.data_code_id], code_stride, lane, wave, kFWaves);
+    } else {
+        stage_code_f(code0, codes[sc.code_id], kFThreads);
+        if constexpr (DATA) stage_code_f(code1, codes[sc.data_code_id], kFThreads);
+    }
     __syncthreads();  // the code replicas are staged before any wave correlates
     const int L = codes[sc.code_id].len;
-    const float* c0 = code0 + kCodeMargin;
-    const float* c1 = code1 + kCodeMargin;
+    CodePtr<PACKED> c0, c1;
+    if constexpr (PACKED) {
+        c0 = reinterpret_cast<const uint32_t*>(code0);
+        c1 = reinterpret_cast<const uint32_t*>(code1);
+    } else {
+        c0 = code0 + kCodeMargin;
+        c1 = code1 + kCodeMargin;
+    }
     const int N = static_cast<int>(k.conf.vector_length);
     const int M = N / kAvxLanes;
     const int S = (M + G - 1) / G;
@@ -1268,9 +1300,9 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
                         }
                     }
                     if (job.in_margin)
-                        fast_tail_products<FMT, NT, DATA, true>(job, span, c0, c1, L, tailz, lane, sh.tailp);
+                        fast_tail_products<FMT, NT, DATA, true, PACKED>(job, span, c0, c1, L, tailz, lane, sh.tailp);
                     else
-                        fast_tail_products<FMT, NT, DATA, false>(job, span, c0, c1, L, tailz, lane, sh.tailp);
+                        fast_tail_products<FMT, NT, DATA, false, PACKED>(job, span, c0, c1, L, tailz, lane, sh.tailp);
                     if (lane == 0) publish_seq(&sh.tail_seq, e + 1);
                 }
                 GNSSHIP_FSTAMP(e, 2);
@@ -1286,9 +1318,9 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
             if (!job.runnable) break;
             const i4v span = sample_span<FMT>(samples, job.off, N);
             if (job.in_margin)
-                fast_produce<FMT, NT, DATA, true, G, kFWaves>(job, span, c0, c1, L, Zs, rs, Pp, rg, ready, sh.acc_groups, gbase, lane, pw, e, xa, cv);
+                fast_produce<FMT, NT, DATA, true, G, kFWaves, PACKED>(job, span, c0, c1, L, Zs, rs, Pp, rg, ready, sh.acc_groups, gbase, lane, pw, e, xa, cv);
             else
-                fast_produce<FMT, NT, DATA, false, G, kFWaves>(job, span, c0, c1, L, Zs, rs, Pp, rg, ready, sh.acc_groups, gbase, lane, pw, e, xa, cv);
+                fast_produce<FMT, NT, DATA, false, G, kFWaves, PACKED>(job, span, c0, c1, L, Zs, rs, Pp, rg, ready, sh.acc_groups, gbase, lane, pw, e, xa, cv);
             if (pw < 2) GNSSHIP_FSTAMP(e, 3 + pw);  // 3, 4: producers 0 and 1 done
             if (pw == 0) {
                 // cn0_and_tracking_lock_status (:972-1029) on the LDS copy of its members, beside the loop update
@@ -1567,6 +1599,7 @@ static bool fast_thru(int n_chans)
 struct FastPlan {
     size_t bytes = 0;
     int G = 8, rs = 0, rg = 0;
+    bool packed = false;  // the replicas as sign bits (code_bits.h)
 };
 #ifndef GNSSHIP_FAST_G
 #define GNSSHIP_FAST_G 8
@@ -1575,16 +1608,24 @@ constexpr int kFastG = GNSSHIP_FAST_G;
 constexpr int kFastSlotRingGroups = 16;
 constexpr int kFastMinRingGroups = 4;
 constexpr size_t kFastMaxSlotBytes = 48 * 1024;
+// The tap layout new with GPS L5 — 3 taps + the data prompt, two 10230-chip replicas — keeps its
+// replicas packed: as floats they take 80 KiB and leave the latency form 3 product groups (fewer than
+// kFastMinRingGroups) and the throughput form none; packed, 7 and 3.  It is instantiated in that form
+// only, so its codes must be ±1 (otherwise the run falls to trk_persist.hip).  Every other layout
+// keeps the float replicas and the plans it had.
+static bool fast_packed_layout(const TrkParams& p) { return p.n_taps == 3 && p.jobs_per_channel > 1; }
+
 static FastPlan fast_plan(const TrkParams& p, int code_cap_floats, int n_chans)
 {
     FastPlan f;
+    f.packed = fast_packed_layout(p);
     const int N = static_cast<int>(p.conf.vector_length);
     const int M = N / kAvxLanes;
     const int G = kFastG;
     const int S = std::max(1, (M + G - 1) / G);
     const int n_groups = (S + 3) / 4;
     const int ntt = p.n_taps + (p.jobs_per_channel > 1 ? 1 : 0);
-    const size_t codes = static_cast<size_t>(p.jobs_per_channel > 1 ? 2 : 1) * code_cap_floats * sizeof(float);
+    const size_t codes = static_cast<size_t>(p.jobs_per_channel > 1 ? 2 : 1) * fast_code_stride(f.packed, code_cap_floats) * sizeof(float);
     const size_t slot_b = kAvxLanes * sizeof(uint64_t);
     // a group's products (ProdLayout: 4 tasks of G iterations × 2·ntt slots × 16 chains, each task
     // padded by 16 floats) and its flag
@@ -1624,9 +1665,10 @@ static FastPlan fast_plan(const TrkParams& p, int code_cap_floats, int n_chans)
 bool trk_fast_thru(int n_chans) { return fast_thru(n_chans); }
 int trk_device_cus() { return device_cus(); }
 
-bool trk_fast_supported(const TrkParams& p, int code_cap_floats, int n_chans)
+bool trk_fast_supported(const TrkParams& p, int code_cap_floats, int n_chans, bool codes_binary)
 {
     if (!trk_persist_supports(p) || p.conf.rotator != GNSSHIP_ROTATOR_AVX || p.conf.high_dyn) return false;
+    if (fast_packed_layout(p) && !codes_binary) return false;  // sign-bit replicas need every chip ±1
     if (p.n_taps + (p.jobs_per_channel > 1 ? 1 : 0) > 2 * 4) return false;  // the accumulator's two taps per lane row
     if (const char* env = std::getenv("GNSSHIP_TRK_FAST")) {  // A/B against trk_persist.hip
         if (env[0] == '0') return false;
@@ -1655,8 +1697,9 @@ hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params,
     dim3 grid(n_chans), block(waves * kWave);
 #define GNSSHIP_FAST(F, NTV, DV, SR)                                                                                                               \
     do {                                                                                                                                         \
-        auto kfn = form == 1 ? trk_fast_kernel<F, NTV, DV, kFastG, true, SR, GNSSHIP_THRU_WAVES>                                                  \
-                             : form == 2 ? trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWavesLong> : trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWaves>; \
+        constexpr bool PK = (NTV) == 3 && (DV);  /* fast_packed_layout */                                                                        \
+        auto kfn = form == 1 ? trk_fast_kernel<F, NTV, DV, kFastG, true, SR, GNSSHIP_THRU_WAVES, PK>                                              \
+                             : form == 2 ? trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWavesLong, PK> : trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWaves, PK>; \
         hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.bytes)); \
         if (e0 != hipSuccess) return e0;                                                                                                         \
         hipLaunchKernelGGL(kfn, grid, block, f.bytes, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans, \
@@ -1670,6 +1713,7 @@ hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params,
 #define GNSSHIP_FAST_F(F)                                    \
     do {                                                     \
         if (nt == 3 && !data) GNSSHIP_FAST_R(F, 3, false);   \
+        else if (nt == 3 && data) GNSSHIP_FAST_R(F, 3, true); \
         else if (nt == 5 && !data) GNSSHIP_FAST_R(F, 5, false); \
         else if (nt == 5 && data) GNSSHIP_FAST_R(F, 5, true); \
         else return hipErrorInvalidValue;                    \

@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "code_bits.h"
 #include "corr_device.h"
 #include "trk_engine.h"
 #include "trk_loop.h"
@@ -49,40 +50,9 @@ constexpr int kLThreads = kLWaves * kWave;
 template <int NTT>
 constexpr int lane_block() { return NTT > 3 ? 4 : GNSSHIP_LANE_BLOCK; }
 
-// Sign-bit replica of a padded code (engine.h padded_code_quads): bit p of the table is chip
-// p − kCodeMargin < 0 (p over the replica and its wrapped margins).
-__host__ __device__ constexpr int lane_code_words(int code_cap_floats) { return (code_cap_floats + 31) / 32; }
-
-// The chip (±1.0f) the resampler picks for tap shift `sh` at sample n (sn = step·(float)n): the chip
-// index as code_at (corr_device.h) forms it, looked up in the sign-bit replica.
-static_assert(kCodeMargin == 32, "chip i sits at bit i & 31 of word (i >> 5) + 1");
-template <bool IN_MARGIN>
-__device__ __forceinline__ float code_chip(const uint32_t* bits, int L, float sn, float sh, float rem)
-{
-    int i = cvt_floor_i32(__fsub_rn(__fadd_rn(sn, sh), rem));
-    if constexpr (!IN_MARGIN) i = wrap_index(i, L);
-    const uint32_t w = bits[(i >> 5) + 1];
-    return __builtin_bit_cast(float, ((w >> (i & 31)) << 31) | 0x3f800000u);
-}
-
 // acc + a·c for a chip c = ±1: a·c is exact (a or −a), so the fused form rounds exactly as the
 // reference's product-then-add (_mm256_mul_ps, _mm256_add_ps, :252-260)
 __device__ __forceinline__ f2 add_chip(f2 acc, f2 a, float c) { return __builtin_elementwise_fma(a, f2{c, c}, acc); }
-
-// Build the sign-bit replica of code `cd` at dst (the whole wave, one 64-chip ballot per step).
-__device__ void stage_code_bits(uint32_t* dst, const CodeDesc& cd, int words, int lane)
-{
-    const int P = cd.len + 2 * kCodeMargin;
-    for (int base = 0; base < 32 * words; base += kWave) {
-        const int i = base + lane;
-        const float v = i < P ? cd.ptr[i - kCodeMargin] : 1.0f;
-        const unsigned long long m = __ballot(v < 0.0f);
-        if (lane == 0) {
-            dst[base >> 5] = static_cast<uint32_t>(m);
-            if ((base >> 5) + 1 < words) dst[(base >> 5) + 1] = static_cast<uint32_t>(m >> 32);
-        }
-    }
-}
 
 // The epoch's correlator arguments for the lane's channel (do_correlation_step, :1037-1062, and
 // Cpu_Multicorrelator_Real_Codes::Carrier_wipeoff_multicorrelator_resampler, cpu_multicorrelator_real_
@@ -408,6 +378,7 @@ hipError_t launch_trk_lane(const TrkParams* params_dev, const TrkParams& params,
 #define GNSSHIP_LANE_F(F)                                   \
     do {                                                    \
         if (nt == 3 && !data) GNSSHIP_LANE(F, 3, false);    \
+        else if (nt == 3 && data) GNSSHIP_LANE(F, 3, true);   \
         else if (nt == 5 && !data) GNSSHIP_LANE(F, 5, false); \
         else if (nt == 5 && data) GNSSHIP_LANE(F, 5, true); \
         else return hipErrorInvalidValue;                   \

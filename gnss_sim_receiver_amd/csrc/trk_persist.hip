@@ -29,7 +29,9 @@
 //    (16× shorter than the generic chain); it publishes z_l at every renormalisation, and the
 //    correlating lane of (segment, l) continues that lane's chain itself — the same float products
 //    in the same order, so every phasor is bit-identical to the reference's (the sums are trees;
-//    the exact AVX engines are trk_fast.hip and trk_lane.hip).
+//    the exact AVX engines are trk_fast.hip and trk_lane.hip).  The GPS L5 tap layout (3 taps + data
+//    prompt) instead runs u_avx's sixteen chains on sixteen lanes, serial sums and all (chains_avx):
+//    bit-exact here too.
 //
 // High-dynamics tracking and epochs too long for LDS stay on the round-based path (trk_kernel.hip).
 #include <cstdlib>
@@ -301,6 +303,93 @@ __device__ void consume_avx(PEpoch& ep, const f2* Z, const f2* T, i4v span, int 
     }
 }
 
+// ---- correlation (AVX, u_avx's own accumulation order) -------------------------------------------
+// The tap layout of GPS L5 (3 taps + data prompt) is held to the reference's sums bit for bit on every
+// engine, this one included, so its AVX form does not use the task tree above: the sixteen lanes of one
+// wave ARE u_avx's sixteen chains (trk_lane.hip's scheme with float replicas).  Lane l starts at
+// phase·inc^l, takes the samples 16m + l, forms a = x·z_l (_mm256_complexmul_ps rounding), advances
+// z_l·dz (renormalised after iteration m ≡ 0 mod 64, :266-272) and adds a·code to its own accumulators
+// in iteration order (_mm256_mul_ps, _mm256_add_ps, :252-260); the chains combine as :279-291, the
+// N mod 16 tail runs on lane 0 (:294-308).  One dependent chain of N/16 iterations per epoch: the
+// reference's own single-core latency — this engine is the fallback behind trk_fast and trk_lane.
+constexpr bool avx_serial_layout(int nt, bool data) { return nt == 3 && data; }
+
+// ((d_k + d_{k+4}) + d_{k+8}) + d_{k+12} for k = 0..3, then (((0 + s_0) + s_1) + s_2) + s_3, valid at
+// lane 0 of the 16-lane row (as trk_lane.hip's avx_chain_sum_row)
+__device__ __forceinline__ float chain_sum_row(float d)
+{
+    float s = d + dpp_mov<0x12C>(d);  // row_ror:12 — lane k reads lane k + 4
+    s = s + dpp_mov<0x128>(d);        // row_ror:8  — lane k + 8
+    s = s + dpp_mov<0x124>(d);        // row_ror:4  — lane k + 12
+    float r = 0.0f + s;
+    r = r + dpp_mov<0x101>(s);  // row_shl:1 — lane 0 reads lane 1
+    r = r + dpp_mov<0x102>(s);  // row_shl:2
+    r = r + dpp_mov<0x103>(s);  // row_shl:3
+    return r;
+}
+
+__device__ __forceinline__ f2 mul_add(f2 acc, f2 a, float c)  // acc + fl(a·c), no fusion
+{
+    return f2{__fadd_rn(acc.x, __fmul_rn(a.x, c)), __fadd_rn(acc.y, __fmul_rn(a.y, c))};
+}
+
+// Lanes 0..15 of one wave (l = lane); the tap sums land in ep.taps as the loop update reads them.
+template <int FMT, int NT, bool DATA, bool IN_MARGIN>
+__device__ void chains_avx(PEpoch& ep, i4v span, int N, const float* code0, const float* code1, int L, int l)
+{
+    constexpr int SB = sample_bytes<FMT>();
+    constexpr int NTT = NT + (DATA ? 1 : 0);
+    constexpr int kB = 8;  // iterations whose samples are loaded together
+    const DevJob& job = ep.job;
+    const int M = N / kAvxLanes, tail = N - kAvxLanes * M;
+    const f2 inc = f2{job.inc_re, job.inc_im}, dz = f2{ep.dz_re, ep.dz_im};
+    const float step = job.code_step, rem = job.rem_code;
+    float shifts[NTT];
+#pragma unroll
+    for (int t = 0; t < NTT; t++) shifts[t] = t < NT ? job.shifts[t] : 0.0f;
+    f2 z = f2{job.p0_re, job.p0_im};  // phase_vec[l] = phase·inc^l (:204-208)
+    for (int i = 0; i < kAvxLanes - 1; i++)
+        if (i < l) z = cmul_exact(z, inc);
+    f2 acc[NTT];
+#pragma unroll
+    for (int t = 0; t < NTT; t++) acc[t] = f2{0.0f, 0.0f};
+    for (int m0 = 0; m0 < M; m0 += kB) {
+        f2 x[kB];
+#pragma unroll
+        for (int u = 0; u < kB; u++) x[u] = m0 + u < M ? load_sample<FMT>(span, (kAvxLanes * (m0 + u) + l) * SB, 0) : f2{0.0f, 0.0f};
+#pragma unroll
+        for (int u = 0; u < kB; u++) {
+            const int m = m0 + u;
+            if (m >= M) break;
+            const f2 a = cmul_exact_pk(x[u], z);
+            z = cmul_exact_pk(z, dz);
+            if ((m & (kAvxSeg - 1)) == 0) z = normalise_avx(z);
+            const float sn = __fmul_rn(step, static_cast<float>(kAvxLanes * m + l));
+#pragma unroll
+            for (int t = 0; t < NTT; t++) acc[t] = mul_add(acc[t], a, code_at<IN_MARGIN>(t < NT ? code0 : code1, L, sn, shifts[t], rem));
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < NTT; t++) acc[t] = f2{chain_sum_row(acc[t].x), chain_sum_row(acc[t].y)};
+    if (l != 0) return;
+    f2 ph = normalise_avx(z);  // _phase = normalise(z_0), then sample by sample
+    for (int q = 0; q < tail; q++) {
+        const int n = kAvxLanes * M + q;
+        const f2 wo = cmul_exact(load_sample<FMT>(span, n * SB, 0), ph);
+        ph = cmul_exact(ph, inc);
+        const float sn = __fmul_rn(step, static_cast<float>(n));
+#pragma unroll
+        for (int t = 0; t < NTT; t++) acc[t] = mul_add(acc[t], wo, code_at<false>(t < NT ? code0 : code1, L, sn, shifts[t], rem));
+    }
+    for (int i = 0; i < 2 * kMaxTaps + 2; i++) ep.taps[i] = 0.0f;
+#pragma unroll
+    for (int t = 0; t < NTT; t++) {
+        const int o = (DATA && t == NT) ? 2 * kMaxTaps : 2 * t;
+        ep.taps[o] = acc[t].x;
+        ep.taps[o + 1] = acc[t].y;
+    }
+}
+
 // do_correlation_step's arguments for the epoch at c.nitems_read (derive_job on the device; the
 // generic lane factor needs arg/|inc| in double, the AVX path needs dz instead).
 // p0 / inc: (cos rem, −sin rem) and (cos −step, sin −step), evaluated by two lanes of wave 0 at once.
@@ -441,7 +530,14 @@ __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk
         f2 acc[NT + 1];
 #pragma unroll
         for (int t = 0; t <= NT; t++) acc[t] = f2{0.0f, 0.0f};
-        if constexpr (AVX) {
+        constexpr bool kSerialAvx = AVX && avx_serial_layout(NT, DATA);
+        if constexpr (kSerialAvx) {
+            if (wave == 1 && lane < kAvxLanes) {
+                if (ep.in_margin) chains_avx<FMT, NT, DATA, true>(ep, span, N, c0, c1, L, lane);
+                else chains_avx<FMT, NT, DATA, false>(ep, span, N, c0, c1, L, lane);
+            }
+            if (tid == 0) GNSSHIP_TRK_STAMP(e, 2);
+        } else if constexpr (AVX) {
             if (wave == 0 && lane < kAvxLanes) {
                 if (avx_g == 16) replay_avx<16>(ep, Z, T, N, lane, &ep.published);
                 else if (avx_g == 32) replay_avx<32>(ep, Z, T, N, lane, &ep.published);
@@ -457,7 +553,7 @@ __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk
             if (tid == 0) GNSSHIP_TRK_STAMP(e, 2);
         }
         if (lane == 0) GNSSHIP_TRK_STAMP(e, wave <= 1 ? 3 + wave : 14 + wave);  // waves 2, 3: slots 16, 17
-        if constexpr (AVX) {
+        if constexpr (AVX && !kSerialAvx) {
             constexpr int kOut = NT + (DATA ? 1 : 0);
 #pragma unroll
             for (int t = 0; t < kOut; t++) {
@@ -607,6 +703,9 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
         if (nt == 3 && !data) {                                                   \
             if (avx) GNSSHIP_PERSIST(F, 3, false, true);                          \
             else GNSSHIP_PERSIST(F, 3, false, false);                             \
+        } else if (nt == 3 && data) { /* GPS L5: pilot taps + the L5I prompt */    \
+            if (avx) GNSSHIP_PERSIST(F, 3, true, true);                           \
+            else GNSSHIP_PERSIST(F, 3, true, false);                              \
         } else if (nt == 5 && !data) {                                            \
             if (avx) GNSSHIP_PERSIST(F, 5, false, true);                          \
             else GNSSHIP_PERSIST(F, 5, false, false);                             \

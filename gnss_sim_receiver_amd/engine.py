@@ -405,6 +405,31 @@ class PcpsAcquisition:
             pass
 
 
+def gps_l5i_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, doppler_step: int, sampled_ms: int = 1, **kw) -> PcpsAcquisition:
+    """GpsL5iPcpsAcquisition's parameters (gps_l5i_pcps_acquisition.cc:49-69): ms_per_code 1, the L5I
+    chip rate, code_length = floor(fs / 1000) samples and a search window of sampled_ms of them.
+    The local code is codes.gps_l5i_acquisition_code(prn, fs_in, sampled_ms); a front end faster than
+    codes.GPS_L5_OPT_ACQ_FS_SPS designs its resampler with acq_resampler_design(lib, fs, that rate)
+    and passes the resampled rate here.  Other PcpsAcquisition arguments pass through."""
+    from . import codes
+    code_length = int(np.floor(fs_in / (codes.GPS_L5I_CODE_RATE_CPS / codes.GPS_L5I_CODE_LENGTH_CHIPS)))
+    return PcpsAcquisition(ctx, fs_in, sampled_ms * code_length, doppler_max, doppler_step, chip_rate=codes.GPS_L5I_CODE_RATE_CPS,
+                           ms_per_code=1, **kw)
+
+
+def gps_l5_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
+    """GpsL5DllPllTracking's configuration (gps_l5_dll_pll_tracking.cc:44-65): vector_length =
+    round(fs / 1000), the L5Q pilot tracked (track_pilot = 1; data-only tracking is rejected by
+    gnsship_trk_create), extend_correlation_symbols at least 1.  Tracking code: codes.gps_l5q_code_gen_float,
+    data code (start's data_code_id): codes.gps_l5i_code_gen_float."""
+    from . import codes
+    vl = int(round(fs_in / (codes.GPS_L5I_CODE_RATE_CPS / codes.GPS_L5I_CODE_LENGTH_CHIPS)))
+    c = abi.TrkConf.defaults(abi.SYS_GPS_L5, fs_in, vl, **kw)
+    if c.extend_correlation_symbols < 1:
+        c.extend_correlation_symbols = 1
+    return c
+
+
 def firdes_low_pass(lib, gain: float, fs: float, cutoff: float, transition: float) -> np.ndarray:
     """gr::filter::firdes::low_pass (Hamming) as the library restates it."""
     n = ctypes.c_int()

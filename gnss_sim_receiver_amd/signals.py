@@ -27,8 +27,17 @@ SYSTEMS = {
     # (dll_pll_veml_tracking.cc:684-697 with galileo_e1_code_gen_sinboc11_float).
     "GAL": (2.0 * C.GALILEO_E1_CODE_CHIP_RATE_CPS, 2 * C.GALILEO_E1_B_CODE_LENGTH_CHIPS, C.GALILEO_E1_FREQ_HZ,
             lambda prn: C.galileo_e1_code_gen_sinboc11_float("1C", prn)),
+    # GPS L5: the tracking code is the L5Q pilot, the data code L5I (dll_pll_veml_tracking.cc:670-678)
+    "GPS_L5": (C.GPS_L5Q_CODE_RATE_CPS, C.GPS_L5Q_CODE_LENGTH_CHIPS, C.GPS_L5_FREQ_HZ, C.gps_l5q_code_gen_float),
 }
-DATA_CODES = {"GAL": lambda prn: C.galileo_e1_code_gen_sinboc11_float("1B", prn)}
+DATA_CODES = {"GAL": lambda prn: C.galileo_e1_code_gen_sinboc11_float("1B", prn), "GPS_L5": C.gps_l5i_code_gen_float}
+# secondary codes a system's satellites carry unless the Satellite names its own: (pilot, data component)
+DEFAULT_SECONDARY = {"GPS_L5": (C.GPS_L5Q_NH_CODE_STR, C.GPS_L5I_NH_CODE_STR)}
+# how the two components combine: Galileo E1 OS (E1B − E1C)/√2 on one phase; GPS L5 (IS-GPS-705) the
+# data component in phase and the pilot in quadrature, (I5 + j·Q5)/√2
+QUADRATURE_PILOT = {"GPS_L5"}
+# code periods per data symbol where a data component exists (E1-B: 1; L5I: 10 — 100 sps)
+DATA_SYMBOL_PERIODS = {"GAL": 1, "GPS_L5": 10}
 
 
 @dataclass
@@ -50,6 +59,8 @@ class Satellite:
     # cyclic secondary code, one chip per code period: E1-C CS25 on the Galileo pilot, the B1I NH
     # code on the BeiDou signal
     secondary: str = None
+    # cyclic secondary code of the data component, one chip per code period (GPS L5: NH10 on L5I)
+    secondary_data: str = None
     # line-of-sight dynamics: the Doppler ramps at this rate from doppler_hz at sample 0
     doppler_rate_hz_s: float = 0.0
     # code periods per navigation bit when not the system default (BeiDou GEO D2: 2)
@@ -60,6 +71,11 @@ class Satellite:
             self.code = SYSTEMS[self.system][3](self.prn)
         if self.code_data is None and self.system in DATA_CODES:
             self.code_data = DATA_CODES[self.system](self.prn)
+        if self.system in DEFAULT_SECONDARY:
+            if self.secondary is None:
+                self.secondary = DEFAULT_SECONDARY[self.system][0]
+            if self.secondary_data is None:
+                self.secondary_data = DEFAULT_SECONDARY[self.system][1]
 
     @property
     def chip_rate(self):
@@ -109,9 +125,15 @@ def generate_if(fs: float, n_samples: int, sats: list, seed: int = 0, noise: boo
             data_sign = 1.0
             if s.bits:
                 pat = np.array([1.0 if b == "0" else -1.0 for b in s.bits])
-                per_bit = s.symbols_per_bit or (1 if s.code_data is not None else 20)
+                per_bit = s.symbols_per_bit or (DATA_SYMBOL_PERIODS.get(s.system, 1) if s.code_data is not None else 20)
                 data_sign = pat[np.mod(np.floor_divide(period, per_bit), len(pat))]
-            if s.code_data is not None:  # Galileo E1 OS: (E1B − E1C)/√2 with sinBOC(1,1) subcarriers
+            if s.code_data is not None and s.system in QUADRATURE_PILOT:  # GPS L5: (d·NH10·c_I + j·NH20·c_Q)/√2
+                cd = data_sign * s.code_data[np.mod(chip, s.code_len)].astype(np.float64)
+                if s.secondary_data:
+                    sec_d = np.array([1.0 if b == "0" else -1.0 for b in s.secondary_data])
+                    cd = cd * sec_d[np.mod(period, len(sec_d))]
+                c = (cd + 1j * c) / np.sqrt(2.0)
+            elif s.code_data is not None:  # Galileo E1 OS: (E1B − E1C)/√2 with sinBOC(1,1) subcarriers
                 c = (data_sign * s.code_data[np.mod(chip, s.code_len)].astype(np.float64) - c) / np.sqrt(2.0)
             else:
                 c = c * data_sign
@@ -218,17 +240,28 @@ def generate_if_device(fs: float, n_samples: int, sats: list, seed: int = 0, sta
             sign = 1.0
             if s.bits:
                 pat = torch.as_tensor([1.0 if b == "0" else -1.0 for b in s.bits], dtype=torch.float64, device=device)
-                per_bit = s.symbols_per_bit or (1 if code_d is not None else 20)
+                per_bit = s.symbols_per_bit or (DATA_SYMBOL_PERIODS.get(s.system, 1) if code_d is not None else 20)
                 sign = pat[torch.remainder(torch.div(period, per_bit, rounding_mode="floor"), len(pat))]
-            if code_d is not None:
+            cq = None  # the quadrature component (GPS L5: the pilot)
+            if code_d is not None and s.system in QUADRATURE_PILOT:
+                cd = sign * code_d[idx]
+                if s.secondary_data:
+                    sec_d = torch.as_tensor([1.0 if b == "0" else -1.0 for b in s.secondary_data], dtype=torch.float64, device=device)
+                    cd = cd * sec_d[torch.remainder(period, len(sec_d))]
+                c, cq = cd / np.sqrt(2.0), c / np.sqrt(2.0)
+            elif code_d is not None:
                 c = (sign * code_d[idx] - c) / np.sqrt(2.0)
             else:
                 c = c * sign
             cp = 2.0 * np.pi * (s.f_if_hz + s.doppler_hz) * (n / fs) + s.carrier_phase_rad
             if s.doppler_rate_hz_s:
                 cp = cp + np.pi * s.doppler_rate_hz_s * (n / fs) ** 2
-            acc_re += amp * c * torch.cos(cp)
-            acc_im += amp * c * torch.sin(cp)
+            cos_cp, sin_cp = torch.cos(cp), torch.sin(cp)
+            acc_re += amp * c * cos_cp
+            acc_im += amp * c * sin_cp
+            if cq is not None:  # (c + j·cq)·e^{j·cp}
+                acc_re -= amp * cq * sin_cp
+                acc_im += amp * cq * cos_cp
         if noise:
             acc_re += torch.randn(b1 - b0, generator=g, dtype=torch.float64, device=device)
             acc_im += torch.randn(b1 - b0, generator=g, dtype=torch.float64, device=device)

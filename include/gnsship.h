@@ -135,6 +135,14 @@ int gnsship_gps_l1_ca_code_gen_complex_sampled(float* dest, uint32_t prn, int32_
 int gnsship_beidou_b1i_code_gen_float(float* dest, int32_t prn, uint32_t chip_shift);
 /* beidou_b1i_code_gen_complex_sampled (:142): dest = n complex (code in real); returns n or <0 */
 int gnsship_beidou_b1i_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t sampling_freq, uint32_t chip_shift);
+/* gps_l5i_code_gen_float / gps_l5q_code_gen_float (gps_l5_signal_replica.cc:175, :244): dest[10230] = ±1,
+ * PRN 1..32 (GNSSHIP_E_INVAL otherwise) */
+int gnsship_gps_l5i_code_gen_float(float* dest, int32_t prn);
+int gnsship_gps_l5q_code_gen_float(float* dest, int32_t prn);
+/* gps_l5i_code_gen_complex_sampled (:193, code in real) / gps_l5q_code_gen_complex_sampled (:262, code in
+ * imag): dest = n complex, chip index ceil(ts·(i+1)/tc) − 1 in float; returns n or <0 */
+int gnsship_gps_l5i_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t sampling_freq);
+int gnsship_gps_l5q_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t sampling_freq);
 /* samples per code period: (int)(fs / (chip_rate / code_len)) as the generators compute it */
 int gnsship_code_samples_per_code(int32_t chip_rate, int32_t code_len, int32_t fs);
 
@@ -313,6 +321,12 @@ int gnsship_acq_resampler_destroy(gnsship_acq_resampler* r);
 #define GNSSHIP_SYS_GPS_L1CA 0 /* GPS L1 C/A: 3 taps, bit sync on the 160-symbol preamble */
 #define GNSSHIP_SYS_GAL_E1 1   /* Galileo E1 B/C: VEML 5 taps on the pilot + data prompt, CS25 secondary */
 #define GNSSHIP_SYS_BDS_B1I 2  /* BeiDou B1I MEO/IGSO (PRN 6-58): 3 taps, 20-chip NH secondary code */
+/* GPS L5 (dll_pll_veml_tracking.cc:213-247, gps_l5_dll_pll_tracking.cc:44-65): 3 taps on the L5Q pilot
+ * (NH20 secondary code) + the L5I data prompt (NH10, 10 symbols per bit).  track_pilot must be 1:
+ * data-only tracking (the reference's d_interchange_iq) is not restated and gnsship_trk_create
+ * rejects it with GNSSHIP_E_INVAL.  slope, spc and y_intercept are set as the block sets them
+ * (1, early_late_space_chips, 1), whatever the configuration carries. */
+#define GNSSHIP_SYS_GPS_L5 3
 
 typedef struct gnsship_trk_conf { /* Dll_Pll_Conf (dll_pll_conf.h:33-80), same names and units */
     double fs_in;
@@ -367,7 +381,7 @@ typedef struct gnsship_trk_conf { /* Dll_Pll_Conf (dll_pll_conf.h:33-80), same n
 
 typedef struct gnsship_trk_start_args { /* Gnss_Synchro fields start_tracking reads (:647-649) */
     int32_t code_id;      /* code-bank entry of the tracking replica (pilot for E1) */
-    int32_t data_code_id; /* E1 with track_pilot: data replica; otherwise ignored */
+    int32_t data_code_id; /* E1 with track_pilot and GPS L5: data replica (E1-B / L5I); otherwise ignored */
     double acq_delay_samples;
     double acq_doppler_hz;
     uint64_t acq_samplestamp_samples;

@@ -8,6 +8,7 @@
 #ifndef GNSSHIP_CPP_HPP
 #define GNSSHIP_CPP_HPP
 
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstdint>
@@ -591,6 +592,49 @@ private:
     uint32_t resampler_latency_ = 0;
 };
 
+// ---- GPS L5 (gps_l5_signal_replica.h, GPS_L5.h:32-46, gps_l5i_pcps_acquisition.cc:49-69, :151-170) ----
+constexpr double GPS_L5_FREQ_HZ = 1176.45e6;
+constexpr double GPS_L5I_CODE_RATE_CPS = 10.23e6;
+constexpr double GPS_L5Q_CODE_RATE_CPS = 10.23e6;
+constexpr int32_t GPS_L5I_CODE_LENGTH_CHIPS = 10230;
+constexpr int32_t GPS_L5Q_CODE_LENGTH_CHIPS = 10230;
+constexpr uint32_t GPS_L5_OPT_ACQ_FS_SPS = 10000000;
+// The reference's generators under their names (dest: 10230 floats; sampled: samplesPerCode complex).
+// false: PRN outside 1..32 (the reference writes all +1 there).
+inline bool gps_l5i_code_gen_float(float* dest, uint32_t prn) { return gnsship_gps_l5i_code_gen_float(dest, static_cast<int32_t>(prn)) == GNSSHIP_OK; }
+inline bool gps_l5q_code_gen_float(float* dest, uint32_t prn) { return gnsship_gps_l5q_code_gen_float(dest, static_cast<int32_t>(prn)) == GNSSHIP_OK; }
+inline int gps_l5i_code_gen_complex_sampled(std::complex<float>* dest, uint32_t prn, int32_t sampling_freq)
+{
+    return gnsship_gps_l5i_code_gen_complex_sampled(reinterpret_cast<float*>(dest), prn, sampling_freq);
+}
+inline int gps_l5q_code_gen_complex_sampled(std::complex<float>* dest, uint32_t prn, int32_t sampling_freq)
+{
+    return gnsship_gps_l5q_code_gen_complex_sampled(reinterpret_cast<float*>(dest), prn, sampling_freq);
+}
+// GpsL5iPcpsAcquisition's Acq_Conf: ms_per_code 1, the L5I chip rate, the automatic resampler (when
+// conf.use_automatic_resampler) designed for GPS_L5_OPT_ACQ_FS_SPS.  The caller's other fields are kept.
+inline Acq_Conf gps_l5i_acq_conf(Acq_Conf conf)
+{
+    conf.ms_per_code = 1U;
+    conf.chips_per_second = static_cast<uint32_t>(GPS_L5I_CODE_RATE_CPS);
+    conf.SetDerivedParams();
+    conf.ConfigureAutomaticResampler(static_cast<double>(GPS_L5_OPT_ACQ_FS_SPS));
+    return conf;
+}
+// GpsL5iPcpsAcquisition::set_local_code: code_length = floor(resampled_fs / 1000) samples of the sampled
+// L5I code, copied sampled_ms times (vector_length = sampled_ms · samples_per_ms, doubled with
+// bit_transition_flag: the rest stays zero).  Empty: PRN outside 1..32.
+inline std::vector<std::complex<float>> gps_l5i_acquisition_code(uint32_t prn, const Acq_Conf& conf)
+{
+    const int64_t fs = conf.resampled_fs ? conf.resampled_fs : conf.fs_in;
+    const auto code_length = static_cast<size_t>(std::floor(static_cast<double>(fs) / (GPS_L5I_CODE_RATE_CPS / GPS_L5I_CODE_LENGTH_CHIPS)));
+    const auto vector_length = static_cast<size_t>(std::floor(conf.sampled_ms * (static_cast<float>(fs) * 0.001F)) * (conf.bit_transition_flag ? 2.0 : 1.0));
+    std::vector<std::complex<float>> one(code_length), out(std::max(vector_length, code_length * conf.sampled_ms));
+    if (gps_l5i_code_gen_complex_sampled(one.data(), prn, static_cast<int32_t>(fs)) < 0) return {};
+    for (uint32_t i = 0; i < conf.sampled_ms; i++) std::copy(one.begin(), one.end(), out.begin() + static_cast<size_t>(i) * code_length);
+    return out;
+}
+
 // Mirror of Dll_Pll_Conf (src/algorithms/tracking/libs/dll_pll_conf.h:33-80): same field names and
 // defaults (FLAGS_* defaults from gnss_sdr_flags.cc:48-57 for the lock-detector fields).
 struct Dll_Pll_Conf {
@@ -611,7 +655,7 @@ struct Dll_Pll_Conf {
     int32_t cn0_samples{20}, cn0_smoother_samples{200}, carrier_lock_test_smoother_samples{25}, cn0_min{25};
     int32_t max_code_lock_fail{50}, max_carrier_lock_fail{5000};
     bool carrier_aiding{true}, track_pilot{true};
-    char system{'G'};    // 'G' GPS L1 C/A, 'E' Galileo E1, 'C' BeiDou B1I
+    char system{'G'};    // 'G' GPS (signal "1C": L1 C/A, "L5": the L5Q pilot + L5I prompt), 'E' Galileo E1, 'C' BeiDou B1I
     char signal[3]{"1C"};
     // Not a Dll_Pll_Conf member: the reference's correlations follow the volk_gnsssdr rotator variant
     // its dispatcher picks on the host (volk_gnsssdr_rank_archs.c); AUTO makes the same choice.
@@ -665,7 +709,10 @@ public:
         c.smoother_length = conf.smoother_length;
         c.rotator = conf.rotator;
         c.if_hz = conf.if_hz;
-        c.system = conf.system == 'E' ? GNSSHIP_SYS_GAL_E1 : conf.system == 'C' ? GNSSHIP_SYS_BDS_B1I : GNSSHIP_SYS_GPS_L1CA;
+        const bool l5 = conf.system == 'G' && conf.signal[0] == 'L' && conf.signal[1] == '5';  // GpsL5DllPllTracking (system 'G', signal "L5")
+        c.system = conf.system == 'E' ? GNSSHIP_SYS_GAL_E1 : conf.system == 'C' ? GNSSHIP_SYS_BDS_B1I : l5 ? GNSSHIP_SYS_GPS_L5 : GNSSHIP_SYS_GPS_L1CA;
+        // gps_l5_dll_pll_tracking.cc:49-53 (track_pilot = false — the block's interchange_iq — is refused by gnsship_trk_create)
+        if (l5 && c.extend_correlation_symbols < 1) c.extend_correlation_symbols = 1;
         code_base_ = 1024 + 2 * max_channels * next_engine_id();
         std::lock_guard<std::mutex> lk(dev_->mutex());
         if (gnsship_trk_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)

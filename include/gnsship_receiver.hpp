@@ -97,7 +97,8 @@ private:
     unsigned state_ = 0;
 };
 
-// The configuration keys of the 1C channels (conf/gnss-sdr_GPS_L1_gr_complex.conf).
+// The configuration keys of the 1C channels (conf/gnss-sdr_GPS_L1_gr_complex.conf); with trk.signal = "L5"
+// the same keys of the L5 channels (Channels_L5, Acquisition_L5, Tracking_L5).
 struct Receiver_Conf {
     int channels{1};                     // Channels_1C.count
     int in_acquisition{1};               // Channels.in_acquisition (capped at channels)
@@ -132,6 +133,9 @@ class Gnss_Receiver_Hip {
 public:
     explicit Gnss_Receiver_Hip(const Receiver_Conf& conf) : conf_(conf), dev_(Device::get(conf.device))
     {
+        // Channels_L5 (trk.system 'G', trk.signal "L5"): acquisition on L5I, tracking on the L5Q pilot
+        l5_ = conf_.trk.system == 'G' && conf_.trk.signal[0] == 'L' && conf_.trk.signal[1] == '5';
+        if (l5_) conf_.acq = gps_l5i_acq_conf(conf_.acq);
         n_ = std::max(1, conf_.channels);
         max_acq_ = std::min(std::max(0, conf_.in_acquisition), n_);
         conf_.satellite.resize(static_cast<size_t>(n_), 0U);
@@ -195,11 +199,20 @@ private:
         f.stop_acquisition = [this, c]() { acq_[static_cast<size_t>(c)]->set_active(false); };
         f.start_tracking = [this, c]() {  // trk_->start_tracking(); queue (channel, 1)
             const Acq_Outcome& s = acq_[static_cast<size_t>(c)]->gnss_synchro();
-            float code[1023];
-            gnsship_gps_l1_ca_code_gen_float(code, static_cast<int32_t>(prn_[static_cast<size_t>(c)]), 0);
-            if (!trk_->start_tracking(c, code, nullptr, 1023, s.Acq_delay_samples, s.Acq_doppler_hz, s.Acq_samplestamp_samples, now_,
-                    static_cast<int>(prn_[static_cast<size_t>(c)])))
-                error_ = true;
+            const uint32_t prn = prn_[static_cast<size_t>(c)];
+            if (l5_) {  // start_tracking :670-678: the L5Q pilot tracked, L5I on the data prompt
+                std::vector<float> pilot(GPS_L5Q_CODE_LENGTH_CHIPS), data(GPS_L5I_CODE_LENGTH_CHIPS);
+                if (!gps_l5q_code_gen_float(pilot.data(), prn) || !gps_l5i_code_gen_float(data.data(), prn) ||
+                    !trk_->start_tracking(c, pilot.data(), data.data(), GPS_L5Q_CODE_LENGTH_CHIPS, s.Acq_delay_samples, s.Acq_doppler_hz,
+                        s.Acq_samplestamp_samples, now_, static_cast<int>(prn)))
+                    error_ = true;
+            } else {
+                float code[1023];
+                gnsship_gps_l1_ca_code_gen_float(code, static_cast<int32_t>(prn), 0);
+                if (!trk_->start_tracking(c, code, nullptr, 1023, s.Acq_delay_samples, s.Acq_doppler_hz, s.Acq_samplestamp_samples, now_,
+                        static_cast<int>(prn)))
+                    error_ = true;
+            }
             queue_.push_back({c, 1});
         };
         f.stop_tracking = [this, c]() { trk_->stop_tracking(c); };
@@ -211,6 +224,11 @@ private:
     void set_signal(int c, uint32_t prn)
     {
         prn_[static_cast<size_t>(c)] = prn;
+        if (l5_) {  // GpsL5iPcpsAcquisition::set_local_code: the search runs on L5I
+            const std::vector<std::complex<float>> code = gps_l5i_acquisition_code(prn, conf_.acq);
+            if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
+            return;
+        }
         std::vector<float> code(2 * static_cast<size_t>(acq_[static_cast<size_t>(c)]->consumed_samples()));
         gnsship_gps_l1_ca_code_gen_complex_sampled(code.data(), prn, static_cast<int32_t>(conf_.acq.fs_in), 0);
         if (!acq_[static_cast<size_t>(c)]->set_local_code(reinterpret_cast<const std::complex<float>*>(code.data()))) error_ = true;
@@ -433,6 +451,7 @@ private:
     std::vector<gnsship_trk_epoch> rec_buf_;
     std::vector<gnsship_trk_dump_record> dump_buf_;
     bool error_ = false;
+    bool l5_ = false;  // GPS L5 channels (acquisition L5I, tracking L5Q pilot + L5I prompt)
 };
 
 }  // namespace gnsship
