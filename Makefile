@@ -62,6 +62,12 @@ $(L5_MIRROR_TEST): tests/cpp/l5_mirror_test.cpp include/gnsship_cpp.hpp include/
 	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/l5_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
 all: $(L5_MIRROR_TEST)
 
+# BeiDou B3I and GPS L2C through the C++ mirror (tests/test_cpp_mirror_b3i_l2c.py, tests/test_codes_b3i_l2c.py)
+B3I_L2C_MIRROR_TEST := tests/cpp/b3i_l2c_mirror_test
+$(B3I_L2C_MIRROR_TEST): tests/cpp/b3i_l2c_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
+	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/b3i_l2c_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
+all: $(B3I_L2C_MIRROR_TEST)
+
 # Profiling variant (workgroup phase timestamps in corr_batch_kernel; scripts/corr_wg_profile.py)
 PROF_LIB := scripts/libgnsship_prof.so
 PROF_OBJS := $(patsubst $(CSRC)/%.hip,$(PROF_OBJDIR)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(PROF_OBJDIR)/%.cpp.o,$(CPP_SRCS))

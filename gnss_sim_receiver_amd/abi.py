@@ -76,7 +76,7 @@ class AcqResult(ctypes.Structure):
     ]
 
 
-SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5 = 0, 1, 2, 3
+SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5, SYS_BDS_B3I, SYS_GPS_L2C = 0, 1, 2, 3, 4, 5
 # gnsship_trk_last_engine (include/gnsship.h GNSSHIP_TRK_ENGINE_*)
 TRK_ENGINE_NONE, TRK_ENGINE_FAST_LATENCY, TRK_ENGINE_FAST_THROUGHPUT, TRK_ENGINE_PERSIST, TRK_ENGINE_ROUNDS, TRK_ENGINE_LANES = 0, 1, 2, 3, 4, 5
 TRK_ENGINE_NAMES = {0: "none", 1: "trk_fast_kernel (latency form)", 2: "trk_fast_kernel (throughput form)", 3: "trk_persist_kernel",
@@ -200,6 +200,10 @@ _SIGNATURES = {
     "gnsship_gps_l5q_code_gen_float": ([_f32p, ctypes.c_int32], _i),
     "gnsship_gps_l5i_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_int32], _i),
     "gnsship_gps_l5q_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_int32], _i),
+    "gnsship_beidou_b3i_code_gen_float": ([_f32p, ctypes.c_int32, ctypes.c_uint32], _i),
+    "gnsship_beidou_b3i_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32], _i),
+    "gnsship_gps_l2c_m_code_gen_float": ([_f32p, ctypes.c_int32], _i),
+    "gnsship_gps_l2c_m_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_int32], _i),
     "gnsship_code_samples_per_code": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32], _i),
     "gnsship_corr_create": ([_vp, _i, _i, _vpp], _i),
     "gnsship_corr_set_local_code_and_taps": ([_vp, _i, _f32p, _f32p], _i),

@@ -8,6 +8,11 @@
 //                 1 + x + x^3 + x^4 + x^6 + x^7 + x^8 + x^12 + x^13) advanced per PRN and component
 //                 (IS-GPS-705 Table 3-Ia; reference gps_l5_signal_replica.cc:24-187); their sampled
 //                 forms index the chips with ceil() in float (:193-298), unlike the L1 generators
+//  BeiDou B3I   : G1 (13 stages, 1 + x + x^3 + x^4 + x^13, reset to all ones at 1111111111100) ⊕ G2 (13 stages,
+//                 1 + x + x^5 + x^6 + x^7 + x^9 + x^10 + x^12 + x^13) started at a per-PRN phase
+//                 (BDS-SIS-ICD-B3I; reference beidou_b3i_signal_replica.cc:26-165), sampled as B1I
+//  GPS L2 CM     : 27-stage modular register, polynomial octal 0445112474, per-PRN initial state
+//                 (IS-GPS-200 Table 3-IIa; reference gps_l2c_signal_replica.cc:25-39), sampled as L5Q
 //  sampled forms: the Borre-style upsampling with a float chip clock and the last sample forced
 //                 to the last chip  (gps_sdr_signal_replica.cc:145-185, beidou_b1i_signal_replica.cc:142-180)
 //
@@ -152,6 +157,58 @@ int sample_code_ceil(const int8_t* chips, int code_len, int32_t chip_rate, int32
     return n;
 }
 
+// BeiDou B3I G2 register phase of PRN 1..63 (bit i = cell i, cell 0 the output), and the GPS L2 CM
+// register's initial state of PRN 1..50 (bit 0 the output).  tests/test_codes_b3i_l2c.py recovers each from
+// the fixture chips: G1 ⊕ code gives G2, whose first 13 outputs are its cells; the modular L2 CM
+// register's output k depends on its bits 0..k only.
+constexpr uint16_t kB3iG2Phase[63] = {0x15FF, 0x1E2B, 0x178A, 0x1FFB, 0x191F, 0x1264, 0x1FD2, 0x1DFD, 0x1402, 0x041B, 0x1D70, 0x059E,
+    0x0C95, 0x0E26, 0x1189, 0x1C7C, 0x04C5, 0x00EC, 0x1157, 0x02DE, 0x042D, 0x058A, 0x02CF, 0x0662, 0x0748, 0x0929, 0x16D3, 0x15E2, 0x02F5,
+    0x0FFF, 0x0D8F, 0x1589, 0x12AB, 0x19A5, 0x1A5D, 0x1F74, 0x0567, 0x1D10, 0x1B90, 0x1ACE, 0x1034, 0x0BD9, 0x0DBC, 0x1A71, 0x0722, 0x0AC5,
+    0x13E6, 0x1F48, 0x0149, 0x10AC, 0x1E4C, 0x098F, 0x0018, 0x1004, 0x06A6, 0x1646, 0x0E78, 0x05CA, 0x19F6, 0x1245, 0x0E20, 0x0642, 0x044E};
+constexpr uint32_t kL2cmInit[50] = {0x78A1FB4, 0x7B8181D, 0x00BCE64, 0x0D96BD4, 0x6060739, 0x70D35DB, 0x1529038, 0x63D9CF1, 0x09EC391,
+    0x76C3226, 0x72E9465, 0x0523F86, 0x0456803, 0x2635AE9, 0x0059900, 0x2482346, 0x5816816, 0x216A3C5, 0x0D02464, 0x140E2BC, 0x090275B,
+    0x753C8D7, 0x097C77F, 0x78503B0, 0x701785C, 0x0214EB1, 0x72E3725, 0x77DA872, 0x3272F1C, 0x7225407, 0x74A645B, 0x0A0F48B, 0x50357C3,
+    0x7B47F1E, 0x17B9EF1, 0x7BB7B2B, 0x4768C4A, 0x7E5D7EB, 0x2588FC1, 0x0482A48, 0x40A6CE4, 0x7AAEC4C, 0x7081274, 0x0851DF9, 0x09E5EBD,
+    0x2D9B674, 0x72CEEEE, 0x0C2CCDD, 0x3B4F61D, 0x63D021E};
+
+int b3i_chips(int32_t prn, uint32_t chip_shift, int8_t* chips)
+{
+    if (prn < 1 || prn > 63) return GNSSHIP_E_INVAL;
+    constexpr int L = kL5Len;
+    static uint8_t g1[L];
+    static const bool ready = [] {
+        // G1: feedback cells 0, 9, 10, 12; back to all ones when the shifted register reads 1111111111100
+        uint32_t s = 0x1FFFu;
+        for (int i = 0; i < L; i++) {
+            g1[i] = s & 1u;
+            s = (s >> 1) | (static_cast<uint32_t>(__builtin_parity(s & 0x1601u)) << 12);
+            if (s == 0x1FFCu) s = 0x1FFFu;
+        }
+        return true;
+    }();
+    (void)ready;
+    static thread_local uint8_t g2[L];
+    lfsr_sequence<13>(kB3iG2Phase[prn - 1], 0x11DBu /* cells 0,1,3,4,6,7,8,12 */, L, g2);
+    uint32_t d = chip_shift % L;
+    for (int i = 0; i < L; i++) {
+        chips[i] = (g1[(i + chip_shift) % L] ^ g2[d]) ? 1 : -1;
+        d = d + 1 == L ? 0 : d + 1;
+    }
+    return GNSSHIP_OK;
+}
+
+// PRN outside 1..50 is an error (the reference leaves the bits zero there: a code of all +1)
+int l2cm_chips(int32_t prn, int8_t* chips)
+{
+    if (prn < 1 || prn > 50) return GNSSHIP_E_INVAL;
+    uint32_t x = kL2cmInit[prn - 1];
+    for (int i = 0; i < kL5Len; i++) {
+        chips[i] = (x & 1u) ? -1 : 1;  // 1 − 2·bit
+        x = (x >> 1) ^ ((x & 1u) * 0445112474u);
+    }
+    return GNSSHIP_OK;
+}
+
 // Borre upsampling (float chip clock), code value placed in re (imag_part=false) or im.
 // tc_double_div: the B1I generator forms the chip period as 1.0 / float (a double division,
 // beidou_b1i_signal_replica.cc:146), the GPS one as 1.0F / float (gps_sdr_signal_replica.cc:150).
@@ -165,7 +222,7 @@ int sample_code(const int8_t* chips, int code_len, int32_t chip_rate, int32_t fs
     for (int32_t i = 0; i < n; i++) {
         const float aux = (ts * (static_cast<float>(i) + 1)) / tc;
         int32_t k = static_cast<int32_t>(static_cast<int64_t>(aux + 1)) - 1;
-        if (i == n - 1) k = code_len - 1;
+        if (i == n - 1 || k >= code_len) k = code_len - 1;  // (past the last chip the reference reads its array unchecked)
         const float v = static_cast<float>(chips[k]);
         dest[2 * i] = imag_part ? 0.0F : v;
         dest[2 * i + 1] = imag_part ? v : 0.0F;
@@ -235,6 +292,40 @@ extern "C" int gnsship_gps_l5q_code_gen_complex_sampled(float* dest, uint32_t pr
     static thread_local int8_t c[kL5Len];
     if (int rc = l5_chips(1, static_cast<int32_t>(prn), c)) return rc;
     return sample_code_ceil(c, kL5Len, 10230000, fs, true, false, dest);
+}
+
+extern "C" int gnsship_beidou_b3i_code_gen_float(float* dest, int32_t prn, uint32_t chip_shift)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    static thread_local int8_t c[kL5Len];
+    if (int rc = b3i_chips(prn, chip_shift, c)) return rc;
+    for (int i = 0; i < kL5Len; i++) dest[i] = static_cast<float>(c[i]);
+    return GNSSHIP_OK;
+}
+
+extern "C" int gnsship_beidou_b3i_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t fs, uint32_t chip_shift)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    static thread_local int8_t c[kL5Len];
+    if (int rc = b3i_chips(static_cast<int32_t>(prn), chip_shift, c)) return rc;
+    return sample_code(c, kL5Len, 10230000, fs, false, true, dest);
+}
+
+extern "C" int gnsship_gps_l2c_m_code_gen_float(float* dest, int32_t prn)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    static thread_local int8_t c[kL5Len];
+    if (int rc = l2cm_chips(prn, c)) return rc;
+    for (int i = 0; i < kL5Len; i++) dest[i] = static_cast<float>(c[i]);
+    return GNSSHIP_OK;
+}
+
+extern "C" int gnsship_gps_l2c_m_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t fs)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    static thread_local int8_t c[kL5Len];
+    if (int rc = l2cm_chips(static_cast<int32_t>(prn), c)) return rc;
+    return sample_code_ceil(c, kL5Len, 511500, fs, true, false, dest);
 }
 
 extern "C" int gnsship_code_samples_per_code(int32_t chip_rate, int32_t code_len, int32_t fs)

@@ -216,6 +216,45 @@ bool build_params(const gnsship_trk_conf& c, TrkParams& p)
         g.data_secondary_len = 10;
         set_bits(g.data_secondary_bits, "0000110101");  // NH10 on the data component (GPS_L5I_NH_CODE_STR)
         break;
+    case GNSSHIP_SYS_BDS_B3I:  // :415-434, start_tracking :799-834 (MEO/IGSO branch: d_secondary = true); Beidou_B3I.h
+        p.code_chip_rate = 10.23e6;
+        p.carrier_freq = 1268.52e6;
+        p.code_period = 0.001;
+        p.code_length_chips = 10230;
+        p.code_samples_per_chip = 1;
+        g.symbols_per_bit = 20;
+        p.veml = 0;
+        p.track_pilot = 0;
+        p.conf.track_pilot = 0;
+        p.conf.slope = 1.0F;
+        p.conf.spc = c.early_late_space_chips;
+        p.conf.y_intercept = 1.0F;
+        // beidou_b3i_dll_pll_tracking.cc: extend_correlation_symbols within [1, 20]
+        p.conf.extend_correlation_symbols = c.extend_correlation_symbols < 1 ? 1 : c.extend_correlation_symbols > 20 ? 20 : c.extend_correlation_symbols;
+        g.secondary = 1;
+        g.secondary_len = 20;
+        set_bits(g.secondary_bits, "00000100110101001110");  // NH20 (BEIDOU_B3I_SECONDARY_CODE_STR)
+        g.data_secondary_len = 20;
+        set_bits(g.data_secondary_bits, "00000100110101001110");
+        p.single_code_bits = 1;
+        break;
+    case GNSSHIP_SYS_GPS_L2C:  // :196-212 (2S), start_tracking :666-668; gps_l2_m_dll_pll_tracking.cc:44-62
+        p.code_chip_rate = 0.5115e6;
+        p.carrier_freq = 1227.6e6;
+        p.code_period = 0.02;  // one telemetry symbol: the loop filters below are updated every 20 ms
+        p.code_length_chips = 10230;
+        p.code_samples_per_chip = 1;
+        g.symbols_per_bit = 1;
+        p.veml = 0;
+        p.track_pilot = 0;  // no pilot component (:208; the adapter forces it too, :54-59)
+        p.conf.track_pilot = 0;
+        p.conf.slope = 1.0F;
+        p.conf.spc = c.early_late_space_chips;
+        p.conf.y_intercept = 1.0F;
+        p.conf.extend_correlation_symbols = 1;  // no secondary code, one symbol per bit: nothing to extend over
+        g.secondary = 0;  // state 2 goes straight to 4, as Galileo E1 without the pilot
+        p.single_code_bits = 1;
+        break;
     default: return false;
     }
     p.n_taps = p.veml ? 5 : 3;
@@ -232,19 +271,20 @@ bool build_params(const gnsship_trk_conf& c, TrkParams& p)
         p.shifts[2] = c.early_late_space_chips * spcf;
     }
     // extended integration (:515-523): enabled when extend_correlation_symbols > 1
-    g.extend = c.extend_correlation_symbols > 1 ? c.extend_correlation_symbols : 1;
+    // (p.conf's value: GPS L5, B3I and L2C apply their adapters' limits above)
+    g.extend = p.conf.extend_correlation_symbols > 1 ? p.conf.extend_correlation_symbols : 1;
     g.T_ext = static_cast<float>(g.extend) * static_cast<float>(p.code_period);
-    // BeiDou B1I GEO satellites (start_tracking :765-781; Beidou_B1I.h:41-49): D2 navigation at 2
-    // symbols per bit, no NH code, bit synchronisation on the 22-symbol preamble, extend ≤ 2
+    // BeiDou B1I / B3I GEO satellites (start_tracking :765-781, :803-819; Beidou_B1I.h:41-49): D2 navigation
+    // at 2 symbols per bit, no NH code, bit synchronisation on the 22-symbol preamble, extend ≤ 2
     p.sync[1] = g;
-    if (c.system == GNSSHIP_SYS_BDS_B1I) {
+    if (c.system == GNSSHIP_SYS_BDS_B1I || c.system == GNSSHIP_SYS_BDS_B3I) {
         SymSync& geo = p.sync[1];
         std::memset(geo.secondary_bits, 0, sizeof(geo.secondary_bits));
         std::memset(geo.data_secondary_bits, 0, sizeof(geo.data_secondary_bits));
         geo.symbols_per_bit = 2;
         geo.secondary = 0;
         geo.secondary_len = 22;
-        set_bits(geo.secondary_bits, "1111110000001100001100");  // BEIDOU_B1I_GEO_PREAMBLE_SYMBOLS_STR
+        set_bits(geo.secondary_bits, "1111110000001100001100");  // BEIDOU_B1I_GEO_PREAMBLE_SYMBOLS_STR (B3I's is the same)
         geo.data_secondary_len = 0;
         if (geo.extend > 2) geo.extend = 2;
         geo.T_ext = static_cast<float>(geo.extend) * static_cast<float>(p.code_period);
@@ -484,7 +524,7 @@ static int trk_start_state(gnsship_trk* t, int channel, const gnsship_trk_start_
     c.code_id = a->code_id;
     c.prn = a->prn > 0 ? static_cast<uint32_t>(a->prn) : 0u;
     // GEO satellites use the D2 symbol-sync profile (start_tracking :765-781)
-    c.geo = (p.conf.system == GNSSHIP_SYS_BDS_B1I && ((a->prn > 0 && a->prn < 6) || a->prn > 58)) ? 1 : 0;
+    c.geo = ((p.conf.system == GNSSHIP_SYS_BDS_B1I || p.conf.system == GNSSHIP_SYS_BDS_B3I) && ((a->prn > 0 && a->prn < 6) || a->prn > 58)) ? 1 : 0;
     c.data_code_id = p.track_pilot ? a->data_code_id : a->code_id;
     c.acq_sample_stamp = a->acq_samplestamp_samples;
     c.carrier_doppler_hz = a->acq_doppler_hz;
@@ -762,7 +802,7 @@ static int trk_enqueue(gnsship_trk* t, const void* src, int fmt, uint64_t buffer
                 n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, ctx->stream);
         else if (fast)
             e = launch_trk_fast(t->params_dev, t->params, t->chans_dev, nc, ctx->codes_dev, n_codes, code_cap, src, fmt, buffer_first_sample,
-                n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, ctx->stream);
+                n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, binary, ctx->stream);
         else
             e = launch_trk_persist(t->params_dev, t->params, t->chans_dev, nc, ctx->codes_dev, n_codes, code_cap, src, fmt, buffer_first_sample,
                 n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, avx, ctx->stream);

@@ -21,7 +21,7 @@ struct LoopSet {
 };
 
 // Symbol synchronisation of one satellite class: the members start_tracking sets per PRN
-// (:762-797).  Profile 0 is the system's; profile 1 the BeiDou B1I GEO one (PRN 1-5, 59+: D2
+// (:762-834).  Profile 0 is the system's; profile 1 the BeiDou B1I / B3I GEO one (PRN 1-5, 59+: D2
 // navigation at 2 symbols per bit, 22-symbol preamble search, no NH code, extend capped at 2).
 struct SymSync {
     int32_t symbols_per_bit, secondary, secondary_len, data_secondary_len;
@@ -54,7 +54,10 @@ struct TrkParams {
     // carrier IF fused into the correlator NCO (gnsship_trk_conf::if_hz): 2π·if_hz/fs, and the IF phase
     // per sample as the exact fraction if_mod / fs_int of a cycle (0 ≤ if_mod < fs_int)
     int32_t has_if;
-    int32_t pad_if;
+    // BeiDou B3I and GPS L2C (one 10230-chip replica, 3 taps, no data prompt): with ±1 codes trk_fast holds
+    // the replica as sign bits and trk_persist's AVX form runs u_avx's sixteen chains.  Read by the host-side
+    // dispatch only (the kernels take it as a template argument); 0 for every other system.
+    int32_t single_code_bits;
     double if_step_rad;
     int64_t if_mod, fs_int;
     // RN(1/fs_in) and RN(1/carrier_freq): the loop's quotients by them as exact FMA sequences (exact_div.h)
@@ -69,7 +72,7 @@ struct Smoother {
 // One channel: the dll_pll_veml_tracking members the per-epoch path reads or writes.
 struct TrkChannel {
     int32_t state;  // 0 idle / lost, 2 wide tracking, 3 coherent integration, 4 narrow tracking
-    int32_t geo;    // symbol-sync profile (TrkParams::sync): 1 for a BeiDou B1I GEO satellite
+    int32_t geo;    // symbol-sync profile (TrkParams::sync): 1 for a BeiDou B1I / B3I GEO satellite
     uint32_t prn;   // Gnss_Synchro::PRN (dump records)
     int32_t narrow;     // loop set / taps in use (1 after entering extended integration)
     int32_t ext_count;  // d_extend_correlation_symbols_count
@@ -141,7 +144,8 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
     gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool avx, hipStream_t stream);
 // The latency-optimised persistent loop for the AVX rotator (trk_fast.hip): register-resident loop
 // state, flagless phasor slots, lock detectors beside the loop update.
-// codes_binary: every chip of the channels' codes is ±1 (the GPS L5 tap layout holds its replicas as sign bits).
+// codes_binary: every chip of the channels' codes is ±1 (the GPS L5 tap layout holds its replicas as sign
+// bits, and so do BeiDou B3I and GPS L2C — TrkParams::single_code_bits — which otherwise keep floats).
 bool trk_fast_supported(const TrkParams& p, int code_cap_floats, int n_chans, bool codes_binary);
 bool trk_fast_thru(int n_chans);  // the throughput form (more channels than CUs)
 int trk_device_cus();             // compute units of the current device
@@ -154,6 +158,6 @@ hipError_t launch_trk_lane(const TrkParams* params_dev, const TrkParams& params,
     gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, hipStream_t stream);
 hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes, int n_codes,
     int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, hipStream_t stream);
+    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool codes_binary, hipStream_t stream);
 
 }  // namespace gnsship

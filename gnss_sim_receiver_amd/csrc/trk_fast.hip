@@ -1613,12 +1613,24 @@ constexpr size_t kFastMaxSlotBytes = 48 * 1024;
 // kFastMinRingGroups) and the throughput form none; packed, 7 and 3.  It is instantiated in that form
 // only, so its codes must be ±1 (otherwise the run falls to trk_persist.hip).  Every other layout
 // keeps the float replicas and the plans it had.
-static bool fast_packed_layout(const TrkParams& p) { return p.n_taps == 3 && p.jobs_per_channel > 1; }
+static bool fast_packed_only_layout(const TrkParams& p) { return p.n_taps == 3 && p.jobs_per_channel > 1; }
+// BeiDou B3I and GPS L2C (TrkParams::single_code_bits: 3 taps, one 10230-chip replica) are built in both
+// forms.  The float replica takes 40 KiB: at N = 12500 that leaves the throughput form (72 KiB) one product
+// group — no plan — where the sign-bit replica (1.3 KiB) leaves 4, and it costs the latency form 3
+// groups at N = 8184 to 40000 (DESIGN.md has the plan table and what each form measured).  So they run packed whenever their codes are ±1, and the float form
+// otherwise (or with GNSSHIP_TRK_FAST_PACKED=0, the A/B knob, which touches these two systems only).
+static bool fast_packed_layout(const TrkParams& p, bool codes_binary)
+{
+    if (fast_packed_only_layout(p)) return true;
+    if (!p.single_code_bits || !codes_binary || p.n_taps != 3 || p.jobs_per_channel > 1) return false;
+    const char* env = std::getenv("GNSSHIP_TRK_FAST_PACKED");
+    return !(env && env[0] == '0');
+}
 
-static FastPlan fast_plan(const TrkParams& p, int code_cap_floats, int n_chans)
+static FastPlan fast_plan(const TrkParams& p, int code_cap_floats, int n_chans, bool codes_binary)
 {
     FastPlan f;
-    f.packed = fast_packed_layout(p);
+    f.packed = fast_packed_layout(p, codes_binary);
     const int N = static_cast<int>(p.conf.vector_length);
     const int M = N / kAvxLanes;
     const int G = kFastG;
@@ -1668,22 +1680,22 @@ int trk_device_cus() { return device_cus(); }
 bool trk_fast_supported(const TrkParams& p, int code_cap_floats, int n_chans, bool codes_binary)
 {
     if (!trk_persist_supports(p) || p.conf.rotator != GNSSHIP_ROTATOR_AVX || p.conf.high_dyn) return false;
-    if (fast_packed_layout(p) && !codes_binary) return false;  // sign-bit replicas need every chip ±1
+    if (fast_packed_only_layout(p) && !codes_binary) return false;  // sign-bit replicas need every chip ±1
     if (p.n_taps + (p.jobs_per_channel > 1 ? 1 : 0) > 2 * 4) return false;  // the accumulator's two taps per lane row
     if (const char* env = std::getenv("GNSSHIP_TRK_FAST")) {  // A/B against trk_persist.hip
         if (env[0] == '0') return false;
-        if (env[0] == '1') return fast_plan(p, code_cap_floats, n_chans).bytes > 0;
+        if (env[0] == '1') return fast_plan(p, code_cap_floats, n_chans, codes_binary).bytes > 0;
     }
     // every channel count: with more channels than CUs the throughput form (fast_thru), which keeps
     // u_avx's accumulation order as the latency form does (trk_persist.hip's tree sums do not)
-    return fast_plan(p, code_cap_floats, n_chans).bytes > 0;
+    return fast_plan(p, code_cap_floats, n_chans, codes_binary).bytes > 0;
 }
 
 hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes, int n_codes,
     int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, hipStream_t stream)
+    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool codes_binary, hipStream_t stream)
 {
-    const FastPlan f = fast_plan(params, code_cap_floats, n_chans);
+    const FastPlan f = fast_plan(params, code_cap_floats, n_chans, codes_binary);
     if (f.bytes == 0) return hipErrorInvalidValue;
     const int N = static_cast<int>(params.conf.vector_length);
     const int S = std::max(1, (N / kAvxLanes + f.G - 1) / f.G);
@@ -1695,9 +1707,8 @@ hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params,
     const int form = thru ? 1 : (N >= kLongEpoch ? 2 : 0);
     const int waves = form == 1 ? GNSSHIP_THRU_WAVES : form == 2 ? kFWavesLong : kFWaves;
     dim3 grid(n_chans), block(waves * kWave);
-#define GNSSHIP_FAST(F, NTV, DV, SR)                                                                                                               \
+#define GNSSHIP_FAST(F, NTV, DV, SR, PK)                                                                                                             \
     do {                                                                                                                                         \
-        constexpr bool PK = (NTV) == 3 && (DV);  /* fast_packed_layout */                                                                        \
         auto kfn = form == 1 ? trk_fast_kernel<F, NTV, DV, kFastG, true, SR, GNSSHIP_THRU_WAVES, PK>                                              \
                              : form == 2 ? trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWavesLong, PK> : trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWaves, PK>; \
         hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.bytes)); \
@@ -1705,17 +1716,18 @@ hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params,
         hipLaunchKernelGGL(kfn, grid, block, f.bytes, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans, \
             code_cap_floats, f.rs, f.rg, rec, dump, trace, ran_count);                                                                           \
     } while (0)
-#define GNSSHIP_FAST_R(F, NTV, DV)                        \
+#define GNSSHIP_FAST_R(F, NTV, DV, PK)                    \
     do {                                                  \
-        if (sring) GNSSHIP_FAST(F, NTV, DV, true);        \
-        else GNSSHIP_FAST(F, NTV, DV, false);             \
+        if (sring) GNSSHIP_FAST(F, NTV, DV, true, PK);    \
+        else GNSSHIP_FAST(F, NTV, DV, false, PK);         \
     } while (0)
 #define GNSSHIP_FAST_F(F)                                    \
     do {                                                     \
-        if (nt == 3 && !data) GNSSHIP_FAST_R(F, 3, false);   \
-        else if (nt == 3 && data) GNSSHIP_FAST_R(F, 3, true); \
-        else if (nt == 5 && !data) GNSSHIP_FAST_R(F, 5, false); \
-        else if (nt == 5 && data) GNSSHIP_FAST_R(F, 5, true); \
+        if (nt == 3 && !data && !f.packed) GNSSHIP_FAST_R(F, 3, false, false); \
+        else if (nt == 3 && !data) GNSSHIP_FAST_R(F, 3, false, true); /* B3I, L2C */ \
+        else if (nt == 3 && data) GNSSHIP_FAST_R(F, 3, true, true); /* GPS L5: packed only */ \
+        else if (nt == 5 && !data) GNSSHIP_FAST_R(F, 5, false, false); \
+        else if (nt == 5 && data) GNSSHIP_FAST_R(F, 5, true, false); \
         else return hipErrorInvalidValue;                    \
     } while (0)
     switch (fmt) {

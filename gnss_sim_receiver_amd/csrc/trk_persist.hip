@@ -31,7 +31,8 @@
 //    in the same order, so every phasor is bit-identical to the reference's (the sums are trees;
 //    the exact AVX engines are trk_fast.hip and trk_lane.hip).  The GPS L5 tap layout (3 taps + data
 //    prompt) instead runs u_avx's sixteen chains on sixteen lanes, serial sums and all (chains_avx):
-//    bit-exact here too.
+//    bit-exact here too.  So do BeiDou B3I and GPS L2C (TrkParams::single_code_bits), chosen at launch:
+//    GPS L1 and BeiDou B1I, which share their tap layout, keep the tree form.
 //
 // High-dynamics tracking and epochs too long for LDS stay on the round-based path (trk_kernel.hip).
 #include <cstdlib>
@@ -312,6 +313,8 @@ __device__ void consume_avx(PEpoch& ep, const f2* Z, const f2* T, i4v span, int 
 // in iteration order (_mm256_mul_ps, _mm256_add_ps, :252-260); the chains combine as :279-291, the
 // N mod 16 tail runs on lane 0 (:294-308).  One dependent chain of N/16 iterations per epoch: the
 // reference's own single-core latency — this engine is the fallback behind trk_fast and trk_lane.
+// (the default of trk_persist_kernel's SERIAL argument; launch_trk_persist also sets it for 3 taps without a
+// data prompt when TrkParams::single_code_bits is set — BeiDou B3I, GPS L2C)
 constexpr bool avx_serial_layout(int nt, bool data) { return nt == 3 && data; }
 
 // ((d_k + d_{k+4}) + d_{k+8}) + d_{k+12} for k = 0..3, then (((0 + s_0) + s_1) + s_2) + s_3, valid at
@@ -446,7 +449,7 @@ __device__ void stage_code(float* dst, const CodeDesc& cd)
 template <bool THRU>
 constexpr int persist_waves_per_simd() { return THRU ? 4 : 1; }
 
-template <int FMT, int NT, bool DATA, bool AVX, bool THRU>
+template <int FMT, int NT, bool DATA, bool AVX, bool THRU, bool SERIAL = avx_serial_layout(NT, DATA)>
 __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk_persist_kernel(const TrkParams* __restrict__ pk, TrkChannel* __restrict__ chans,
     const CodeDesc* __restrict__ codes, int n_codes, const void* __restrict__ samples, uint64_t buf_first, int64_t buf_len, int max_rounds,
     int n_chans, int code_cap_floats, int avx_g, gnsship_trk_epoch* __restrict__ rec, gnsship_trk_dump_record* __restrict__ dump,
@@ -530,7 +533,7 @@ __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk
         f2 acc[NT + 1];
 #pragma unroll
         for (int t = 0; t <= NT; t++) acc[t] = f2{0.0f, 0.0f};
-        constexpr bool kSerialAvx = AVX && avx_serial_layout(NT, DATA);
+        constexpr bool kSerialAvx = AVX && SERIAL;
         if constexpr (kSerialAvx) {
             if (wave == 1 && lane < kAvxLanes) {
                 if (ep.in_margin) chains_avx<FMT, NT, DATA, true>(ep, span, N, c0, c1, L, lane);
@@ -690,9 +693,10 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
     if (const char* env = std::getenv("GNSSHIP_TRK_THRU")) thru = env[0] == '1';
     const int nt = params.n_taps;
     dim3 grid(n_chans), block(kPThreads);
-#define GNSSHIP_PERSIST(F, NTV, DV, AV)                                                                                                        \
+#define GNSSHIP_PERSIST(F, NTV, DV, AV) GNSSHIP_PERSIST_S(F, NTV, DV, AV, avx_serial_layout(NTV, DV))
+#define GNSSHIP_PERSIST_S(F, NTV, DV, AV, SV)                                                                                                  \
     do {                                                                                                                                       \
-        auto kfn = thru ? trk_persist_kernel<F, NTV, DV, AV, true> : trk_persist_kernel<F, NTV, DV, AV, false>;                                                                                         \
+        auto kfn = thru ? trk_persist_kernel<F, NTV, DV, AV, true, SV> : trk_persist_kernel<F, NTV, DV, AV, false, SV>;                         \
         hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)); \
         if (e0 != hipSuccess) return e0;                                                                                                       \
         hipLaunchKernelGGL(kfn, grid, block, lds, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans,  \
@@ -701,7 +705,8 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
 #define GNSSHIP_PERSIST_F(F)                                                      \
     do {                                                                          \
         if (nt == 3 && !data) {                                                   \
-            if (avx) GNSSHIP_PERSIST(F, 3, false, true);                          \
+            if (avx && params.single_code_bits) GNSSHIP_PERSIST_S(F, 3, false, true, true); /* B3I, L2C: chains_avx */ \
+            else if (avx) GNSSHIP_PERSIST(F, 3, false, true);                     \
             else GNSSHIP_PERSIST(F, 3, false, false);                             \
         } else if (nt == 3 && data) { /* GPS L5: pilot taps + the L5I prompt */    \
             if (avx) GNSSHIP_PERSIST(F, 3, true, true);                           \
@@ -723,6 +728,7 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
     default: return hipErrorInvalidValue;
     }
 #undef GNSSHIP_PERSIST_F
+#undef GNSSHIP_PERSIST_S
 #undef GNSSHIP_PERSIST
     return hipGetLastError();
 }

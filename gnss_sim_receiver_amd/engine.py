@@ -430,6 +430,56 @@ def gps_l5_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
     return c
 
 
+def beidou_b3i_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, doppler_step: int, sampled_ms: int = 1, **kw) -> PcpsAcquisition:
+    """BeidouB3iPcpsAcquisition's parameters (beidou_b3i_pcps_acquisition.cc:46-63): ms_per_code 1, the B3I
+    chip rate, code_length = floor(fs / 1000) samples and a search window of sampled_ms of them.  The
+    reference passes an optimum acquisition rate of 100e6, so no resampler is ever designed.  The local
+    code is codes.beidou_b3i_acquisition_code(prn, fs_in, sampled_ms)."""
+    from . import codes
+    code_length = int(np.floor(fs_in / (codes.BEIDOU_B3I_CODE_RATE_CPS / codes.BEIDOU_B3I_CODE_LENGTH_CHIPS)))
+    return PcpsAcquisition(ctx, fs_in, sampled_ms * code_length, doppler_max, doppler_step, chip_rate=codes.BEIDOU_B3I_CODE_RATE_CPS,
+                           ms_per_code=1, **kw)
+
+
+def gps_l2_m_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, doppler_step: int, sampled_ms: int = 20, **kw) -> PcpsAcquisition:
+    """GpsL2MPcpsAcquisition's parameters (gps_l2_m_pcps_acquisition.cc:50-78): ms_per_code 20, the L2 CM
+    chip rate, code_length = floor(fs / 50) samples, a search window of floor(sampled_ms · samples_per_ms)
+    samples holding sampled_ms / 20 codes (samples_per_code = samples_per_ms · 20).  The local code is
+    codes.gps_l2c_m_acquisition_code(prn, fs_in, sampled_ms); a front end faster than
+    codes.GPS_L2C_OPT_ACQ_FS_SPS designs its resampler with acq_resampler_design(lib, fs, that rate) and
+    passes the resampled rate here."""
+    from . import codes
+    spms = np.float32(np.float32(fs_in) * np.float32(0.001))
+    return PcpsAcquisition(ctx, fs_in, int(np.floor(np.float32(sampled_ms) * spms)), doppler_max, doppler_step,
+                           chip_rate=codes.GPS_L2_M_CODE_RATE_CPS, ms_per_code=20, **kw)
+
+
+def beidou_b3i_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
+    """BeidouB3iDllPllTracking's configuration (beidou_b3i_dll_pll_tracking.cc): vector_length =
+    round(fs / 1000), extend_correlation_symbols within [1, 20] (a GEO channel — start's prn in 1..5 or
+    above 58 — is further capped at 2 by the engine).  Tracking code: codes.beidou_b3i_code_gen_float."""
+    from . import codes
+    vl = int(round(fs_in / (codes.BEIDOU_B3I_CODE_RATE_CPS / codes.BEIDOU_B3I_CODE_LENGTH_CHIPS)))
+    c = abi.TrkConf.defaults(abi.SYS_BDS_B3I, fs_in, vl, **kw)
+    c.extend_correlation_symbols = min(max(c.extend_correlation_symbols, 1), 20)
+    c.track_pilot = 0
+    return c
+
+
+def gps_l2c_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
+    """GpsL2MDllPllTracking's configuration (gps_l2_m_dll_pll_tracking.cc:44-62): vector_length =
+    round(fs / 50) — one 20 ms L2 CM code period, which is one telemetry symbol —
+    extend_correlation_symbols = 1 and track_pilot = 0 (the signal has no pilot).  The reference's L2C
+    configurations run the loops at pll_bw_hz = 2, dll_bw_hz = 0.25: Dll_Pll_Conf's defaults (35 / 2 Hz)
+    are unstable at a 20 ms update interval.  Tracking code: codes.gps_l2c_m_code_gen_float."""
+    from . import codes
+    vl = int(round(fs_in / (codes.GPS_L2_M_CODE_RATE_CPS / codes.GPS_L2_M_CODE_LENGTH_CHIPS)))
+    c = abi.TrkConf.defaults(abi.SYS_GPS_L2C, fs_in, vl, **kw)
+    c.extend_correlation_symbols = 1
+    c.track_pilot = 0
+    return c
+
+
 def firdes_low_pass(lib, gain: float, fs: float, cutoff: float, transition: float) -> np.ndarray:
     """gr::filter::firdes::low_pass (Hamming) as the library restates it."""
     n = ctypes.c_int()

@@ -29,15 +29,21 @@ SYSTEMS = {
             lambda prn: C.galileo_e1_code_gen_sinboc11_float("1C", prn)),
     # GPS L5: the tracking code is the L5Q pilot, the data code L5I (dll_pll_veml_tracking.cc:670-678)
     "GPS_L5": (C.GPS_L5Q_CODE_RATE_CPS, C.GPS_L5Q_CODE_LENGTH_CHIPS, C.GPS_L5_FREQ_HZ, C.gps_l5q_code_gen_float),
+    # BeiDou B3I: one component, NH20 on MEO / IGSO satellites (a GEO satellite: secondary="", symbols_per_bit=2, as B1I)
+    "BDS_B3I": (C.BEIDOU_B3I_CODE_RATE_CPS, C.BEIDOU_B3I_CODE_LENGTH_CHIPS, C.BEIDOU_B3I_FREQ_HZ, C.beidou_b3i_code_gen_float),
+    # GPS L2C: the L2 CM code alone (no L2 CL), 20 ms per period = one telemetry symbol, no secondary code
+    "GPS_L2C": (C.GPS_L2_M_CODE_RATE_CPS, C.GPS_L2_M_CODE_LENGTH_CHIPS, C.GPS_L2_FREQ_HZ, C.gps_l2c_m_code_gen_float),
 }
 DATA_CODES = {"GAL": lambda prn: C.galileo_e1_code_gen_sinboc11_float("1B", prn), "GPS_L5": C.gps_l5i_code_gen_float}
 # secondary codes a system's satellites carry unless the Satellite names its own: (pilot, data component)
-DEFAULT_SECONDARY = {"GPS_L5": (C.GPS_L5Q_NH_CODE_STR, C.GPS_L5I_NH_CODE_STR)}
+DEFAULT_SECONDARY = {"GPS_L5": (C.GPS_L5Q_NH_CODE_STR, C.GPS_L5I_NH_CODE_STR), "BDS_B3I": (C.BEIDOU_B3I_SECONDARY_CODE_STR, None)}
 # how the two components combine: Galileo E1 OS (E1B − E1C)/√2 on one phase; GPS L5 (IS-GPS-705) the
 # data component in phase and the pilot in quadrature, (I5 + j·Q5)/√2
 QUADRATURE_PILOT = {"GPS_L5"}
 # code periods per data symbol where a data component exists (E1-B: 1; L5I: 10 — 100 sps)
 DATA_SYMBOL_PERIODS = {"GAL": 1, "GPS_L5": 10}
+# code periods per navigation bit of a single-component signal when not 20 (L2 CM: one 20 ms period per symbol)
+BIT_PERIODS = {"GPS_L2C": 1}
 
 
 @dataclass
@@ -125,7 +131,7 @@ def generate_if(fs: float, n_samples: int, sats: list, seed: int = 0, noise: boo
             data_sign = 1.0
             if s.bits:
                 pat = np.array([1.0 if b == "0" else -1.0 for b in s.bits])
-                per_bit = s.symbols_per_bit or (DATA_SYMBOL_PERIODS.get(s.system, 1) if s.code_data is not None else 20)
+                per_bit = s.symbols_per_bit or (DATA_SYMBOL_PERIODS.get(s.system, 1) if s.code_data is not None else BIT_PERIODS.get(s.system, 20))
                 data_sign = pat[np.mod(np.floor_divide(period, per_bit), len(pat))]
             if s.code_data is not None and s.system in QUADRATURE_PILOT:  # GPS L5: (d·NH10·c_I + j·NH20·c_Q)/√2
                 cd = data_sign * s.code_data[np.mod(chip, s.code_len)].astype(np.float64)
@@ -240,7 +246,7 @@ def generate_if_device(fs: float, n_samples: int, sats: list, seed: int = 0, sta
             sign = 1.0
             if s.bits:
                 pat = torch.as_tensor([1.0 if b == "0" else -1.0 for b in s.bits], dtype=torch.float64, device=device)
-                per_bit = s.symbols_per_bit or (DATA_SYMBOL_PERIODS.get(s.system, 1) if code_d is not None else 20)
+                per_bit = s.symbols_per_bit or (DATA_SYMBOL_PERIODS.get(s.system, 1) if code_d is not None else BIT_PERIODS.get(s.system, 20))
                 sign = pat[torch.remainder(torch.div(period, per_bit, rounding_mode="floor"), len(pat))]
             cq = None  # the quadrature component (GPS L5: the pilot)
             if code_d is not None and s.system in QUADRATURE_PILOT:

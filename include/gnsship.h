@@ -143,6 +143,16 @@ int gnsship_gps_l5q_code_gen_float(float* dest, int32_t prn);
  * imag): dest = n complex, chip index ceil(ts·(i+1)/tc) − 1 in float; returns n or <0 */
 int gnsship_gps_l5i_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t sampling_freq);
 int gnsship_gps_l5q_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t sampling_freq);
+/* beidou_b3i_code_gen_float (beidou_b3i_signal_replica.cc:168): dest[10230] = ±1, PRN 1..63 (GNSSHIP_E_INVAL otherwise) */
+int gnsship_beidou_b3i_code_gen_float(float* dest, int32_t prn, uint32_t chip_shift);
+/* beidou_b3i_code_gen_complex_sampled (:196): dest = n complex (code in real), the B1I sampling rule; returns n or <0 */
+int gnsship_beidou_b3i_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t sampling_freq, uint32_t chip_shift);
+/* gps_l2c_m_code_gen_float (gps_l2c_signal_replica.cc:57): the L2 CM code, dest[10230] = ±1 (1 − 2·bit), PRN 1..50;
+ * GNSSHIP_E_INVAL otherwise (the reference writes all +1 there) */
+int gnsship_gps_l2c_m_code_gen_float(float* dest, int32_t prn);
+/* gps_l2c_m_code_gen_complex_sampled (:75): dest = n complex (code in imag), chip index ceil(ts·(i+1)/tc) − 1 in
+ * float; returns n or <0 */
+int gnsship_gps_l2c_m_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t sampling_freq);
 /* samples per code period: (int)(fs / (chip_rate / code_len)) as the generators compute it */
 int gnsship_code_samples_per_code(int32_t chip_rate, int32_t code_len, int32_t fs);
 
@@ -327,6 +337,15 @@ int gnsship_acq_resampler_destroy(gnsship_acq_resampler* r);
  * rejects it with GNSSHIP_E_INVAL.  slope, spc and y_intercept are set as the block sets them
  * (1, early_late_space_chips, 1), whatever the configuration carries. */
 #define GNSSHIP_SYS_GPS_L5 3
+/* BeiDou B3I (dll_pll_veml_tracking.cc:415-434, :799-834; Beidou_B3I.h): 3 taps, no pilot (track_pilot is forced
+ * to 0).  MEO/IGSO satellites carry the 20-chip NH secondary code (20 symbols per bit); GEO satellites — start's
+ * prn in 1..5 or > 58, as B1I — 2 symbols per bit, no NH, the D2 preamble as synchronisation pattern and
+ * extend_correlation_symbols capped at 2.  extend_correlation_symbols is clamped to [1, 20]. */
+#define GNSSHIP_SYS_BDS_B3I 4
+/* GPS L2C, the L2 CM code (:196-212, :666-668; gps_l2_m_dll_pll_tracking.cc:44-62): 3 taps, one 20 ms code period
+ * per telemetry symbol (vector_length = fs / 50, the loop filters updated every 20 ms), no secondary code, no
+ * pilot: track_pilot is forced to 0 and extend_correlation_symbols to 1. */
+#define GNSSHIP_SYS_GPS_L2C 5
 
 typedef struct gnsship_trk_conf { /* Dll_Pll_Conf (dll_pll_conf.h:33-80), same names and units */
     double fs_in;

@@ -635,6 +635,72 @@ inline std::vector<std::complex<float>> gps_l5i_acquisition_code(uint32_t prn, c
     return out;
 }
 
+// ---- BeiDou B3I (beidou_b3i_signal_replica.h, Beidou_B3I.h, beidou_b3i_pcps_acquisition.cc:46-63) and GPS L2C,
+// the L2 CM code (gps_l2c_signal_replica.h, GPS_L2C.h, gps_l2_m_pcps_acquisition.cc:50-78, :150-170) ----
+constexpr double BEIDOU_B3I_FREQ_HZ = 1268.52e6;
+constexpr double BEIDOU_B3I_CODE_RATE_CPS = 10.23e6;
+constexpr int32_t BEIDOU_B3I_CODE_LENGTH_CHIPS = 10230;
+constexpr char BEIDOU_B3I_SECONDARY_CODE_STR[21] = "00000100110101001110";
+constexpr char BEIDOU_B3I_GEO_PREAMBLE_SYMBOLS_STR[23] = "1111110000001100001100";
+constexpr double GPS_L2_FREQ_HZ = 1227.6e6;
+constexpr double GPS_L2_M_CODE_RATE_CPS = 0.5115e6;
+constexpr int32_t GPS_L2_M_CODE_LENGTH_CHIPS = 10230;
+constexpr uint32_t GPS_L2C_OPT_ACQ_FS_SPS = 2000000;
+// The reference's generators under their names (dest: 10230 floats; sampled: samplesPerCode complex).
+// false / negative: PRN outside 1..63 (B3I; the reference writes nothing there) or 1..50 (L2 CM; the
+// reference writes all +1 there).
+inline bool beidou_b3i_code_gen_float(float* dest, int32_t prn, uint32_t chip_shift) { return gnsship_beidou_b3i_code_gen_float(dest, prn, chip_shift) == GNSSHIP_OK; }
+inline int beidou_b3i_code_gen_complex_sampled(std::complex<float>* dest, uint32_t prn, int32_t sampling_freq, uint32_t chip_shift)
+{
+    return gnsship_beidou_b3i_code_gen_complex_sampled(reinterpret_cast<float*>(dest), prn, sampling_freq, chip_shift);
+}
+inline bool gps_l2c_m_code_gen_float(float* dest, uint32_t prn) { return gnsship_gps_l2c_m_code_gen_float(dest, static_cast<int32_t>(prn)) == GNSSHIP_OK; }
+inline int gps_l2c_m_code_gen_complex_sampled(std::complex<float>* dest, uint32_t prn, int32_t sampling_freq)
+{
+    return gnsship_gps_l2c_m_code_gen_complex_sampled(reinterpret_cast<float*>(dest), prn, sampling_freq);
+}
+// BeidouB3iPcpsAcquisition's Acq_Conf: ms_per_code 1, the B3I chip rate; its optimum acquisition rate is 100e6,
+// so no resampler is ever designed.  The caller's other fields are kept.
+inline Acq_Conf beidou_b3i_acq_conf(Acq_Conf conf)
+{
+    conf.ms_per_code = 1U;
+    conf.chips_per_second = static_cast<uint32_t>(BEIDOU_B3I_CODE_RATE_CPS);
+    conf.SetDerivedParams();
+    conf.ConfigureAutomaticResampler(100e6);
+    return conf;
+}
+// GpsL2MPcpsAcquisition's Acq_Conf: ms_per_code 20 (samples_per_code = samples_per_ms · 20; a sampled_ms that is
+// no multiple of 20 becomes 20, acq_conf.cc:48-53), the L2 CM chip rate, the automatic resampler designed for
+// GPS_L2C_OPT_ACQ_FS_SPS.
+inline Acq_Conf gps_l2_m_acq_conf(Acq_Conf conf)
+{
+    conf.ms_per_code = 20U;
+    if (conf.sampled_ms % 20U != 0U || conf.sampled_ms == 0U) conf.sampled_ms = 20U;
+    conf.chips_per_second = static_cast<uint32_t>(GPS_L2_M_CODE_RATE_CPS);
+    conf.SetDerivedParams();
+    conf.ConfigureAutomaticResampler(static_cast<double>(GPS_L2C_OPT_ACQ_FS_SPS));
+    return conf;
+}
+// set_local_code of the two adapters: code_length = floor(fs / 1000) (B3I) or floor(fs / 50) (L2 CM) samples of
+// the sampled code, copied sampled_ms / ms_per_code times into vector_length = floor(sampled_ms · samples_per_ms)
+// samples (doubled with bit_transition_flag: the rest stays zero).  Empty: PRN out of range.
+inline std::vector<std::complex<float>> acquisition_code_10230(uint32_t prn, const Acq_Conf& conf, bool l2c)
+{
+    const int64_t fs = conf.resampled_fs ? conf.resampled_fs : conf.fs_in;
+    const double rate = l2c ? GPS_L2_M_CODE_RATE_CPS : BEIDOU_B3I_CODE_RATE_CPS;
+    const auto code_length = static_cast<size_t>(std::floor(static_cast<double>(fs) / (rate / 10230.0)));
+    const auto vector_length = static_cast<size_t>(std::floor(conf.sampled_ms * (static_cast<float>(fs) * 0.001F)) * (conf.bit_transition_flag ? 2.0 : 1.0));
+    const uint32_t num_codes = conf.sampled_ms / (l2c ? 20U : 1U);
+    std::vector<std::complex<float>> one(code_length), out(std::max(vector_length, code_length * num_codes));
+    const int rc = l2c ? gps_l2c_m_code_gen_complex_sampled(one.data(), prn, static_cast<int32_t>(fs))
+                       : beidou_b3i_code_gen_complex_sampled(one.data(), prn, static_cast<int32_t>(fs), 0);
+    if (rc < 0) return {};
+    for (uint32_t i = 0; i < num_codes; i++) std::copy(one.begin(), one.end(), out.begin() + static_cast<size_t>(i) * code_length);
+    return out;
+}
+inline std::vector<std::complex<float>> beidou_b3i_acquisition_code(uint32_t prn, const Acq_Conf& conf) { return acquisition_code_10230(prn, conf, false); }
+inline std::vector<std::complex<float>> gps_l2c_m_acquisition_code(uint32_t prn, const Acq_Conf& conf) { return acquisition_code_10230(prn, conf, true); }
+
 // Mirror of Dll_Pll_Conf (src/algorithms/tracking/libs/dll_pll_conf.h:33-80): same field names and
 // defaults (FLAGS_* defaults from gnss_sdr_flags.cc:48-57 for the lock-detector fields).
 struct Dll_Pll_Conf {
@@ -655,7 +721,9 @@ struct Dll_Pll_Conf {
     int32_t cn0_samples{20}, cn0_smoother_samples{200}, carrier_lock_test_smoother_samples{25}, cn0_min{25};
     int32_t max_code_lock_fail{50}, max_carrier_lock_fail{5000};
     bool carrier_aiding{true}, track_pilot{true};
-    char system{'G'};    // 'G' GPS (signal "1C": L1 C/A, "L5": the L5Q pilot + L5I prompt), 'E' Galileo E1, 'C' BeiDou B1I
+    // 'G' GPS (signal "1C": L1 C/A, "L5": the L5Q pilot + L5I prompt, "2S": L2C, the L2 CM code), 'E' Galileo E1,
+    // 'C' BeiDou (signal "B3": B3I, anything else: B1I)
+    char system{'G'};
     char signal[3]{"1C"};
     // Not a Dll_Pll_Conf member: the reference's correlations follow the volk_gnsssdr rotator variant
     // its dispatcher picks on the host (volk_gnsssdr_rank_archs.c); AUTO makes the same choice.
@@ -710,9 +778,22 @@ public:
         c.rotator = conf.rotator;
         c.if_hz = conf.if_hz;
         const bool l5 = conf.system == 'G' && conf.signal[0] == 'L' && conf.signal[1] == '5';  // GpsL5DllPllTracking (system 'G', signal "L5")
-        c.system = conf.system == 'E' ? GNSSHIP_SYS_GAL_E1 : conf.system == 'C' ? GNSSHIP_SYS_BDS_B1I : l5 ? GNSSHIP_SYS_GPS_L5 : GNSSHIP_SYS_GPS_L1CA;
+        const bool b3 = conf.system == 'C' && conf.signal[0] == 'B' && conf.signal[1] == '3';  // BeidouB3iDllPllTracking
+        const bool l2c = conf.system == 'G' && conf.signal[0] == '2' && conf.signal[1] == 'S';  // GpsL2MDllPllTracking
+        c.system = conf.system == 'E' ? GNSSHIP_SYS_GAL_E1 : b3 ? GNSSHIP_SYS_BDS_B3I : conf.system == 'C' ? GNSSHIP_SYS_BDS_B1I
+                   : l5 ? GNSSHIP_SYS_GPS_L5 : l2c ? GNSSHIP_SYS_GPS_L2C : GNSSHIP_SYS_GPS_L1CA;
         // gps_l5_dll_pll_tracking.cc:49-53 (track_pilot = false — the block's interchange_iq — is refused by gnsship_trk_create)
         if (l5 && c.extend_correlation_symbols < 1) c.extend_correlation_symbols = 1;
+        if (b3) {  // beidou_b3i_dll_pll_tracking.cc:47-59
+            c.vector_length = static_cast<uint32_t>(std::round(conf.fs_in / (BEIDOU_B3I_CODE_RATE_CPS / BEIDOU_B3I_CODE_LENGTH_CHIPS)));
+            c.extend_correlation_symbols = std::min(std::max(c.extend_correlation_symbols, 1), 20);
+            c.track_pilot = 0;
+        }
+        if (l2c) {  // gps_l2_m_dll_pll_tracking.cc:47-59: one 20 ms code per epoch, no extension, no pilot
+            c.vector_length = static_cast<uint32_t>(std::round(conf.fs_in / (GPS_L2_M_CODE_RATE_CPS / GPS_L2_M_CODE_LENGTH_CHIPS)));
+            c.extend_correlation_symbols = 1;
+            c.track_pilot = 0;
+        }
         code_base_ = 1024 + 2 * max_channels * next_engine_id();
         std::lock_guard<std::mutex> lk(dev_->mutex());
         if (gnsship_trk_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)

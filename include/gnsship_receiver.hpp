@@ -98,7 +98,8 @@ private:
 };
 
 // The configuration keys of the 1C channels (conf/gnss-sdr_GPS_L1_gr_complex.conf); with trk.signal = "L5"
-// the same keys of the L5 channels (Channels_L5, Acquisition_L5, Tracking_L5).
+// the same keys of the L5 channels (Channels_L5, Acquisition_L5, Tracking_L5), with "2S" of the L2C channels
+// (Channels_2S, ...; vector_length = round(fs / 50)), with trk.system 'C' and trk.signal "B3" of the BeiDou B3I ones.
 struct Receiver_Conf {
     int channels{1};                     // Channels_1C.count
     int in_acquisition{1};               // Channels.in_acquisition (capped at channels)
@@ -136,15 +137,21 @@ public:
         // Channels_L5 (trk.system 'G', trk.signal "L5"): acquisition on L5I, tracking on the L5Q pilot
         l5_ = conf_.trk.system == 'G' && conf_.trk.signal[0] == 'L' && conf_.trk.signal[1] == '5';
         if (l5_) conf_.acq = gps_l5i_acq_conf(conf_.acq);
+        // Channels_B3 (system 'C', signal "B3") and Channels_2S (system 'G', signal "2S"): acquisition and tracking on
+        // the same code; a B3I GEO satellite is recognised by the PRN start_tracking passes on
+        b3_ = conf_.trk.system == 'C' && conf_.trk.signal[0] == 'B' && conf_.trk.signal[1] == '3';
+        l2c_ = conf_.trk.system == 'G' && conf_.trk.signal[0] == '2' && conf_.trk.signal[1] == 'S';
+        if (b3_) conf_.acq = beidou_b3i_acq_conf(conf_.acq);
+        if (l2c_) conf_.acq = gps_l2_m_acq_conf(conf_.acq);
         n_ = std::max(1, conf_.channels);
         max_acq_ = std::min(std::max(0, conf_.in_acquisition), n_);
         conf_.satellite.resize(static_cast<size_t>(n_), 0U);
-        if (conf_.trk.vector_length == 0) conf_.trk.vector_length = static_cast<uint32_t>(std::lround(conf_.trk.fs_in / 1000.0));
+        if (conf_.trk.vector_length == 0 || l2c_) conf_.trk.vector_length = static_cast<uint32_t>(std::lround(conf_.trk.fs_in / (l2c_ ? 50.0 : 1000.0)));
         vl_ = static_cast<int64_t>(conf_.trk.vector_length);
         block_ = conf_.block_samples > 0 ? conf_.block_samples : static_cast<int64_t>(conf_.trk.fs_in / 10.0);
         tail_ = 2 * vl_;
         trk_ = std::make_unique<Dll_Pll_Veml_Tracking_Hip>(conf_.trk, n_, conf_.device);
-        for (uint32_t p = 1; p <= 32; p++) available_.push_back(p);  // set_signals_list (GPS 1C)
+        for (uint32_t p = 1; p <= (b3_ ? 63U : 32U); p++) available_.push_back(p);  // set_signals_list (GPS: 1-32, BeiDou: 1-63)
         prn_.assign(static_cast<size_t>(n_), 0U);
         apos_.assign(static_cast<size_t>(n_), 0U);
         fsm_.resize(static_cast<size_t>(n_));
@@ -206,6 +213,12 @@ private:
                     !trk_->start_tracking(c, pilot.data(), data.data(), GPS_L5Q_CODE_LENGTH_CHIPS, s.Acq_delay_samples, s.Acq_doppler_hz,
                         s.Acq_samplestamp_samples, now_, static_cast<int>(prn)))
                     error_ = true;
+            } else if (b3_ || l2c_) {  // start_tracking :666-668, :799-801: one replica, no data prompt
+                std::vector<float> code(10230);
+                if (!(b3_ ? beidou_b3i_code_gen_float(code.data(), static_cast<int32_t>(prn), 0) : gps_l2c_m_code_gen_float(code.data(), prn)) ||
+                    !trk_->start_tracking(c, code.data(), nullptr, 10230, s.Acq_delay_samples, s.Acq_doppler_hz, s.Acq_samplestamp_samples, now_,
+                        static_cast<int>(prn)))
+                    error_ = true;
             } else {
                 float code[1023];
                 gnsship_gps_l1_ca_code_gen_float(code, static_cast<int32_t>(prn), 0);
@@ -226,6 +239,11 @@ private:
         prn_[static_cast<size_t>(c)] = prn;
         if (l5_) {  // GpsL5iPcpsAcquisition::set_local_code: the search runs on L5I
             const std::vector<std::complex<float>> code = gps_l5i_acquisition_code(prn, conf_.acq);
+            if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
+            return;
+        }
+        if (b3_ || l2c_) {  // BeidouB3iPcpsAcquisition / GpsL2MPcpsAcquisition::set_local_code
+            const std::vector<std::complex<float>> code = b3_ ? beidou_b3i_acquisition_code(prn, conf_.acq) : gps_l2c_m_acquisition_code(prn, conf_.acq);
             if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
             return;
         }
@@ -452,6 +470,7 @@ private:
     std::vector<gnsship_trk_dump_record> dump_buf_;
     bool error_ = false;
     bool l5_ = false;  // GPS L5 channels (acquisition L5I, tracking L5Q pilot + L5I prompt)
+    bool b3_ = false, l2c_ = false;  // BeiDou B3I / GPS L2C channels (acquisition and tracking on one code)
 };
 
 }  // namespace gnsship

@@ -2,9 +2,10 @@
 // tracking, re-acquisition after a loss of lock) → per-channel tracking dumps, the Channel role of
 // GNSS-SDR without GNU Radio (include/gnsship_receiver.hpp).  Keys mirror the reference's
 // configuration (conf/gnss-sdr_GPS_L1_gr_complex.conf); GPS L1 C/A channels, or with --signal L5 GPS L5
-// channels (acquisition on L5I, tracking on the L5Q pilot with the L5I data prompt).
+// channels (acquisition on L5I, tracking on the L5Q pilot with the L5I data prompt), with --signal 2S GPS L2C
+// channels (the L2 CM code, 20 ms epochs), with --signal B3 BeiDou B3I channels (a GEO satellite follows its PRN).
 //
-//   gnsship_rx --file F [--item gr_complex|ishort|ibyte] [--fs 4000000] [--seconds S] [--signal 1C|L5]
+//   gnsship_rx --file F [--item gr_complex|ishort|ibyte] [--fs 4000000] [--seconds S] [--signal 1C|L5|2S|B3]
 //              [--channels 5] [--in-acquisition 1] [--satellite CH:PRN ...] [--repeat-satellite]
 //              [--pfa 0.01] [--doppler-max 10000] [--doppler-step 250]
 //              [--pll-bw 40] [--dll-bw 4] [--order 3] [--pull-in-time-s 10] [--rotator auto|generic|avx]
@@ -87,11 +88,13 @@ int main(int argc, char** argv)
     if (file.empty()) usage("--file is required");
     const int sample_bytes = item == "gr_complex" ? 8 : item == "ishort" ? 4 : item == "ibyte" ? 2 : 0;
     if (!sample_bytes) usage("--item must be gr_complex, ishort or ibyte");
-    if (signal != "1C" && signal != "L5") usage("--signal must be 1C or L5");
-    std::snprintf(rc.trk.signal, sizeof(rc.trk.signal), "%s", signal.c_str());  // system stays 'G'
+    if (signal != "1C" && signal != "L5" && signal != "2S" && signal != "B3") usage("--signal must be 1C, L5, 2S or B3");
+    std::snprintf(rc.trk.signal, sizeof(rc.trk.signal), "%s", signal.c_str());
+    if (signal == "B3") rc.trk.system = 'C';  // otherwise 'G'
     rc.acq.fs_in = static_cast<int64_t>(fs);
     rc.trk.fs_in = fs;
-    rc.trk.vector_length = static_cast<uint32_t>(std::lround(fs / 1000.0));  // gps_l1_ca_dll_pll_tracking.cc:47, gps_l5_dll_pll_tracking.cc:47
+    // gps_l1_ca_dll_pll_tracking.cc:47, gps_l5_dll_pll_tracking.cc:47, beidou_b3i_dll_pll_tracking.cc:47; gps_l2_m_dll_pll_tracking.cc:47
+    rc.trk.vector_length = static_cast<uint32_t>(std::lround(fs / (signal == "2S" ? 50.0 : 1000.0)));
     rc.trk.rotator = rotator == "generic" ? GNSSHIP_ROTATOR_GENERIC : rotator == "avx" ? GNSSHIP_ROTATOR_AVX : GNSSHIP_ROTATOR_AUTO;
     rc.block_samples = static_cast<int64_t>(fs * block_ms / 1000.0);
     rc.dump_filename = dump;
