@@ -22,18 +22,27 @@
 //    rounding) and per tap a·code[tap] (_mm256_mul_ps); four iterations of one product slot (2·tap +
 //    component) go to the product ring as one 16-byte store, slot-major (ProdLayout); a group's flag
 //    is set once its products have landed.  Producer 0 also runs the lock detectors (lock_status)
-//    beside the control wave's speculative loop update, kept only when the lock test passes;
+//    beside the control wave's speculative loop update, kept only when the lock test passes; in the
+//    steady regime it forms the prompt from the stored taps itself and starts as soon as they land;
 //  * the accumulator waves (one per four product slots): lane (slot row, chain l) keeps u_avx's
 //    accumulator of chain l for ONE slot and adds its products in iteration order (dotProdVal +=
 //    c, :257-260), four per 16-byte load, as the groups land (the group's flag and loads in one
 //    batch); then combines the 16 chains exactly as u_avx does — ((d_k + d_{k+4}) + d_{k+8}) +
 //    d_{k+12}, then the four lanes serially from 0 (:279-291) — and adds the serial N mod 16 tail
-//    (:298-308): every tap bit-identical to the reference's;
+//    (:298-308): every tap bit-identical to the reference's; where the epoch's E / P / L are its own
+//    taps they also evaluate the PLL and DLL discriminators;
 //  * the control wave: the channel's loop state in its registers for the whole run (RChan,
 //    trk_loop.h); epoch_pre → run_dll_pll (publishing the next carrier step for the phasor wave
 //    right after the carrier filter) → update_tracking_vars; in state 4 it publishes the next epoch's
 //    correlator arguments (the seed) before the lock test's outcome — which a failed test cancels (the
 //    channel stops) — and only then finishes this epoch and writes its records.
+//    The steady regime (FJob::steady, decided per epoch when it is seeded: state 4, both
+//    discriminators from the accumulator waves, the pull-in over, no FLL) takes everything the seed
+//    does not need off that chain: PLL value → carrier filter → early step → DLL value → code filter →
+//    update_tracking_vars → seed, and only then epoch_pre (accumulators, symbol counters, record
+//    fields), the lock outcome, epoch_post and the records.  The control wave hands the lock wave
+//    nothing in such an epoch.  Every other epoch (states 2 and 3, secondary codes, extended
+//    integration, FLL, pull-in) keeps the order above and the prompt hand-off (pre_seq).
 // Roles go by SIMD (the phasor wave with accumulator 0, the control wave with accumulator 1, the
 // producers in pairs, numbered round-robin over their SIMDs); the throughput form (more channels than
 // CUs) runs the same roles with fewer producers, two workgroups per CU.
@@ -180,14 +189,46 @@ constexpr int kRoleControl = 0, kRoleReplay = 1, kRoleProducer = 2, kRoleAccum =
 constexpr uint64_t kSlotEmpty = ~0ull;  // an unwritten phasor slot (NaN, NaN)
 
 // The epoch's correlation as the producers need it (LDS: the seed from wave 0, dz from wave 1).
+// This is the job as a wave holds it (uniform_job): the per-epoch fields come from LDS (FJobLds), M, S
+// and tail are the run's constants from the wave's own kernel-scope values, the shifts the wave's
+// copy of the run's wide or narrow set, re-read from the parameters only when the job's narrow bit changes.
 struct FJob {
     int64_t off;  // first sample of the epoch in the IF buffer
     float rem_code, code_step;  // do_correlation_step's rem_code_phase_chips·spc, code_phase_step_chips·spc
     float shifts[5];
     float dz_re, dz_im;  // normalise(inc^16)
     float rem_carr, step;  // the carrier arguments (IF folded in), for the trace
-    int32_t runnable, in_margin, M, S, tail, pad;
+    // steady: the epoch runs in the steady regime (see the control wave's epoch loop) — state 4, both
+    // discriminators from the accumulator waves, no pull-in, no FLL — decided when it was seeded
+    int32_t runnable, in_margin, M, S, tail, steady;
+    int32_t narrow;  // which of the run's two tap-shift sets `shifts` holds (the caller fills them: job_shifts)
 };
+
+// The per-epoch job in LDS: two 16-byte words, each written with one store and read with one load.
+//   a = { off (low), off (bits 32-55) | flags << 24, rem_code, code_step }      wave 0 (the seed)
+//   b = { rem_carr, step, dz_re, dz_im }      wave 0 (the seed; dz too when it confirms wave 1's
+//                                             prediction), dz otherwise from wave 1
+// The flags share off's top byte: a sample offset into a device buffer stays far below 2^56.
+typedef uint32_t u4v __attribute__((ext_vector_type(4)));
+constexpr uint32_t kJobRunnable = 1u, kJobInMargin = 2u, kJobSteady = 4u, kJobNarrow = 8u;
+struct alignas(16) FJobLds {
+    uint32_t w[8];  // a = w[0..3], b = w[4..7]
+};
+__device__ __forceinline__ void job_store_a(FJobLds& s, int64_t off, uint32_t flags, float rem_code, float code_step)
+{
+    // off is a sample index into a device buffer (≥ 0, far below 2^56: 2^56 samples of the smallest
+    // format would be 2^57 bytes); its top byte carries the flags
+    const uint64_t o = static_cast<uint64_t>(off);
+    *reinterpret_cast<u4v*>(&s.w[0]) = u4v{static_cast<uint32_t>(o), (static_cast<uint32_t>(o >> 32) & 0x00ffffffu) | (flags << 24),
+        __builtin_bit_cast(uint32_t, rem_code), __builtin_bit_cast(uint32_t, code_step)};
+}
+__device__ __forceinline__ void job_store_b(FJobLds& s, float rem_carr, float step, float dz_re, float dz_im)
+{
+    *reinterpret_cast<u4v*>(&s.w[4]) = u4v{__builtin_bit_cast(uint32_t, rem_carr), __builtin_bit_cast(uint32_t, step),
+        __builtin_bit_cast(uint32_t, dz_re), __builtin_bit_cast(uint32_t, dz_im)};
+}
+__device__ __forceinline__ void job_store_carr(FJobLds& s, float rem_carr, float step) { *reinterpret_cast<f2*>(&s.w[4]) = f2{rem_carr, step}; }
+__device__ __forceinline__ void job_store_dz(FJobLds& s, f2 dz) { *reinterpret_cast<f2*>(&s.w[6]) = dz; }
 
 // What the loop hands the derive wave once its carrier filter ran (state 4): the next epoch's
 // carrier step, and the inputs of its remainder phase if the epoch length stays n_pred samples.
@@ -198,20 +239,21 @@ struct SpecArgs {
     int32_t n_pred;
 };
 
-struct SpecPred {
+struct alignas(16) SpecPred {
     float rem, step, dz_re, dz_im;
 };
 
 struct FShared {
-    FJob job;
+    FJobLds job;  // the epoch's job: the seed from wave 0, dz from wave 0 or wave 1
     float taps[2][2 * kMaxTaps + 2];  // epoch e's tap sums in [e & 1] (+ the data prompt at 2·kMaxTaps), as epoch_pre reads them
     int32_t taps_seq[kMaxAccWaves];    // [a]: e + 1 once accumulator wave a stored its taps of epoch e
     gnsship_trk_dump_record drec;  // log_data's record of the epoch
-    double coh;       // the coherent time lock_status is called with (0: no lock test this epoch)
-    int32_t seed_seq; // e + 1 once wave 0 published epoch e's NCO arguments (sh.job without dz)
+    double coh;       // the coherent time lock_status is called with (0: no lock test this epoch); not in a steady epoch
+    int32_t seed_seq; // e + 1 once wave 0 published epoch e's NCO arguments (sh.job, dz only with a confirmed prediction)
     int32_t job_seq;  // e + 1 once wave 1 completed epoch e's job (dz) — the producers start
-    int32_t pre_seq;  // e + 1 once wave 0 published this epoch's prompt / pull-in / coh
-    int32_t lock_seq; // e + 1 once wave 2 published the lock outcome
+    int32_t pre_seq;  // e + 1 once wave 0 published this epoch's prompt / pull-in / coh (never for a steady epoch: the
+                      // lock wave takes the prompt from taps[] once every taps_seq[a] reached e + 1)
+    int32_t lock_seq; // e + 1 once the lock wave (producer 0) published the lock outcome — every runnable epoch, cancelled ones too
     int32_t locked;
     int32_t tail_seq;   // e + 1 once wave 1 stored epoch e's N mod 16 tail products
     int32_t acc_groups[kMaxAccWaves]; // [a]: product groups accumulator wave a has consumed (counted over the run)
@@ -228,25 +270,29 @@ struct FShared {
 // The job as wave-uniform values (scalar registers): read from LDS it would otherwise be per-lane,
 // and a per-lane buffer resource turns every sample load into a waterfall loop.
 __device__ __forceinline__ float unif(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
-__device__ __forceinline__ FJob uniform_job(const FJob& s)
+// M, S, tail: the run's constants as the calling wave holds them; the shifts are left to the caller.
+__device__ __forceinline__ FJob uniform_job(const FJobLds& s, int M, int S, int tail)
 {
     FJob j;
-    const uint64_t off = static_cast<uint64_t>(s.off);
-    j.off = static_cast<int64_t>((static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(off >> 32)))) << 32) |
-                                 static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(off & 0xffffffffu))));
-    j.rem_code = unif(s.rem_code);
-    j.code_step = unif(s.code_step);
-    for (int t = 0; t < 5; t++) j.shifts[t] = unif(s.shifts[t]);
-    j.dz_re = unif(s.dz_re);
-    j.dz_im = unif(s.dz_im);
-    j.rem_carr = unif(s.rem_carr);
-    j.step = unif(s.step);
-    j.runnable = __builtin_amdgcn_readfirstlane(s.runnable);
-    j.in_margin = __builtin_amdgcn_readfirstlane(s.in_margin);
-    j.M = __builtin_amdgcn_readfirstlane(s.M);
-    j.S = __builtin_amdgcn_readfirstlane(s.S);
-    j.tail = __builtin_amdgcn_readfirstlane(s.tail);
-    j.pad = 0;
+    const u4v a = *reinterpret_cast<const u4v*>(&s.w[0]), b = *reinterpret_cast<const u4v*>(&s.w[4]);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(a.x), hi = __builtin_amdgcn_readfirstlane(a.y);
+    j.off = static_cast<int64_t>((static_cast<uint64_t>(hi & 0x00ffffffu) << 32) | lo);
+    const uint32_t flags = hi >> 24;
+    j.rem_code = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(a.z));
+    j.code_step = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(a.w));
+    j.rem_carr = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(b.x));
+    j.step = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(b.y));
+    j.dz_re = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(b.z));
+    j.dz_im = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(b.w));
+    j.narrow = (flags & kJobNarrow) ? 1 : 0;
+#pragma unroll
+    for (int t = 0; t < 5; t++) j.shifts[t] = 0.0f;
+    j.runnable = (flags & kJobRunnable) ? 1 : 0;
+    j.in_margin = (flags & kJobInMargin) ? 1 : 0;
+    j.steady = (flags & kJobSteady) ? 1 : 0;
+    j.M = M;
+    j.S = S;
+    j.tail = tail;
     return j;
 }
 
@@ -1124,23 +1170,33 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
         smin_n = fminf(smin_n, shv_n[t]);
         smax_n = fmaxf(smax_n, shv_n[t]);
     }
-    // wave 0: the job's code and sample arguments for an epoch starting at absolute sample nir
-    auto code_fields = [&](FJob& j, uint64_t nir) __attribute__((always_inline)) {
-        const bool nw = uni(rc.narrow) != 0;
-        j.off = static_cast<int64_t>(nir - buf_first);
-        j.rem_code = __fmul_rn(static_cast<float>(rc.rem_code_phase_chips), spcf);
-        j.code_step = __fmul_rn(static_cast<float>(rc.code_phase_step_chips), spcf);
+    // every wave: the epoch's job from LDS with this wave's own run constants; its tap shifts are the
+    // wave's copy `cur` of the set the job's narrow bit names, read from the parameters when that bit
+    // differs from the copy's (cur_nw; −1: no copy yet) — at the run's first epoch and when narrow changes
+    auto read_job = [&](float (&cur)[5], int& cur_nw) __attribute__((always_inline)) {
+        FJob j = uniform_job(sh.job, M, S, tail);
+        if constexpr (THRU) {  // no register for a copy: the set is read every epoch
 #pragma unroll
-        for (int t = 0; t < 5; t++) j.shifts[t] = nw ? shv_n[t] : shv_w[t];
-        const float smin = nw ? smin_n : smin_w, smax = nw ? smax_n : smax_w;
-        const double span = static_cast<double>(j.code_step) * static_cast<double>(N > 0 ? N - 1 : 0);
-        const double lo = fmin(0.0, span) + smin - j.rem_code - 2.0;
-        const double hi = fmax(0.0, span) + smax - j.rem_code + 2.0;
-        j.in_margin = (isfinite(lo) && isfinite(hi) && lo >= -kCodeMargin && hi < static_cast<double>(L + kCodeMargin)) ? 1 : 0;
-        j.M = M;
-        j.S = S;
-        j.tail = tail;
+            for (int t = 0; t < 5; t++) j.shifts[t] = t < NT ? (j.narrow ? k.shifts_n[t] : k.shifts[t]) : 0.0f;
+            return j;
+        }
+        if (j.narrow != cur_nw) {
+#pragma unroll
+            for (int t = 0; t < 5; t++) cur[t] = t < NT ? (j.narrow ? k.shifts_n[t] : k.shifts[t]) : 0.0f;
+            cur_nw = j.narrow;
+        }
+#pragma unroll
+        for (int t = 0; t < 5; t++) j.shifts[t] = cur[t];
+        return j;
     };
+    // The steady regime's run-wide conditions (make_seed adds the channel's: state 4, the run's spacing,
+    // no pull-in).  It is compiled into the latency form of the three-tap layout without a data prompt
+    // (GPS L1 C/A and the other single-replica signals).  The five-tap and data-prompt layouts (E1, L5:
+    // secondary codes, so the regime's conditions fail at run time anyway) and the throughput form —
+    // whose rate does not hang on one channel's chain — have no registers to spare for the second
+    // order and keep the hand-off in every epoch.
+    constexpr bool kSteadyForm = !THRU && NT == 3 && !DATA;
+    const bool steady_run = kSteadyForm && pre_disc && !kp.conf.enable_fll_steady_state;
     // wave 0: do_correlation_step's arguments for the epoch at nitems_read (all but the phasors)
     auto make_seed = [&](int e) {
         const bool runnable = e < max_rounds && (rc.state == 2 || rc.state == 3 || rc.state == 4) && rc.nitems_read >= buf_first &&
@@ -1151,13 +1207,25 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
         const float stepf = static_cast<float>(rc.carrier_phase_step_rad + if_step);
         if (runnable) rc.epoch_start = rc.nitems_read;
         seed_start = rc.epoch_start;
+        // the steady regime, decided here for the epoch being seeded: state 4 with both discriminators
+        // from the accumulator waves (pre_disc, the run's spacing), the pull-in over and no FLL branch
+        const bool steady = runnable && steady_run && rc.state == 4 && rc.pull_in == 0 &&
+                            __builtin_bit_cast(uint32_t, rc.spc) == __builtin_bit_cast(uint32_t, kp.conf.early_late_space_chips);
         if (lane == 0) {
-            FJob& j = sh.job;
-            j.runnable = runnable ? 1 : 0;
-            if (runnable) {
-                code_fields(j, rc.nitems_read);
-                j.rem_carr = rem_carr;
-                j.step = stepf;
+            FJobLds& j = sh.job;
+            if (runnable) {  // the job's code and sample arguments
+                const bool nw = uni(rc.narrow) != 0;
+                const float rem_code = __fmul_rn(static_cast<float>(rc.rem_code_phase_chips), spcf);
+                const float code_step = __fmul_rn(static_cast<float>(rc.code_phase_step_chips), spcf);
+                const float smin = nw ? smin_n : smin_w, smax = nw ? smax_n : smax_w;
+                const double span = static_cast<double>(code_step) * static_cast<double>(N > 0 ? N - 1 : 0);
+                const double lo = fmin(0.0, span) + smin - rem_code - 2.0;
+                const double hi = fmax(0.0, span) + smax - rem_code + 2.0;
+                const bool in_margin = isfinite(lo) && isfinite(hi) && lo >= -kCodeMargin && hi < static_cast<double>(L + kCodeMargin);
+                const uint32_t flags = kJobRunnable | (in_margin ? kJobInMargin : 0u) | (steady ? kJobSteady : 0u) | (nw ? kJobNarrow : 0u);
+                job_store_a(j, static_cast<int64_t>(rc.nitems_read - buf_first), flags, rem_code, code_step);
+            } else {
+                job_store_a(j, 0, 0u, 0.0f, 0.0f);
             }
             // wave 1's speculative replay of this epoch (whole-epoch slots): confirmed here when its
             // remainder phase and step are the seed's floats, and the job goes out with the seed
@@ -1165,13 +1233,14 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
             if (!SRING && __hip_atomic_load(&sh.pred_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >= e + 1) {
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");  // sh.pred is read after its sequence number
                 code = 2;
-                if (runnable && __builtin_bit_cast(uint32_t, sh.pred.rem) == __builtin_bit_cast(uint32_t, rem_carr) &&
-                    __builtin_bit_cast(uint32_t, sh.pred.step) == __builtin_bit_cast(uint32_t, stepf)) {
-                    j.dz_re = sh.pred.dz_re;
-                    j.dz_im = sh.pred.dz_im;
+                const SpecPred pr = sh.pred;
+                if (runnable && __builtin_bit_cast(uint32_t, pr.rem) == __builtin_bit_cast(uint32_t, rem_carr) &&
+                    __builtin_bit_cast(uint32_t, pr.step) == __builtin_bit_cast(uint32_t, stepf)) {
+                    job_store_b(j, rem_carr, stepf, pr.dz_re, pr.dz_im);
                     code = 1;
                 }
             }
+            if (code != 1) job_store_carr(j, rem_carr, stepf);
             sh.verdict = 4 * (e + 1) + code;
             publish_seq(&sh.seed_seq, e + 1);
             if (code == 1) publish_seq(&sh.job_seq, e + 1);
@@ -1184,6 +1253,8 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
     // places for one role's memory operations are not charged to another (a merged loop made the
     // control wave wait for the producers' sample loads it never issued).
     if (role == kRoleReplay) {
+        float shc[5];  // this wave's tap shifts (read_job)
+        int sh_nw = -1;
         for (int e = 0;; e++) {
             FJob job;
                 // ---- derive: the phasors of the seeded epoch ----
@@ -1245,13 +1316,12 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
                     const int v = __builtin_amdgcn_readfirstlane(sh.verdict);
                     int status = (v >> 2) == e + 1 ? (v & 3) : 3;
                     if (status == 3) {  // the seed was made before the prediction was published: compare here
-                        const FJob sd = uniform_job(sh.job);
+                        const FJob sd = read_job(shc, sh_nw);
                         status = 2;
                         if (sd.runnable && __builtin_bit_cast(uint32_t, sd.step) == __builtin_bit_cast(uint32_t, step_pre) &&
                             __builtin_bit_cast(uint32_t, sd.rem_carr) == __builtin_bit_cast(uint32_t, rem_pred)) {
                             if (lane == 0) {
-                                sh.job.dz_re = dz.x;
-                                sh.job.dz_im = dz.y;
+                                job_store_dz(sh.job, dz);
                                 publish_seq(&sh.job_seq, e + 1);
                             }
                             status = 1;
@@ -1267,23 +1337,20 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
                 }
                 if (!published) {
                     wait_seq(&sh.seed_seq, e + 1);
-                    const FJob sd = uniform_job(sh.job);
+                    const FJob sd = read_job(shc, sh_nw);
                     if (sd.runnable) {
                         // (cos rem, −sin rem) and (cos −step, sin −step) (cpu_multicorrelator_real_codes.cc:115,123),
                         // each glibc's cosf / sinf (glibc_sincosf.h)
                         if (!(spec && __builtin_bit_cast(uint32_t, sd.step) == __builtin_bit_cast(uint32_t, step_pre))) derive_step(sd.step, inc, dz);
                         zinit = derive_chains(sd.rem_carr, inc, lane);
-                        if (lane == 0) {
-                            sh.job.dz_re = dz.x;
-                            sh.job.dz_im = dz.y;
-                        }
+                        if (lane == 0) job_store_dz(sh.job, dz);
                     }
                     if (lane == 0) publish_seq(&sh.job_seq, e + 1);
                     if (!sd.runnable) break;
                 }
                 GNSSHIP_FSTAMP(e, 1);
                 GNSSHIP_FCLK(e, 12);
-                job = uniform_job(sh.job);
+                job = read_job(shc, sh_nw);
                 if (!published) {
                     xl = (lane & 1) ? zinit.y : zinit.x;
                     if (lane < 2 * kAvxLanes) xl = fast_replay<G, SRING>(xl, job.dz_re, (lane & 1) ? job.dz_im : -job.dz_im, M, S, tail, Zs, rs, lane);
@@ -1311,10 +1378,15 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
     } else if (role == kRoleProducer) {
         f2 xa[G < 8 ? G : 8];
         float cv[G][NTT];
+        bool lost = false;  // producer 0: its last lock test failed (the next epoch, if seeded, is cancelled)
+        float shc[5];  // this wave's tap shifts (read_job)
+        int sh_nw = -1;
+        // producer 0: the coherent time a steady epoch's lock test is called with (epoch_pre's return value)
+        const double coh_steady = k.code_period * static_cast<double>(k.sync[uni(sc.geo)].extend);
         for (int e = 0;; e++) {
             const int gbase = e * n_groups;  // the epoch's first product-group tag - 1
             wait_seq(&sh.job_seq, e + 1);
-            const FJob job = uniform_job(sh.job);
+            const FJob job = read_job(shc, sh_nw);
             if (!job.runnable) break;
             const i4v span = sample_span<FMT>(samples, job.off, N);
             if (job.in_margin)
@@ -1324,21 +1396,48 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
             if (pw < 2) GNSSHIP_FSTAMP(e, 3 + pw);  // 3, 4: producers 0 and 1 done
             if (pw == 0) {
                 // cn0_and_tracking_lock_status (:972-1029) on the LDS copy of its members, beside the loop update
-                wait_seq(&sh.pre_seq, e + 1);
-                const double coh = sh.coh;
-                if (lane == 0) {
-                    GNSSHIP_TRK_LOOP_STAMP(8);
-                    sh.locked = (coh > 0.0 && !lock_status(k, sc, coh)) ? 0 : 1;
-                    GNSSHIP_TRK_LOOP_STAMP(26);
-                    publish_seq(&sh.lock_seq, e + 1);
+                bool locked = true;
+                if (kSteadyForm && job.steady) {
+                    // the steady regime: the detectors start from the taps themselves — the prompt as
+                    // epoch_pre's save_correlation_results forms it on zeroed accumulators (0 + 1·tap),
+                    // the coherent time as it returns it — with nothing from the control wave.  An epoch
+                    // seeded before a lock test that failed (this wave reported the loss itself) is
+                    // cancelled: the detectors' state must not see it.
+#pragma unroll
+                    for (int a = 0; a < NA; a++) wait_seq(&sh.taps_seq[a], e + 1);
+                    if (lane == 0) {
+                        GNSSHIP_FSTAMP(e, 8);
+                        if (!lost) {
+                            const float* tp = sh.taps[e & 1] + (k.veml ? 2 : 0);
+                            sc.p[0] = __fadd_rn(0.0f, __fmul_rn(1.0f, tp[2]));
+                            sc.p[1] = __fadd_rn(0.0f, __fmul_rn(1.0f, tp[3]));
+                            locked = lock_status(k, sc, coh_steady);
+                        }
+                        sh.locked = locked ? 1 : 0;
+                        GNSSHIP_FSTAMP(e, 26);
+                        publish_seq(&sh.lock_seq, e + 1);
+                    }
+                } else {
+                    wait_seq(&sh.pre_seq, e + 1);
+                    const double coh = sh.coh;
+                    if (lane == 0) {
+                        GNSSHIP_FSTAMP(e, 8);
+                        locked = !(coh > 0.0 && !lock_status(k, sc, coh));
+                        sh.locked = locked ? 1 : 0;
+                        GNSSHIP_FSTAMP(e, 26);
+                        publish_seq(&sh.lock_seq, e + 1);
+                    }
                 }
+                lost = __builtin_amdgcn_readfirstlane(locked ? 0 : 1) != 0;  // lane 0 ran the test
             }
         }
     } else if (role == kRoleAccum) {
+        float shc[5];  // this wave's tap shifts (read_job)
+        int sh_nw = -1;
         for (int e = 0;; e++) {
             const int gbase = e * n_groups;  // the epoch's first product-group tag - 1
             wait_seq(&sh.job_seq, e + 1);
-            const FJob job = uniform_job(sh.job);
+            const FJob job = read_job(shc, sh_nw);
             if (!job.runnable) break;
             // ---- the epoch's taps in u_avx's order ----
             {
@@ -1404,10 +1503,11 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
             GNSSHIP_FSTAMP(e, 6);
         }
     } else {
+        float shc[5];  // this wave's tap shifts (read_job; the trace shows them)
+        int sh_nw = -1;
         for (int e = 0;; e++) {
-            const int gbase = e * n_groups;  // the epoch's first product-group tag - 1
             wait_seq(&sh.job_seq, e + 1);
-            const FJob job = uniform_job(sh.job);
+            const FJob job = read_job(shc, sh_nw);
             if (!job.runnable) break;
 #pragma unroll
             for (int a = 0; a < NA; a++) wait_seq(&sh.taps_seq[a], e + 1);  // the accumulator waves' taps of this epoch
@@ -1417,7 +1517,7 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
                 // there (state 0), so nothing of this epoch is kept — no lock test, no record — and
                 // the seed for the next one says "not runnable", which ends every wave's loop
                 cancel = false;
-                if (lane == 0) {
+                if (!job.steady && lane == 0) {  // (a steady epoch: the lock wave skips it by itself)
                     sh.coh = 0.0;
                     publish_seq(&sh.pre_seq, e + 1);
                 }
@@ -1433,80 +1533,213 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
                 r.flags = 8;
                 gnsship_trk_dump_record* dr = dump ? &sh.drec : nullptr;
                 const uint64_t es = rc.epoch_start;  // this epoch's first sample
-                const double coh = epoch_pre(kp, rc, taps, pdata, r, nullptr, dr);
-                GNSSHIP_FSTAMP(e, 17);
-                // hand the prompt to the lock detectors (producer 0; coh 0: no lock test this epoch)
-                if (lane == 0) {
-                    sc.p[0] = rc.p[0];
-                    sc.p[1] = rc.p[1];
-                    sc.pull_in = rc.pull_in;
-                    sh.coh = coh;
-                    publish_seq(&sh.pre_seq, e + 1);
-                }
-                GNSSHIP_FSTAMP(e, 18);
+                // The steady regime (the job's flag, set when the epoch was seeded): both discriminators
+                // come from the accumulator waves and the lock wave forms the prompt itself, so nothing
+                // epoch_pre writes is read before the next seed — it runs after make_seed(e + 1), and
+                // this wave publishes no prompt (no pre_seq, sc.p, sc.pull_in or sh.coh).
                 bool seeded = false;
-                if (coh > 0.0) {  // the loop runs speculatively beside the lock test
-                    // what the record shows if the test fails (the channel then stops: nothing else of the
+                // Two forms of the epoch's middle, chosen at compile time: where the steady regime exists
+                // (kSteadyForm) one copy of epoch_pre and the loop update in a two-pass loop; elsewhere the
+                // straight order (epoch_pre, hand-off, loop update, seed), which needs fewer registers.
+                if constexpr (kSteadyForm) {
+                    const bool steady = kSteadyForm && job.steady != 0;
+                    double coh = steady ? 1.0 : 0.0;  // (a steady epoch's own value comes from epoch_pre in pass 1)
+                    // what the record shows if the lock test fails (the channel then stops: nothing else of the
                     // loop's output is ever read)
-                    const double k_rcs = rc.rem_code_phase_samples, k_acc = rc.acc_carrier_phase_rad, k_dop = rc.carrier_doppler_hz;
-                    const double k_cf = rc.code_freq_chips, k_rcc = rc.rem_code_phase_chips;
-                    const float k_rem = rc.rem_carr_phase_rad;
-                    const int32_t k_len = rc.current_prn_length_samples;
-                    // state 4: the next epoch's carrier step to wave 1 once the carrier filter ran (the seed
-                    // repeats it; wave 1 checks they agree)
-                    auto early_step = [&](double dop) {
-                        if (rc.state == 4 && lane == 0) {
-                            sh.spec.step_d = div_fs(kp, kTwoPi * dop);  // update_tracking_vars' carrier_phase_step_rad
-                            sh.spec.rate = rc.carrier_phase_rate_step_rad;
-                            sh.spec.if_num = rc.if_num;
-                            sh.spec.rem_prev = rc.rem_carr_phase_rad;
-                            sh.spec.n_pred = rc.current_prn_length_samples;
-                            publish_seq(&sh.step_seq, e + 2);
+                    double k_rcs = 0.0, k_acc = 0.0, k_dop = 0.0, k_cf = 0.0, k_rcc = 0.0, k_ifc = 0.0;
+                    float k_rem = 0.0f;
+                    int32_t k_len = 0;
+                    uint64_t k_nir = 0;
+                    int64_t k_ifn = 0;
+                    // Two passes over one copy of the code (a second inlined copy of epoch_pre and the loop
+                    // costs the control wave registers it does not have): epoch_pre runs in pass 0 for a
+                    // hand-off epoch and in pass 1 — after the loop update and the seed — for a steady one;
+                    // the loop update and the seed run in pass 0.
+    #pragma unroll 1
+                    for (int pass = 0; pass < (kSteadyForm ? 2 : 1); pass++) {
+                        if ((pass == 1) == steady) {
+                            coh = epoch_pre(kp, rc, taps, pdata, r, nullptr, dr);
+                            GNSSHIP_FSTAMP(e, 17);
+                            // hand the prompt to the lock detectors (producer 0; coh 0: no lock test this epoch)
+                            if (!steady) {
+                                if (lane == 0) {
+                                    sc.p[0] = rc.p[0];
+                                    sc.p[1] = rc.p[1];
+                                    sc.pull_in = rc.pull_in;
+                                    sh.coh = coh;
+                                    publish_seq(&sh.pre_seq, e + 1);
+                                }
+                                GNSSHIP_FSTAMP(e, 18);
+                            }
                         }
-                        GNSSHIP_FSTAMP(e, 32);
-                    };
-                    // the accumulator waves' discriminators (state 4 with the run's spacing; epoch_pre
-                    // left E / P / L equal to 0 + the taps, as they formed them)
-                    PreDisc pd{0.0, 0.0, 0};
-                    if (pre_disc && r.state == 4 && __builtin_bit_cast(uint32_t, unif(rc.spc)) == __builtin_bit_cast(uint32_t, k.conf.early_late_space_chips)) {
-                        wait_seq(&sh.pll_seq, e + 1);
-                        wait_seq(&sh.dll_seq, e + 1);
-                        pd.pll = sh.pre_pll[e & 1];
-                        pd.dll = sh.pre_dll[e & 1];
-                        pd.ok = 3;
+                        if (pass == 0 && (steady || coh > 0.0)) {  // the loop runs speculatively beside the lock test
+                            k_rcs = rc.rem_code_phase_samples;
+                            k_acc = rc.acc_carrier_phase_rad;
+                            k_dop = rc.carrier_doppler_hz;
+                            k_cf = rc.code_freq_chips;
+                            k_rcc = rc.rem_code_phase_chips;
+                            k_rem = rc.rem_carr_phase_rad;
+                            k_len = rc.current_prn_length_samples;
+                            // the accumulator waves' discriminators (state 4 with the run's spacing; E / P / L
+                            // are 0 + the taps, as they formed them): the PLL's is awaited here, the DLL's after
+                            // the carrier filter, where run_dll_pll reads it
+                            PreDisc pd{0.0, 0.0, 0};
+                            if (steady || (pre_disc && r.state == 4 && __builtin_bit_cast(uint32_t, unif(rc.spc)) == __builtin_bit_cast(uint32_t, k.conf.early_late_space_chips))) {
+                                wait_seq(&sh.pll_seq, e + 1);
+                                pd.pll = sh.pre_pll[e & 1];
+                                pd.ok = 3;
+                                if constexpr (!kSteadyForm) {
+                                    wait_seq(&sh.dll_seq, e + 1);
+                                    pd.dll = sh.pre_dll[e & 1];
+                                }
+                            }
+                            // state 4: the next epoch's carrier step to wave 1 once the carrier filter ran (the seed
+                            // repeats it; wave 1 checks they agree)
+                            auto early_step = [&](double dop) {
+                                if (rc.state == 4 && lane == 0) {
+                                    sh.spec.step_d = div_fs(kp, kTwoPi * dop);  // update_tracking_vars' carrier_phase_step_rad
+                                    sh.spec.rate = rc.carrier_phase_rate_step_rad;
+                                    sh.spec.if_num = rc.if_num;
+                                    sh.spec.rem_prev = rc.rem_carr_phase_rad;
+                                    sh.spec.n_pred = rc.current_prn_length_samples;
+                                    publish_seq(&sh.step_seq, e + 2);
+                                }
+                                GNSSHIP_FSTAMP(e, 32);
+                                if (kSteadyForm && pd.ok) {
+                                    wait_seq(&sh.dll_seq, e + 1);
+                                    pd.dll = sh.pre_dll[e & 1];
+                                }
+                            };
+                            epoch_loop(kp, rc, nullptr, early_step, &pd);
+                            // State 4: epoch_post cannot change what the next epoch's correlation needs (the
+                            // channel stays runnable — 4, or 3 for extended integration — on the same taps), so
+                            // the next epoch is seeded now, before the lock test's outcome, and wave 1 derives
+                            // it while this epoch finishes.  A failed test (the channel stops) cancels it.
+                            k_nir = rc.nitems_read;
+                            k_ifn = rc.if_num;
+                            k_ifc = rc.if_cyc;
+                            if (rc.state == 4) {
+                                epoch_consume(kp, rc);
+                                make_seed(e + 1);
+                                GNSSHIP_FSTAMP(e, 33);
+                                rc.epoch_start = es;  // epoch_pre / epoch_post and the record still describe this epoch
+                                seeded = true;
+                            }
+                        }
                     }
-                    epoch_loop(kp, rc, nullptr, early_step, &pd);
-                    // State 4: epoch_post cannot change what the next epoch's correlation needs (the
-                    // channel stays runnable — 4, or 3 for extended integration — on the same taps), so
-                    // the next epoch is seeded now, before the lock test's outcome, and wave 1 derives
-                    // it while this epoch finishes.  A failed test (the channel stops) cancels it.
-                    const uint64_t k_nir = rc.nitems_read;
-                    const int64_t k_ifn = rc.if_num;
-                    const double k_ifc = rc.if_cyc;
-                    if (rc.state == 4) {
-                        epoch_consume(kp, rc);
-                        make_seed(e + 1);
-                        GNSSHIP_FSTAMP(e, 33);
-                        rc.epoch_start = es;  // epoch_post and the record still describe this epoch
-                        seeded = true;
+                    if (coh > 0.0) {
+                        wait_seq(&sh.lock_seq, e + 1);
+                        GNSSHIP_FSTAMP(e, 19);
+                        const bool locked = sh.locked != 0;
+                        if (!locked) {  // the reference runs the loop only on a passed lock test
+                            rc.rem_code_phase_samples = k_rcs;
+                            rc.acc_carrier_phase_rad = k_acc;
+                            rc.carrier_doppler_hz = k_dop;
+                            rc.code_freq_chips = k_cf;
+                            rc.rem_code_phase_chips = k_rcc;
+                            rc.rem_carr_phase_rad = k_rem;
+                            rc.current_prn_length_samples = k_len;
+                            rc.nitems_read = k_nir;
+                            rc.if_num = k_ifn;
+                            rc.if_cyc = k_ifc;
+                            cancel = seeded;
+                        }
+                        epoch_post(kp, rc, taps, pdata, r, locked, dr);
                     }
-                    wait_seq(&sh.lock_seq, e + 1);
-                    GNSSHIP_FSTAMP(e, 19);
-                    const bool locked = sh.locked != 0;
-                    if (!locked) {  // the reference runs the loop only on a passed lock test
-                        rc.rem_code_phase_samples = k_rcs;
-                        rc.acc_carrier_phase_rad = k_acc;
-                        rc.carrier_doppler_hz = k_dop;
-                        rc.code_freq_chips = k_cf;
-                        rc.rem_code_phase_chips = k_rcc;
-                        rc.rem_carr_phase_rad = k_rem;
-                        rc.current_prn_length_samples = k_len;
-                        rc.nitems_read = k_nir;
-                        rc.if_num = k_ifn;
-                        rc.if_cyc = k_ifc;
-                        cancel = seeded;
+                } else {
+                    const bool steady = kSteadyForm && job.steady != 0;
+                    double coh = 1.0;  // (a steady epoch has a lock test: epoch_pre would return code_period · extend)
+                    if (!steady) {
+                        coh = epoch_pre(kp, rc, taps, pdata, r, nullptr, dr);
+                        GNSSHIP_FSTAMP(e, 17);
+                        // hand the prompt to the lock detectors (producer 0; coh 0: no lock test this epoch)
+                        if (lane == 0) {
+                            sc.p[0] = rc.p[0];
+                            sc.p[1] = rc.p[1];
+                            sc.pull_in = rc.pull_in;
+                            sh.coh = coh;
+                            publish_seq(&sh.pre_seq, e + 1);
+                        }
+                        GNSSHIP_FSTAMP(e, 18);
                     }
-                    epoch_post(kp, rc, taps, pdata, r, locked, dr);
+                    if (coh > 0.0) {  // the loop runs speculatively beside the lock test
+                        // what the record shows if the test fails (the channel then stops: nothing else of the
+                        // loop's output is ever read)
+                        const double k_rcs = rc.rem_code_phase_samples, k_acc = rc.acc_carrier_phase_rad, k_dop = rc.carrier_doppler_hz;
+                        const double k_cf = rc.code_freq_chips, k_rcc = rc.rem_code_phase_chips;
+                        const float k_rem = rc.rem_carr_phase_rad;
+                        const int32_t k_len = rc.current_prn_length_samples;
+                        // the accumulator waves' discriminators (state 4 with the run's spacing; E / P / L are
+                        // 0 + the taps, as they formed them): the PLL's is awaited here, the DLL's after the
+                        // carrier filter, where run_dll_pll reads it
+                        PreDisc pd{0.0, 0.0, 0};
+                        if (steady || (pre_disc && r.state == 4 && __builtin_bit_cast(uint32_t, unif(rc.spc)) == __builtin_bit_cast(uint32_t, k.conf.early_late_space_chips))) {
+                            wait_seq(&sh.pll_seq, e + 1);
+                            pd.pll = sh.pre_pll[e & 1];
+                            pd.ok = 3;
+                            if constexpr (THRU) {
+                                wait_seq(&sh.dll_seq, e + 1);
+                                pd.dll = sh.pre_dll[e & 1];
+                            }
+                        }
+                        // state 4: the next epoch's carrier step to wave 1 once the carrier filter ran (the seed
+                        // repeats it; wave 1 checks they agree)
+                        auto early_step = [&](double dop) {
+                            if (rc.state == 4 && lane == 0) {
+                                sh.spec.step_d = div_fs(kp, kTwoPi * dop);  // update_tracking_vars' carrier_phase_step_rad
+                                sh.spec.rate = rc.carrier_phase_rate_step_rad;
+                                sh.spec.if_num = rc.if_num;
+                                sh.spec.rem_prev = rc.rem_carr_phase_rad;
+                                sh.spec.n_pred = rc.current_prn_length_samples;
+                                publish_seq(&sh.step_seq, e + 2);
+                            }
+                            GNSSHIP_FSTAMP(e, 32);
+                            if (!THRU && pd.ok) {
+                                wait_seq(&sh.dll_seq, e + 1);
+                                pd.dll = sh.pre_dll[e & 1];
+                            }
+                        };
+                        epoch_loop(kp, rc, nullptr, early_step, &pd);
+                        // State 4: epoch_post cannot change what the next epoch's correlation needs (the
+                        // channel stays runnable — 4, or 3 for extended integration — on the same taps), so
+                        // the next epoch is seeded now, before the lock test's outcome, and wave 1 derives
+                        // it while this epoch finishes.  A failed test (the channel stops) cancels it.
+                        const uint64_t k_nir = rc.nitems_read;
+                        const int64_t k_ifn = rc.if_num;
+                        const double k_ifc = rc.if_cyc;
+                        if (rc.state == 4) {
+                            epoch_consume(kp, rc);
+                            make_seed(e + 1);
+                            GNSSHIP_FSTAMP(e, 33);
+                            rc.epoch_start = es;  // epoch_post and the record still describe this epoch
+                            seeded = true;
+                        }
+                        if (steady) {
+                            // epoch_pre, off the seed's chain: in state 4 with the pull-in over it is the
+                            // record's first fields and save_correlation_results
+                            r.sample_counter = es;
+                            r.state = 4;
+                            save_correlation_results(kp, rc, taps, pdata);
+                            GNSSHIP_FSTAMP(e, 81);
+                        }
+                        wait_seq(&sh.lock_seq, e + 1);
+                        GNSSHIP_FSTAMP(e, 19);
+                        const bool locked = sh.locked != 0;
+                        if (!locked) {  // the reference runs the loop only on a passed lock test
+                            rc.rem_code_phase_samples = k_rcs;
+                            rc.acc_carrier_phase_rad = k_acc;
+                            rc.carrier_doppler_hz = k_dop;
+                            rc.code_freq_chips = k_cf;
+                            rc.rem_code_phase_chips = k_rcc;
+                            rc.rem_carr_phase_rad = k_rem;
+                            rc.current_prn_length_samples = k_len;
+                            rc.nitems_read = k_nir;
+                            rc.if_num = k_ifn;
+                            rc.if_cyc = k_ifc;
+                            cancel = seeded;
+                        }
+                        epoch_post(kp, rc, taps, pdata, r, locked, dr);
+                    }
                 }
                 GNSSHIP_FSTAMP(e, 24);
                 epoch_finish(kp, rc, r, !seeded);  // (a stopped channel consumes nothing either way)

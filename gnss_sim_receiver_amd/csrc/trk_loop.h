@@ -796,6 +796,40 @@ __device__ __forceinline__ int next_mod(int i, int n)
     return v < n ? v : (v == n ? 0 : v % n);
 }
 
+// save_correlation_results (:1262-1350): the epoch's taps into the accumulators (the secondary code's
+// sign stripped), the data prompt and the symbol counters — epoch_pre's part for states 3 and 4.
+template <class K, class C>
+__device__ __forceinline__ void save_correlation_results(const K& k, C& c, const float* taps, const float* pdata)
+{
+    const int eo = k.veml ? 2 : 0;
+    float sgn = 1.0f;
+    if (syncset(k, c).secondary) {
+        sgn = bit_at(syncset(k, c).secondary_bits, c.current_symbol) ? -1.0f : 1.0f;
+        c.current_symbol = next_mod(c.current_symbol, syncset(k, c).secondary_len);
+    }
+    if (k.veml) {
+        cadd(c.ve, taps, sgn);
+        cadd(c.vl, taps + 8, sgn);
+    }
+    cadd(c.e, taps + eo, sgn);
+    cadd(c.p, taps + eo + 2, sgn);
+    cadd(c.l, taps + eo + 4, sgn);
+    const float* src = k.track_pilot ? pdata : taps + eo + 2;
+    if (syncset(k, c).symbols_per_bit > 1) {
+        if (syncset(k, c).data_secondary_len > 0) {
+            cadd(c.p_data, src, bit_at(syncset(k, c).data_secondary_bits, c.current_data_symbol) ? -1.0f : 1.0f);
+            c.current_data_symbol = next_mod(c.current_data_symbol, syncset(k, c).data_secondary_len);
+        } else {
+            cadd(c.p_data, src, 1.0f);
+            c.current_data_symbol = next_mod(c.current_data_symbol, syncset(k, c).symbols_per_bit);
+        }
+    } else {
+        c.p_data[0] = src[0];
+        c.p_data[1] = src[1];
+    }
+    c.cloop = k.track_pilot ? 0 : 1;
+}
+
 template <class K, class C>
 __device__ GNSSHIP_LOOP_INLINE double epoch_pre(const K& k, C& c, const float* taps, const float* pdata, gnsship_trk_epoch& rec, TrkHist* h,
     gnsship_trk_dump_record* dump)
@@ -830,33 +864,7 @@ __device__ GNSSHIP_LOOP_INLINE double epoch_pre(const K& k, C& c, const float* t
         if (seconds_exceed(nir - c.acq_sample_stamp, k.conf.bit_synchronization_time_limit_s, fs_int)) mem(c).carrier_fail = 300000;
         return k.code_period;
     }
-    // save_correlation_results
-    float sgn = 1.0f;
-    if (syncset(k, c).secondary) {
-        sgn = bit_at(syncset(k, c).secondary_bits, c.current_symbol) ? -1.0f : 1.0f;
-        c.current_symbol = next_mod(c.current_symbol, syncset(k, c).secondary_len);
-    }
-    if (k.veml) {
-        cadd(c.ve, taps, sgn);
-        cadd(c.vl, taps + 8, sgn);
-    }
-    cadd(c.e, taps + eo, sgn);
-    cadd(c.p, taps + eo + 2, sgn);
-    cadd(c.l, taps + eo + 4, sgn);
-    const float* src = k.track_pilot ? pdata : taps + eo + 2;
-    if (syncset(k, c).symbols_per_bit > 1) {
-        if (syncset(k, c).data_secondary_len > 0) {
-            cadd(c.p_data, src, bit_at(syncset(k, c).data_secondary_bits, c.current_data_symbol) ? -1.0f : 1.0f);
-            c.current_data_symbol = next_mod(c.current_data_symbol, syncset(k, c).data_secondary_len);
-        } else {
-            cadd(c.p_data, src, 1.0f);
-            c.current_data_symbol = next_mod(c.current_data_symbol, syncset(k, c).symbols_per_bit);
-        }
-    } else {
-        c.p_data[0] = src[0];
-        c.p_data[1] = src[1];
-    }
-    c.cloop = k.track_pilot ? 0 : 1;
+    save_correlation_results(k, c, taps, pdata);
     if (st == 3) {  // coherent integration (:1933-1970): accumulate, NCO advance only
         update_tracking_vars(k, c, h);
         if (c.current_data_symbol == 0) {

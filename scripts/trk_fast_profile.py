@@ -5,8 +5,9 @@
 Stamps (wall_clock64, 100 MHz) per channel-epoch, lane 0 of the stamping wave: 0 derive start (wave 1),
 1 job published, 2 replay + tail done (wave 1), 3/4 producer waves 2/3 done, 5 accumulation done
 (wave 0), 6 taps combined and stored, 7 loop update + records done; 8 lock_status start (wave 2),
-9 run_dll_pll start, 10 its end, 11 update_tracking_vars end (wave 0).  The channels bit-synchronise
-first (state 4, as in bench.py)."""
+9 run_dll_pll start, 10 its end, 11 update_tracking_vars end (wave 0).  Stamps 8 and 26 go to the lock
+wave's own epoch.  A steady epoch (trk_fast.hip) runs epoch_pre after the seed and publishes no
+prompt: stamp 17 then follows stamp 33 (the "steady:" rows) and stamp 18 stays empty, so its rows drop out.  The channels bit-synchronise first (state 4, as in bench.py)."""
 import ctypes
 import os
 import sys
@@ -63,7 +64,7 @@ def main():
     rows = [("derive", 0, 1), ("derive -> replay done", 1, 2), ("derive -> producer 2 done", 1, 3), ("derive -> producer 3 done", 1, 4),
             ("derive -> accumulation done", 1, 5), ("replay done -> accumulation done", 2, 5), ("accumulation -> taps stored", 5, 6),
             ("taps stored -> loop done", 6, 7), ("  taps -> run_dll_pll", 6, 9), ("  run_dll_pll", 9, 10), ("  update_tracking_vars", 10, 11),
-            ("  tracking_vars -> loop done", 11, 7), ("loop done -> next derive", 7, SLOTS), ("  taps -> epoch_pre done", 16, 17),
+            ("  tracking_vars -> loop done", 11, 7), ("loop done -> next derive", 7, SLOTS), ("  taps -> epoch_pre done (steady epoch: it runs after the seed)", 16, 17),
             ("  epoch_pre -> published", 17, 18), ("  published -> run_dll_pll", 18, 9), ("  lock_status (wave 2)", 8, 26),
             ("  tracking_vars -> lock seen", 11, 19), ("  lock seen -> epoch_post done", 19, 24), ("  epoch_finish", 24, 25),
             ("  epoch_finish -> loop done (records)", 25, 7), ("seed (tracking_vars) -> next derive start", 11, SLOTS), ("  tracking_vars -> seed published", 11, 33), ("  seed published -> next derive start", 33, SLOTS), ("derive: sincos", 0, 35), ("derive: chains", 35, 36), ("derive: dz + publish", 36, 1), ("  run_dll_pll: PLL discriminator", 9, 37), ("  run_dll_pll: carrier filter", 37, 38), ("  run_dll_pll: DLL discriminator", 38, 39), ("  run_dll_pll: code loop filter", 39, 40), ("  run_dll_pll: code freq", 40, 10),
@@ -79,7 +80,13 @@ def main():
             ("tail: replay end -> producer 1 has its last slots", 34, 31), ("tail: replay end -> group 6 ready", 34, 54),
             ("tail: replay end -> group 7 ready", 34, 55), ("tail: replay end -> group 6 seen", 34, 62), ("tail: replay end -> group 7 seen", 34, 63),
             ("tail: group 7 seen -> accumulation done", 63, 5), ("tail: replay end -> last group seen", 34, 29),
-            ("tail: last group seen -> accumulation done", 29, 5), ("tail: accumulation done -> taps stored", 5, 6)]
+            ("tail: last group seen -> accumulation done", 29, 5), ("tail: accumulation done -> taps stored", 5, 6),
+            ("steady: seed published -> epoch_pre done", 33, 17), ("steady: epoch_pre done -> lock seen", 17, 19),
+            ("lock: taps stored -> lock_status start", 6, 8), ("lock: taps stored -> lock_status end", 6, 26),
+            ("lock: lock_status end -> seed published", 26, 33), ("lock: lock_status end -> next job published", 26, SLOTS + 1),
+            ("next epoch: job published -> group 0 ready (producer 0)", SLOTS + 1, SLOTS + 48),
+            ("next epoch: job published -> group 1 ready", SLOTS + 1, SLOTS + 49), ("next epoch: job published -> group 2 ready", SLOTS + 1, SLOTS + 50),
+            ("next epoch: job published -> group 3 ready", SLOTS + 1, SLOTS + 51)]
     for nm, a, b in rows:
         ok = (v[:, :, a] > 0) & (v[:, :, b] > 0)
         if not ok.any():
