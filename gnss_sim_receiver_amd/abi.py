@@ -76,6 +76,16 @@ class AcqResult(ctypes.Structure):
     ]
 
 
+COND_MAX_BANDS, COND_MAX_TAPS = 4, 4096
+
+
+class CondBand(ctypes.Structure):
+    """gnsship_cond_band — one band of the signal conditioner: the Freq_Xlating_Fir_Filter adapter's IF,
+    decimation_factor and taps (freq_xlating_fir_filter.cc:60-62,96-105)."""
+    _fields_ = [("if_hz", ctypes.c_double), ("decimation", ctypes.c_int), ("taps", ctypes.POINTER(ctypes.c_float)),
+                ("n_taps", ctypes.c_int)]
+
+
 SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5, SYS_BDS_B3I, SYS_GPS_L2C = 0, 1, 2, 3, 4, 5
 # gnsship_trk_last_engine (include/gnsship.h GNSSHIP_TRK_ENGINE_*)
 TRK_ENGINE_NONE, TRK_ENGINE_FAST_LATENCY, TRK_ENGINE_FAST_THROUGHPUT, TRK_ENGINE_PERSIST, TRK_ENGINE_ROUNDS, TRK_ENGINE_LANES = 0, 1, 2, 3, 4, 5
@@ -234,6 +244,12 @@ _SIGNATURES = {
     "gnsship_acq_resampler_run": ([_vp, _vp, _i, _i, ctypes.c_int64, _f32p, _vpp, ctypes.POINTER(ctypes.c_int64)], _i),
     "gnsship_acq_resampler_reset": ([_vp], _i),
     "gnsship_acq_resampler_destroy": ([_vp], _i),
+    "gnsship_cond_lowpass_taps": ([ctypes.c_double, _i, ctypes.c_double, ctypes.c_double, _f32p, _i, ctypes.POINTER(_i)], _i),
+    "gnsship_cond_create": ([_vp, ctypes.c_double, ctypes.POINTER(CondBand), _i, ctypes.c_int64, _vpp], _i),
+    "gnsship_cond_run": ([_vp, _vp, _i, _i, ctypes.c_int64, _vpp, ctypes.POINTER(_f32p), _vpp, ctypes.POINTER(ctypes.c_int64)], _i),
+    "gnsship_cond_reset": ([_vp, ctypes.c_uint64], _i),
+    "gnsship_cond_samples_in": ([_vp, ctypes.POINTER(ctypes.c_uint64)], _i),
+    "gnsship_cond_destroy": ([_vp], _i),
     "gnsship_trk_create": ([_vp, ctypes.POINTER(TrkConf), _i, _vpp], _i),
     "gnsship_trk_start": ([_vp, _i, ctypes.POINTER(TrkStartArgs)], _i),
     "gnsship_trk_start_many": ([_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(TrkStartArgs)], _i),

@@ -543,6 +543,84 @@ class AcqResampler:
             self.h = None
 
 
+def cond_lowpass_taps(lib, fs: float, decimation: int, bw: float = 0.0, tw: float = 0.0) -> np.ndarray:
+    """The Freq_Xlating_Fir_Filter adapter's filter_type=lowpass taps (freq_xlating_fir_filter.cc:99-106):
+    firdes::low_pass(1, fs, bw, tw), bw = 0 → (fs / decimation) / 2, tw = 0 → bw / 10."""
+    n = ctypes.c_int()
+    rc = lib.gnsship_cond_lowpass_taps(fs, decimation, bw, tw, None, 0, ctypes.byref(n))
+    if rc != abi.OK:
+        raise abi.GnssHipError(rc, "gnsship_cond_lowpass_taps: bad arguments")
+    taps = np.zeros(n.value, np.float32)
+    check(lib.gnsship_cond_lowpass_taps(fs, decimation, bw, tw, fptr(taps), len(taps), ctypes.byref(n)), "gnsship_cond_lowpass_taps")
+    return taps
+
+
+class SignalConditioner:
+    """The signal conditioner's frequency-translating FIR decimator (freq_xlating_fir_filter_ccf(decimation,
+    taps, IF, fs) per band) over one sample stream.  bands: [(if_hz, decimation, taps), ...], up to 4."""
+
+    def __init__(self, ctx: Context, fs_in: float, bands, max_in_samples: int):
+        self.ctx = ctx
+        self.fs_in = fs_in
+        self.bands = [(float(f), int(d), np.ascontiguousarray(t, np.float32)) for f, d, t in bands]
+        arr = (abi.CondBand * max(1, len(self.bands)))()
+        for i, (f, d, t) in enumerate(self.bands):
+            arr[i] = abi.CondBand(if_hz=f, decimation=d, taps=fptr(t), n_taps=len(t))
+        h = ctypes.c_void_p()
+        check(ctx.lib.gnsship_cond_create(ctx.h, fs_in, arr, len(self.bands), max_in_samples, ctypes.byref(h)), "gnsship_cond_create", ctx.h)
+        self.h = h
+
+    @property
+    def n_bands(self) -> int:
+        return len(self.bands)
+
+    def run(self, x, fmt: int = None, on_device: bool = False, n_in: int = None, dev_dst=None, host: bool = None):
+        """Filter a host array, or a device pointer with on_device=True, fmt and n_in.  dev_dst: per-band
+        device pointers (None entries = the handle's own buffers).  Returns the list of per-band complex64
+        arrays when host (the default for a host input), else [(device pointer, n_out), ...]."""
+        nb = self.n_bands
+        if on_device:
+            ptr = ctypes.c_void_p(x)
+        else:
+            x = np.ascontiguousarray(x)
+            fmt = sample_format(x) if fmt is None else fmt
+            n_in = x.nbytes // _FMT_BYTES[fmt] if n_in is None else n_in
+            ptr = ctypes.c_void_p(x.ctypes.data)
+        host = (not on_device) if host is None else host
+        dst = None
+        if dev_dst is not None:
+            dst = (ctypes.c_void_p * nb)(*[int(p) if p else None for p in dev_dst])
+        dev = (ctypes.c_void_p * nb)()
+        n_out = (ctypes.c_int64 * nb)()
+        outs, hp = None, None
+        if host:
+            outs = [np.zeros(max(0, n_in // d), np.complex64) for _, d, _ in self.bands]
+            hp = (abi._f32p * nb)(*[fptr(o.view(np.float32)) for o in outs])
+        check(self.ctx.lib.gnsship_cond_run(self.h, ptr, fmt, int(on_device), n_in, dst, hp, dev, n_out), "gnsship_cond_run", self.ctx.h)
+        self.last_dev = [(dev[b], n_out[b]) for b in range(nb)]
+        return outs if host else self.last_dev
+
+    def reset(self, first_sample: int = 0):
+        check(self.ctx.lib.gnsship_cond_reset(self.h, first_sample), "gnsship_cond_reset", self.ctx.h)
+
+    def samples_in(self) -> int:
+        n = ctypes.c_uint64()
+        check(self.ctx.lib.gnsship_cond_samples_in(self.h, ctypes.byref(n)), "gnsship_cond_samples_in", self.ctx.h)
+        return n.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.gnsship_cond_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.close()
+        except Exception:
+            pass
+
+
 class DllPllVemlTracking:
     """dll_pll_veml_tracking (dll_pll_veml_tracking.cc) for up to ``max_channels`` channels, the
     per-epoch loop resident on the device: ``start_tracking`` → :meth:`start`, ``general_work``

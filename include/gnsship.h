@@ -317,6 +317,59 @@ int gnsship_acq_resampler_reset(gnsship_acq_resampler* r);
 int gnsship_acq_resampler_destroy(gnsship_acq_resampler* r);
 
 /* ---------------------------------------------------------------------------------------------
+ * Signal conditioner: the frequency-translating FIR decimator the flowgraph puts in front of the
+ * channels (Signal_Conditioner, gnss_flowgraph.cc:1008-1140; its InputFilter in the
+ * Freq_Xlating_Fir_Filter form, src/algorithms/input_filter/adapters/freq_xlating_fir_filter.cc:36-117,
+ * e.g. conf/gnss-sdr_BDS_B3I_GPS_L1_CA_ibyte.conf:41-96).  gr::filter::freq_xlating_fir_filter_ccf(D,
+ * taps, fc, fs) restated from its published definition (GNU Radio is not in the reference tree):
+ *   y[k] = sum_{i<T} h[i] * x[kD - i] * exp(-j*2*pi*frac(fc*(n0 + kD - i)/fs)),
+ * zeros before the stream, n0 = the absolute index of the stream's first sample (0 after create), the
+ * fraction exact in integers.  Output k belongs to stream sample kD; the group delay (T - 1)/2 input
+ * samples is not compensated, as in the reference.  Fir_Filter is the same stage with if_hz = 0.
+ * One handle filters up to GNSSHIP_COND_MAX_BANDS bands of one input stream in one kernel launch per
+ * run; the history (max T - 1 samples) and the sample count live on the device, so the same stream cut
+ * into runs at any multiples of the decimations gives bit-identical outputs. */
+#define GNSSHIP_COND_MAX_BANDS 4
+#define GNSSHIP_COND_MAX_TAPS 4096
+#define GNSSHIP_COND_MAX_IN_SAMPLES (1LL << 30) /* per run: sizes the launch grid and the handle's output buffers */
+typedef struct gnsship_cond gnsship_cond;
+/* One band: the adapter's IF, decimation_factor and taps_ (freq_xlating_fir_filter.cc:60-62,96-105). */
+typedef struct gnsship_cond_band {
+    double if_hz;       /* IF: the band centre moved to 0 [Hz]; a whole number                     */
+    int decimation;     /* decimation_factor >= 1                                                  */
+    const float* taps;  /* taps_ (copied by create), 1..GNSSHIP_COND_MAX_TAPS of them              */
+    int n_taps;
+} gnsship_cond_band;
+/* The adapter's filter_type=lowpass design (freq_xlating_fir_filter.cc:99-106): firdes::low_pass(1, fs,
+ * bw, tw) with bw = 0 -> (fs / decimation) / 2 and tw = 0 -> bw / 10.  Host only; taps == NULL: only
+ * *n_taps.  E_INVAL for what firdes rejects. */
+int gnsship_cond_lowpass_taps(double fs, int decimation, double bw, double tw, float* taps, int taps_cap, int* n_taps);
+/* freq_xlating_fir_filter_ccf::make(decimation, taps, IF, sampling_frequency) (:115) for every band.
+ * fs_in (sampling_frequency, :61) a whole number of Hz below 2^31.  E_INVAL (gnsship_last_error says
+ * why) for a non-integer fs_in or if_hz, decimation < 1, n_bands outside 1..4, n_taps outside 1..4096,
+ * max_in_samples outside 1..GNSSHIP_COND_MAX_IN_SAMPLES or below a band's decimation. */
+int gnsship_cond_create(gnsship_ctx* ctx, double fs_in, const gnsship_cond_band* bands, int n_bands, int64_t max_in_samples,
+    gnsship_cond** out);
+/* The block's work() over n_in samples in `fmt` (converted in the loads, no scaling; the byte / short
+ * item types of :118-159 without their converter blocks): n_in / decimation CF32 outputs per band.
+ * n_in must be a multiple of every band's decimation and <= max_in_samples, else E_INVAL and no
+ * state changes.  Band b is written to dev_dst[b] (a caller's device buffer, e.g. a slot of a
+ * gnsship_dev_alloc ring) or, where dev_dst or dev_dst[b] is NULL, to the handle's own buffer (valid
+ * until the next run); dev_out[b] / n_out[b] (arrays of n_bands, may be NULL) report where and how
+ * many.  host_out (may be NULL) / host_out[b] (may be NULL): also copied to the host before returning;
+ * asynchronous on the context stream otherwise. */
+int gnsship_cond_run(gnsship_cond* c, const void* in, int fmt, int in_on_device, int64_t n_in, void* const* dev_dst,
+    float* const* host_out, void** dev_out, int64_t* n_out);
+/* Restart the stream (a receiver starting mid-file, as the flowgraph's conditioner starts with the
+ * source, gnss_flowgraph.cc:1127-1136): zero history, the next input sample has absolute index
+ * first_sample (the phase origin stays at sample 0). */
+int gnsship_cond_reset(gnsship_cond* c, uint64_t first_sample);
+/* Absolute index of the next input sample (first_sample + everything run since; nitems_read of the
+ * block's input). */
+int gnsship_cond_samples_in(gnsship_cond* c, uint64_t* n);
+int gnsship_cond_destroy(gnsship_cond* c);
+
+/* ---------------------------------------------------------------------------------------------
  * Closed-loop tracking engine: the per-epoch DLL/PLL of dll_pll_veml_tracking
  * resident on the device.  Replaces, for N channels at once, the general_work loop of
  * src/algorithms/tracking/gnuradio_blocks/dll_pll_veml_tracking.cc:1728-2094 around

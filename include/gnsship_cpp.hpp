@@ -245,6 +245,112 @@ private:
     std::vector<float> taps_;
 };
 
+// The Freq_Xlating_Fir_Filter adapter's configuration (src/algorithms/input_filter/adapters/
+// freq_xlating_fir_filter.cc:36-106), property names and defaults as there.  filter_type "lowpass"
+// designs firdes::low_pass(1, sampling_frequency, bw, tw) (:99-106; bw = 0 -> (fs / decimation_factor) / 2,
+// tw = 0 -> bw / 10); the adapter's other filter types use GNU Radio's pm_remez, which is not restated:
+// give their taps explicitly in `taps` (then filter_type is not read).
+struct Freq_Xlating_Fir_Filter_Conf {
+    double IF{0.0};                          // :41,60
+    double sampling_frequency{4000000.0};    // :42,61
+    int decimation_factor{1};                // :50,62
+    std::string filter_type{"lowpass"};      // the adapter's default "bandpass" needs pm_remez: pass taps
+    double bw{0.0};                          // :101-102
+    double tw{0.0};                          // :103-104
+    std::vector<float> taps;                 // explicit taps_ (:97,105), empty = design by filter_type
+};
+
+// Mirror of Freq_Xlating_Fir_Filter (freq_xlating_fir_filter.cc; the block of :115,
+// gr::filter::freq_xlating_fir_filter_ccf::make(decimation_factor, taps, IF, sampling_frequency)) for up to
+// GNSSHIP_COND_MAX_BANDS bands of one input stream — one adapter per band in the reference
+// (conf/gnss-sdr_BDS_B3I_GPS_L1_CA_ibyte.conf:41-96), one kernel launch for all of them here.  The output
+// stays on the device (dev_out()), where gnsship_acq_run and gnsship_trk_run* consume it in place.
+class Freq_Xlating_Fir_Filter_Hip {
+public:
+    Freq_Xlating_Fir_Filter_Hip(const std::vector<Freq_Xlating_Fir_Filter_Conf>& bands, int64_t max_in_samples, int device = 0)
+        : dev_(Device::get(device)), conf_(bands)
+    {
+        if (bands.empty() || bands.size() > GNSSHIP_COND_MAX_BANDS) throw std::invalid_argument("Freq_Xlating_Fir_Filter_Hip: 1..4 bands");
+        std::vector<gnsship_cond_band> cb(bands.size());
+        for (size_t b = 0; b < bands.size(); b++) {
+            Freq_Xlating_Fir_Filter_Conf& c = conf_[b];
+            if (c.sampling_frequency != conf_[0].sampling_frequency)
+                throw std::invalid_argument("Freq_Xlating_Fir_Filter_Hip: the bands share one input stream (sampling_frequency)");
+            if (c.taps.empty()) {
+                if (c.filter_type != "lowpass")
+                    throw std::invalid_argument("Freq_Xlating_Fir_Filter_Hip: filter_type " + c.filter_type + " needs explicit taps (pm_remez is not restated)");
+                int n = 0;
+                if (gnsship_cond_lowpass_taps(c.sampling_frequency, c.decimation_factor, c.bw, c.tw, nullptr, 0, &n) != GNSSHIP_OK)
+                    throw std::invalid_argument("gnsship_cond_lowpass_taps");
+                c.taps.resize(static_cast<size_t>(n));
+                if (gnsship_cond_lowpass_taps(c.sampling_frequency, c.decimation_factor, c.bw, c.tw, c.taps.data(), n, &n) != GNSSHIP_OK)
+                    throw std::invalid_argument("gnsship_cond_lowpass_taps");
+            }
+            cb[b] = gnsship_cond_band{c.IF, c.decimation_factor, c.taps.data(), static_cast<int>(c.taps.size())};
+        }
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        if (gnsship_cond_create(dev_->ctx(), conf_[0].sampling_frequency, cb.data(), static_cast<int>(cb.size()), max_in_samples, &h_) != GNSSHIP_OK)
+            throw std::invalid_argument(std::string("gnsship_cond_create: ") + gnsship_last_error(dev_->ctx()));
+        dev_out_.assign(cb.size(), nullptr);
+        n_out_.assign(cb.size(), 0);
+    }
+    Freq_Xlating_Fir_Filter_Hip(const Freq_Xlating_Fir_Filter_Conf& band, int64_t max_in_samples, int device = 0)
+        : Freq_Xlating_Fir_Filter_Hip(std::vector<Freq_Xlating_Fir_Filter_Conf>{band}, max_in_samples, device)
+    {
+    }
+    ~Freq_Xlating_Fir_Filter_Hip()
+    {
+        if (h_) gnsship_cond_destroy(h_);
+    }
+    Freq_Xlating_Fir_Filter_Hip(const Freq_Xlating_Fir_Filter_Hip&) = delete;
+    Freq_Xlating_Fir_Filter_Hip& operator=(const Freq_Xlating_Fir_Filter_Hip&) = delete;
+
+    int n_bands() const { return static_cast<int>(conf_.size()); }
+    const std::vector<float>& taps(int band = 0) const { return conf_[static_cast<size_t>(band)].taps; }
+    int decimation(int band = 0) const { return conf_[static_cast<size_t>(band)].decimation_factor; }
+    double output_rate(int band = 0) const { return conf_[static_cast<size_t>(band)].sampling_frequency / decimation(band); }
+    // n_in samples in `fmt` (a multiple of every band's decimation_factor), host or device memory.  dev_dst: per-band
+    // device destinations (nullptr / nullptr entries = the handle's own buffers, valid until the next work());
+    // host_out: per-band host copies (nullptr = none; without one the call is asynchronous on the context stream).
+    bool work(const void* in, int fmt, bool in_on_device, int64_t n_in, void* const* dev_dst = nullptr, std::complex<float>* const* host_out = nullptr)
+    {
+        std::vector<float*> ho(conf_.size(), nullptr);
+        if (host_out)
+            for (size_t b = 0; b < conf_.size(); b++) ho[b] = reinterpret_cast<float*>(host_out[b]);
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_cond_run(h_, in, fmt, in_on_device ? 1 : 0, n_in, dev_dst, host_out ? ho.data() : nullptr, dev_out_.data(), n_out_.data()) ==
+               GNSSHIP_OK;
+    }
+    // one band, gr_complex in and out on the host: the adapter's gr_complex -> gr_complex item types (:111-116)
+    bool work(const std::complex<float>* in, int64_t n_in, std::complex<float>* out)
+    {
+        if (conf_.size() != 1) return false;
+        std::complex<float>* ho[1] = {out};
+        return work(in, GNSSHIP_FMT_CF32, false, n_in, nullptr, ho);
+    }
+    void* dev_out(int band = 0) const { return dev_out_[static_cast<size_t>(band)]; }
+    int64_t n_out(int band = 0) const { return n_out_[static_cast<size_t>(band)]; }
+    bool reset(uint64_t first_sample = 0)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_cond_reset(h_, first_sample) == GNSSHIP_OK;
+    }
+    uint64_t samples_in() const
+    {
+        uint64_t n = 0;
+        gnsship_cond_samples_in(h_, &n);
+        return n;
+    }
+    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
+
+private:
+    std::shared_ptr<Device> dev_;
+    std::vector<Freq_Xlating_Fir_Filter_Conf> conf_;
+    gnsship_cond* h_ = nullptr;
+    std::vector<void*> dev_out_;
+    std::vector<int64_t> n_out_;
+};
+
 // What acquisition_core writes into Gnss_Synchro (gnss_synchro.h:52-55; pcps_acquisition.cc:683-696).
 struct Acq_Outcome {
     double Acq_delay_samples{0.0};

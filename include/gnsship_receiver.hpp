@@ -112,6 +112,12 @@ struct Receiver_Conf {
     int acq_piece{8192};                 // samples per acquisition general_work call
     std::string dump_filename;           // Tracking_1C.dump_filename ("" = dump off)
     int device{0};
+    // Optional Signal_Conditioner ahead of the channels (gnss_flowgraph.cc:1008-1140) with InputFilter.implementation =
+    // Freq_Xlating_Fir_Filter (conf/gnss-sdr_BDS_B3I_GPS_L1_CA_ibyte.conf:41-96): the source's samples enter through
+    // work_raw() at input_filter.sampling_frequency, the channels run on the conditioned stream, so acq.fs_in and
+    // trk.fs_in are sampling_frequency / decimation_factor and the channels' own IF is 0.  Off: exactly the receiver above.
+    bool use_conditioner{false};
+    Freq_Xlating_Fir_Filter_Conf input_filter;   // InputFilter.*
 };
 
 // One control event, in stream order.
@@ -151,6 +157,13 @@ public:
         block_ = conf_.block_samples > 0 ? conf_.block_samples : static_cast<int64_t>(conf_.trk.fs_in / 10.0);
         tail_ = 2 * vl_;
         trk_ = std::make_unique<Dll_Pll_Veml_Tracking_Hip>(conf_.trk, n_, conf_.device);
+        if (conf_.use_conditioner) {
+            const double fs_out = conf_.input_filter.sampling_frequency / std::max(1, conf_.input_filter.decimation_factor);
+            if (fs_out != conf_.trk.fs_in || static_cast<int64_t>(fs_out) != conf_.acq.fs_in)
+                throw std::invalid_argument("Gnss_Receiver_Hip: the channels run at InputFilter.sampling_frequency / decimation_factor");
+            cond_block_ = block_ * conf_.input_filter.decimation_factor;
+            cond_ = std::make_unique<Freq_Xlating_Fir_Filter_Hip>(conf_.input_filter, cond_block_, conf_.device);
+        }
         for (uint32_t p = 1; p <= (b3_ ? 63U : 32U); p++) available_.push_back(p);  // set_signals_list (GPS: 1-32, BeiDou: 1-63)
         prn_.assign(static_cast<size_t>(n_), 0U);
         apos_.assign(static_cast<size_t>(n_), 0U);
@@ -184,6 +197,29 @@ public:
         }
         return true;
     }
+
+    // With the conditioner on: feed the next n_in samples of the source in `fmt` (GNSSHIP_FMT_*; a multiple of the
+    // decimation).  The stage runs on the device in pieces of one processing block; the conditioned block comes back
+    // to the host, where the acquisition blocks buffer their dwells as the reference's do, and goes on to work().
+    bool work_raw(const void* raw, int fmt, int64_t n_in)
+    {
+        if (!cond_) return false;
+        const int d = cond_->decimation();
+        const int64_t bytes = fmt == GNSSHIP_FMT_CF32 ? 8 : fmt == GNSSHIP_FMT_CI16 ? 4 : 2;
+        if (n_in % d != 0) return false;
+        const char* p = static_cast<const char*>(raw);
+        while (n_in > 0) {
+            const int64_t m = std::min(n_in, cond_block_);
+            cond_host_.resize(static_cast<size_t>(m / d));
+            std::complex<float>* ho[1] = {cond_host_.data()};
+            if (!cond_->work(p, fmt, false, m, nullptr, ho)) return false;
+            if (!work(cond_host_.data(), m / d)) return false;
+            p += m * bytes;
+            n_in -= m;
+        }
+        return true;
+    }
+    const Freq_Xlating_Fir_Filter_Hip* conditioner() const { return cond_.get(); }
 
     const std::vector<Receiver_Event>& events() const { return events_; }
     // Every tracking epoch record in stream order per channel (the Gnss_Synchro stream).
@@ -453,6 +489,9 @@ private:
     int n_ = 1, max_acq_ = 1, acq_count_ = 0;
     int64_t vl_ = 0, block_ = 0, tail_ = 0;
     std::unique_ptr<Dll_Pll_Veml_Tracking_Hip> trk_;
+    std::unique_ptr<Freq_Xlating_Fir_Filter_Hip> cond_;  // the optional conditioner stage
+    int64_t cond_block_ = 0;                             // its run size, in input samples
+    std::vector<std::complex<float>> cond_host_;
     std::vector<std::unique_ptr<Pcps_Acquisition_Hip>> acq_;
     std::vector<ChannelFsm> fsm_;
     std::vector<uint32_t> prn_;

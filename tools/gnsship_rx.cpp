@@ -11,13 +11,22 @@
 //              [--pll-bw 40] [--dll-bw 4] [--order 3] [--pull-in-time-s 10] [--rotator auto|generic|avx]
 //              [--max-carrier-lock-fail 5000] [--max-code-lock-fail 50] [--cn0-min 25]
 //              [--block-ms 100] [--acq-piece 8192] [--dump PREFIX] [--events CSV] [--records BIN]
+//              [--if-hz 0] [--decimation 1] [--filter-bw 0] [--filter-tw 0]
+//
+// --if-hz / --decimation (either one) put the signal conditioner ahead of the channels (InputFilter.implementation =
+// Freq_Xlating_Fir_Filter, filter_type lowpass: IF, decimation_factor, bw, tw; 0 = the adapter's defaults): the file is
+// read at --fs and goes to the device as it is, acquisition and tracking run on the conditioned stream at fs / decimation.
+// The receiver core brings every conditioned block back to the host (its acquisition blocks buffer their dwells there)
+// and uploads the tracking window again: one device-to-host and one host-to-device copy of the conditioned block per block.
 //
 // ishort / ibyte samples are converted to gr_complex without scaling (Ishort_To_Complex /
 // Ibyte_To_Complex, item_type_helpers.cc:27-73).  stdout: one JSON summary line.
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -37,6 +46,9 @@ int main(int argc, char** argv)
 {
     std::string file, item = "gr_complex", dump, events_csv, records_bin, rotator = "auto", signal = "1C";
     double fs = 4e6, seconds = 0.0, block_ms = 100.0;
+    double if_hz = 0.0, filter_bw = 0.0, filter_tw = 0.0;
+    int decimation = 1;
+    bool conditioner = false;
     gnsship::Receiver_Conf rc;
     rc.channels = 5;
     rc.in_acquisition = 1;
@@ -80,6 +92,14 @@ int main(int argc, char** argv)
         else if (a == "--rotator") rotator = val();
         else if (a == "--block-ms") block_ms = std::atof(val().c_str());
         else if (a == "--acq-piece") rc.acq_piece = std::atoi(val().c_str());
+        else if (a == "--if-hz") {
+            if_hz = std::atof(val().c_str());
+            conditioner = true;
+        } else if (a == "--decimation") {
+            decimation = std::atoi(val().c_str());
+            conditioner = true;
+        } else if (a == "--filter-bw") filter_bw = std::atof(val().c_str());
+        else if (a == "--filter-tw") filter_tw = std::atof(val().c_str());
         else if (a == "--dump") dump = val();
         else if (a == "--events") events_csv = val();
         else if (a == "--records") records_bin = val();
@@ -91,6 +111,23 @@ int main(int argc, char** argv)
     if (signal != "1C" && signal != "L5" && signal != "2S" && signal != "B3") usage("--signal must be 1C, L5, 2S or B3");
     std::snprintf(rc.trk.signal, sizeof(rc.trk.signal), "%s", signal.c_str());
     if (signal == "B3") rc.trk.system = 'C';  // otherwise 'G'
+    const double fs_file = fs;  // the rate the file is read at; fs from here on is the channels' rate
+    if (conditioner) {
+        if (decimation < 1 || std::fmod(fs, static_cast<double>(decimation)) != 0.0) usage("--decimation must divide --fs");
+        if (fs != std::floor(fs) || if_hz != std::floor(if_hz)) usage("--fs and --if-hz must be whole numbers of Hz with the conditioner on");
+        int n_taps = 0;  // the adapter's low-pass design, checked before the device is touched
+        if (filter_bw < 0.0 || filter_tw < 0.0 || gnsship_cond_lowpass_taps(fs, decimation, filter_bw, filter_tw, nullptr, 0, &n_taps) != GNSSHIP_OK)
+            usage("--filter-bw must lie in (0, fs/2] and --filter-tw be positive (0 = the adapter's defaults)");
+        if (n_taps > GNSSHIP_COND_MAX_TAPS) usage("--filter-tw gives more than 4096 taps");
+        rc.use_conditioner = true;
+        rc.input_filter.IF = if_hz;
+        rc.input_filter.sampling_frequency = fs_file;
+        rc.input_filter.decimation_factor = decimation;
+        rc.input_filter.filter_type = "lowpass";
+        rc.input_filter.bw = filter_bw;
+        rc.input_filter.tw = filter_tw;
+        fs = fs_file / decimation;
+    }
     rc.acq.fs_in = static_cast<int64_t>(fs);
     rc.trk.fs_in = fs;
     // gps_l1_ca_dll_pll_tracking.cc:47, gps_l5_dll_pll_tracking.cc:47, beidou_b3i_dll_pll_tracking.cc:47; gps_l2_m_dll_pll_tracking.cc:47
@@ -108,9 +145,19 @@ int main(int argc, char** argv)
         for (int c = 0; c < rc.channels; c++) std::remove((dump + std::to_string(c) + ".dat").c_str());
 
     const auto t_init = std::chrono::steady_clock::now();
-    gnsship::Gnss_Receiver_Hip rx(rc);
-    const int64_t block = rc.block_samples > 0 ? rc.block_samples : static_cast<int64_t>(fs / 10);
-    const int64_t limit = seconds > 0 ? static_cast<int64_t>(seconds * fs) : INT64_MAX;
+    std::unique_ptr<gnsship::Gnss_Receiver_Hip> rxp;
+    try {
+        rxp = std::make_unique<gnsship::Gnss_Receiver_Hip>(rc);
+    } catch (const std::invalid_argument& e) {  // a configuration the engines refuse
+        usage(e.what());
+    } catch (const std::exception& e) {
+        std::fprintf(stderr, "gnsship_rx: %s\n", e.what());
+        return 1;
+    }
+    gnsship::Gnss_Receiver_Hip& rx = *rxp;
+    const int64_t block = (rc.block_samples > 0 ? rc.block_samples : static_cast<int64_t>(fs / 10)) * decimation;  // file samples
+    const int64_t limit = seconds > 0 ? static_cast<int64_t>(seconds * fs_file) : INT64_MAX;
+    const int fmt = item == "gr_complex" ? GNSSHIP_FMT_CF32 : item == "ishort" ? GNSSHIP_FMT_CI16 : GNSSHIP_FMT_CI8;
     std::vector<char> raw(static_cast<size_t>(block) * sample_bytes);
     std::vector<std::complex<float>> x(static_cast<size_t>(block));
     int64_t total = 0;
@@ -119,8 +166,18 @@ int main(int argc, char** argv)
     while (total < limit) {
         const auto r0 = std::chrono::steady_clock::now();
         const int64_t want = std::min<int64_t>(block, limit - total);
-        const size_t got = std::fread(raw.data(), static_cast<size_t>(sample_bytes), static_cast<size_t>(want), f);
+        size_t got = std::fread(raw.data(), static_cast<size_t>(sample_bytes), static_cast<size_t>(want), f);
+        if (conditioner) got -= got % static_cast<size_t>(decimation);  // a whole number of conditioned samples
         if (got == 0) break;
+        if (conditioner) {
+            io_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - r0).count();
+            if (!rx.work_raw(raw.data(), fmt, static_cast<int64_t>(got))) {
+                std::fprintf(stderr, "gnsship_rx: conditioner / engine error\n");
+                return 1;
+            }
+            total += static_cast<int64_t>(got);
+            continue;
+        }
         if (item == "gr_complex") {
             std::memcpy(x.data(), raw.data(), got * 8);
         } else if (item == "ishort") {
@@ -172,7 +229,7 @@ int main(int argc, char** argv)
     }
     std::printf("{\"samples\": %lld, \"signal_s\": %.6f, \"wall_s\": %.6f, \"init_s\": %.6f, \"io_s\": %.6f, \"realtime_factor\": %.3f, "
                 "\"acq_positive\": %d, \"acq_negative\": %d, \"losses\": %d, \"channels\": [",
-        static_cast<long long>(total), static_cast<double>(total) / fs, wall, init_s, io_s, (static_cast<double>(total) / fs) / wall, n_pos, n_neg,
+        static_cast<long long>(total), static_cast<double>(total) / fs_file, wall, init_s, io_s, (static_cast<double>(total) / fs_file) / wall, n_pos, n_neg,
         n_lost);
     for (int c = 0; c < rc.channels; c++) {
         const size_t nr = c < static_cast<int>(rx.records().size()) ? rx.records()[static_cast<size_t>(c)].size() : 0;
