@@ -19,6 +19,57 @@ HEADER_PATH = os.path.join(REPO_DIR, "include", "gnsship.h")
 
 OK, E_INVAL, E_NOMEM, E_DEVICE, E_STATE, E_RCCL = 0, -1, -2, -3, -4, -5
 FMT_CF32, FMT_CI16, FMT_CI8 = 0, 1, 2
+# read by the signal conditioner only: real-sampled IF (the Freq_Xlating_Fir_Filter adapter's float / short / byte)
+FMT_RF32, FMT_RI16, FMT_RI8 = 3, 4, 5
+# bit-packed items (GNSSHIP_FMT_PACKED): components, field order in a byte, value map
+PACKED_REAL, PACKED_IQ, PACKED_QI = 0, 1, 2
+PACKED_LSB_FIRST, PACKED_MSB_FIRST = 0, 1
+PACKED_MAP_2S1, PACKED_MAP_S = 0, 1
+
+
+def fmt_packed(bits: int, components: int, order: int, value_map: int) -> int:
+    """GNSSHIP_FMT_PACKED(bits, components, order, map): `bits`-wide two's-complement fields s, 8/bits per byte,
+    field j at bit offset bits·j (LSB first) or 8 − bits·(j + 1) (MSB first), value 2s + 1 or s; REAL: one field
+    per sample, IQ / QI: fields 2m, 2m + 1 are (re, im) / (im, re)."""
+    if bits not in (2, 4) or components not in (0, 1, 2) or order not in (0, 1) or value_map not in (0, 1):
+        raise ValueError(f"fmt_packed({bits}, {components}, {order}, {value_map})")
+    return 0x100 | (bits << 4) | (components << 2) | (order << 1) | value_map
+
+
+def fmt_is_packed(fmt: int) -> bool:
+    return (fmt & ~0xFF) == 0x100
+
+
+def fmt_packed_fields(fmt: int):
+    """(bits, components, order, map) of a packed format value."""
+    return (fmt >> 4) & 0xF, (fmt >> 2) & 0x3, (fmt >> 1) & 0x1, fmt & 0x1
+
+
+_COMPONENTS = {"real": PACKED_REAL, "iq": PACKED_IQ, "qi": PACKED_QI}
+
+
+def fmt_two_bit_packed(sample_type: str = "real", big_endian_bytes: bool = False) -> int:
+    """Two_Bit_Packed_File_Signal_Source with byte items (sample_type, big_endian_bytes; the adapter's defaults)."""
+    return fmt_packed(2, _COMPONENTS[sample_type], PACKED_MSB_FIRST if big_endian_bytes else PACKED_LSB_FIRST, PACKED_MAP_2S1)
+
+
+def fmt_four_bit_cpx(sample_type: str = "iq") -> int:
+    """Four_Bit_Cpx_File_Signal_Source (sample_type iq / qi)."""
+    if sample_type not in ("iq", "qi"):
+        raise ValueError(f"Four_Bit_Cpx sample_type {sample_type!r}")
+    return fmt_packed(4, _COMPONENTS[sample_type], PACKED_LSB_FIRST, PACKED_MAP_2S1)
+
+
+FMT_NSR = fmt_packed(2, PACKED_REAL, PACKED_LSB_FIRST, PACKED_MAP_S)          # Nsr_File_Signal_Source
+FMT_TWO_BIT_CPX = fmt_packed(2, PACKED_IQ, PACKED_MSB_FIRST, PACKED_MAP_2S1)  # Two_Bit_Cpx_File_Signal_Source
+# every named preset (tests and mirrors use these)
+PACKED_PRESETS = {
+    **{f"two_bit_packed_{t}_{'msb' if be else 'lsb'}": fmt_two_bit_packed(t, be) for t in ("real", "iq", "qi") for be in (False, True)},
+    "nsr": FMT_NSR,
+    "two_bit_cpx": FMT_TWO_BIT_CPX,
+    "four_bit_cpx_iq": fmt_four_bit_cpx("iq"),
+    "four_bit_cpx_qi": fmt_four_bit_cpx("qi"),
+}
 STAGE_ANCHORS, STAGE_CORRELATE = 1, 2
 MAX_TAPS = 8
 _ERRNAMES = {E_INVAL: "E_INVAL", E_NOMEM: "E_NOMEM", E_DEVICE: "E_DEVICE", E_STATE: "E_STATE", E_RCCL: "E_RCCL"}
@@ -245,6 +296,7 @@ _SIGNATURES = {
     "gnsship_acq_resampler_reset": ([_vp], _i),
     "gnsship_acq_resampler_destroy": ([_vp], _i),
     "gnsship_cond_lowpass_taps": ([ctypes.c_double, _i, ctypes.c_double, ctypes.c_double, _f32p, _i, ctypes.POINTER(_i)], _i),
+    "gnsship_cond_fmt_bits": ([_i], _i),
     "gnsship_cond_create": ([_vp, ctypes.c_double, ctypes.POINTER(CondBand), _i, ctypes.c_int64, _vpp], _i),
     "gnsship_cond_run": ([_vp, _vp, _i, _i, ctypes.c_int64, _vpp, ctypes.POINTER(_f32p), _vpp, ctypes.POINTER(ctypes.c_int64)], _i),
     "gnsship_cond_reset": ([_vp, ctypes.c_uint64], _i),

@@ -26,10 +26,18 @@
 // The launch also writes the next call's history (the last max T − 1 raw samples of history ‖ input) and
 // sample count into the other half of a double buffer.  Nothing returns to the host.
 // LDS: 8·(L + max T − 1) B = 16 KiB (max T ≤ 1025, L = 2049 − max T) or 64 KiB (L = 8193 − max T).
-// HBM: s B in + Σ_b 8/D_b B out per input sample (s = 8, 4 or 2), plus the tile overlap re-read from L2.
+// HBM: s B in + Σ_b 8/D_b B out per input sample (s = 8, 4 or 2; real items 4, 2 or 1; bit-packed items
+// 0.25 to 1), plus the tile overlap re-read from L2.
+//
+// Input items beside the three complex ones: real-sampled IF (the adapter's float / short / byte item
+// types, freq_xlating_fir_filter.cc:118-159: freq_xlating_fir_filter_fcf / _scf) and 2- or 4-bit fields
+// packed into bytes (GNSSHIP_FMT_PACKED: the reference's Two_Bit_Packed, Nsr, Two_Bit_Cpx and
+// Four_Bit_Cpx file sources).  Both are conversions in the span's load; a real span is held as one float
+// per sample and mixed with two multiplies, which equals the complex mix of (x, 0) up to signs of zero.
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "engine.h"
@@ -64,6 +72,14 @@ struct CondBandDev {
     uint32_t step_mod;   // (fc_mod · kCondThreads) mod fs
 };
 
+// A packed format for the loads.  shifts: the bit offset of the field of each sample slot of a byte, 8 bits
+// per slot — real: slots 0..3; complex: re of slots 0, 1 in bits 0-15 and im in bits 16-31.
+// info: field width | log2(samples per byte) << 8 | (1: value 2s + 1, 0: value s) << 16.
+struct CondPack {
+    uint32_t shifts;
+    uint32_t info;
+};
+
 struct CondArgs {
     CondBandDev band[kCondMaxBands];
     int32_t n_bands;
@@ -75,19 +91,53 @@ struct CondArgs {
     float2* hist_new;
     const int64_t* count_old;  // absolute index of this call's first sample
     int64_t* count_new;
+    CondPack pack;       // packed formats only (last: the other formats' argument layout is unchanged)
 };
 
+// Load shapes of the packed formats (kernel template values beside GNSSHIP_FMT_*; not ABI values): the
+// field width, order and value map are wave-uniform scalars (CondPack), so one instantiation serves every
+// real and one every complex packing.
+constexpr int kCondPackedReal = 6, kCondPackedCplx = 7;
+
 template <int FMT>
-__device__ __forceinline__ float2 cond_load(const void* in, int64_t i)
+constexpr bool cond_is_real() { return FMT == GNSSHIP_FMT_RF32 || FMT == GNSSHIP_FMT_RI16 || FMT == GNSSHIP_FMT_RI8 || FMT == kCondPackedReal; }
+
+// Field j of a byte: the two's-complement integer s of `bits` bits at bit offset `shift`; the sample value
+// is 2s + 1 (m = 1) or s (m = 0).
+__device__ __forceinline__ float cond_field(uint32_t byte, uint32_t shift, uint32_t bits, int m)
+{
+    const int32_t s = static_cast<int32_t>(byte << (32u - bits - shift)) >> (32u - bits);
+    return static_cast<float>(s * (m + 1) + m);
+}
+
+// Sample i of the call's input as (re, im); im = 0 for the real formats.  Packed: sample i sits in byte
+// i >> log2(samples per byte) at slot i mod (samples per byte), whatever i the tile starts at.
+template <int FMT>
+__device__ __forceinline__ float2 cond_load(const void* in, int64_t i, const CondPack pk)
 {
     if constexpr (FMT == GNSSHIP_FMT_CF32) {
         return reinterpret_cast<const float2*>(in)[i];
     } else if constexpr (FMT == GNSSHIP_FMT_CI16) {
         const short2 v = reinterpret_cast<const short2*>(in)[i];
         return make_float2(static_cast<float>(v.x), static_cast<float>(v.y));
-    } else {
+    } else if constexpr (FMT == GNSSHIP_FMT_CI8) {
         const char2 v = reinterpret_cast<const char2*>(in)[i];
         return make_float2(static_cast<float>(v.x), static_cast<float>(v.y));
+    } else if constexpr (FMT == GNSSHIP_FMT_RF32) {
+        return make_float2(reinterpret_cast<const float*>(in)[i], 0.0f);
+    } else if constexpr (FMT == GNSSHIP_FMT_RI16) {
+        return make_float2(static_cast<float>(reinterpret_cast<const short*>(in)[i]), 0.0f);
+    } else if constexpr (FMT == GNSSHIP_FMT_RI8) {
+        return make_float2(static_cast<float>(reinterpret_cast<const signed char*>(in)[i]), 0.0f);
+    } else {
+        const uint32_t bits = pk.info & 0xffu, l = (pk.info >> 8) & 0xffu;
+        const int m = static_cast<int>(pk.info >> 16);
+        const uint32_t byte = reinterpret_cast<const uint8_t*>(in)[i >> l];
+        const uint32_t sh = pk.shifts >> (8u * (static_cast<uint32_t>(i) & ((1u << l) - 1u)));
+        if constexpr (FMT == kCondPackedReal)
+            return make_float2(cond_field(byte, sh & 0xffu, bits, m), 0.0f);
+        else
+            return make_float2(cond_field(byte, sh & 0xffu, bits, m), cond_field(byte, (sh >> 16) & 0xffu, bits, m));
     }
 }
 
@@ -106,19 +156,32 @@ __global__ __launch_bounds__(kCondThreads) void cond_xlating_fir_kernel(const vo
     // the next call's history and sample count (the other half of the double buffer)
     for (int64_t i = static_cast<int64_t>(blockIdx.x) * kCondThreads + tid; i < n_hist; i += static_cast<int64_t>(gridDim.x) * kCondThreads) {
         const int64_t g = a.n_in - n_hist + i;
-        a.hist_new[i] = g < 0 ? a.hist_old[n_hist + g] : cond_load<FMT>(in, g);
+        a.hist_new[i] = g < 0 ? a.hist_old[n_hist + g] : cond_load<FMT>(in, g, a.pack);
     }
     if (blockIdx.x == 0 && tid == 0) *a.count_new = first + a.n_in;
 
     // the span, once from HBM into registers
-    float2 raw[kCondRegs];
+    constexpr bool kReal = cond_is_real<FMT>();
+    using raw_t = std::conditional_t<kReal, float, float2>;
+    raw_t raw[kCondRegs];
 #pragma unroll
     for (int r = 0; r < kCondRegs; r++) {
         const int idx = r * kCondThreads + tid;
-        raw[r] = make_float2(0.0f, 0.0f);
-        if (idx < span) {
-            const int64_t g = g0 + idx;
-            raw[r] = g < 0 ? a.hist_old[n_hist + g] : cond_load<FMT>(in, g);
+        if constexpr (kReal) {
+            // through a scalar: a conditional write into raw[] made the 32-register form one 32-wide vector
+            // value (1.8 KiB of scratch, 1 wave/SIMD); this way 187 VGPRs, none
+            float v = 0.0f;
+            if (idx < span) {
+                const int64_t g = g0 + idx;
+                v = g < 0 ? a.hist_old[n_hist + g].x : cond_load<FMT>(in, g, a.pack).x;
+            }
+            raw[r] = v;
+        } else {
+            raw[r] = make_float2(0.0f, 0.0f);
+            if (idx < span) {
+                const int64_t g = g0 + idx;
+                raw[r] = g < 0 ? a.hist_old[n_hist + g] : cond_load<FMT>(in, g, a.pack);
+            }
         }
     }
     // (absolute index of this lane's slot 0) mod fs; before the stream's sample 0 the samples are zero
@@ -138,8 +201,14 @@ __global__ __launch_bounds__(kCondThreads) void cond_xlating_fir_kernel(const vo
                 double s, c;
                 sincospi(static_cast<double>(rr) * inv_scale, &s, &c);
                 const float cf = static_cast<float>(c), sf = static_cast<float>(s);
-                const float2 x = raw[r];
-                cond_lds[idx] = make_float2(__fadd_rn(__fmul_rn(x.x, cf), __fmul_rn(x.y, sf)), __fsub_rn(__fmul_rn(x.y, cf), __fmul_rn(x.x, sf)));
+                if constexpr (kReal) {
+                    // (x, 0)·(cos, −sin): what the complex form gives up to signs of zero
+                    const float x = raw[r];
+                    cond_lds[idx] = make_float2(__fmul_rn(x, cf), -__fmul_rn(x, sf));
+                } else {
+                    const float2 x = raw[r];
+                    cond_lds[idx] = make_float2(__fadd_rn(__fmul_rn(x.x, cf), __fmul_rn(x.y, sf)), __fsub_rn(__fmul_rn(x.y, cf), __fmul_rn(x.x, sf)));
+                }
             }
             rr += bd.step_mod;  // < 2·fs < 2³²
             if (rr >= a.fs) rr -= a.fs;
@@ -165,7 +234,51 @@ __global__ __launch_bounds__(kCondThreads) void cond_xlating_fir_kernel(const vo
 
 __global__ void cond_set_count_kernel(int64_t* count, int64_t value) { *count = value; }
 
+// The loads' description of a valid packed format (zeros for the others).  Field j of a byte in stream
+// order sits at bit offset bits·j (LSB first) or 8 − bits·(j + 1) (MSB first); a complex sample m takes
+// fields 2m, 2m + 1 as (re, im) (IQ) or (im, re) (QI).
+CondPack cond_pack(int fmt)
+{
+    CondPack pk = {0u, 0u};
+    if (!GNSSHIP_FMT_IS_PACKED(fmt)) return pk;
+    const int bits = GNSSHIP_FMT_PACKED_BITS(fmt), comp = GNSSHIP_FMT_PACKED_COMPONENTS(fmt);
+    const bool msb = GNSSHIP_FMT_PACKED_ORDER(fmt) == GNSSHIP_FMT_PACKED_MSB_FIRST;
+    const int fields = 8 / bits;
+    auto offset = [&](int j) { return static_cast<uint32_t>(msb ? 8 - bits * (j + 1) : bits * j); };
+    int log2_spb = 0;
+    if (comp == GNSSHIP_FMT_PACKED_REAL) {
+        for (int j = 0; j < fields; j++) pk.shifts |= offset(j) << (8 * j);
+        log2_spb = fields == 4 ? 2 : 1;
+    } else {
+        const int re = comp == GNSSHIP_FMT_PACKED_QI ? 1 : 0;
+        for (int m = 0; m < fields / 2; m++) pk.shifts |= (offset(2 * m + re) << (8 * m)) | (offset(2 * m + 1 - re) << (16 + 8 * m));
+        log2_spb = fields == 4 ? 1 : 0;
+    }
+    const uint32_t two_s_plus_1 = GNSSHIP_FMT_PACKED_MAP(fmt) == GNSSHIP_FMT_PACKED_MAP_2S1 ? 1u : 0u;
+    pk.info = static_cast<uint32_t>(bits) | (static_cast<uint32_t>(log2_spb) << 8) | (two_s_plus_1 << 16);
+    return pk;
+}
+
 }  // namespace
+
+// Bits per input sample of a format the conditioner reads (0: not one).  fmt_bytes() stays 0 for the real
+// and packed formats: the engines do not read them.
+extern "C" int gnsship_cond_fmt_bits(int fmt)
+{
+    switch (fmt) {
+    case GNSSHIP_FMT_CF32: return 64;
+    case GNSSHIP_FMT_CI16: return 32;
+    case GNSSHIP_FMT_CI8: return 16;
+    case GNSSHIP_FMT_RF32: return 32;
+    case GNSSHIP_FMT_RI16: return 16;
+    case GNSSHIP_FMT_RI8: return 8;
+    default: break;
+    }
+    if (!GNSSHIP_FMT_IS_PACKED(fmt)) return 0;
+    const int bits = GNSSHIP_FMT_PACKED_BITS(fmt), comp = GNSSHIP_FMT_PACKED_COMPONENTS(fmt);
+    if ((bits != 2 && bits != 4) || comp > GNSSHIP_FMT_PACKED_QI) return 0;
+    return comp == GNSSHIP_FMT_PACKED_REAL ? bits : 2 * bits;
+}
 
 struct gnsship_cond {
     gnsship_ctx* ctx = nullptr;
@@ -299,14 +412,17 @@ extern "C" int gnsship_cond_run(gnsship_cond* c, const void* in, int fmt, int in
 {
     if (!c) return GNSSHIP_E_INVAL;
     gnsship_ctx* ctx = c->ctx;
-    if (!in || fmt_bytes(fmt) == 0) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cond_run: null input or unknown sample format");
+    const int bps = gnsship_cond_fmt_bits(fmt);
+    if (!in || bps == 0) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cond_run: null input or unknown sample format");
     if (n_in < 1 || n_in > c->max_in) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cond_run: 1 <= n_in <= max_in_samples");
     for (int b = 0; b < c->n_bands; b++)
         if (n_in % c->band[b].decim != 0) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cond_run: n_in must be a multiple of every band's decimation");
+    if (bps < 8 && n_in % (8 / bps) != 0)
+        return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cond_run: n_in must be a multiple of the samples per byte of a packed format");
     if (int rc = set_device(ctx)) return rc;
     const void* src = in;
     if (!in_on_device) {
-        const size_t bytes = fmt_bytes(fmt) * static_cast<size_t>(n_in);
+        const size_t bytes = (static_cast<size_t>(n_in) * static_cast<size_t>(bps) + 7) / 8;
         if (c->stage_cap < bytes) {
             if (c->stage_dev) {
                 (void)hipStreamSynchronize(ctx->stream);  // an earlier run may still read it
@@ -335,6 +451,7 @@ extern "C" int gnsship_cond_run(gnsship_cond* c, const void* in, int fmt, int in
     a.hist_new = c->hist_dev[c->cur ^ 1];
     a.count_old = c->count_dev + c->cur;
     a.count_new = c->count_dev + (c->cur ^ 1);
+    a.pack = cond_pack(fmt);
     const int64_t blocks = (n_in + c->tile - 1) / c->tile;  // <= 2^30: n_in <= GNSSHIP_COND_MAX_IN_SAMPLES
     const size_t lds = sizeof(float2) * static_cast<size_t>(c->n_hist + c->tile);
     const dim3 grid(static_cast<unsigned>(blocks)), block(kCondThreads);
@@ -351,8 +468,24 @@ extern "C" int gnsship_cond_run(gnsship_cond* c, const void* in, int fmt, int in
     case GNSSHIP_FMT_CI16:
         GNSSHIP_COND_LAUNCH(GNSSHIP_FMT_CI16);
         break;
-    default:
+    case GNSSHIP_FMT_CI8:
         GNSSHIP_COND_LAUNCH(GNSSHIP_FMT_CI8);
+        break;
+    case GNSSHIP_FMT_RF32:
+        GNSSHIP_COND_LAUNCH(GNSSHIP_FMT_RF32);
+        break;
+    case GNSSHIP_FMT_RI16:
+        GNSSHIP_COND_LAUNCH(GNSSHIP_FMT_RI16);
+        break;
+    case GNSSHIP_FMT_RI8:
+        GNSSHIP_COND_LAUNCH(GNSSHIP_FMT_RI8);
+        break;
+    default:  // a valid packed format: gnsship_cond_fmt_bits accepted it
+        if (GNSSHIP_FMT_PACKED_COMPONENTS(fmt) == GNSSHIP_FMT_PACKED_REAL) {
+            GNSSHIP_COND_LAUNCH(kCondPackedReal);
+        } else {
+            GNSSHIP_COND_LAUNCH(kCondPackedCplx);
+        }
         break;
     }
 #undef GNSSHIP_COND_LAUNCH

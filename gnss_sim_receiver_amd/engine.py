@@ -575,16 +575,23 @@ class SignalConditioner:
         return len(self.bands)
 
     def run(self, x, fmt: int = None, on_device: bool = False, n_in: int = None, dev_dst=None, host: bool = None):
-        """Filter a host array, or a device pointer with on_device=True, fmt and n_in.  dev_dst: per-band
-        device pointers (None entries = the handle's own buffers).  Returns the list of per-band complex64
-        arrays when host (the default for a host input), else [(device pointer, n_out), ...]."""
+        """Filter a host array, or a device pointer with on_device=True, fmt and n_in.  fmt defaults to the
+        array's complex format (sample_format); a real float32 / int16 / int8 array needs fmt=FMT_RF32 /
+        FMT_RI16 / FMT_RI8 and a uint8 array of packed bytes a packed fmt (abi.fmt_packed and the presets),
+        n_in then defaulting to bytes × samples per byte.  dev_dst: per-band device pointers (None entries
+        = the handle's own buffers).  Returns the list of per-band complex64 arrays when host (the default
+        for a host input), else [(device pointer, n_out), ...]."""
         nb = self.n_bands
         if on_device:
             ptr = ctypes.c_void_p(x)
         else:
             x = np.ascontiguousarray(x)
             fmt = sample_format(x) if fmt is None else fmt
-            n_in = x.nbytes // _FMT_BYTES[fmt] if n_in is None else n_in
+            if n_in is None:
+                bits = self.ctx.lib.gnsship_cond_fmt_bits(fmt)
+                if bits <= 0:
+                    raise ValueError(f"SignalConditioner.run: unknown sample format {fmt}")
+                n_in = x.nbytes * 8 // bits
             ptr = ctypes.c_void_p(x.ctypes.data)
         host = (not on_device) if host is None else host
         dst = None

@@ -54,6 +54,38 @@ extern "C" {
 #define GNSSHIP_FMT_CF32 0 /* interleaved float32 I,Q  (gr_complex)            */
 #define GNSSHIP_FMT_CI16 1 /* interleaved int16  I,Q  (lv_16sc_t / cshort)      */
 #define GNSSHIP_FMT_CI8 2  /* interleaved int8   I,Q  (ibyte/cbyte), no scaling  */
+/* Read by the signal conditioner only (gnsship_cond_run); every other entry point rejects them.
+ * Real-sampled IF, one value per sample, imaginary part 0, no scaling: the Freq_Xlating_Fir_Filter
+ * adapter's input_item_type float / short / byte (freq_xlating_fir_filter.cc:118-159). */
+#define GNSSHIP_FMT_RF32 3 /* float32 */
+#define GNSSHIP_FMT_RI16 4 /* int16   */
+#define GNSSHIP_FMT_RI8 5  /* int8    */
+/* Bit-packed items: a byte holds 8/bits fields, bits = 2 or 4.  Field j in stream order sits at bit
+ * offset bits*j (LSB_FIRST) or 8 - bits*(j + 1) (MSB_FIRST) and is a two's-complement integer s; the
+ * sample value is 2s + 1 (MAP_2S1) or s (MAP_S).  REAL: one field per sample; IQ: fields 2m, 2m + 1 are
+ * re, im of sample m; QI: im, re. */
+#define GNSSHIP_FMT_PACKED_REAL 0
+#define GNSSHIP_FMT_PACKED_IQ 1
+#define GNSSHIP_FMT_PACKED_QI 2
+#define GNSSHIP_FMT_PACKED_LSB_FIRST 0
+#define GNSSHIP_FMT_PACKED_MSB_FIRST 1
+#define GNSSHIP_FMT_PACKED_MAP_2S1 0
+#define GNSSHIP_FMT_PACKED_MAP_S 1
+#define GNSSHIP_FMT_PACKED(bits, components, order, map) (0x100 | ((bits) << 4) | ((components) << 2) | ((order) << 1) | (map))
+#define GNSSHIP_FMT_IS_PACKED(fmt) (((fmt) & ~0xff) == 0x100)
+#define GNSSHIP_FMT_PACKED_BITS(fmt) (((fmt) >> 4) & 0xf)
+#define GNSSHIP_FMT_PACKED_COMPONENTS(fmt) (((fmt) >> 2) & 0x3)
+#define GNSSHIP_FMT_PACKED_ORDER(fmt) (((fmt) >> 1) & 0x1)
+#define GNSSHIP_FMT_PACKED_MAP(fmt) ((fmt) & 0x1)
+/* The reference's packed file sources (byte items, little-endian host):
+ * Two_Bit_Packed_File_Signal_Source, sample_type real / iq / qi, big_endian_bytes false (LSB_FIRST) / true
+ * (unpack_2bit_samples.cc:150-207); Nsr_File_Signal_Source (unpack_byte_2bit_samples.cc:50-65);
+ * Two_Bit_Cpx_File_Signal_Source (unpack_byte_2bit_cpx_samples.cc:77-90, re = bits 7:6, im = 5:4, ...);
+ * Four_Bit_Cpx_File_Signal_Source, sample_type iq / qi (unpack_byte_4bit_samples.cc:44-65). */
+#define GNSSHIP_FMT_TWO_BIT_PACKED(components, order) GNSSHIP_FMT_PACKED(2, components, order, GNSSHIP_FMT_PACKED_MAP_2S1)
+#define GNSSHIP_FMT_NSR GNSSHIP_FMT_PACKED(2, GNSSHIP_FMT_PACKED_REAL, GNSSHIP_FMT_PACKED_LSB_FIRST, GNSSHIP_FMT_PACKED_MAP_S)
+#define GNSSHIP_FMT_TWO_BIT_CPX GNSSHIP_FMT_PACKED(2, GNSSHIP_FMT_PACKED_IQ, GNSSHIP_FMT_PACKED_MSB_FIRST, GNSSHIP_FMT_PACKED_MAP_2S1)
+#define GNSSHIP_FMT_FOUR_BIT_CPX(components) GNSSHIP_FMT_PACKED(4, components, GNSSHIP_FMT_PACKED_LSB_FIRST, GNSSHIP_FMT_PACKED_MAP_2S1)
 
 #define GNSSHIP_MAX_TAPS 8
 
@@ -350,10 +382,19 @@ int gnsship_cond_lowpass_taps(double fs, int decimation, double bw, double tw, f
  * max_in_samples outside 1..GNSSHIP_COND_MAX_IN_SAMPLES or below a band's decimation. */
 int gnsship_cond_create(gnsship_ctx* ctx, double fs_in, const gnsship_cond_band* bands, int n_bands, int64_t max_in_samples,
     gnsship_cond** out);
+/* Bits per input sample of a format gnsship_cond_run reads: 64 / 32 / 16 (CF32 / CI16 / CI8), 32 / 16 / 8
+ * (RF32 / RI16 / RI8), the field width (packed REAL) or twice it (packed IQ / QI); 0 for any other value.
+ * Host only. */
+int gnsship_cond_fmt_bits(int fmt);
 /* The block's work() over n_in samples in `fmt` (converted in the loads, no scaling; the byte / short
  * item types of :118-159 without their converter blocks): n_in / decimation CF32 outputs per band.
- * n_in must be a multiple of every band's decimation and <= max_in_samples, else E_INVAL and no
- * state changes.  Band b is written to dev_dst[b] (a caller's device buffer, e.g. a slot of a
+ * Real items (GNSSHIP_FMT_RF32 / RI16 / RI8: freq_xlating_fir_filter_fcf / _scf, :118-150) are x with a
+ * zero imaginary part; the factor 256 of GNU Radio's char_to_short in front of the byte form (:147), a
+ * gain, is not applied.  Packed items (GNSSHIP_FMT_PACKED) are unpacked in the loads; `in` is
+ * byte-granular, ceil(n_in * bits / 8) bytes, and sample 0 is field 0 of its first byte.
+ * n_in must be a multiple of every band's decimation, of the samples per byte of a packed format,
+ * and <= max_in_samples, else E_INVAL and no state changes.  One stream keeps one kind of item (real or
+ * complex) between resets: a real run reads only the real part of the carried history.  Band b is written to dev_dst[b] (a caller's device buffer, e.g. a slot of a
  * gnsship_dev_alloc ring) or, where dev_dst or dev_dst[b] is NULL, to the handle's own buffer (valid
  * until the next run); dev_out[b] / n_out[b] (arrays of n_bands, may be NULL) report where and how
  * many.  host_out (may be NULL) / host_out[b] (may be NULL): also copied to the host before returning;

@@ -258,6 +258,55 @@ struct Freq_Xlating_Fir_Filter_Conf {
     double bw{0.0};                          // :101-102
     double tw{0.0};                          // :103-104
     std::vector<float> taps;                 // explicit taps_ (:97,105), empty = design by filter_type
+    // :37,57: "gr_complex" (freq_xlating_fir_filter_ccf, :111-116), or the real-sampled "float" (_fcf,
+    // :118-124), "short" (_scf, :125-131) and "byte" (char_to_short + _scf, :143-150; its factor 256 not applied)
+    std::string input_item_type{"gr_complex"};
+    // GNSSHIP_FMT_* of input_item_type; -1 for a name the adapter does not know (:160-165)
+    int input_format() const
+    {
+        if (input_item_type == "gr_complex") return GNSSHIP_FMT_CF32;
+        if (input_item_type == "float") return GNSSHIP_FMT_RF32;
+        if (input_item_type == "short") return GNSSHIP_FMT_RI16;
+        if (input_item_type == "byte") return GNSSHIP_FMT_RI8;
+        return -1;
+    }
+};
+
+// The packed file sources' configurations, property names and defaults as in the adapters; format() is the
+// GNSSHIP_FMT_PACKED value the signal conditioner reads their byte items with (-1: not a known sample_type).
+// Two_Bit_Packed_File_Signal_Source with byte items (two_bit_packed_file_signal_source.cc:33-36,79-91;
+// unpack_2bit_samples.cc:150-207).  Short items with big_endian_items are a host byte swap, not mirrored.
+struct Two_Bit_Packed_File_Signal_Source_Conf {
+    std::string sample_type{"real"};  // "real", "iq", "qi" (:33)
+    bool big_endian_bytes{false};     // :35: the first sample of a byte in its most significant bits
+    int format() const
+    {
+        const int order = big_endian_bytes ? GNSSHIP_FMT_PACKED_MSB_FIRST : GNSSHIP_FMT_PACKED_LSB_FIRST;
+        if (sample_type == "real") return GNSSHIP_FMT_TWO_BIT_PACKED(GNSSHIP_FMT_PACKED_REAL, order);
+        if (sample_type == "iq") return GNSSHIP_FMT_TWO_BIT_PACKED(GNSSHIP_FMT_PACKED_IQ, order);
+        if (sample_type == "qi") return GNSSHIP_FMT_TWO_BIT_PACKED(GNSSHIP_FMT_PACKED_QI, order);
+        return -1;
+    }
+};
+// Nsr_File_Signal_Source (unpack_byte_2bit_samples.cc:50-65): real, LSB first, the field value itself.
+struct Nsr_File_Signal_Source_Conf {
+    int format() const { return GNSSHIP_FMT_NSR; }
+};
+// Two_Bit_Cpx_File_Signal_Source (unpack_byte_2bit_cpx_samples.cc:77-90 + interleaved_short_to_complex(false,
+// true), two_bit_cpx_file_signal_source.cc:69; swap = the second short is the real part, restated from GNU
+// Radio's published meaning): re = bits 7:6, im = 5:4, then 3:2, 1:0.
+struct Two_Bit_Cpx_File_Signal_Source_Conf {
+    int format() const { return GNSSHIP_FMT_TWO_BIT_CPX; }
+};
+// Four_Bit_Cpx_File_Signal_Source (four_bit_cpx_file_signal_source.cc:33-50,108; unpack_byte_4bit_samples.cc:44-65).
+struct Four_Bit_Cpx_File_Signal_Source_Conf {
+    std::string sample_type{"iq"};  // "iq", "qi" (:33)
+    int format() const
+    {
+        if (sample_type == "iq") return GNSSHIP_FMT_FOUR_BIT_CPX(GNSSHIP_FMT_PACKED_IQ);
+        if (sample_type == "qi") return GNSSHIP_FMT_FOUR_BIT_CPX(GNSSHIP_FMT_PACKED_QI);
+        return -1;
+    }
 };
 
 // Mirror of Freq_Xlating_Fir_Filter (freq_xlating_fir_filter.cc; the block of :115,
@@ -274,8 +323,10 @@ public:
         std::vector<gnsship_cond_band> cb(bands.size());
         for (size_t b = 0; b < bands.size(); b++) {
             Freq_Xlating_Fir_Filter_Conf& c = conf_[b];
-            if (c.sampling_frequency != conf_[0].sampling_frequency)
-                throw std::invalid_argument("Freq_Xlating_Fir_Filter_Hip: the bands share one input stream (sampling_frequency)");
+            if (c.sampling_frequency != conf_[0].sampling_frequency || c.input_item_type != conf_[0].input_item_type)
+                throw std::invalid_argument("Freq_Xlating_Fir_Filter_Hip: the bands share one input stream (sampling_frequency, input_item_type)");
+            if (c.input_format() < 0)
+                throw std::invalid_argument("Freq_Xlating_Fir_Filter_Hip: unknown input_item_type " + c.input_item_type);
             if (c.taps.empty()) {
                 if (c.filter_type != "lowpass")
                     throw std::invalid_argument("Freq_Xlating_Fir_Filter_Hip: filter_type " + c.filter_type + " needs explicit taps (pm_remez is not restated)");
@@ -321,6 +372,12 @@ public:
         return gnsship_cond_run(h_, in, fmt, in_on_device ? 1 : 0, n_in, dev_dst, host_out ? ho.data() : nullptr, dev_out_.data(), n_out_.data()) ==
                GNSSHIP_OK;
     }
+    // the same with the items of the configuration's input_item_type (gr_complex / float / short / byte)
+    bool work_items(const void* in, bool in_on_device, int64_t n_in, void* const* dev_dst = nullptr, std::complex<float>* const* host_out = nullptr)
+    {
+        return work(in, conf_[0].input_format(), in_on_device, n_in, dev_dst, host_out);
+    }
+    int input_format() const { return conf_[0].input_format(); }
     // one band, gr_complex in and out on the host: the adapter's gr_complex -> gr_complex item types (:111-116)
     bool work(const std::complex<float>* in, int64_t n_in, std::complex<float>* out)
     {

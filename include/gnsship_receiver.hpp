@@ -201,20 +201,27 @@ public:
     // With the conditioner on: feed the next n_in samples of the source in `fmt` (GNSSHIP_FMT_*; a multiple of the
     // decimation).  The stage runs on the device in pieces of one processing block; the conditioned block comes back
     // to the host, where the acquisition blocks buffer their dwells as the reference's do, and goes on to work().
+    // Real (GNSSHIP_FMT_RF32 / RI16 / RI8) and bit-packed (GNSSHIP_FMT_PACKED) items too: n_in then also a multiple of
+    // the samples per byte, the pieces cut at whole bytes.
     bool work_raw(const void* raw, int fmt, int64_t n_in)
     {
         if (!cond_) return false;
         const int d = cond_->decimation();
-        const int64_t bytes = fmt == GNSSHIP_FMT_CF32 ? 8 : fmt == GNSSHIP_FMT_CI16 ? 4 : 2;
-        if (n_in % d != 0) return false;
+        const int64_t bits = gnsship_cond_fmt_bits(fmt);
+        if (bits == 0) return false;
+        const int64_t spb = bits < 8 ? 8 / bits : 1;  // samples per byte of a packed format
+        int64_t unit = d;                             // lcm(d, spb): spb is 1, 2 or 4
+        while (unit % spb != 0) unit += d;
+        const int64_t piece = cond_block_ - cond_block_ % unit;
+        if (n_in % unit != 0 || piece == 0) return false;
         const char* p = static_cast<const char*>(raw);
         while (n_in > 0) {
-            const int64_t m = std::min(n_in, cond_block_);
+            const int64_t m = std::min(n_in, piece);
             cond_host_.resize(static_cast<size_t>(m / d));
             std::complex<float>* ho[1] = {cond_host_.data()};
             if (!cond_->work(p, fmt, false, m, nullptr, ho)) return false;
             if (!work(cond_host_.data(), m / d)) return false;
-            p += m * bytes;
+            p += m * bits / 8;
             n_in -= m;
         }
         return true;

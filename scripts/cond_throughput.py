@@ -9,6 +9,11 @@
    (a) on the conditioned 10 Msps band (if_hz = 0, N = 10000) and (b) as before this stage existed, on the
    50 Msps ibyte stream with the IF fused into the carrier NCO (if_hz = 7 161 000, N = 50000).
 
+--fmt times part 1 with another input form of the same random stream (real int8, or random bytes of a packed
+form; the channels of part 2 read ibyte and run with --fmt ci8 only).  --shape twobit-packed is the shape of the
+reference's packed configuration instead (conf/gnss-sdr_GPS_L1_nsr_twobit_packed.conf:35-91: 20.48 Msps, one band
+at IF 5 500 000 Hz — the configuration's non-integer IF rounded to whole Hz —, decimation 8, default low-pass taps).
+
 Needs a GPU.  One JSON line at the end carries every figure.
 """
 import argparse
@@ -26,6 +31,15 @@ sys.path.insert(0, ROOT)
 FS = 50_000_000
 F_IF = 7_161_000
 DECIM = 5
+# --shape: (input rate, band centres, decimation)
+SHAPES = {"c5": (FS, [F_IF, -F_IF], DECIM), "twobit-packed": (20_480_000, [5_500_000], 8)}
+
+
+def input_forms(abi):
+    """--fmt name -> (format value, bytes per sample)."""
+    two = abi.fmt_two_bit_packed
+    return {"ci8": (abi.FMT_CI8, 2.0), "ri8": (abi.FMT_RI8, 1.0), "2bit-real": (two("real"), 0.25), "2bit-iq": (two("iq"), 0.5),
+            "4bit-iq": (abi.fmt_four_bit_cpx("iq"), 1.0), "nsr": (abi.FMT_NSR, 0.25), "2bit-cpx": (abi.FMT_TWO_BIT_CPX, 0.5)}
 
 
 def main() -> int:
@@ -36,6 +50,8 @@ def main() -> int:
     ap.add_argument("--epochs", type=int, default=160, help="timed tracking epochs")
     ap.add_argument("--repeats", type=int, default=5, help="tracking timings (median reported)")
     ap.add_argument("--no-channels", action="store_true")
+    ap.add_argument("--fmt", default="ci8", help="input form of the conditioner run: ci8, ri8, 2bit-real, 2bit-iq, 4bit-iq, nsr, 2bit-cpx")
+    ap.add_argument("--shape", default="c5", choices=sorted(SHAPES))
     args = ap.parse_args()
 
     import torch
@@ -45,39 +61,51 @@ def main() -> int:
     torch.cuda.init()  # torch's HIP runtime first (tests/conftest.py)
     from gnss_sim_receiver_amd import abi, engine, signals
 
-    out = {"fs_in": FS, "bands_hz": [F_IF, -F_IF], "decimation": DECIM}
+    forms = input_forms(abi)
+    if args.fmt not in forms:
+        print(f"cond_throughput: --fmt must be one of {sorted(forms)}", file=sys.stderr)
+        return 2
+    fmt, sample_bytes = forms[args.fmt]
+    fs, centres, decim = SHAPES[args.shape]
+    out = {"fs_in": fs, "bands_hz": centres, "decimation": decim, "fmt": args.fmt}
     with engine.Context(0) as ctx:
-        taps = engine.cond_lowpass_taps(ctx.lib, float(FS), DECIM)
+        taps = engine.cond_lowpass_taps(ctx.lib, float(fs), decim)
         out["n_taps"] = len(taps)
-        n_in = FS // 1000 * args.block_ms
+        n_in = fs // 1000 * args.block_ms
         rng = np.random.default_rng(5)
-        raw = rng.integers(-100, 101, 2 * n_in, dtype=np.int8)
+        if args.fmt == "ci8":
+            raw = rng.integers(-100, 101, 2 * n_in, dtype=np.int8)
+        elif args.fmt == "ri8":
+            raw = rng.integers(-100, 101, n_in, dtype=np.int8)
+        else:
+            raw = rng.integers(0, 256, int(n_in * sample_bytes), dtype=np.uint8)
         src = ctx.upload(raw)
-        cond = engine.SignalConditioner(ctx, FS, [(F_IF, DECIM, taps), (-F_IF, DECIM, taps)], n_in)
+        cond = engine.SignalConditioner(ctx, fs, [(f, decim, taps) for f in centres], n_in)
         for _ in range(args.warmup):
-            cond.run(src.ptr, fmt=abi.FMT_CI8, on_device=True, n_in=n_in)
+            cond.run(src.ptr, fmt=fmt, on_device=True, n_in=n_in)
         ctx.sync()
         ms = []
         for _ in range(max(10, args.runs)):
             ctx.event_record(0)
-            cond.run(src.ptr, fmt=abi.FMT_CI8, on_device=True, n_in=n_in)
+            cond.run(src.ptr, fmt=fmt, on_device=True, n_in=n_in)
             ctx.event_record(1)
             ctx.sync()
             ms.append(ctx.event_elapsed_ms(0, 1))
         med = statistics.median(ms)
         msps = n_in / med / 1e3
-        rtf = msps * 1e6 / FS
+        rtf = msps * 1e6 / fs
         # algorithmic bytes: s B in + sum_b 8/D_b B out per input sample
-        gbs = n_in * (2 + 2 * 8 / DECIM) / med / 1e6
+        gbs = n_in * (sample_bytes + len(centres) * 8 / decim) / med / 1e6
         out.update(block_samples=n_in, cond_ms_median=med, cond_ms_min=min(ms), cond_ms_max=max(ms), input_msps=msps, real_time_factor=rtf,
                    algorithmic_gb_s=gbs)
-        print(f"conditioner: {n_in} samples per run, 2 bands, {len(taps)} taps, D {DECIM}: median {med:.3f} ms over {len(ms)} runs "
-              f"(min {min(ms):.3f}, max {max(ms):.3f}) = {msps:.0f} Msps in, {rtf:.1f}x real time of the 50 Msps stream, "
+        print(f"conditioner, {args.fmt} in: {n_in} samples per run, {len(centres)} band{'s' if len(centres) > 1 else ''}, {len(taps)} taps, "
+              f"D {decim}: median {med:.3f} ms over {len(ms)} runs "
+              f"(min {min(ms):.3f}, max {max(ms):.3f}) = {msps:.0f} Msps in, {rtf:.1f}x real time of the {fs / 1e6:g} Msps stream, "
               f"{gbs:.1f} GB/s algorithmic")
         cond.close()
         src.free()
 
-        if not args.no_channels:
+        if not args.no_channels and args.fmt == "ci8" and args.shape == "c5":
             n_ch = 12
             rng = np.random.default_rng(0x6E550005)
             sats = [signals.Satellite(prn=p, doppler_hz=float(rng.uniform(-4000, 4000)), code_delay_chips=float(rng.uniform(0, 1000)),
@@ -129,7 +157,7 @@ def main() -> int:
             band.free()
     print(json.dumps(out))
     if not out["real_time_factor"] > 1.0:
-        print("cond_throughput: the conditioner is slower than its 50 Msps stream", file=sys.stderr)
+        print("cond_throughput: the conditioner is slower than its input stream", file=sys.stderr)
         return 1
     return 0
 

@@ -5,7 +5,8 @@
 // channels (acquisition on L5I, tracking on the L5Q pilot with the L5I data prompt), with --signal 2S GPS L2C
 // channels (the L2 CM code, 20 ms epochs), with --signal B3 BeiDou B3I channels (a GEO satellite follows its PRN).
 //
-//   gnsship_rx --file F [--item gr_complex|ishort|ibyte] [--fs 4000000] [--seconds S] [--signal 1C|L5|2S|B3]
+//   gnsship_rx --file F [--item gr_complex|ishort|ibyte|float|short|byte|2bit|nsr|2bit-cpx|4bit-cpx]
+//              [--sample-type real|iq|qi] [--big-endian-bytes] [--fs 4000000] [--seconds S] [--signal 1C|L5|2S|B3]
 //              [--channels 5] [--in-acquisition 1] [--satellite CH:PRN ...] [--repeat-satellite]
 //              [--pfa 0.01] [--doppler-max 10000] [--doppler-step 250]
 //              [--pll-bw 40] [--dll-bw 4] [--order 3] [--pull-in-time-s 10] [--rotator auto|generic|avx]
@@ -20,7 +21,15 @@
 // and uploads the tracking window again: one device-to-host and one host-to-device copy of the conditioned block per block.
 //
 // ishort / ibyte samples are converted to gr_complex without scaling (Ishort_To_Complex /
-// Ibyte_To_Complex, item_type_helpers.cc:27-73).  stdout: one JSON summary line.
+// Ibyte_To_Complex, item_type_helpers.cc:27-73).
+//
+// --item float|short|byte is a real-sampled IF stream (the Freq_Xlating_Fir_Filter adapter's input_item_type).  The
+// packed items are the byte files of the reference's packed sources: 2bit = Two_Bit_Packed_File_Signal_Source
+// (--sample-type real|iq|qi, default real; --big-endian-bytes), nsr = Nsr_File_Signal_Source (real), 2bit-cpx =
+// Two_Bit_Cpx_File_Signal_Source, 4bit-cpx = Four_Bit_Cpx_File_Signal_Source (--sample-type iq|qi, default iq).
+// With the conditioner on they go to the device as they are (GNSSHIP_FMT_*).  Real items need the conditioner
+// (--if-hz / --decimation); packed complex items without it are unpacked to gr_complex here, as ishort / ibyte are.
+// stdout: one JSON summary line.
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -40,15 +49,25 @@ namespace {
     std::exit(2);
 }
 
+// Field j (stream order) of a byte of a packed format, value map applied (GNSSHIP_FMT_PACKED, include/gnsship.h).
+float packed_field(uint8_t byte, int j, int fmt)
+{
+    const int bits = GNSSHIP_FMT_PACKED_BITS(fmt);
+    const int off = GNSSHIP_FMT_PACKED_ORDER(fmt) == GNSSHIP_FMT_PACKED_MSB_FIRST ? 8 - bits * (j + 1) : bits * j;
+    int s = (byte >> off) & ((1 << bits) - 1);
+    if (s >= (1 << (bits - 1))) s -= 1 << bits;
+    return static_cast<float>(GNSSHIP_FMT_PACKED_MAP(fmt) == GNSSHIP_FMT_PACKED_MAP_2S1 ? 2 * s + 1 : s);
+}
+
 }  // namespace
 
 int main(int argc, char** argv)
 {
-    std::string file, item = "gr_complex", dump, events_csv, records_bin, rotator = "auto", signal = "1C";
+    std::string file, item = "gr_complex", sample_type, dump, events_csv, records_bin, rotator = "auto", signal = "1C";
     double fs = 4e6, seconds = 0.0, block_ms = 100.0;
     double if_hz = 0.0, filter_bw = 0.0, filter_tw = 0.0;
     int decimation = 1;
-    bool conditioner = false;
+    bool conditioner = false, big_endian_bytes = false;
     gnsship::Receiver_Conf rc;
     rc.channels = 5;
     rc.in_acquisition = 1;
@@ -67,6 +86,8 @@ int main(int argc, char** argv)
         };
         if (a == "--file") file = val();
         else if (a == "--item") item = val();
+        else if (a == "--sample-type") sample_type = val();
+        else if (a == "--big-endian-bytes") big_endian_bytes = true;
         else if (a == "--signal") signal = val();
         else if (a == "--fs") fs = std::atof(val().c_str());
         else if (a == "--seconds") seconds = std::atof(val().c_str());
@@ -106,8 +127,35 @@ int main(int argc, char** argv)
         else usage(("unknown option " + a).c_str());
     }
     if (file.empty()) usage("--file is required");
-    const int sample_bytes = item == "gr_complex" ? 8 : item == "ishort" ? 4 : item == "ibyte" ? 2 : 0;
-    if (!sample_bytes) usage("--item must be gr_complex, ishort or ibyte");
+    int fmt = -1;
+    if (item == "gr_complex") fmt = GNSSHIP_FMT_CF32;
+    else if (item == "ishort") fmt = GNSSHIP_FMT_CI16;
+    else if (item == "ibyte") fmt = GNSSHIP_FMT_CI8;
+    else if (item == "float") fmt = GNSSHIP_FMT_RF32;
+    else if (item == "short") fmt = GNSSHIP_FMT_RI16;
+    else if (item == "byte") fmt = GNSSHIP_FMT_RI8;
+    else if (item == "2bit") {
+        gnsship::Two_Bit_Packed_File_Signal_Source_Conf src;
+        if (!sample_type.empty()) src.sample_type = sample_type;
+        src.big_endian_bytes = big_endian_bytes;
+        fmt = src.format();
+        if (fmt < 0) usage("--sample-type must be real, iq or qi with --item 2bit");
+    } else if (item == "nsr") fmt = gnsship::Nsr_File_Signal_Source_Conf().format();
+    else if (item == "2bit-cpx") fmt = gnsship::Two_Bit_Cpx_File_Signal_Source_Conf().format();
+    else if (item == "4bit-cpx") {
+        gnsship::Four_Bit_Cpx_File_Signal_Source_Conf src;
+        if (!sample_type.empty()) src.sample_type = sample_type;
+        fmt = src.format();
+        if (fmt < 0) usage("--sample-type must be iq or qi with --item 4bit-cpx");
+    } else usage("--item must be gr_complex, ishort, ibyte, float, short, byte, 2bit, nsr, 2bit-cpx or 4bit-cpx");
+    if ((!sample_type.empty() || big_endian_bytes) && item != "2bit" && !(item == "4bit-cpx" && !big_endian_bytes))
+        usage("--sample-type goes with --item 2bit or 4bit-cpx, --big-endian-bytes with --item 2bit");
+    const bool packed = GNSSHIP_FMT_IS_PACKED(fmt);
+    const bool real_items = fmt == GNSSHIP_FMT_RF32 || fmt == GNSSHIP_FMT_RI16 || fmt == GNSSHIP_FMT_RI8 ||
+                            (packed && GNSSHIP_FMT_PACKED_COMPONENTS(fmt) == GNSSHIP_FMT_PACKED_REAL);
+    if (real_items && !conditioner) usage("real-sampled items need the conditioner (--if-hz / --decimation)");
+    const int64_t sample_bits = gnsship_cond_fmt_bits(fmt);
+    const int64_t per_byte = sample_bits < 8 ? 8 / sample_bits : 1;  // samples per byte of a packed item
     if (signal != "1C" && signal != "L5" && signal != "2S" && signal != "B3") usage("--signal must be 1C, L5, 2S or B3");
     std::snprintf(rc.trk.signal, sizeof(rc.trk.signal), "%s", signal.c_str());
     if (signal == "B3") rc.trk.system = 'C';  // otherwise 'G'
@@ -157,17 +205,19 @@ int main(int argc, char** argv)
     gnsship::Gnss_Receiver_Hip& rx = *rxp;
     const int64_t block = (rc.block_samples > 0 ? rc.block_samples : static_cast<int64_t>(fs / 10)) * decimation;  // file samples
     const int64_t limit = seconds > 0 ? static_cast<int64_t>(seconds * fs_file) : INT64_MAX;
-    const int fmt = item == "gr_complex" ? GNSSHIP_FMT_CF32 : item == "ishort" ? GNSSHIP_FMT_CI16 : GNSSHIP_FMT_CI8;
-    std::vector<char> raw(static_cast<size_t>(block) * sample_bytes);
+    int64_t unit = conditioner ? decimation : 1;  // samples handed on at a time: whole conditioned samples, whole bytes
+    while (unit % per_byte != 0) unit += conditioner ? decimation : 1;
+    std::vector<char> raw(static_cast<size_t>((block * sample_bits + 7) / 8));
     std::vector<std::complex<float>> x(static_cast<size_t>(block));
     int64_t total = 0;
     double io_s = 0.0;
     const auto t0 = std::chrono::steady_clock::now();
     while (total < limit) {
         const auto r0 = std::chrono::steady_clock::now();
-        const int64_t want = std::min<int64_t>(block, limit - total);
-        size_t got = std::fread(raw.data(), static_cast<size_t>(sample_bytes), static_cast<size_t>(want), f);
-        if (conditioner) got -= got % static_cast<size_t>(decimation);  // a whole number of conditioned samples
+        int64_t want = std::min<int64_t>(block, limit - total);
+        want -= want % per_byte;
+        size_t got = static_cast<size_t>(static_cast<int64_t>(std::fread(raw.data(), 1, static_cast<size_t>(want * sample_bits / 8), f)) * 8 / sample_bits);
+        got -= got % static_cast<size_t>(unit);  // a whole number of conditioned samples and of bytes
         if (got == 0) break;
         if (conditioner) {
             io_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - r0).count();
@@ -180,6 +230,14 @@ int main(int argc, char** argv)
         }
         if (item == "gr_complex") {
             std::memcpy(x.data(), raw.data(), got * 8);
+        } else if (packed) {  // a complex packed item (real ones need the conditioner)
+            const uint8_t* s = reinterpret_cast<const uint8_t*>(raw.data());
+            const int re = GNSSHIP_FMT_PACKED_COMPONENTS(fmt) == GNSSHIP_FMT_PACKED_QI ? 1 : 0;
+            for (size_t i = 0; i < got; i++) {
+                const uint8_t b = s[i / static_cast<size_t>(per_byte)];
+                const int j = 2 * static_cast<int>(i % static_cast<size_t>(per_byte));
+                x[i] = {packed_field(b, j + re, fmt), packed_field(b, j + 1 - re, fmt)};
+            }
         } else if (item == "ishort") {
             const int16_t* s = reinterpret_cast<const int16_t*>(raw.data());
             for (size_t i = 0; i < got; i++) x[i] = {static_cast<float>(s[2 * i]), static_cast<float>(s[2 * i + 1])};
