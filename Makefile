@@ -68,6 +68,12 @@ $(B3I_L2C_MIRROR_TEST): tests/cpp/b3i_l2c_mirror_test.cpp include/gnsship_cpp.hp
 	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/b3i_l2c_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
 all: $(B3I_L2C_MIRROR_TEST)
 
+# Galileo E5a / E5b through the C++ mirror (tests/test_cpp_mirror_e5.py)
+E5_MIRROR_TEST := tests/cpp/e5_mirror_test
+$(E5_MIRROR_TEST): tests/cpp/e5_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
+	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/e5_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
+all: $(E5_MIRROR_TEST)
+
 # The signal conditioner through the C++ mirror (tests/test_cpp_mirror_cond.py)
 COND_MIRROR_TEST := tests/cpp/cond_mirror_test
 $(COND_MIRROR_TEST): tests/cpp/cond_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)

@@ -138,6 +138,7 @@ class CondBand(ctypes.Structure):
 
 
 SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5, SYS_BDS_B3I, SYS_GPS_L2C = 0, 1, 2, 3, 4, 5
+SYS_GAL_E5A, SYS_GAL_E5B = 6, 7
 # gnsship_trk_last_engine (include/gnsship.h GNSSHIP_TRK_ENGINE_*)
 TRK_ENGINE_NONE, TRK_ENGINE_FAST_LATENCY, TRK_ENGINE_FAST_THROUGHPUT, TRK_ENGINE_PERSIST, TRK_ENGINE_ROUNDS, TRK_ENGINE_LANES = 0, 1, 2, 3, 4, 5
 TRK_ENGINE_NAMES = {0: "none", 1: "trk_fast_kernel (latency form)", 2: "trk_fast_kernel (throughput form)", 3: "trk_persist_kernel",
@@ -262,6 +263,18 @@ _SIGNATURES = {
     "gnsship_gps_l5i_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_int32], _i),
     "gnsship_gps_l5q_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_int32], _i),
     "gnsship_beidou_b3i_code_gen_float": ([_f32p, ctypes.c_int32, ctypes.c_uint32], _i),
+    "gnsship_galileo_e5_a_code_gen_complex_primary": ([_f32p, ctypes.c_int32, ctypes.c_char_p], _i),
+    "gnsship_galileo_e5_b_code_gen_complex_primary": ([_f32p, ctypes.c_int32, ctypes.c_char_p], _i),
+    "gnsship_galileo_e5_a_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint32], _i),
+    "gnsship_galileo_e5_b_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_int32, ctypes.c_uint32], _i),
+    "gnsship_galileo_e5a_i_code_gen_float": ([_f32p, ctypes.c_int32], _i),
+    "gnsship_galileo_e5a_q_code_gen_float": ([_f32p, ctypes.c_int32], _i),
+    "gnsship_galileo_e5b_i_code_gen_float": ([_f32p, ctypes.c_int32], _i),
+    "gnsship_galileo_e5b_q_code_gen_float": ([_f32p, ctypes.c_int32], _i),
+    "gnsship_galileo_e5a_i_secondary_code": ([ctypes.c_char_p], _i),
+    "gnsship_galileo_e5b_i_secondary_code": ([ctypes.c_char_p], _i),
+    "gnsship_galileo_e5a_q_secondary_code": ([ctypes.c_char_p, ctypes.c_int32], _i),
+    "gnsship_galileo_e5b_q_secondary_code": ([ctypes.c_char_p, ctypes.c_int32], _i),
     "gnsship_beidou_b3i_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32], _i),
     "gnsship_gps_l2c_m_code_gen_float": ([_f32p, ctypes.c_int32], _i),
     "gnsship_gps_l2c_m_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_int32], _i),

@@ -13,6 +13,10 @@
 //                 (BDS-SIS-ICD-B3I; reference beidou_b3i_signal_replica.cc:26-165), sampled as B1I
 //  GPS L2 CM     : 27-stage modular register, polynomial octal 0445112474, per-PRN initial state
 //                 (IS-GPS-200 Table 3-IIa; reference gps_l2c_signal_replica.cc:25-39), sampled as L5Q
+//  Galileo E5    : E5a-I / E5a-Q / E5b-I / E5b-Q primaries, 10230 chips: one 28-stage linear recurrence per component
+//                 (the ICD's two 14-stage registers multiplied out; E5a-I and E5a-Q share theirs) from the PRN's
+//                 first 28 chips (galileo_e5_tables.h; reference galileo_e5_signal_replica.cc:31-216 reads tables);
+//                 sampled with resampler()'s truncating float index (gnss_signal_replica.cc:275-290)
 //  sampled forms: the Borre-style upsampling with a float chip clock and the last sample forced
 //                 to the last chip  (gps_sdr_signal_replica.cc:145-185, beidou_b1i_signal_replica.cc:142-180)
 //
@@ -22,7 +26,10 @@
 #include <cstdint>
 #include <cstring>
 
+#include "galileo_e5_tables.h"
 #include "gnsship.h"
+
+namespace e5 = gnsship::e5;
 
 namespace {
 
@@ -230,7 +237,133 @@ int sample_code(const int8_t* chips, int code_len, int32_t chip_rate, int32_t fs
     return n;
 }
 
+// Galileo E5a-I / E5a-Q / E5b-I / E5b-Q primary (component 0..3): chip n = parity of the previous 28 chips under
+// the component's feedback mask, from the PRN's first 28 chips (galileo_e5_tables.h; the OS SIS ICD's two 14-stage
+// registers multiplied out — one recurrence holds over the whole truncated code).  Bit 1 ↔ chip −1, as the
+// reference's hex_to_binary_converter reads its tables (gnss_signal_replica.cc:43-146).
+int e5_chips(int component, int32_t prn, int8_t* chips)
+{
+    if (prn < 1 || prn > 50 || component < 0 || component > 3) return GNSSHIP_E_INVAL;
+    uint32_t w = e5::kStart[component][prn - 1];  // bit j = chip n − 28 + j
+    const uint32_t fb = e5::kFeedback[component];
+    for (int i = 0; i < e5::kStages; i++) chips[i] = ((w >> i) & 1u) ? -1 : 1;
+    for (int i = e5::kStages; i < kL5Len; i++) {
+        const uint32_t b = __builtin_parity(w & fb);
+        w = (w >> 1) | (b << (e5::kStages - 1));
+        chips[i] = b ? -1 : 1;
+    }
+    return GNSSHIP_OK;
+}
+
+// signal_id → first component (0 E5a-I .. 3 E5b-Q) and whether both components are asked for
+bool e5_signal(const char* id, char band, int& component, bool& both)
+{
+    if (!id || id[0] != band || (id[1] != 'I' && id[1] != 'Q' && id[1] != 'X')) return false;
+    component = (band == '5' ? 0 : 2) + (id[1] == 'Q' ? 1 : 0);
+    both = id[1] == 'X';
+    return true;
+}
+
+int e5_primary(float* dest, int32_t prn, const char* signal_id, char band)
+{
+    int comp;
+    bool both;
+    if (!dest || !e5_signal(signal_id, band, comp, both)) return GNSSHIP_E_INVAL;
+    static thread_local int8_t re[kL5Len], im[kL5Len];
+    if (int rc = e5_chips(comp, prn, re)) return rc;
+    if (both)
+        if (int rc = e5_chips(comp + 1, prn, im)) return rc;
+    for (int i = 0; i < kL5Len; i++) {
+        dest[2 * i] = static_cast<float>(re[i]);
+        dest[2 * i + 1] = both ? static_cast<float>(im[i]) : 0.0F;
+    }
+    return GNSSHIP_OK;
+}
+
+// galileo_e5_a_code_gen_complex_sampled (galileo_e5_signal_replica.cc:96-122): resampler()'s index
+// (gnss_signal_replica.cc:275-290) unless fs is the chip rate, then the delay rotation.  An index past the last
+// chip (the reference reads its vector unchecked there) is held at the last chip.
+int e5_sampled(float* dest, uint32_t prn, const char* signal_id, int32_t fs, uint32_t chip_shift, char band)
+{
+    if (!dest || fs <= 0) return GNSSHIP_E_INVAL;
+    static thread_local float primary[2 * kL5Len];
+    if (int rc = e5_primary(primary, static_cast<int32_t>(prn), signal_id, band)) return rc;
+    constexpr uint32_t L = kL5Len;
+    constexpr int32_t chip_rate = 10230000;
+    const auto n = static_cast<uint32_t>(static_cast<double>(fs) / (static_cast<double>(chip_rate) / static_cast<double>(L)));
+    if (n == 0) return GNSSHIP_E_INVAL;
+    const uint32_t delay = ((L - chip_shift) % L) * n / L;
+    const float fs_in = static_cast<float>(chip_rate), t_out = 1.0F / static_cast<float>(fs);
+    for (uint32_t i = 0; i < n; i++) {
+        uint32_t k = i;
+        if (fs != chip_rate) {
+            const float aux = (t_out * (static_cast<float>(i) + 1.0F)) * fs_in;
+            k = static_cast<uint32_t>(static_cast<int32_t>(static_cast<int64_t>(aux + 1)) - 1);
+            if (i == n - 1 || k >= L) k = L - 1;
+        }
+        const uint32_t o = (i + delay) % n;
+        dest[2 * o] = primary[2 * k];
+        dest[2 * o + 1] = primary[2 * k + 1];
+    }
+    return static_cast<int>(n);
+}
+
+int e5_float(float* dest, int component, int32_t prn)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    static thread_local int8_t c[kL5Len];
+    if (int rc = e5_chips(component, prn, c)) return rc;
+    for (int i = 0; i < kL5Len; i++) dest[i] = static_cast<float>(c[i]);
+    return GNSSHIP_OK;
+}
+
+int e5_q_secondary(char* dest, const uint32_t (*rows)[4], int count, int32_t prn)
+{
+    if (!dest || prn < 1 || prn > count) return GNSSHIP_E_INVAL;
+    for (int i = 0; i < 100; i++) dest[i] = ((rows[prn - 1][i >> 5] >> (i & 31)) & 1u) ? '1' : '0';
+    dest[100] = '\0';
+    return GNSSHIP_OK;
+}
+
 }  // namespace
+
+extern "C" int gnsship_galileo_e5_a_code_gen_complex_primary(float* dest, int32_t prn, const char* signal_id)
+{
+    return e5_primary(dest, prn, signal_id, '5');
+}
+extern "C" int gnsship_galileo_e5_b_code_gen_complex_primary(float* dest, int32_t prn, const char* signal_id)
+{
+    return e5_primary(dest, prn, signal_id, '7');
+}
+extern "C" int gnsship_galileo_e5_a_code_gen_complex_sampled(float* dest, uint32_t prn, const char* signal_id, int32_t fs, uint32_t chip_shift)
+{
+    return e5_sampled(dest, prn, signal_id, fs, chip_shift, '5');
+}
+extern "C" int gnsship_galileo_e5_b_code_gen_complex_sampled(float* dest, uint32_t prn, const char* signal_id, int32_t fs, uint32_t chip_shift)
+{
+    return e5_sampled(dest, prn, signal_id, fs, chip_shift, '7');
+}
+extern "C" int gnsship_galileo_e5a_i_code_gen_float(float* dest, int32_t prn) { return e5_float(dest, 0, prn); }
+extern "C" int gnsship_galileo_e5a_q_code_gen_float(float* dest, int32_t prn) { return e5_float(dest, 1, prn); }
+extern "C" int gnsship_galileo_e5b_i_code_gen_float(float* dest, int32_t prn) { return e5_float(dest, 2, prn); }
+extern "C" int gnsship_galileo_e5b_q_code_gen_float(float* dest, int32_t prn) { return e5_float(dest, 3, prn); }
+extern "C" int gnsship_galileo_e5a_i_secondary_code(char* dest)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    std::memcpy(dest, e5::kE5aISecondary, sizeof(e5::kE5aISecondary));
+    return GNSSHIP_OK;
+}
+extern "C" int gnsship_galileo_e5b_i_secondary_code(char* dest)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    std::memcpy(dest, e5::kE5bISecondary, sizeof(e5::kE5bISecondary));
+    return GNSSHIP_OK;
+}
+extern "C" int gnsship_galileo_e5a_q_secondary_code(char* dest, int32_t prn)
+{
+    return e5_q_secondary(dest, e5::kE5aQSecondary, e5::kE5aQSecondaryCount, prn);
+}
+extern "C" int gnsship_galileo_e5b_q_secondary_code(char* dest, int32_t prn) { return e5_q_secondary(dest, e5::kE5bQSecondary, 50, prn); }
 
 extern "C" int gnsship_gps_l1_ca_code_gen_float(float* dest, int32_t prn, uint32_t chip_shift)
 {

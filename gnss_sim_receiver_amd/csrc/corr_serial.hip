@@ -24,6 +24,7 @@ __global__ __launch_bounds__(kSerThreads) void corr_serial_kernel(const void* __
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ SerialSync sy;
     const SerialJob& sj = jobs[blockIdx.x];
+    if (sj.job.n_samples <= 0) return;  // an idle slot (the tracking round loop's channels that do not run this round)
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     if (tid == 0) sy = SerialSync{};
     __syncthreads();

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "galileo_e5_tables.h"
 #include "trk_engine.h"
 
 namespace gnsship {
@@ -74,6 +75,12 @@ struct gnsship_trk {
     bool high_dyn = false;
     HdPlan hd;
     TrkHist* hist_dev = nullptr;
+    // Galileo E5a / E5b: the round-based loop takes its correlations from the serial-order correlator (corr_serial.hip:
+    // the generic rotator's taps bit for bit) instead of the batch correlator's chunked sums, so its records equal
+    // the reference's as the persistent engines' do.  The older systems keep the batch correlator: their round-loop
+    // records stay what they were.
+    bool serial_rounds = false;
+    SerialJob* serial_dev = nullptr;
     bool force_rounds = false;  // GNSSHIP_TRK_ROUNDS=1: the round-based loop even where the persistent one applies
     // gnsship_trk_launch → gnsship_trk_collect: the enqueued run's rounds (−1: none pending)
     int pending_rounds = -1;
@@ -255,6 +262,40 @@ bool build_params(const gnsship_trk_conf& c, TrkParams& p)
         g.secondary = 0;  // state 2 goes straight to 4, as Galileo E1 without the pilot
         p.single_code_bits = 1;
         break;
+    case GNSSHIP_SYS_GAL_E5A:  // :292-322 (5X), start_tracking :699-722; galileo_e5a_dll_pll_tracking.cc:47-58
+    case GNSSHIP_SYS_GAL_E5B: {  // :323-353 (7X), :723-746; galileo_e5b_dll_pll_tracking.cc
+        const bool a = c.system == GNSSHIP_SYS_GAL_E5A;
+        const char* i_sec = a ? e5::kE5aISecondary : e5::kE5bISecondary;
+        const int i_len = static_cast<int>(std::strlen(i_sec));  // 20 / 4: also the symbols per bit
+        p.code_chip_rate = 10.23e6;
+        p.carrier_freq = a ? 1176.45e6 : 1207.14e6;
+        p.code_period = 0.001;
+        p.code_length_chips = 10230;
+        p.code_samples_per_chip = 1;
+        g.symbols_per_bit = i_len;
+        p.veml = 0;
+        p.track_pilot = c.track_pilot ? 1 : 0;
+        p.conf.slope = 1.0F;
+        p.conf.spc = c.early_late_space_chips;
+        p.conf.y_intercept = 1.0F;
+        if (p.conf.extend_correlation_symbols < 1) p.conf.extend_correlation_symbols = 1;
+        g.secondary = 1;
+        if (p.track_pilot) {  // the pilot's 100-chip code is the channel's own (prn_secondary_bits); the I code off the data prompt
+            g.secondary_len = 100;
+            g.data_secondary_len = i_len;
+            set_bits(g.data_secondary_bits, i_sec);
+            p.interchange_iq = 1;
+            p.prn_secondary = 1;
+            const int rows = a ? e5::kE5aQSecondaryCount : 50;
+            for (int prn = 1; prn <= rows; prn++)
+                std::memcpy(p.prn_secondary_bits[prn], a ? e5::kE5aQSecondary[prn - 1] : e5::kE5bQSecondary[prn - 1], 4 * sizeof(uint32_t));
+        } else {  // synchronise on and remove the I code; d_data_secondary_code_length stays 0
+            if (p.conf.extend_correlation_symbols > i_len) p.conf.extend_correlation_symbols = i_len;
+            g.secondary_len = i_len;
+            set_bits(g.secondary_bits, i_sec);
+            p.single_code_bits = 1;
+        }
+    } break;
     default: return false;
     }
     p.n_taps = p.veml ? 5 : 3;
@@ -367,7 +408,7 @@ hipError_t upload_hd_code(gnsship_trk* t, int job, const CodeDesc& cd)
 void release(gnsship_trk* t)
 {
     void* ptrs[] = {t->params_dev, t->chans_dev, t->jobs_dev, t->chunks_dev, t->items_dev, t->anchors_dev, t->partials_dev, t->out_dev, t->rec_dev,
-        t->ran_dev, t->stage_dev, t->hist_dev, t->dump_dev, t->trace_dev, t->start_stage_dev};
+        t->ran_dev, t->stage_dev, t->hist_dev, t->dump_dev, t->trace_dev, t->start_stage_dev, t->serial_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     hd_plan_free(t->hd);
@@ -481,6 +522,8 @@ extern "C" int gnsship_trk_create(gnsship_ctx* ctx, const gnsship_trk_conf* conf
     if (e == hipSuccess) e = hipMalloc(&t->partials_dev, sizeof(float) * 2 * kMaxTaps * static_cast<size_t>(t->n_chunks));
     if (e == hipSuccess) e = hipMalloc(&t->out_dev, sizeof(float) * 2 * kMaxTaps * static_cast<size_t>(t->n_jobs));
     t->high_dyn = conf->high_dyn != 0;
+    t->serial_rounds = !t->high_dyn && (conf->system == GNSSHIP_SYS_GAL_E5A || conf->system == GNSSHIP_SYS_GAL_E5B);
+    if (e == hipSuccess && t->serial_rounds) e = hipMalloc(&t->serial_dev, sizeof(SerialJob) * static_cast<size_t>(t->n_jobs));
     if (e == hipSuccess && t->high_dyn) {
         t->hd.jobs.assign(t->n_jobs, HdJob{});
         for (int i = 0; i < t->n_jobs; i++) {
@@ -519,6 +562,12 @@ static int trk_start_state(gnsship_trk* t, int channel, const gnsship_trk_start_
     if (p.track_pilot && (a->data_code_id < 0 || a->data_code_id >= static_cast<int>(ctx->codes_host.size()) || !ctx->codes_host[a->data_code_id].ptr))
         return fail(ctx, GNSSHIP_E_STATE, "gnsship_trk_start: data code not in the code bank");
     if (a->first_sample < a->acq_samplestamp_samples) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_trk_start: first_sample before the acquisition stamp");
+    if (p.conf.system == GNSSHIP_SYS_GAL_E5A || p.conf.system == GNSSHIP_SYS_GAL_E5B) {
+        // with the pilot tracked the PRN selects the channel's secondary code: only PRNs that have one
+        const int last = (p.prn_secondary && p.conf.system == GNSSHIP_SYS_GAL_E5A) ? e5::kE5aQSecondaryCount : 50;
+        if (a->prn < 1 || a->prn > last)
+            return fail(ctx, GNSSHIP_E_INVAL, "gnsship_trk_start: Galileo E5a / E5b PRN outside 1..50 (E5a pilot secondary codes: 1..47)");
+    }
     std::memset(&c, 0, sizeof(c));
     const gnsship_trk_conf& k = p.conf;
     c.code_id = a->code_id;
@@ -601,6 +650,34 @@ extern "C" int gnsship_trk_start(gnsship_trk* t, int channel, const gnsship_trk_
     HIP_TRY(ctx, hipMemcpyAsync(t->chans_dev + channel, &c, sizeof(TrkChannel), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return GNSSHIP_OK;
+}
+
+// The round's jobs as the serial-order correlator takes them (gnsship_trk::serial_rounds): the job the step kernel
+// just wrote, the code replica its chunks carry, output row = job.  A job that does not run this round has
+// n_samples 0 and is skipped by corr_serial_kernel.
+__global__ void trk_serial_jobs_kernel(const DevJob* __restrict__ jobs, const ChunkDesc* __restrict__ chunks, SerialJob* __restrict__ serial, int n_jobs)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_jobs) return;
+    const DevJob j = jobs[i];
+    const ChunkDesc& d = chunks[j.first_chunk];
+    serial[i].job = j;
+    serial[i].code = d.code;
+    serial[i].code_len = d.code_len;
+    serial[i].out_index = i;
+    if (!d.code) serial[i].job.n_samples = 0;
+}
+
+// d_interchange_iq (dll_pll_veml_tracking.cc:1945-1949, :1997-2001): the symbol handed to telemetry has the data
+// prompt's imaginary part as Prompt_I and its real part as Prompt_Q.  One pass over the run's epoch records after the
+// loop, whichever engine wrote them: the records with a valid symbol (flag 1).  log_data's records are not exchanged.
+__global__ void trk_exchange_kernel(gnsship_trk_epoch* __restrict__ rec, size_t n)
+{
+    const size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n || !(rec[i].flags & 1)) return;
+    const double re = rec[i].prompt_i;
+    rec[i].prompt_i = rec[i].prompt_q;
+    rec[i].prompt_q = re;
 }
 
 // Scatter of staged channel states: block b copies channel record b to its slot idx[b].
@@ -827,9 +904,21 @@ static int trk_enqueue(gnsship_trk* t, const void* src, int fmt, uint64_t buffer
             if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_hd(tracking)");
             continue;
         }
+        if (t->serial_rounds) {
+            hipLaunchKernelGGL(trk_serial_jobs_kernel, dim3((t->n_jobs + 63) / 64), dim3(64), 0, ctx->stream, t->jobs_dev, t->chunks_dev, t->serial_dev,
+                t->n_jobs);
+            if ((e = hipGetLastError()) != hipSuccess) return hip_fail(ctx, e, "trk_serial_jobs_kernel");
+            e = launch_corr_serial(src, fmt, t->serial_dev, t->n_jobs, t->out_dev, ctx->stream);
+            if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_serial(tracking)");
+            continue;
+        }
         e = launch_corr_batch(src, fmt, t->jobs_dev, t->n_jobs, t->chunks_dev, t->items_dev, t->n_items, t->classes, max_len, t->any_multi,
             t->anchors_dev, t->partials_dev, t->out_dev, ctx->stream, GNSSHIP_STAGE_CORRELATE);  // anchors: replayed by the step kernel
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_batch(tracking)");
+    }
+    if (out && t->params.interchange_iq) {
+        hipLaunchKernelGGL(trk_exchange_kernel, dim3(static_cast<unsigned>((nrec + 255) / 256)), dim3(256), 0, ctx->stream, t->rec_dev, nrec);
+        HIP_TRY(ctx, hipGetLastError());
     }
     t->pending_rounds = max_rounds;
     t->pending_out = out;

@@ -11,6 +11,7 @@ namespace gnsship {
 constexpr int kTrkMaxSecondary = 256;  // longest sign pattern searched (GPS preamble: 160 symbols)
 constexpr int kTrkMaxCn0Samples = 64;  // prompt buffer of the CN0 / carrier-lock estimators
 constexpr int kTrkMaxSmoother = 64;    // high_dyn: smoother_length bound (ring of 2·smoother_length)
+constexpr int kTrkPrnRows = 51;        // per-PRN secondary patterns: rows 1..50 (Galileo E5a-Q / E5b-Q), row 0 unused
 
 // Signal constants the reference selects per system/signal (dll_pll_veml_tracking.cc:142-330,
 // start_tracking :662-826) plus the loop-filter coefficients derived from Dll_Pll_Conf once.
@@ -62,6 +63,15 @@ struct TrkParams {
     int64_t if_mod, fs_int;
     // RN(1/fs_in) and RN(1/carrier_freq): the loop's quotients by them as exact FMA sequences (exact_div.h)
     double inv_fs, inv_carrier_freq;
+    // Galileo E5a / E5b with the pilot tracked (:706, :730): the secondary code belongs to the satellite, not to
+    // the system.  prn_secondary = 1: a channel's synchronisation pattern is row TrkChannel::prn of
+    // prn_secondary_bits (SymSync::secondary_bits' form; gnsship_trk_start admits only PRNs with a row) instead
+    // of sync[geo].secondary_bits; every other member of the profile still applies.  interchange_iq
+    // (d_interchange_iq, :313, :344): the valid-symbol prompt of the epoch record has I and Q exchanged — by a pass
+    // over the run's records after the loop (trk_abi.hip; the host reads this member, the loop does not, so every
+    // other system's loop is the code it was).
+    int32_t prn_secondary, interchange_iq;
+    uint32_t prn_secondary_bits[kTrkPrnRows][kTrkMaxSecondary / 32];
 };
 
 struct Smoother {

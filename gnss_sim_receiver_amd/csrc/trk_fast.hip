@@ -1130,7 +1130,7 @@ __global__ __launch_bounds__(W * kWave, (fast_waves_per_simd<THRU, W>())) void t
     if (role == kRoleControl) rchan_load(sc, &sc, rc);
     // wave 0's loop parameters in registers for the run (two workgroups per CU have no registers to
     // spare: they keep reading TrkParams)
-    KFast kf = make_kfast(k, sc.geo);
+    KFast kf = make_kfast(k, sc);
     // the sign patterns epoch_pre reads every epoch (bit_at), in LDS: a global load there is a
     // dependent memory round trip on the loop's chain
     __shared__ uint32_t sec_bits[kTrkMaxSecondary / 32], dsec_bits[kTrkMaxSecondary / 32];

@@ -212,6 +212,16 @@ __device__ __forceinline__ const LoopSet& loopset(const TrkParams& k, const RCha
 __device__ __forceinline__ const SymSync& syncset(const TrkParams& k, const TrkChannel& c) { return k.sync[c.geo]; }
 __device__ __forceinline__ const SymSync& syncset(const TrkParams& k, const RChan& c) { return k.sync[uni(c.geo)]; }
 __device__ __forceinline__ const SymSync& syncset(const TrkParams& k, const LoopRegs& c) { return k.sync[c.geo]; }
+// The pattern the channel's secondary code is synchronised on and stripped with: its profile's, or — where the
+// secondary code belongs to the satellite (TrkParams::prn_secondary: Galileo E5a-Q / E5b-Q) — the channel's PRN row.
+__device__ __forceinline__ const uint32_t* secondary_bits(const TrkParams& k, const TrkChannel& c)
+{
+    return k.prn_secondary ? k.prn_secondary_bits[c.prn] : k.sync[c.geo].secondary_bits;
+}
+__device__ __forceinline__ const uint32_t* secondary_bits(const TrkParams& k, const RChan& c)
+{
+    return uni(k.prn_secondary) ? k.prn_secondary_bits[uni(static_cast<int>(c.prn))] : k.sync[uni(c.geo)].secondary_bits;
+}
 
 // The parameters one channel's loop reads, as register values for a whole run (the fast kernel's
 // control wave): inside the epoch loop every TrkParams member is otherwise a dependent scalar load on
@@ -238,10 +248,11 @@ struct KFast {
     int32_t code_length_chips, veml, track_pilot, fp_order, has_if;
     float spc_n;
     LoopSet ls_w, ls_n;  // the wide set and this channel's narrow set (k.ls[0], k.ls[1 + geo])
-    SyncView sv;         // k.sync[geo]
+    SyncView sv;         // k.sync[geo], its secondary pattern the channel's own (secondary_bits)
 };
-__device__ __forceinline__ KFast make_kfast(const TrkParams& k, int geo)
+__device__ __forceinline__ KFast make_kfast(const TrkParams& k, const TrkChannel& c)
 {
+    const int geo = c.geo;
     KFast f;
     f.conf.fs_in = k.conf.fs_in;
     f.conf.pull_in_time_s = k.conf.pull_in_time_s;
@@ -271,11 +282,13 @@ __device__ __forceinline__ KFast make_kfast(const TrkParams& k, int geo)
     f.ls_w = k.ls[0];
     f.ls_n = k.ls[1 + g];
     const SymSync& s = k.sync[g];
-    f.sv = SyncView{s.symbols_per_bit, s.secondary, s.secondary_len, s.data_secondary_len, s.extend, s.T_ext, s.secondary_bits, s.data_secondary_bits};
+    f.sv = SyncView{s.symbols_per_bit, s.secondary, s.secondary_len, s.data_secondary_len, s.extend, s.T_ext,
+        k.prn_secondary ? k.prn_secondary_bits[uni(static_cast<int>(c.prn))] : s.secondary_bits, s.data_secondary_bits};
     return f;
 }
 __device__ __forceinline__ LoopSet loopset(const KFast& k, const RChan& c) { return uni(c.narrow) ? k.ls_n : k.ls_w; }
 __device__ __forceinline__ const SyncView& syncset(const KFast& k, const RChan&) { return k.sv; }
+__device__ __forceinline__ const uint32_t* secondary_bits(const KFast& k, const RChan&) { return k.sv.secondary_bits; }
 
 // The members cn0_and_tracking_lock_status owns (prompt buffer, smoothers, fail counters, CN0 and
 // lock test) and the sign history live in memory for both channel forms.
@@ -697,7 +710,7 @@ __device__ GNSSHIP_LOOP_INLINE bool acquire_secondary(const K& k, C& c)
     const uint32_t* bits = mem(c).sign_bits;
     for (int i = 0; i < syncset(k, c).secondary_len; i++) {
         const int neg = bit_at(bits, i);
-        const int one = bit_at(syncset(k, c).secondary_bits, i);
+        const int one = bit_at(secondary_bits(k, c), i);
         corr += (neg ^ one) ? 1 : -1;  // +1 for (real < 0, '0') and (real ≥ 0, '1')
     }
     if (abs(corr) == syncset(k, c).secondary_len) {
@@ -804,7 +817,7 @@ __device__ __forceinline__ void save_correlation_results(const K& k, C& c, const
     const int eo = k.veml ? 2 : 0;
     float sgn = 1.0f;
     if (syncset(k, c).secondary) {
-        sgn = bit_at(syncset(k, c).secondary_bits, c.current_symbol) ? -1.0f : 1.0f;
+        sgn = bit_at(secondary_bits(k, c), c.current_symbol) ? -1.0f : 1.0f;
         c.current_symbol = next_mod(c.current_symbol, syncset(k, c).secondary_len);
     }
     if (k.veml) {

@@ -480,6 +480,64 @@ def gps_l2c_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
     return c
 
 
+def _e5_pcps_acquisition(ctx, fs_in, doppler_max, doppler_step, sampled_ms, kw):
+    from . import codes
+    code_length = int(np.floor(fs_in / (codes.GALILEO_E5A_CODE_CHIP_RATE_CPS / codes.GALILEO_E5A_CODE_LENGTH_CHIPS)))
+    return PcpsAcquisition(ctx, fs_in, sampled_ms * code_length, doppler_max, doppler_step, chip_rate=codes.GALILEO_E5A_CODE_CHIP_RATE_CPS,
+                           ms_per_code=1, **kw)
+
+
+def galileo_e5a_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, doppler_step: int, sampled_ms: int = 1,
+                                 acquire_pilot: bool = False, acquire_iq: bool = False, **kw) -> PcpsAcquisition:
+    """GalileoE5aPcpsAcquisition's parameters (galileo_e5a_pcps_acquisition.cc:48-76): ms_per_code 1, the E5a chip
+    rate, code_length = floor(fs / 1000) samples and a search window of sampled_ms of them.  The local code is
+    codes.galileo_e5a_acquisition_code(prn, fs_in, sampled_ms, acquire_pilot, acquire_iq) — the sampled "5I" code,
+    "5Q" with acquire_pilot, "5X" with acquire_iq (which overrides acquire_pilot, :152-180); the two flags are
+    kept on the returned object so that callers build the matching code.  A front end faster than
+    codes.GALILEO_E5A_OPT_ACQ_FS_SPS designs its resampler with acq_resampler_design(lib, fs, that rate) and
+    passes the resampled rate here, as for GPS L5."""
+    acq = _e5_pcps_acquisition(ctx, fs_in, doppler_max, doppler_step, sampled_ms, kw)
+    acq.acquire_iq = bool(acquire_iq)
+    acq.acquire_pilot = bool(acquire_pilot) and not acq.acquire_iq
+    return acq
+
+
+def galileo_e5b_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, doppler_step: int, sampled_ms: int = 1,
+                                 acquire_pilot: bool = False, acquire_iq: bool = False, **kw) -> PcpsAcquisition:
+    """GalileoE5bPcpsAcquisition's parameters: galileo_e5a_pcps_acquisition's twin with the "7I" / "7Q" / "7X" codes
+    (codes.galileo_e5b_acquisition_code) and codes.GALILEO_E5B_OPT_ACQ_FS_SPS."""
+    acq = _e5_pcps_acquisition(ctx, fs_in, doppler_max, doppler_step, sampled_ms, kw)
+    acq.acquire_iq = bool(acquire_iq)
+    acq.acquire_pilot = bool(acquire_pilot) and not acq.acquire_iq
+    return acq
+
+
+def _e5_trk_conf(system: int, i_secondary_len: int, fs_in: float, kw) -> "abi.TrkConf":
+    from . import codes
+    vl = int(round(fs_in / (codes.GALILEO_E5A_CODE_CHIP_RATE_CPS / codes.GALILEO_E5A_CODE_LENGTH_CHIPS)))
+    kw.setdefault("track_pilot", 1)
+    c = abi.TrkConf.defaults(system, fs_in, vl, **kw)
+    c.extend_correlation_symbols = max(c.extend_correlation_symbols, 1)
+    if not c.track_pilot:
+        c.extend_correlation_symbols = min(c.extend_correlation_symbols, i_secondary_len)
+    return c
+
+
+def galileo_e5a_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
+    """GalileoE5aDllPllTracking's configuration (galileo_e5a_dll_pll_tracking.cc:47-58): vector_length =
+    round(fs / 1000), extend_correlation_symbols at least 1 and, in data-only mode (track_pilot = 0), at most
+    the 20 chips of the I secondary code.  track_pilot = 1 (the default here): tracking code
+    codes.galileo_e5a_q_code_gen_float, data code (start's data_code_id) codes.galileo_e5a_i_code_gen_float, and
+    start's prn selects the pilot's secondary code.  track_pilot = 0: tracking code the I primary."""
+    return _e5_trk_conf(abi.SYS_GAL_E5A, 20, fs_in, kw)
+
+
+def galileo_e5b_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
+    """GalileoE5bDllPllTracking's configuration: as galileo_e5a_trk_conf with the E5b codes and the 4-chip I
+    secondary code (4 symbols per bit)."""
+    return _e5_trk_conf(abi.SYS_GAL_E5B, 4, fs_in, kw)
+
+
 def firdes_low_pass(lib, gain: float, fs: float, cutoff: float, transition: float) -> np.ndarray:
     """gr::filter::firdes::low_pass (Hamming) as the library restates it."""
     n = ctypes.c_int()

@@ -33,15 +33,24 @@ SYSTEMS = {
     "BDS_B3I": (C.BEIDOU_B3I_CODE_RATE_CPS, C.BEIDOU_B3I_CODE_LENGTH_CHIPS, C.BEIDOU_B3I_FREQ_HZ, C.beidou_b3i_code_gen_float),
     # GPS L2C: the L2 CM code alone (no L2 CL), 20 ms per period = one telemetry symbol, no secondary code
     "GPS_L2C": (C.GPS_L2_M_CODE_RATE_CPS, C.GPS_L2_M_CODE_LENGTH_CHIPS, C.GPS_L2_FREQ_HZ, C.gps_l2c_m_code_gen_float),
+    # Galileo E5a / E5b: the tracking code is the Q pilot, the data code the I component (dll_pll_veml_tracking.cc:699-746)
+    "GAL_E5A": (C.GALILEO_E5A_CODE_CHIP_RATE_CPS, C.GALILEO_E5A_CODE_LENGTH_CHIPS, C.GALILEO_E5A_FREQ_HZ, C.galileo_e5a_q_code_gen_float),
+    "GAL_E5B": (C.GALILEO_E5B_CODE_CHIP_RATE_CPS, C.GALILEO_E5B_CODE_LENGTH_CHIPS, C.GALILEO_E5B_FREQ_HZ, C.galileo_e5b_q_code_gen_float),
 }
-DATA_CODES = {"GAL": lambda prn: C.galileo_e1_code_gen_sinboc11_float("1B", prn), "GPS_L5": C.gps_l5i_code_gen_float}
-# secondary codes a system's satellites carry unless the Satellite names its own: (pilot, data component)
-DEFAULT_SECONDARY = {"GPS_L5": (C.GPS_L5Q_NH_CODE_STR, C.GPS_L5I_NH_CODE_STR), "BDS_B3I": (C.BEIDOU_B3I_SECONDARY_CODE_STR, None)}
+DATA_CODES = {"GAL": lambda prn: C.galileo_e1_code_gen_sinboc11_float("1B", prn), "GPS_L5": C.gps_l5i_code_gen_float,
+              "GAL_E5A": C.galileo_e5a_i_code_gen_float, "GAL_E5B": C.galileo_e5b_i_code_gen_float}
+# secondary codes a system's satellites carry unless the Satellite names its own, as a function of the PRN
+# (the Galileo E5 pilots carry one 100-chip code per satellite): (pilot, data component)
+DEFAULT_SECONDARY = {"GPS_L5": lambda prn: (C.GPS_L5Q_NH_CODE_STR, C.GPS_L5I_NH_CODE_STR),
+                     "BDS_B3I": lambda prn: (C.BEIDOU_B3I_SECONDARY_CODE_STR, None),
+                     "GAL_E5A": lambda prn: (C.galileo_e5a_q_secondary(prn), C.GALILEO_E5A_I_SECONDARY_CODE),
+                     "GAL_E5B": lambda prn: (C.galileo_e5b_q_secondary(prn), C.GALILEO_E5B_I_SECONDARY_CODE)}
 # how the two components combine: Galileo E1 OS (E1B − E1C)/√2 on one phase; GPS L5 (IS-GPS-705) the
 # data component in phase and the pilot in quadrature, (I5 + j·Q5)/√2
-QUADRATURE_PILOT = {"GPS_L5"}
-# code periods per data symbol where a data component exists (E1-B: 1; L5I: 10 — 100 sps)
-DATA_SYMBOL_PERIODS = {"GAL": 1, "GPS_L5": 10}
+# — and Galileo E5a / E5b alike, (d·sec_I·c_I + j·sec_Q[prn]·c_Q)/√2
+QUADRATURE_PILOT = {"GPS_L5", "GAL_E5A", "GAL_E5B"}
+# code periods per data symbol where a data component exists (E1-B: 1; L5I: 10 — 100 sps; E5a-I: 20; E5b-I: 4)
+DATA_SYMBOL_PERIODS = {"GAL": 1, "GPS_L5": 10, "GAL_E5A": 20, "GAL_E5B": 4}
 # code periods per navigation bit of a single-component signal when not 20 (L2 CM: one 20 ms period per symbol)
 BIT_PERIODS = {"GPS_L2C": 1}
 
@@ -77,11 +86,12 @@ class Satellite:
             self.code = SYSTEMS[self.system][3](self.prn)
         if self.code_data is None and self.system in DATA_CODES:
             self.code_data = DATA_CODES[self.system](self.prn)
-        if self.system in DEFAULT_SECONDARY:
+        if self.system in DEFAULT_SECONDARY and (self.secondary is None or self.secondary_data is None):
+            pilot, data = DEFAULT_SECONDARY[self.system](self.prn)
             if self.secondary is None:
-                self.secondary = DEFAULT_SECONDARY[self.system][0]
+                self.secondary = pilot
             if self.secondary_data is None:
-                self.secondary_data = DEFAULT_SECONDARY[self.system][1]
+                self.secondary_data = data
 
     @property
     def chip_rate(self):

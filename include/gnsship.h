@@ -185,6 +185,31 @@ int gnsship_gps_l2c_m_code_gen_float(float* dest, int32_t prn);
 /* gps_l2c_m_code_gen_complex_sampled (:75): dest = n complex (code in imag), chip index ceil(ts·(i+1)/tc) − 1 in
  * float; returns n or <0 */
 int gnsship_gps_l2c_m_code_gen_complex_sampled(float* dest, uint32_t prn, int32_t sampling_freq);
+/* galileo_e5_a_code_gen_complex_primary / galileo_e5_b_… (galileo_e5_signal_replica.cc:31-93, :125-187): dest =
+ * 10230 complex, chips ±1.  signal_id "5I" / "5Q" ("7I" / "7Q"): that component in the real part, the imaginary part
+ * zero; "5X" ("7X"): the I component in the real part and the Q component in the imaginary part.  PRN 1..50 and one of
+ * those signal ids, GNSSHIP_E_INVAL otherwise (the reference leaves dest untouched there). */
+int gnsship_galileo_e5_a_code_gen_complex_primary(float* dest, int32_t prn, const char* signal_id);
+int gnsship_galileo_e5_b_code_gen_complex_primary(float* dest, int32_t prn, const char* signal_id);
+/* galileo_e5_a_code_gen_complex_sampled / galileo_e5_b_… (:96-122, :190-216): dest = n complex.  The primary is
+ * sampled by resampler() (gnss_signal_replica.cc:275-290): chip (int)((1/fs·(i + 1))·10.23e6 + 1) − 1 in float, the
+ * last sample forced to the last chip, and not at all when sampling_freq == 10230000; then rotated by
+ * ((10230 − chip_shift) % 10230)·n / 10230 samples.  Returns n or <0. */
+int gnsship_galileo_e5_a_code_gen_complex_sampled(float* dest, uint32_t prn, const char* signal_id, int32_t sampling_freq, uint32_t chip_shift);
+int gnsship_galileo_e5_b_code_gen_complex_sampled(float* dest, uint32_t prn, const char* signal_id, int32_t sampling_freq, uint32_t chip_shift);
+/* The four primaries as the tracker's code-bank replicas: dest[10230] = ±1, PRN 1..50 */
+int gnsship_galileo_e5a_i_code_gen_float(float* dest, int32_t prn);
+int gnsship_galileo_e5a_q_code_gen_float(float* dest, int32_t prn);
+int gnsship_galileo_e5b_i_code_gen_float(float* dest, int32_t prn);
+int gnsship_galileo_e5b_q_code_gen_float(float* dest, int32_t prn);
+/* Secondary codes as '0' / '1' strings with a terminating NUL.  I components (Galileo_E5a.h:3581, Galileo_E5b.h:53):
+ * dest[21] / dest[5], one fixed code each.  Q (pilot) components: dest[101], one 100-chip code per PRN — E5b-Q for
+ * PRN 1..50, E5a-Q for PRN 1..47 (GALILEO_E5A_Q_SECONDARY_CODE ends there; the reference has no pattern for PRN
+ * 48..50, and neither has this library: GNSSHIP_E_INVAL). */
+int gnsship_galileo_e5a_i_secondary_code(char* dest);
+int gnsship_galileo_e5b_i_secondary_code(char* dest);
+int gnsship_galileo_e5a_q_secondary_code(char* dest, int32_t prn);
+int gnsship_galileo_e5b_q_secondary_code(char* dest, int32_t prn);
 /* samples per code period: (int)(fs / (chip_rate / code_len)) as the generators compute it */
 int gnsship_code_samples_per_code(int32_t chip_rate, int32_t code_len, int32_t fs);
 
@@ -440,6 +465,21 @@ int gnsship_cond_destroy(gnsship_cond* c);
  * per telemetry symbol (vector_length = fs / 50, the loop filters updated every 20 ms), no secondary code, no
  * pilot: track_pilot is forced to 0 and extend_correlation_symbols to 1. */
 #define GNSSHIP_SYS_GPS_L2C 5
+/* Galileo E5a ("5X", dll_pll_veml_tracking.cc:292-322, :699-722; galileo_e5a_dll_pll_tracking.cc:47-58) and E5b
+ * ("7X", :323-353, :723-746): 10230 chips at 10.23 Mcps, 1 ms, 3 taps; slope, spc and y_intercept set as the block
+ * sets them (1, early_late_space_chips, 1); extend_correlation_symbols raised to 1 at least.
+ *   track_pilot = 1: 3 taps on the Q primary (start's code_id) + the I primary on the data prompt (data_code_id) —
+ *     the GPS L5 layout.  The pilot's 100-chip secondary code belongs to the satellite: start's prn selects it
+ *     (E5a: 1..47, E5b: 1..50; GNSSHIP_E_INVAL otherwise).  The I secondary code (E5a 20 chips / 20 symbols per bit,
+ *     E5b 4 / 4) is stripped from the data prompt.  d_interchange_iq (:313, :344, :1945-1949, :1997-2001): the
+ *     valid-symbol prompt_i / prompt_q of gnsship_trk_epoch are the data prompt's imaginary / real part; dump
+ *     records (log_data) are not exchanged.
+ *   track_pilot = 0: 3 taps on the I primary, no data prompt — the BeiDou B3I layout; the I secondary code is the
+ *     synchronisation pattern and is removed from the taps, the symbol prompt sums the epochs' own prompts over
+ *     symbols-per-bit epochs (d_data_secondary_code_length stays 0), no exchange, and extend_correlation_symbols is
+ *     capped at the I secondary length (20 / 4).  start's prn must be in 1..50. */
+#define GNSSHIP_SYS_GAL_E5A 6
+#define GNSSHIP_SYS_GAL_E5B 7
 
 typedef struct gnsship_trk_conf { /* Dll_Pll_Conf (dll_pll_conf.h:33-80), same names and units */
     double fs_in;
@@ -494,18 +534,19 @@ typedef struct gnsship_trk_conf { /* Dll_Pll_Conf (dll_pll_conf.h:33-80), same n
 
 typedef struct gnsship_trk_start_args { /* Gnss_Synchro fields start_tracking reads (:647-649) */
     int32_t code_id;      /* code-bank entry of the tracking replica (pilot for E1) */
-    int32_t data_code_id; /* E1 with track_pilot and GPS L5: data replica (E1-B / L5I); otherwise ignored */
+    int32_t data_code_id; /* E1 / E5a / E5b with track_pilot and GPS L5: data replica (E1-B / E5a-I / E5b-I / L5I); otherwise ignored */
     double acq_delay_samples;
     double acq_doppler_hz;
     uint64_t acq_samplestamp_samples;
     uint64_t first_sample; /* nitems_read when the block first runs after start (state-1 pull-in) */
-    int32_t prn;           /* Gnss_Synchro::PRN: BeiDou B1I PRN 1-5 and 59+ are GEO satellites (:765-781) */
+    int32_t prn;           /* Gnss_Synchro::PRN: BeiDou B1I PRN 1-5 and 59+ are GEO satellites (:765-781);
+                              Galileo E5a / E5b: selects the pilot's secondary code (:706, :730) */
     int32_t reserved;      /* 0 */
 } gnsship_trk_start_args;
 
 typedef struct gnsship_trk_epoch { /* one general_work call of one channel (Gnss_Synchro subset) */
     uint64_t sample_counter;       /* nitems_read at the epoch start */
-    double prompt_i, prompt_q;     /* valid when flags & 1 (state 4 symbol output) */
+    double prompt_i, prompt_q;     /* valid when flags & 1 (state 4 symbol output); E5a / E5b with track_pilot: exchanged */
     double code_phase_samples;     /* d_rem_code_phase_samples */
     double carrier_phase_rads;     /* d_acc_carrier_phase_rad */
     double carrier_doppler_hz;

@@ -9,6 +9,7 @@
 #define GNSSHIP_CPP_HPP
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <complex>
 #include <cstdint>
@@ -864,6 +865,79 @@ inline std::vector<std::complex<float>> acquisition_code_10230(uint32_t prn, con
 inline std::vector<std::complex<float>> beidou_b3i_acquisition_code(uint32_t prn, const Acq_Conf& conf) { return acquisition_code_10230(prn, conf, false); }
 inline std::vector<std::complex<float>> gps_l2c_m_acquisition_code(uint32_t prn, const Acq_Conf& conf) { return acquisition_code_10230(prn, conf, true); }
 
+// ---- Galileo E5a / E5b (galileo_e5_signal_replica.h, Galileo_E5a.h, Galileo_E5b.h, galileo_e5a_pcps_acquisition.cc:48-76,
+// :145-180 and its E5b twin) ----
+constexpr double GALILEO_E5A_FREQ_HZ = 1176.45e6;
+constexpr double GALILEO_E5B_FREQ_HZ = 1207.14e6;
+constexpr double GALILEO_E5A_CODE_CHIP_RATE_CPS = 10.23e6;
+constexpr double GALILEO_E5B_CODE_CHIP_RATE_CPS = 10.23e6;
+constexpr int32_t GALILEO_E5A_CODE_LENGTH_CHIPS = 10230;
+constexpr int32_t GALILEO_E5B_CODE_LENGTH_CHIPS = 10230;
+constexpr int32_t GALILEO_E5A_I_SECONDARY_CODE_LENGTH = 20;
+constexpr int32_t GALILEO_E5B_I_SECONDARY_CODE_LENGTH = 4;
+constexpr int32_t GALILEO_E5A_Q_SECONDARY_CODE_LENGTH = 100;
+constexpr int32_t GALILEO_E5B_Q_SECONDARY_CODE_LENGTH = 100;
+constexpr uint32_t GALILEO_E5A_OPT_ACQ_FS_SPS = 10000000;
+constexpr uint32_t GALILEO_E5B_OPT_ACQ_FS_SPS = 10000000;
+// signal_id "5I" / "5Q" / "5X" ("7I" / "7Q" / "7X"): a single component in the real part, X = I in the real and Q in
+// the imaginary part.  false / negative: PRN outside 1..50 or another signal id (the reference writes nothing there).
+inline bool galileo_e5_a_code_gen_complex_primary(std::complex<float>* dest, int32_t prn, const std::array<char, 3>& signal_id)
+{
+    return gnsship_galileo_e5_a_code_gen_complex_primary(reinterpret_cast<float*>(dest), prn, signal_id.data()) == GNSSHIP_OK;
+}
+inline bool galileo_e5_b_code_gen_complex_primary(std::complex<float>* dest, int32_t prn, const std::array<char, 3>& signal_id)
+{
+    return gnsship_galileo_e5_b_code_gen_complex_primary(reinterpret_cast<float*>(dest), prn, signal_id.data()) == GNSSHIP_OK;
+}
+inline int galileo_e5_a_code_gen_complex_sampled(std::complex<float>* dest, uint32_t prn, const std::array<char, 3>& signal_id,
+    int32_t sampling_freq, uint32_t chip_shift)
+{
+    return gnsship_galileo_e5_a_code_gen_complex_sampled(reinterpret_cast<float*>(dest), prn, signal_id.data(), sampling_freq, chip_shift);
+}
+inline int galileo_e5_b_code_gen_complex_sampled(std::complex<float>* dest, uint32_t prn, const std::array<char, 3>& signal_id,
+    int32_t sampling_freq, uint32_t chip_shift)
+{
+    return gnsship_galileo_e5_b_code_gen_complex_sampled(reinterpret_cast<float*>(dest), prn, signal_id.data(), sampling_freq, chip_shift);
+}
+// GALILEO_E5A_Q_SECONDARY_CODE[prn − 1] / GALILEO_E5B_Q_SECONDARY_CODE[prn − 1] as a '0' / '1' string; empty: no such
+// code (PRN outside 1..50; E5a-Q: outside 1..47, where the reference's table ends)
+inline std::string galileo_e5a_q_secondary_code(int32_t prn)
+{
+    char s[101];
+    return gnsship_galileo_e5a_q_secondary_code(s, prn) == GNSSHIP_OK ? std::string(s) : std::string();
+}
+inline std::string galileo_e5b_q_secondary_code(int32_t prn)
+{
+    char s[101];
+    return gnsship_galileo_e5b_q_secondary_code(s, prn) == GNSSHIP_OK ? std::string(s) : std::string();
+}
+// GalileoE5aPcpsAcquisition's / GalileoE5bPcpsAcquisition's Acq_Conf: ms_per_code 1, the E5 chip rate, the automatic
+// resampler designed for GALILEO_E5A_OPT_ACQ_FS_SPS (E5b's is the same rate).
+inline Acq_Conf galileo_e5_acq_conf(Acq_Conf conf)
+{
+    conf.ms_per_code = 1U;
+    conf.chips_per_second = static_cast<uint32_t>(GALILEO_E5A_CODE_CHIP_RATE_CPS);
+    conf.SetDerivedParams();
+    conf.ConfigureAutomaticResampler(static_cast<double>(GALILEO_E5A_OPT_ACQ_FS_SPS));
+    return conf;
+}
+// set_local_code of the two adapters (:145-180): code_length = floor(fs / 1000) samples of the sampled "5I" code
+// ("5Q" with acquire_pilot, "5X" with acquire_iq, which overrides it; band_b: the "7…" codes), copied sampled_ms times.
+inline std::vector<std::complex<float>> galileo_e5_acquisition_code(uint32_t prn, const Acq_Conf& conf, bool band_b, bool acquire_pilot = false,
+    bool acquire_iq = false)
+{
+    const int64_t fs = conf.resampled_fs ? conf.resampled_fs : conf.fs_in;
+    const auto code_length = static_cast<size_t>(std::floor(static_cast<double>(fs) / (GALILEO_E5A_CODE_CHIP_RATE_CPS / GALILEO_E5A_CODE_LENGTH_CHIPS)));
+    const auto vector_length = static_cast<size_t>(std::floor(conf.sampled_ms * (static_cast<float>(fs) * 0.001F)) * (conf.bit_transition_flag ? 2.0 : 1.0));
+    const std::array<char, 3> id = {{band_b ? '7' : '5', acquire_iq ? 'X' : acquire_pilot ? 'Q' : 'I', '\0'}};
+    std::vector<std::complex<float>> one(code_length), out(std::max(vector_length, code_length * conf.sampled_ms));
+    const int rc = band_b ? galileo_e5_b_code_gen_complex_sampled(one.data(), prn, id, static_cast<int32_t>(fs), 0)
+                          : galileo_e5_a_code_gen_complex_sampled(one.data(), prn, id, static_cast<int32_t>(fs), 0);
+    if (rc < 0) return {};
+    for (uint32_t i = 0; i < conf.sampled_ms; i++) std::copy(one.begin(), one.end(), out.begin() + static_cast<size_t>(i) * code_length);
+    return out;
+}
+
 // Mirror of Dll_Pll_Conf (src/algorithms/tracking/libs/dll_pll_conf.h:33-80): same field names and
 // defaults (FLAGS_* defaults from gnss_sdr_flags.cc:48-57 for the lock-detector fields).
 struct Dll_Pll_Conf {
@@ -884,8 +958,9 @@ struct Dll_Pll_Conf {
     int32_t cn0_samples{20}, cn0_smoother_samples{200}, carrier_lock_test_smoother_samples{25}, cn0_min{25};
     int32_t max_code_lock_fail{50}, max_carrier_lock_fail{5000};
     bool carrier_aiding{true}, track_pilot{true};
-    // 'G' GPS (signal "1C": L1 C/A, "L5": the L5Q pilot + L5I prompt, "2S": L2C, the L2 CM code), 'E' Galileo E1,
-    // 'C' BeiDou (signal "B3": B3I, anything else: B1I)
+    // 'G' GPS (signal "1C": L1 C/A, "L5": the L5Q pilot + L5I prompt, "2S": L2C, the L2 CM code), 'E' Galileo (signal
+    // "5X": E5a, "7X": E5b — the Q pilot + the I prompt with track_pilot, the I component alone without — anything else:
+    // E1), 'C' BeiDou (signal "B3": B3I, anything else: B1I)
     char system{'G'};
     char signal[3]{"1C"};
     // Not a Dll_Pll_Conf member: the reference's correlations follow the volk_gnsssdr rotator variant
@@ -943,7 +1018,9 @@ public:
         const bool l5 = conf.system == 'G' && conf.signal[0] == 'L' && conf.signal[1] == '5';  // GpsL5DllPllTracking (system 'G', signal "L5")
         const bool b3 = conf.system == 'C' && conf.signal[0] == 'B' && conf.signal[1] == '3';  // BeidouB3iDllPllTracking
         const bool l2c = conf.system == 'G' && conf.signal[0] == '2' && conf.signal[1] == 'S';  // GpsL2MDllPllTracking
-        c.system = conf.system == 'E' ? GNSSHIP_SYS_GAL_E1 : b3 ? GNSSHIP_SYS_BDS_B3I : conf.system == 'C' ? GNSSHIP_SYS_BDS_B1I
+        const bool e5a = conf.system == 'E' && conf.signal[0] == '5' && conf.signal[1] == 'X';  // GalileoE5aDllPllTracking
+        const bool e5b = conf.system == 'E' && conf.signal[0] == '7' && conf.signal[1] == 'X';  // GalileoE5bDllPllTracking
+        c.system = e5a ? GNSSHIP_SYS_GAL_E5A : e5b ? GNSSHIP_SYS_GAL_E5B : conf.system == 'E' ? GNSSHIP_SYS_GAL_E1 : b3 ? GNSSHIP_SYS_BDS_B3I : conf.system == 'C' ? GNSSHIP_SYS_BDS_B1I
                    : l5 ? GNSSHIP_SYS_GPS_L5 : l2c ? GNSSHIP_SYS_GPS_L2C : GNSSHIP_SYS_GPS_L1CA;
         // gps_l5_dll_pll_tracking.cc:49-53 (track_pilot = false — the block's interchange_iq — is refused by gnsship_trk_create)
         if (l5 && c.extend_correlation_symbols < 1) c.extend_correlation_symbols = 1;
@@ -951,6 +1028,13 @@ public:
             c.vector_length = static_cast<uint32_t>(std::round(conf.fs_in / (BEIDOU_B3I_CODE_RATE_CPS / BEIDOU_B3I_CODE_LENGTH_CHIPS)));
             c.extend_correlation_symbols = std::min(std::max(c.extend_correlation_symbols, 1), 20);
             c.track_pilot = 0;
+        }
+        if (e5a || e5b) {  // galileo_e5a_dll_pll_tracking.cc:47-58 and its E5b twin
+            c.vector_length = static_cast<uint32_t>(std::round(conf.fs_in / (GALILEO_E5A_CODE_CHIP_RATE_CPS / GALILEO_E5A_CODE_LENGTH_CHIPS)));
+            c.extend_correlation_symbols = std::max(c.extend_correlation_symbols, 1);
+            if (!c.track_pilot)
+                c.extend_correlation_symbols = std::min(c.extend_correlation_symbols,
+                    e5a ? GALILEO_E5A_I_SECONDARY_CODE_LENGTH : GALILEO_E5B_I_SECONDARY_CODE_LENGTH);
         }
         if (l2c) {  // gps_l2_m_dll_pll_tracking.cc:47-59: one 20 ms code per epoch, no extension, no pilot
             c.vector_length = static_cast<uint32_t>(std::round(conf.fs_in / (GPS_L2_M_CODE_RATE_CPS / GPS_L2_M_CODE_LENGTH_CHIPS)));
@@ -968,7 +1052,7 @@ public:
     }
     // start_tracking for one channel: the local code(s) as the block generates them (d_tracking_code,
     // d_data_code; code_len = samples per chip × chips) and the acquisition's Gnss_Synchro fields
-    // (prn selects the BeiDou GEO symbol synchronisation).
+    // (prn selects the BeiDou GEO symbol synchronisation and the Galileo E5a / E5b pilot's secondary code).
     bool start_tracking(int channel, const float* tracking_code, const float* data_code, int code_len, double acq_delay_samples,
         double acq_doppler_hz, uint64_t acq_samplestamp_samples, uint64_t first_sample, int prn = 0)
     {

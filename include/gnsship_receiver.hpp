@@ -99,7 +99,8 @@ private:
 
 // The configuration keys of the 1C channels (conf/gnss-sdr_GPS_L1_gr_complex.conf); with trk.signal = "L5"
 // the same keys of the L5 channels (Channels_L5, Acquisition_L5, Tracking_L5), with "2S" of the L2C channels
-// (Channels_2S, ...; vector_length = round(fs / 50)), with trk.system 'C' and trk.signal "B3" of the BeiDou B3I ones.
+// (Channels_2S, ...; vector_length = round(fs / 50)), with trk.system 'C' and trk.signal "B3" of the BeiDou B3I ones,
+// with trk.system 'E' and trk.signal "5X" / "7X" of the Galileo E5a / E5b ones.
 struct Receiver_Conf {
     int channels{1};                     // Channels_1C.count
     int in_acquisition{1};               // Channels.in_acquisition (capped at channels)
@@ -149,6 +150,12 @@ public:
         l2c_ = conf_.trk.system == 'G' && conf_.trk.signal[0] == '2' && conf_.trk.signal[1] == 'S';
         if (b3_) conf_.acq = beidou_b3i_acq_conf(conf_.acq);
         if (l2c_) conf_.acq = gps_l2_m_acq_conf(conf_.acq);
+        // Channels_5X / Channels_7X (system 'E', signal "5X" / "7X"): acquisition on the I component (acquire_pilot and
+        // acquire_iq at their defaults), tracking on the Q pilot with the I component on the data prompt, or — trk.track_pilot
+        // false — on the I component alone
+        e5a_ = conf_.trk.system == 'E' && conf_.trk.signal[0] == '5' && conf_.trk.signal[1] == 'X';
+        e5b_ = conf_.trk.system == 'E' && conf_.trk.signal[0] == '7' && conf_.trk.signal[1] == 'X';
+        if (e5a_ || e5b_) conf_.acq = galileo_e5_acq_conf(conf_.acq);
         n_ = std::max(1, conf_.channels);
         max_acq_ = std::min(std::max(0, conf_.in_acquisition), n_);
         conf_.satellite.resize(static_cast<size_t>(n_), 0U);
@@ -164,7 +171,8 @@ public:
             cond_block_ = block_ * conf_.input_filter.decimation_factor;
             cond_ = std::make_unique<Freq_Xlating_Fir_Filter_Hip>(conf_.input_filter, cond_block_, conf_.device);
         }
-        for (uint32_t p = 1; p <= (b3_ ? 63U : 32U); p++) available_.push_back(p);  // set_signals_list (GPS: 1-32, BeiDou: 1-63)
+        // set_signals_list (GPS: 1-32, BeiDou: 1-63, Galileo: 1-36)
+        for (uint32_t p = 1; p <= (b3_ ? 63U : (e5a_ || e5b_) ? 36U : 32U); p++) available_.push_back(p);
         prn_.assign(static_cast<size_t>(n_), 0U);
         apos_.assign(static_cast<size_t>(n_), 0U);
         fsm_.resize(static_cast<size_t>(n_));
@@ -256,6 +264,20 @@ private:
                     !trk_->start_tracking(c, pilot.data(), data.data(), GPS_L5Q_CODE_LENGTH_CHIPS, s.Acq_delay_samples, s.Acq_doppler_hz,
                         s.Acq_samplestamp_samples, now_, static_cast<int>(prn)))
                     error_ = true;
+            } else if (e5a_ || e5b_) {  // start_tracking :699-746: the X primary's imaginary part tracked, its real part the data code
+                std::vector<std::complex<float>> x(10230);
+                std::vector<float> i_code(10230), q_code(10230);
+                const std::array<char, 3> id = {{e5a_ ? '5' : '7', 'X', '\0'}};
+                bool ok = e5a_ ? galileo_e5_a_code_gen_complex_primary(x.data(), static_cast<int32_t>(prn), id)
+                               : galileo_e5_b_code_gen_complex_primary(x.data(), static_cast<int32_t>(prn), id);
+                for (size_t i = 0; i < x.size(); i++) {
+                    i_code[i] = x[i].real();
+                    q_code[i] = x[i].imag();
+                }
+                const bool pilot = conf_.trk.track_pilot;
+                if (!ok || !trk_->start_tracking(c, pilot ? q_code.data() : i_code.data(), pilot ? i_code.data() : nullptr, 10230, s.Acq_delay_samples,
+                               s.Acq_doppler_hz, s.Acq_samplestamp_samples, now_, static_cast<int>(prn)))
+                    error_ = true;
             } else if (b3_ || l2c_) {  // start_tracking :666-668, :799-801: one replica, no data prompt
                 std::vector<float> code(10230);
                 if (!(b3_ ? beidou_b3i_code_gen_float(code.data(), static_cast<int32_t>(prn), 0) : gps_l2c_m_code_gen_float(code.data(), prn)) ||
@@ -282,6 +304,11 @@ private:
         prn_[static_cast<size_t>(c)] = prn;
         if (l5_) {  // GpsL5iPcpsAcquisition::set_local_code: the search runs on L5I
             const std::vector<std::complex<float>> code = gps_l5i_acquisition_code(prn, conf_.acq);
+            if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
+            return;
+        }
+        if (e5a_ || e5b_) {  // GalileoE5aPcpsAcquisition / GalileoE5bPcpsAcquisition::set_local_code: the search runs on the I component
+            const std::vector<std::complex<float>> code = galileo_e5_acquisition_code(prn, conf_.acq, e5b_);
             if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
             return;
         }
@@ -517,6 +544,7 @@ private:
     bool error_ = false;
     bool l5_ = false;  // GPS L5 channels (acquisition L5I, tracking L5Q pilot + L5I prompt)
     bool b3_ = false, l2c_ = false;  // BeiDou B3I / GPS L2C channels (acquisition and tracking on one code)
+    bool e5a_ = false, e5b_ = false;  // Galileo E5a / E5b channels (acquisition on the I component, tracking on the Q pilot)
 };
 
 }  // namespace gnsship

@@ -3,10 +3,12 @@
 // GNSS-SDR without GNU Radio (include/gnsship_receiver.hpp).  Keys mirror the reference's
 // configuration (conf/gnss-sdr_GPS_L1_gr_complex.conf); GPS L1 C/A channels, or with --signal L5 GPS L5
 // channels (acquisition on L5I, tracking on the L5Q pilot with the L5I data prompt), with --signal 2S GPS L2C
-// channels (the L2 CM code, 20 ms epochs), with --signal B3 BeiDou B3I channels (a GEO satellite follows its PRN).
+// channels (the L2 CM code, 20 ms epochs), with --signal B3 BeiDou B3I channels (a GEO satellite follows its PRN),
+// with --signal 5X / 7X Galileo E5a / E5b channels (acquisition on the I component, tracking on the Q pilot with the I
+// component on the data prompt; the records' symbols have I and Q exchanged, as the block hands them to telemetry).
 //
 //   gnsship_rx --file F [--item gr_complex|ishort|ibyte|float|short|byte|2bit|nsr|2bit-cpx|4bit-cpx]
-//              [--sample-type real|iq|qi] [--big-endian-bytes] [--fs 4000000] [--seconds S] [--signal 1C|L5|2S|B3]
+//              [--sample-type real|iq|qi] [--big-endian-bytes] [--fs 4000000] [--seconds S] [--signal 1C|L5|2S|B3|5X|7X]
 //              [--channels 5] [--in-acquisition 1] [--satellite CH:PRN ...] [--repeat-satellite]
 //              [--pfa 0.01] [--doppler-max 10000] [--doppler-step 250]
 //              [--pll-bw 40] [--dll-bw 4] [--order 3] [--pull-in-time-s 10] [--rotator auto|generic|avx]
@@ -156,9 +158,11 @@ int main(int argc, char** argv)
     if (real_items && !conditioner) usage("real-sampled items need the conditioner (--if-hz / --decimation)");
     const int64_t sample_bits = gnsship_cond_fmt_bits(fmt);
     const int64_t per_byte = sample_bits < 8 ? 8 / sample_bits : 1;  // samples per byte of a packed item
-    if (signal != "1C" && signal != "L5" && signal != "2S" && signal != "B3") usage("--signal must be 1C, L5, 2S or B3");
+    if (signal != "1C" && signal != "L5" && signal != "2S" && signal != "B3" && signal != "5X" && signal != "7X")
+        usage("--signal must be 1C, L5, 2S, B3, 5X or 7X");
     std::snprintf(rc.trk.signal, sizeof(rc.trk.signal), "%s", signal.c_str());
     if (signal == "B3") rc.trk.system = 'C';  // otherwise 'G'
+    if (signal == "5X" || signal == "7X") rc.trk.system = 'E';
     const double fs_file = fs;  // the rate the file is read at; fs from here on is the channels' rate
     if (conditioner) {
         if (decimation < 1 || std::fmod(fs, static_cast<double>(decimation)) != 0.0) usage("--decimation must divide --fs");
