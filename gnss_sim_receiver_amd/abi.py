@@ -137,6 +137,28 @@ class CondBand(ctypes.Structure):
                 ("n_taps", ctypes.c_int)]
 
 
+MIT_PULSE_BLANKING, MIT_NOTCH, MIT_NOTCH_LITE = 0, 1, 2
+MIT_CHAIN_AUTO, MIT_CHAIN_SERIAL, MIT_CHAIN_SPECULATIVE = 0, 1, 2
+MIT_MAX_LENGTH = 1024
+
+
+class MitConf(ctypes.Structure):
+    """gnsship_mit_conf — the arguments of make_pulse_blanking_cc / make_notch_filter / make_notch_filter_lite
+    (pulse_blanking_cc.cc:26, notch_cc.cc:25, notch_lite_cc.cc:26) and the device form of the notch recursion."""
+    _fields_ = [("kind", ctypes.c_int32), ("pfa", ctypes.c_float), ("threshold", ctypes.c_float), ("p_c_factor", ctypes.c_float),
+                ("length", ctypes.c_int32), ("n_segments_est", ctypes.c_int32), ("n_segments_reset", ctypes.c_int32),
+                ("n_segments_coeff", ctypes.c_int32), ("chain_form", ctypes.c_int32)]
+
+
+class MitState(ctypes.Structure):
+    """gnsship_mit_state — the block's members and the chain counters."""
+    _fields_ = [("noise_power", ctypes.c_float), ("threshold", ctypes.c_float), ("n_segments", ctypes.c_int32),
+                ("n_segments_coeff", ctypes.c_int32), ("filter_state", ctypes.c_int32), ("chain_form", ctypes.c_int32),
+                ("samples_in", ctypes.c_uint64), ("samples_out", ctypes.c_uint64), ("pending_samples", ctypes.c_int64),
+                ("chunk_samples", ctypes.c_int64), ("warmup_samples", ctypes.c_int64), ("chunks_speculated", ctypes.c_uint64),
+                ("chunks_replayed", ctypes.c_uint64)]
+
+
 SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5, SYS_BDS_B3I, SYS_GPS_L2C = 0, 1, 2, 3, 4, 5
 SYS_GAL_E5A, SYS_GAL_E5B = 6, 7
 # gnsship_trk_last_engine (include/gnsship.h GNSSHIP_TRK_ENGINE_*)
@@ -315,6 +337,12 @@ _SIGNATURES = {
     "gnsship_cond_reset": ([_vp, ctypes.c_uint64], _i),
     "gnsship_cond_samples_in": ([_vp, ctypes.POINTER(ctypes.c_uint64)], _i),
     "gnsship_cond_destroy": ([_vp], _i),
+    "gnsship_mit_threshold": ([ctypes.c_double, _i, _f32p], _i),
+    "gnsship_mit_create": ([_vp, ctypes.POINTER(MitConf), ctypes.c_int64, _vpp], _i),
+    "gnsship_mit_run": ([_vp, _vp, _i, ctypes.c_int64, _vp, _f32p, _vpp, ctypes.POINTER(ctypes.c_int64)], _i),
+    "gnsship_mit_reset": ([_vp], _i),
+    "gnsship_mit_state_get": ([_vp, ctypes.POINTER(MitState)], _i),
+    "gnsship_mit_destroy": ([_vp], _i),
     "gnsship_trk_create": ([_vp, ctypes.POINTER(TrkConf), _i, _vpp], _i),
     "gnsship_trk_start": ([_vp, _i, ctypes.POINTER(TrkStartArgs)], _i),
     "gnsship_trk_start_many": ([_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(TrkStartArgs)], _i),

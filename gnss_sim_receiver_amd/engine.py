@@ -686,6 +686,85 @@ class SignalConditioner:
             pass
 
 
+def mit_threshold(lib, pfa: float, length: int) -> float:
+    """thres_ of the three mitigation blocks: the upper pfa quantile of chi²(2·length), as a float32 value."""
+    t = ctypes.c_float()
+    rc = lib.gnsship_mit_threshold(pfa, length, ctypes.byref(t))
+    if rc != abi.OK:
+        raise abi.GnssHipError(rc, "gnsship_mit_threshold: pfa in (0, 1), length in 2..1024")
+    return t.value
+
+
+class InterferenceMitigation:
+    """Pulse blanking, notch or notch-lite filter (pulse_blanking_cc / notch_cc / notch_lite_cc) over one CF32
+    stream.  kind: "pulse-blanking" | "notch" | "notch-lite" or abi.MIT_*; chain_form: "auto" | "serial" |
+    "speculative" or abi.MIT_CHAIN_*.  A run returns the complete segments not yet emitted; the rest stays on
+    the device."""
+
+    KINDS = {"pulse-blanking": abi.MIT_PULSE_BLANKING, "notch": abi.MIT_NOTCH, "notch-lite": abi.MIT_NOTCH_LITE}
+    FORMS = {"auto": abi.MIT_CHAIN_AUTO, "serial": abi.MIT_CHAIN_SERIAL, "speculative": abi.MIT_CHAIN_SPECULATIVE}
+
+    def __init__(self, ctx: Context, kind, max_in_samples: int, pfa: float = None, threshold: float = 0.0, p_c_factor: float = 0.9,
+                 length: int = 32, n_segments_est: int = 12500, n_segments_reset: int = 5000000, n_segments_coeff: int = 1,
+                 chain_form="auto"):
+        self.ctx = ctx
+        self.h = None
+        self.kind = self.KINDS[kind] if isinstance(kind, str) else int(kind)
+        if pfa is None:  # the adapters' defaults
+            pfa = 0.04 if self.kind == abi.MIT_PULSE_BLANKING else 0.001
+        form = self.FORMS[chain_form] if isinstance(chain_form, str) else int(chain_form)
+        self.conf = abi.MitConf(kind=self.kind, pfa=pfa, threshold=threshold, p_c_factor=p_c_factor, length=length,
+                                n_segments_est=n_segments_est, n_segments_reset=n_segments_reset, n_segments_coeff=n_segments_coeff,
+                                chain_form=form)
+        self.max_in_samples = int(max_in_samples)
+        h = ctypes.c_void_p()
+        check(ctx.lib.gnsship_mit_create(ctx.h, ctypes.byref(self.conf), self.max_in_samples, ctypes.byref(h)), "gnsship_mit_create", ctx.h)
+        self.h = h
+        self._pending = 0
+
+    def run(self, x, on_device: bool = False, n_in: int = None, dev_dst=None, host: bool = None):
+        """Filter a host complex64 array, or a device pointer with on_device=True and n_in.  Returns the
+        emitted samples as a complex64 array when host (the default for a host input), else (device
+        pointer, n_out)."""
+        if on_device:
+            ptr = ctypes.c_void_p(x)
+        else:
+            x = np.ascontiguousarray(x, np.complex64)
+            n_in = x.size if n_in is None else n_in
+            ptr = ctypes.c_void_p(x.ctypes.data) if x.size else None
+        host = (not on_device) if host is None else host
+        out = np.zeros(max(0, self._pending + n_in), np.complex64) if host else None
+        dev = ctypes.c_void_p()
+        n_out = ctypes.c_int64()
+        check(self.ctx.lib.gnsship_mit_run(self.h, ptr, int(on_device), n_in, ctypes.c_void_p(dev_dst) if dev_dst else None,
+                                           fptr(out.view(np.float32)) if host and out.size else None, ctypes.byref(dev), ctypes.byref(n_out)),
+              "gnsship_mit_run", self.ctx.h)
+        self._pending += n_in - n_out.value
+        self.last_dev = (dev.value, n_out.value)
+        return out[:n_out.value] if host else self.last_dev
+
+    def reset(self):
+        check(self.ctx.lib.gnsship_mit_reset(self.h), "gnsship_mit_reset", self.ctx.h)
+        self._pending = 0
+
+    def state(self) -> dict:
+        st = abi.MitState()
+        check(self.ctx.lib.gnsship_mit_state_get(self.h, ctypes.byref(st)), "gnsship_mit_state_get", self.ctx.h)
+        return {name: getattr(st, name) for name, _ in abi.MitState._fields_}
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.gnsship_mit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.close()
+        except Exception:
+            pass
+
+
 class DllPllVemlTracking:
     """dll_pll_veml_tracking (dll_pll_veml_tracking.cc) for up to ``max_channels`` channels, the
     per-epoch loop resident on the device: ``start_tracking`` → :meth:`start`, ``general_work``

@@ -436,6 +436,90 @@ int gnsship_cond_samples_in(gnsship_cond* c, uint64_t* n);
 int gnsship_cond_destroy(gnsship_cond* c);
 
 /* ---------------------------------------------------------------------------------------------
+ * Interference mitigation: the Signal_Conditioner's other InputFilter choices, Pulse_Blanking_Filter,
+ * Notch_Filter and Notch_Filter_Lite (src/algorithms/input_filter/adapters/{pulse_blanking_filter,
+ * notch_filter,notch_filter_lite}.cc; blocks gnuradio_blocks/{pulse_blanking_cc,notch_cc,notch_lite_cc}.cc).
+ * CF32 in, CF32 out.  Each block is defined on the stream, not on the scheduler's buffers: the stream is
+ * cut into segments of `length` samples from its first sample, every segment goes through the block's
+ * state machine in order, a run emits every complete segment not yet emitted and keeps the rest (and all
+ * state) on the device, so the same stream cut into runs anywhere gives bit-identical output and state.
+ *   pulse blanking (pulse_blanking_cc.cc:57-98): segment energy E = serial float sum of re*re + im*im;
+ *     estimation noise = (float(n)*noise + E/float(2*length))/float(n + 1); blanked when E/noise > thres.
+ *   notch (notch_cc.cc:63-121): the block advances its input pointer by one sample without a history
+ *     (:72), so output sample k is formed from input sample k + 1 with input sample k as the previous one;
+ *     restated as written: segment s is complete once input sample (s + 1)*length has arrived.
+ *     out = (x - z0*prev) + (p_c*z0)*last_out, z0 = (cosf(a), sinf(a)), a = atan2f of x*conj(prev) (:95-101).
+ *   notch lite (notch_lite_cc.cc:71-138): set_history(2): output k from input k, previous k - 1, zero
+ *     before the stream; one z0 per n_segments_coeff segments from the mean of the two end angles (:104-112).
+ *   estimation phase of both notches (:77-83 / :85-91): unnormalised forward DFT, VOLK's generic
+ *     power spectrum 10*log10f(|X|^2 + 1e-20) and spectral noise floor with the 15 dB exclusion,
+ *     pow(10, dB/10)/(2*length).  Not bit-comparable (DFT order); everything else is. */
+#define GNSSHIP_MIT_PULSE_BLANKING 0
+#define GNSSHIP_MIT_NOTCH 1
+#define GNSSHIP_MIT_NOTCH_LITE 2
+/* How the notches' one-pole recursion y[n] = b[n] + a[n]*y[n-1] runs on the device; same bits either way.
+ * SERIAL: one lane per maximal run of filtered segments.  SPECULATIVE: filtered runs cut into chunks, each
+ * started from the zero state warmup_samples early, confirmed bitwise against its predecessor's final
+ * state and replayed serially where refuted.  AUTO: see DESIGN.md §8. */
+#define GNSSHIP_MIT_CHAIN_AUTO 0
+#define GNSSHIP_MIT_CHAIN_SERIAL 1
+#define GNSSHIP_MIT_CHAIN_SPECULATIVE 2
+#define GNSSHIP_MIT_MAX_LENGTH 1024
+#define GNSSHIP_MIT_MAX_IN_SAMPLES (1LL << 30)
+typedef struct gnsship_mit gnsship_mit;
+/* make_pulse_blanking_cc(pfa, length, n_segments_est, n_segments_reset) (pulse_blanking_cc.cc:26),
+ * make_notch_filter(pfa, p_c_factor, length, n_segments_est, n_segments_reset) (notch_cc.cc:25),
+ * make_notch_filter_lite(p_c_factor, pfa, length, n_segments_est, n_segments_reset, n_segments_coeff)
+ * (notch_lite_cc.cc:26). */
+typedef struct gnsship_mit_conf {
+    int32_t kind;              /* GNSSHIP_MIT_*                                                      */
+    float pfa;                 /* thres_ = upper pfa quantile of chi^2(2*length), unless threshold > 0 */
+    float threshold;           /* > 0: thres_ itself, pfa unused; 0: from pfa                        */
+    float p_c_factor;          /* notches: pole radius                                               */
+    int32_t length;            /* samples per segment, 2..GNSSHIP_MIT_MAX_LENGTH                     */
+    int32_t n_segments_est;    /* segments of a noise estimation window, >= 1                        */
+    int32_t n_segments_reset;  /* n_segments_ above this restarts the estimate                       */
+    int32_t n_segments_coeff;  /* notch lite: segments per z0 update, >= 1                           */
+    int32_t chain_form;        /* GNSSHIP_MIT_CHAIN_*                                                */
+} gnsship_mit_conf;
+typedef struct gnsship_mit_state {
+    float noise_power;         /* noise_power_estimation_ / noise_pow_est_                           */
+    float threshold;           /* thres_                                                             */
+    int32_t n_segments;        /* n_segments_                                                        */
+    int32_t n_segments_coeff;  /* n_segments_coeff_ (lite)                                           */
+    int32_t filter_state;      /* last_filtered_ / filter_state_                                     */
+    int32_t chain_form;        /* the form that runs (AUTO resolved)                                 */
+    uint64_t samples_in;       /* since create / reset                                               */
+    uint64_t samples_out;
+    int64_t pending_samples;   /* arrived, not yet emitted                                           */
+    int64_t chunk_samples;     /* speculative form's chunk and warm-up (whole segments)              */
+    int64_t warmup_samples;
+    uint64_t chunks_speculated; /* chunks started from a predicted state / of those, replayed        */
+    uint64_t chunks_replayed;
+} gnsship_mit_state;
+/* boost::math::quantile(complement(chi_squared(2*length), pfa)) (pulse_blanking_cc.cc:51-52, notch_cc.cc:54-55,
+ * notch_lite_cc.cc:63-64), evaluated in double and rounded to float.  Host only.  E_INVAL for pfa outside
+ * (0, 1) or length outside 2..1024. */
+int gnsship_mit_threshold(double pfa, int length, float* thres);
+/* The block's constructor.  E_INVAL (gnsship_last_error says why) for length outside 2..1024, n_segments_est
+ * < 1, n_segments_coeff < 1 (lite), pfa outside (0, 1) without a threshold, an unknown kind or chain form,
+ * max_in_samples outside 1..GNSSHIP_MIT_MAX_IN_SAMPLES. */
+int gnsship_mit_create(gnsship_ctx* ctx, const gnsship_mit_conf* conf, int64_t max_in_samples, gnsship_mit** out);
+/* general_work over the next n_in CF32 samples of the stream (0 <= n_in <= max_in_samples, else E_INVAL and
+ * no state change).  The complete segments go to dev_dst (a caller's device buffer of at least
+ * pending + n_in samples that does not overlap `in`) or, where NULL, to the handle's own buffer (valid until
+ * the next run); *dev_out / *n_out (may be NULL) report where and how many samples.  host_out (may be NULL,
+ * room for pending + n_in samples): also copied to the host before returning; asynchronous on the context
+ * stream otherwise. */
+int gnsship_mit_run(gnsship_mit* m, const void* in, int in_on_device, int64_t n_in, void* dev_dst, float* host_out,
+    void** dev_out, int64_t* n_out);
+/* A fresh block on a fresh stream: the constructor's state, nothing pending. */
+int gnsship_mit_reset(gnsship_mit* m);
+/* The block's members after everything run so far (waits for the context stream). */
+int gnsship_mit_state_get(gnsship_mit* m, gnsship_mit_state* st);
+int gnsship_mit_destroy(gnsship_mit* m);
+
+/* ---------------------------------------------------------------------------------------------
  * Closed-loop tracking engine: the per-epoch DLL/PLL of dll_pll_veml_tracking
  * resident on the device.  Replaces, for N channels at once, the general_work loop of
  * src/algorithms/tracking/gnuradio_blocks/dll_pll_veml_tracking.cc:1728-2094 around

@@ -409,6 +409,154 @@ private:
     std::vector<int64_t> n_out_;
 };
 
+// The configurations of the interference-mitigation adapters, property names and defaults as there.
+// Pulse_Blanking_Filter (pulse_blanking_filter.cc:37-80).  |IF| > 1 puts a decimation-1
+// freq_xlating_fir_filter_ccf with firdes::low_pass(1, sampling_frequency, bw, tw) in front (:69-80).
+struct Pulse_Blanking_Filter_Conf {
+    float pfa{0.04F};                       // :39-40
+    int length{32};                         // :41-42
+    int segments_est{12500};                // :43-44
+    int segments_reset{5000000};            // :45-46
+    double IF{0.0};                         // :47-49 ("if" / "IF")
+    double sampling_frequency{4000000.0};   // :72-73
+    double bw{2000000.0};                   // :74-75
+    double tw{0.0};                         // :76-77: 0 = bw / 10
+    float threshold{0.0F};                  // not a property: > 0 replaces the pfa quantile
+};
+// Notch_Filter (notch_filter.cc:36-46).
+struct Notch_Filter_Conf {
+    float pfa{0.001F};
+    float p_c_factor{0.9F};
+    int length{32};
+    int segments_est{12500};
+    int segments_reset{5000000};
+    float threshold{0.0F};
+    int chain_form{GNSSHIP_MIT_CHAIN_AUTO};  // not a property: the device form of the recursion
+};
+// Notch_Filter_Lite (notch_filter_lite.cc:35-56).  coeff_rate 0 = the adapter's default, sampling_frequency · 0.1.
+struct Notch_Filter_Lite_Conf {
+    float pfa{0.001F};
+    float p_c_factor{0.9F};
+    int length{32};
+    int segments_est{12500};
+    int segments_reset{5000000};
+    float sampling_frequency{4000000.0F};  // SignalSource.sampling_frequency (:39,43)
+    float coeff_rate{0.0F};                // :44,47
+    float threshold{0.0F};
+    int chain_form{GNSSHIP_MIT_CHAIN_AUTO};
+    // :55-56
+    int n_segments_coeff() const
+    {
+        const float rate = coeff_rate > 0.0F ? coeff_rate : sampling_frequency * 0.1F;
+        const int n = static_cast<int>((sampling_frequency / rate) / static_cast<float>(length));
+        return std::max(1, n);
+    }
+};
+
+// Common part of the three mirrors: one gnsship_mit handle.  work() emits the complete segments not yet
+// emitted (n_out() samples at dev_out(), and in host_out when given) and keeps the rest on the device.
+class Mitigation_Filter_Hip {
+public:
+    virtual ~Mitigation_Filter_Hip()
+    {
+        if (h_) gnsship_mit_destroy(h_);
+    }
+    Mitigation_Filter_Hip(const Mitigation_Filter_Hip&) = delete;
+    Mitigation_Filter_Hip& operator=(const Mitigation_Filter_Hip&) = delete;
+    // dev_dst: a device buffer of at least pending + n_in samples that does not overlap `in` (nullptr = the handle's
+    // own, valid until the next work()); without host_out the call is asynchronous on the context stream.
+    virtual bool work(const std::complex<float>* in, bool in_on_device, int64_t n_in, void* dev_dst = nullptr, std::complex<float>* host_out = nullptr)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_mit_run(h_, in, in_on_device ? 1 : 0, n_in, dev_dst, reinterpret_cast<float*>(host_out), &dev_out_, &n_out_) == GNSSHIP_OK;
+    }
+    void* dev_out() const { return dev_out_; }
+    int64_t n_out() const { return n_out_; }
+    virtual bool reset()
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_mit_reset(h_) == GNSSHIP_OK;
+    }
+    gnsship_mit_state state() const
+    {
+        gnsship_mit_state st{};
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        gnsship_mit_state_get(h_, &st);
+        return st;
+    }
+    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
+
+protected:
+    Mitigation_Filter_Hip(const gnsship_mit_conf& c, int64_t max_in_samples, int device) : dev_(Device::get(device))
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        if (gnsship_mit_create(dev_->ctx(), &c, max_in_samples, &h_) != GNSSHIP_OK)
+            throw std::invalid_argument(std::string("gnsship_mit_create: ") + gnsship_last_error(dev_->ctx()));
+    }
+    std::shared_ptr<Device> dev_;
+    gnsship_mit* h_ = nullptr;
+    void* dev_out_ = nullptr;
+    int64_t n_out_ = 0;
+};
+
+// Mirror of Notch_Filter (notch_filter.cc; the block of notch_cc.cc).
+class Notch_Filter_Hip : public Mitigation_Filter_Hip {
+public:
+    explicit Notch_Filter_Hip(const Notch_Filter_Conf& c, int64_t max_in_samples, int device = 0)
+        : Mitigation_Filter_Hip(gnsship_mit_conf{GNSSHIP_MIT_NOTCH, c.pfa, c.threshold, c.p_c_factor, c.length, c.segments_est, c.segments_reset, 1, c.chain_form},
+              max_in_samples, device)
+    {
+    }
+};
+
+// Mirror of Notch_Filter_Lite (notch_filter_lite.cc; the block of notch_lite_cc.cc).
+class Notch_Filter_Lite_Hip : public Mitigation_Filter_Hip {
+public:
+    explicit Notch_Filter_Lite_Hip(const Notch_Filter_Lite_Conf& c, int64_t max_in_samples, int device = 0)
+        : Mitigation_Filter_Hip(gnsship_mit_conf{GNSSHIP_MIT_NOTCH_LITE, c.pfa, c.threshold, c.p_c_factor, c.length, c.segments_est, c.segments_reset,
+                                    c.n_segments_coeff(), c.chain_form},
+              max_in_samples, device)
+    {
+    }
+};
+
+// Mirror of Pulse_Blanking_Filter (pulse_blanking_filter.cc; the block of pulse_blanking_cc.cc).  With |IF| > 1
+// work() first runs the adapter's decimation-1 frequency-translating low-pass on the device (:69-80, :109-118).
+class Pulse_Blanking_Filter_Hip : public Mitigation_Filter_Hip {
+public:
+    explicit Pulse_Blanking_Filter_Hip(const Pulse_Blanking_Filter_Conf& c, int64_t max_in_samples, int device = 0)
+        : Mitigation_Filter_Hip(gnsship_mit_conf{GNSSHIP_MIT_PULSE_BLANKING, c.pfa, c.threshold, 0.0F, c.length, c.segments_est, c.segments_reset, 1,
+                                    GNSSHIP_MIT_CHAIN_AUTO},
+              max_in_samples, device)
+    {
+        if (std::fabs(c.IF) > 1.0) {
+            Freq_Xlating_Fir_Filter_Conf x;
+            x.IF = c.IF;
+            x.sampling_frequency = c.sampling_frequency;
+            x.decimation_factor = 1;
+            x.bw = c.bw;
+            x.tw = c.tw > 0.0 ? c.tw : c.bw / 10.0;
+            xlat_ = std::make_unique<Freq_Xlating_Fir_Filter_Hip>(x, max_in_samples, device);
+        }
+    }
+    bool xlat() const { return static_cast<bool>(xlat_); }
+    bool work(const std::complex<float>* in, bool in_on_device, int64_t n_in, void* dev_dst = nullptr, std::complex<float>* host_out = nullptr) override
+    {
+        if (!xlat_) return Mitigation_Filter_Hip::work(in, in_on_device, n_in, dev_dst, host_out);
+        if (n_in == 0) return Mitigation_Filter_Hip::work(in, in_on_device, 0, dev_dst, host_out);
+        if (!xlat_->work(in, GNSSHIP_FMT_CF32, in_on_device, n_in)) return false;
+        return Mitigation_Filter_Hip::work(static_cast<const std::complex<float>*>(xlat_->dev_out()), true, n_in, dev_dst, host_out);
+    }
+    bool reset() override
+    {
+        if (xlat_ && !xlat_->reset()) return false;
+        return Mitigation_Filter_Hip::reset();
+    }
+
+private:
+    std::unique_ptr<Freq_Xlating_Fir_Filter_Hip> xlat_;
+};
+
 // What acquisition_core writes into Gnss_Synchro (gnss_synchro.h:52-55; pcps_acquisition.cc:683-696).
 struct Acq_Outcome {
     double Acq_delay_samples{0.0};

@@ -119,6 +119,13 @@ struct Receiver_Conf {
     // trk.fs_in are sampling_frequency / decimation_factor and the channels' own IF is 0.  Off: exactly the receiver above.
     bool use_conditioner{false};
     Freq_Xlating_Fir_Filter_Conf input_filter;   // InputFilter.*
+    // Optional interference mitigation, the InputFilter.implementation choices Pulse_Blanking_Filter, Notch_Filter and
+    // Notch_Filter_Lite ("" = none): runs on the device on the conditioned band, or on a raw gr_complex stream when
+    // no conditioner is configured, before the block goes to the host.  The samples enter through work_raw().
+    std::string mitigation;
+    Pulse_Blanking_Filter_Conf pulse_blanking;
+    Notch_Filter_Conf notch;
+    Notch_Filter_Lite_Conf notch_lite;
 };
 
 // One control event, in stream order.
@@ -171,6 +178,14 @@ public:
             cond_block_ = block_ * conf_.input_filter.decimation_factor;
             cond_ = std::make_unique<Freq_Xlating_Fir_Filter_Hip>(conf_.input_filter, cond_block_, conf_.device);
         }
+        if (conf_.mitigation == "Pulse_Blanking_Filter")
+            mit_ = std::make_unique<Pulse_Blanking_Filter_Hip>(conf_.pulse_blanking, block_, conf_.device);
+        else if (conf_.mitigation == "Notch_Filter")
+            mit_ = std::make_unique<Notch_Filter_Hip>(conf_.notch, block_, conf_.device);
+        else if (conf_.mitigation == "Notch_Filter_Lite")
+            mit_ = std::make_unique<Notch_Filter_Lite_Hip>(conf_.notch_lite, block_, conf_.device);
+        else if (!conf_.mitigation.empty())
+            throw std::invalid_argument("Gnss_Receiver_Hip: mitigation must be Pulse_Blanking_Filter, Notch_Filter or Notch_Filter_Lite");
         // set_signals_list (GPS: 1-32, BeiDou: 1-63, Galileo: 1-36)
         for (uint32_t p = 1; p <= (b3_ ? 63U : (e5a_ || e5b_) ? 36U : 32U); p++) available_.push_back(p);
         prn_.assign(static_cast<size_t>(n_), 0U);
@@ -211,9 +226,21 @@ public:
     // to the host, where the acquisition blocks buffer their dwells as the reference's do, and goes on to work().
     // Real (GNSSHIP_FMT_RF32 / RI16 / RI8) and bit-packed (GNSSHIP_FMT_PACKED) items too: n_in then also a multiple of
     // the samples per byte, the pieces cut at whole bytes.
+    // With a mitigation filter it runs on the conditioned block while that is still on the device, and the segments it
+    // completes go on to work(); without the conditioner the raw stream must be gr_complex (GNSSHIP_FMT_CF32).
     bool work_raw(const void* raw, int fmt, int64_t n_in)
     {
-        if (!cond_) return false;
+        if (!cond_) {
+            if (!mit_ || fmt != GNSSHIP_FMT_CF32) return false;
+            const std::complex<float>* x = static_cast<const std::complex<float>*>(raw);
+            while (n_in > 0) {
+                const int64_t m = std::min(n_in, block_);
+                if (!mitigate(x, false, m)) return false;
+                x += m;
+                n_in -= m;
+            }
+            return true;
+        }
         const int d = cond_->decimation();
         const int64_t bits = gnsship_cond_fmt_bits(fmt);
         if (bits == 0) return false;
@@ -225,16 +252,22 @@ public:
         const char* p = static_cast<const char*>(raw);
         while (n_in > 0) {
             const int64_t m = std::min(n_in, piece);
-            cond_host_.resize(static_cast<size_t>(m / d));
-            std::complex<float>* ho[1] = {cond_host_.data()};
-            if (!cond_->work(p, fmt, false, m, nullptr, ho)) return false;
-            if (!work(cond_host_.data(), m / d)) return false;
+            if (mit_) {
+                if (!cond_->work(p, fmt, false, m)) return false;
+                if (!mitigate(static_cast<const std::complex<float>*>(cond_->dev_out()), true, m / d)) return false;
+            } else {
+                cond_host_.resize(static_cast<size_t>(m / d));
+                std::complex<float>* ho[1] = {cond_host_.data()};
+                if (!cond_->work(p, fmt, false, m, nullptr, ho)) return false;
+                if (!work(cond_host_.data(), m / d)) return false;
+            }
             p += m * bits / 8;
             n_in -= m;
         }
         return true;
     }
     const Freq_Xlating_Fir_Filter_Hip* conditioner() const { return cond_.get(); }
+    const Mitigation_Filter_Hip* mitigation() const { return mit_.get(); }
 
     const std::vector<Receiver_Event>& events() const { return events_; }
     // Every tracking epoch record in stream order per channel (the Gnss_Synchro stream).
@@ -526,6 +559,14 @@ private:
     std::unique_ptr<Freq_Xlating_Fir_Filter_Hip> cond_;  // the optional conditioner stage
     int64_t cond_block_ = 0;                             // its run size, in input samples
     std::vector<std::complex<float>> cond_host_;
+    std::unique_ptr<Mitigation_Filter_Hip> mit_;         // the optional interference mitigation
+    // m <= block_ samples through the mitigation filter; what it emits goes to the channels
+    bool mitigate(const std::complex<float>* x, bool on_device, int64_t m)
+    {
+        cond_host_.resize(static_cast<size_t>(block_ + GNSSHIP_MIT_MAX_LENGTH + 1));
+        if (!mit_->work(x, on_device, m, nullptr, cond_host_.data())) return false;
+        return mit_->n_out() == 0 || work(cond_host_.data(), mit_->n_out());
+    }
     std::vector<std::unique_ptr<Pcps_Acquisition_Hip>> acq_;
     std::vector<ChannelFsm> fsm_;
     std::vector<uint32_t> prn_;

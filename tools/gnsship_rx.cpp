@@ -15,6 +15,13 @@
 //              [--max-carrier-lock-fail 5000] [--max-code-lock-fail 50] [--cn0-min 25]
 //              [--block-ms 100] [--acq-piece 8192] [--dump PREFIX] [--events CSV] [--records BIN]
 //              [--if-hz 0] [--decimation 1] [--filter-bw 0] [--filter-tw 0]
+//              [--input-filter pulse-blanking|notch|notch-lite] [--input-filter-pfa P] [--segment-length 32]
+//              [--segments-est 12500] [--segments-reset 5000000] [--p-c-factor 0.9] [--coeff-rate R]
+//
+// --input-filter puts the interference mitigation (InputFilter.implementation = Pulse_Blanking_Filter, Notch_Filter or
+// Notch_Filter_Lite; pfa, length, segments_est, segments_reset, p_c_factor, coeff_rate: 0 = the adapter's defaults)
+// on the device ahead of the channels: on the conditioned band with --if-hz / --decimation, else on the gr_complex
+// file itself.  Its pfa is --input-filter-pfa, as --pfa is the acquisition's.
 //
 // --if-hz / --decimation (either one) put the signal conditioner ahead of the channels (InputFilter.implementation =
 // Freq_Xlating_Fir_Filter, filter_type lowpass: IF, decimation_factor, bw, tw; 0 = the adapter's defaults): the file is
@@ -70,6 +77,9 @@ int main(int argc, char** argv)
     double if_hz = 0.0, filter_bw = 0.0, filter_tw = 0.0;
     int decimation = 1;
     bool conditioner = false, big_endian_bytes = false;
+    std::string mit;
+    double mit_pfa = 0.0, mit_p_c = 0.9, mit_coeff_rate = 0.0;
+    int mit_length = 32, mit_est = 12500, mit_reset = 5000000;
     gnsship::Receiver_Conf rc;
     rc.channels = 5;
     rc.in_acquisition = 1;
@@ -123,6 +133,13 @@ int main(int argc, char** argv)
             conditioner = true;
         } else if (a == "--filter-bw") filter_bw = std::atof(val().c_str());
         else if (a == "--filter-tw") filter_tw = std::atof(val().c_str());
+        else if (a == "--input-filter") mit = val();
+        else if (a == "--input-filter-pfa") mit_pfa = std::atof(val().c_str());
+        else if (a == "--segment-length") mit_length = std::atoi(val().c_str());
+        else if (a == "--segments-est") mit_est = std::atoi(val().c_str());
+        else if (a == "--segments-reset") mit_reset = std::atoi(val().c_str());
+        else if (a == "--p-c-factor") mit_p_c = std::atof(val().c_str());
+        else if (a == "--coeff-rate") mit_coeff_rate = std::atof(val().c_str());
         else if (a == "--dump") dump = val();
         else if (a == "--events") events_csv = val();
         else if (a == "--records") records_bin = val();
@@ -180,6 +197,20 @@ int main(int argc, char** argv)
         rc.input_filter.tw = filter_tw;
         fs = fs_file / decimation;
     }
+    if (!mit.empty()) {
+        if (mit != "pulse-blanking" && mit != "notch" && mit != "notch-lite") usage("--input-filter must be pulse-blanking, notch or notch-lite");
+        if (!conditioner && item != "gr_complex") usage("--input-filter reads gr_complex items, or the conditioned band (--if-hz / --decimation)");
+        if (mit_length < 2 || mit_length > GNSSHIP_MIT_MAX_LENGTH || mit_est < 1 || mit_pfa < 0.0 || mit_pfa >= 1.0)
+            usage("--segment-length in 2..1024, --segments-est >= 1, --input-filter-pfa in (0, 1)");
+        rc.mitigation = mit == "pulse-blanking" ? "Pulse_Blanking_Filter" : mit == "notch" ? "Notch_Filter" : "Notch_Filter_Lite";
+        if (mit_pfa > 0.0) rc.pulse_blanking.pfa = rc.notch.pfa = rc.notch_lite.pfa = static_cast<float>(mit_pfa);
+        rc.pulse_blanking.length = rc.notch.length = rc.notch_lite.length = mit_length;
+        rc.pulse_blanking.segments_est = rc.notch.segments_est = rc.notch_lite.segments_est = mit_est;
+        rc.pulse_blanking.segments_reset = rc.notch.segments_reset = rc.notch_lite.segments_reset = mit_reset;
+        rc.notch.p_c_factor = rc.notch_lite.p_c_factor = static_cast<float>(mit_p_c);
+        rc.notch_lite.sampling_frequency = static_cast<float>(fs);  // the rate the filter runs at
+        rc.notch_lite.coeff_rate = static_cast<float>(mit_coeff_rate);
+    }
     rc.acq.fs_in = static_cast<int64_t>(fs);
     rc.trk.fs_in = fs;
     // gps_l1_ca_dll_pll_tracking.cc:47, gps_l5_dll_pll_tracking.cc:47, beidou_b3i_dll_pll_tracking.cc:47; gps_l2_m_dll_pll_tracking.cc:47
@@ -223,10 +254,10 @@ int main(int argc, char** argv)
         size_t got = static_cast<size_t>(static_cast<int64_t>(std::fread(raw.data(), 1, static_cast<size_t>(want * sample_bits / 8), f)) * 8 / sample_bits);
         got -= got % static_cast<size_t>(unit);  // a whole number of conditioned samples and of bytes
         if (got == 0) break;
-        if (conditioner) {
+        if (conditioner || !mit.empty()) {
             io_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - r0).count();
             if (!rx.work_raw(raw.data(), fmt, static_cast<int64_t>(got))) {
-                std::fprintf(stderr, "gnsship_rx: conditioner / engine error\n");
+                std::fprintf(stderr, "gnsship_rx: input filter / engine error\n");
                 return 1;
             }
             total += static_cast<int64_t>(got);
