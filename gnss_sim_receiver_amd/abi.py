@@ -161,6 +161,7 @@ class MitState(ctypes.Structure):
 
 SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5, SYS_BDS_B3I, SYS_GPS_L2C = 0, 1, 2, 3, 4, 5
 SYS_GAL_E5A, SYS_GAL_E5B = 6, 7
+SYS_GLO_L1CA, SYS_GLO_L2CA = 8, 9  # glonass_l1_ca / glonass_l2_ca_dll_pll_tracking_cc (include/gnsship.h)
 # gnsship_trk_last_engine (include/gnsship.h GNSSHIP_TRK_ENGINE_*)
 TRK_ENGINE_NONE, TRK_ENGINE_FAST_LATENCY, TRK_ENGINE_FAST_THROUGHPUT, TRK_ENGINE_PERSIST, TRK_ENGINE_ROUNDS, TRK_ENGINE_LANES = 0, 1, 2, 3, 4, 5
 TRK_ENGINE_NAMES = {0: "none", 1: "trk_fast_kernel (latency form)", 2: "trk_fast_kernel (throughput form)", 3: "trk_persist_kernel",
@@ -236,6 +237,10 @@ TRK_DUMP_DTYPE = np.dtype([
 ])
 assert TRK_DUMP_DTYPE.itemsize == 96
 TRK_FLAG_DUMP = 16
+# the record glonass_l1_ca_dll_pll_tracking_cc writes (:641-701): the same without the two rate fields, 88 bytes
+TRK_DUMP_GLONASS_DTYPE = np.dtype([(n, TRK_DUMP_DTYPE.fields[n][0]) for n in TRK_DUMP_DTYPE.names
+                                   if n not in ("carrier_doppler_rate_hz", "code_freq_rate_chips")])
+assert TRK_DUMP_GLONASS_DTYPE.itemsize == 88
 
 # gnsship_trk_corr_trace: one channel-epoch's do_correlation_step arguments and outputs
 TRK_TRACE_DTYPE = np.dtype([
@@ -300,6 +305,13 @@ _SIGNATURES = {
     "gnsship_beidou_b3i_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint32], _i),
     "gnsship_gps_l2c_m_code_gen_float": ([_f32p, ctypes.c_int32], _i),
     "gnsship_gps_l2c_m_code_gen_complex_sampled": ([_f32p, ctypes.c_uint32, ctypes.c_int32], _i),
+    "gnsship_glonass_l1_ca_code_gen_float": ([_f32p, ctypes.c_uint32], _i),
+    "gnsship_glonass_l1_ca_code_gen_complex": ([_f32p, ctypes.c_uint32], _i),
+    "gnsship_glonass_l1_ca_code_gen_complex_sampled": ([_f32p, ctypes.c_int32, ctypes.c_uint32], _i),
+    "gnsship_glonass_l2_ca_code_gen_float": ([_f32p, ctypes.c_uint32], _i),
+    "gnsship_glonass_l2_ca_code_gen_complex": ([_f32p, ctypes.c_uint32], _i),
+    "gnsship_glonass_l2_ca_code_gen_complex_sampled": ([_f32p, ctypes.c_int32, ctypes.c_uint32], _i),
+    "gnsship_glonass_freq_channel": ([ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)], _i),
     "gnsship_code_samples_per_code": ([ctypes.c_int32, ctypes.c_int32, ctypes.c_int32], _i),
     "gnsship_corr_create": ([_vp, _i, _i, _vpp], _i),
     "gnsship_corr_set_local_code_and_taps": ([_vp, _i, _f32p, _f32p], _i),
@@ -322,6 +334,8 @@ _SIGNATURES = {
     "gnsship_acq_set_local_code": ([_vp, _i, _f32p], _i),
     "gnsship_acq_run": ([_vp, _vp, _i, _i, _i, ctypes.POINTER(AcqResult), _f32p], _i),
     "gnsship_acq_num_bins": ([_vp, ctypes.POINTER(_i)], _i),
+    "gnsship_acq_set_grid_fdma": ([_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32)], _i),
+    "gnsship_acq_run_fdma": ([_vp, _vp, _i, _i, _i, ctypes.POINTER(AcqResult), _f32p], _i),
     "gnsship_acq_reset_dwells": ([_vp], _i),
     "gnsship_acq_destroy": ([_vp], _i),
     "gnsship_firdes_low_pass": ([ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _f32p, _i, ctypes.POINTER(_i)], _i),

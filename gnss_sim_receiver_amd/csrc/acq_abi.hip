@@ -111,7 +111,9 @@ struct gnsship_acq {
     int lanes = 1;               // huge: PRN batches in flight together (U and tiles per lane)
     hipStream_t lane_stream = nullptr;  // huge, lanes = 2: the second batch lane
     hipEvent_t ev_fwd = nullptr, ev_lane = nullptr;
-    int n_bins = 0;
+    int n_bins = 0;              // wipeoff rows: the grid's Doppler bins, × fdma_channels on an FDMA grid
+    int fdma_channels = 0;       // > 0: FDMA grid (gnsship_acq_set_grid_fdma), rows channel-major
+    int res_cap = 0;             // entries of res_host: max(max_prns, fdma_channels)
     int dwell_count = 0;
     float2* tw = nullptr;        // N twiddles exp(-2πi t/N)
     float2* wipe = nullptr;      // n_bins × N Doppler wipeoffs
@@ -137,7 +139,7 @@ struct gnsship_acq {
     hipGraphExec_t graph = nullptr;
     struct GraphKey {
         const void* src;
-        int fmt, n_prns, accumulate, keep_grid, dwell;
+        int fmt, n_prns, accumulate, keep_grid, dwell, slot0, n_decisions;
         const float* grid;
         Step2Spec step2;
     } graph_key{};
@@ -207,10 +209,10 @@ static int acq_upload_wipeoffs(gnsship_acq* a, int nb, const std::vector<float>&
     const int N = a->conf.fft_size;
     if (nb != a->n_bins || !a->wipe) {
         acq_free_grid_buffers(a);
+        a->n_bins = 0;  // nothing to run on until every buffer below exists
         HIP_TRY(ctx, hipMalloc(&a->wipe, sizeof(float2) * static_cast<size_t>(nb) * N));
         HIP_TRY(ctx, hipMalloc(&a->X, sizeof(float2) * static_cast<size_t>(nb) * N));
         HIP_TRY(ctx, hipMalloc(&a->rowstat, sizeof(RowStat) * static_cast<size_t>(nb) * a->conf.max_prns));
-        a->n_bins = nb;
         if (a->huge) {
             // PRNs searched per round: the PRNs split over the two batch lanes, one round each (E1 at 25
             // Msps: 2 × 16 PRNs, 1.05 GB of inverse row-stage scratch U), so that batch 0's column stage
@@ -238,6 +240,7 @@ static int acq_upload_wipeoffs(gnsship_acq* a, int nb, const std::vector<float>&
                 HIP_TRY(ctx, hipEventCreateWithFlags(&a->ev_lane, hipEventDisableTiming));
             }
         }
+        a->n_bins = nb;
     }
     std::vector<float2> host(static_cast<size_t>(nb) * N);
     const float two_pi = static_cast<float>(2.0 * M_PI);
@@ -271,6 +274,54 @@ extern "C" int gnsship_acq_set_grid(gnsship_acq* a, int doppler_max, int doppler
     a->conf.doppler_step = doppler_step;
     a->conf.doppler_center = doppler_center;
     a->step2 = Step2Spec{};
+    a->fdma_channels = 0;
+    acq_graph_reset(a);
+    return GNSSHIP_OK;
+}
+
+// The FDMA form of update_grid_doppler_wipeoffs (pcps_acquisition.cc:295-302 with d_doppler_bias, :175-229): the
+// reference runs one acquisition block per frequency channel, each with its own bias in the same grid; here the
+// grids of n_channels channels are stacked channel-major into one table, row (g, i) from
+// (float)(bias_hz[g] − dmax + center + step·i) — the integer sum the reference casts — and every buffer that
+// scales with the row count follows n_channels·nb through acq_upload_wipeoffs.
+extern "C" int gnsship_acq_set_grid_fdma(gnsship_acq* a, int doppler_max, int doppler_step, int doppler_center, int n_channels,
+    const int32_t* bias_hz)
+{
+    if (!a) return GNSSHIP_E_INVAL;
+    gnsship_ctx* ctx = a->ctx;
+    if (doppler_max < 0 || doppler_step <= 0) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_acq_set_grid_fdma: doppler_max >= 0, doppler_step > 0");
+    // GLONASS has 14 frequency channels (k = −7…+6); 32 leaves room and keeps the row count where it is tested
+    if (!bias_hz || n_channels < 1 || n_channels > 32) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_acq_set_grid_fdma: 1..32 channels and their biases");
+    const int nb = static_cast<int>(std::ceil(static_cast<double>(2 * doppler_max) / static_cast<double>(doppler_step)));  // :261
+    if (nb < 1) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_acq_set_grid_fdma: empty Doppler grid");
+    // one workgroup per row in a grid dimension and 16·N bytes of wipe / X per row: bounded like an ordinary grid
+    // of a few thousand bins (4096 rows at N = 10000: 655 MB)
+    if (static_cast<int64_t>(nb) * n_channels > 4096) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_acq_set_grid_fdma: more than 4096 rows (channels x bins)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_channels > a->res_cap) {  // one decision per channel
+        acq_graph_reset(a);
+        gnsship_acq_result* host = nullptr;
+        gnsship_acq_result* dev = nullptr;
+        HIP_TRY(ctx, hipHostMalloc(reinterpret_cast<void**>(&host), sizeof(gnsship_acq_result) * n_channels, hipHostMallocMapped));
+        if (hipError_t e = hipHostGetDevicePointer(reinterpret_cast<void**>(&dev), host, 0); e != hipSuccess) {
+            (void)hipHostFree(host);
+            return hip_fail(ctx, e, "gnsship_acq_set_grid_fdma");
+        }
+        (void)hipHostFree(a->res_host);
+        a->res_host = host;
+        a->res_dev = dev;
+        a->res_cap = n_channels;
+    }
+    std::vector<float> f(static_cast<size_t>(nb) * n_channels);
+    for (int g = 0; g < n_channels; g++)
+        for (int i = 0; i < nb; i++) f[static_cast<size_t>(g) * nb + i] = static_cast<float>(bias_hz[g] - doppler_max + doppler_center + doppler_step * i);
+    if (int rc = acq_upload_wipeoffs(a, nb * n_channels, f)) return rc;
+    a->conf.doppler_max = doppler_max;
+    a->conf.doppler_step = doppler_step;
+    a->conf.doppler_center = doppler_center;
+    a->step2 = Step2Spec{};
+    a->fdma_channels = n_channels;
     acq_graph_reset(a);
     return GNSSHIP_OK;
 }
@@ -285,6 +336,7 @@ extern "C" int gnsship_acq_set_grid_step2(gnsship_acq* a, float doppler_center_s
     if (!a) return GNSSHIP_E_INVAL;
     if (num_doppler_bins_step2 < 1 || !(doppler_step2 > 0.0f))
         return fail(a->ctx, GNSSHIP_E_INVAL, "gnsship_acq_set_grid_step2: num_doppler_bins_step2 >= 1, doppler_step2 > 0");
+    if (a->fdma_channels) return fail(a->ctx, GNSSHIP_E_INVAL, "gnsship_acq_set_grid_step2: no two-step acquisition on an FDMA grid");
     std::vector<float> f(num_doppler_bins_step2);
     for (int i = 0; i < num_doppler_bins_step2; i++) {
         const float doppler = (static_cast<float>(i) - static_cast<float>(std::floor(num_doppler_bins_step2 / 2.0))) * doppler_step2;
@@ -352,6 +404,7 @@ extern "C" int gnsship_acq_create(gnsship_ctx* ctx, const gnsship_acq_conf* conf
     }
     if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&a->res_host), sizeof(gnsship_acq_result) * conf->max_prns, hipHostMallocMapped);
     if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void**>(&a->res_dev), a->res_host, 0);
+    a->res_cap = conf->max_prns;
     if (e == hipSuccess) e = hipMalloc(&a->sig_dev, sizeof(float2) * static_cast<size_t>(N));
     if (e != hipSuccess) {
         gnsship_acq_destroy(a);
@@ -375,7 +428,7 @@ extern "C" int gnsship_acq_reset_dwells(gnsship_acq* a)
 extern "C" int gnsship_acq_num_bins(gnsship_acq* a, int* n_bins)
 {
     if (!a || !n_bins) return GNSSHIP_E_INVAL;
-    *n_bins = a->n_bins;
+    *n_bins = a->fdma_channels ? a->n_bins / a->fdma_channels : a->n_bins;
     return GNSSHIP_OK;
 }
 
@@ -409,15 +462,15 @@ extern "C" int gnsship_acq_set_local_code(gnsship_acq* a, int prn_slot, const fl
 
 // acquisition_core (:600-871), step one, one dwell per call (dwells accumulate into the grid when
 // max_dwells > 1 and a grid is kept on the device; the statistic divides by the dwell count).
-extern "C" int gnsship_acq_run(gnsship_acq* a, const void* sig, int fmt, int sig_on_device, int n_prns, gnsship_acq_result* results,
-    float* grid)
+// The codes of slots [slot0, slot0 + n_codes) are searched over all a->n_bins wipeoff rows; the decision
+// kernel then takes n_decisions decisions over dec_bins rows each: (n_codes, n_bins) on the ordinary
+// grid, (channels, bins per channel) for the one code of an FDMA sweep — the same n_codes·n_bins rows.
+static int acq_run_rows(gnsship_acq* a, const void* sig, int fmt, int sig_on_device, int slot0, int n_codes, int n_decisions, int dec_bins,
+    gnsship_acq_result* results, float* grid)
 {
-    if (!a) return GNSSHIP_E_INVAL;
     gnsship_ctx* ctx = a->ctx;
-    if (!sig || !results || n_prns < 1 || n_prns > a->conf.max_prns || fmt_bytes(fmt) == 0)
-        return fail(ctx, GNSSHIP_E_INVAL, "gnsship_acq_run: bad arguments");
-    for (int p = 0; p < n_prns; p++)
-        if (!a->code_set[p]) return fail(ctx, GNSSHIP_E_STATE, "gnsship_acq_run: set_local_code missing for a prn slot");
+    const int n_prns = n_codes;
+    const float2* codes = a->codes_fft + static_cast<size_t>(slot0) * a->conf.fft_size;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const void* src = sig;
     if (!sig_on_device) {
@@ -426,7 +479,7 @@ extern "C" int gnsship_acq_run(gnsship_acq* a, const void* sig, int fmt, int sig
     }
     const bool keep_grid = (grid != nullptr) || a->conf.max_dwells > 1;
     const RowSpec rs = a->rows();
-    const size_t gbytes = sizeof(float) * static_cast<size_t>(a->conf.max_prns) * a->n_bins * rs.row_len;
+    const size_t gbytes = sizeof(float) * static_cast<size_t>(a->fdma_channels ? 1 : a->conf.max_prns) * a->n_bins * rs.row_len;
     if (keep_grid && a->grid_bytes < gbytes) {
         if (a->grid_dev) HIP_TRY(ctx, hipFree(a->grid_dev));
         a->grid_dev = nullptr;
@@ -453,7 +506,7 @@ extern "C" int gnsship_acq_run(gnsship_acq* a, const void* sig, int fmt, int sig
                 const int lane = two ? (i & 1) : 0;  // batches i and i + 2 share a lane's U and tiles, in stream order
                 // without a kept grid the |y|² rows never reach HBM (tile statistics + finalize's recomputation)
                 float* g = keep_grid ? a->grid_dev + static_cast<size_t>(p0) * a->n_bins * rs.row_len : nullptr;
-                HIP_TRY(ctx, launch_acq_search_huge(a->X, a->codes_fft, p0, np, a->n_bins, a->P, a->plan, a->twC, a->twM, a->U + lane * u_lane, g,
+                HIP_TRY(ctx, launch_acq_search_huge(a->X, codes, p0, np, a->n_bins, a->P, a->plan, a->twC, a->twM, a->U + lane * u_lane, g,
                                  keep_grid ? accumulate : 0, a->tiles + lane * t_lane, rs, a->rowstat, lane ? a->lane_stream : ctx->stream));
             }
             if (two) {  // the decision reads every batch's row statistics
@@ -462,14 +515,14 @@ extern "C" int gnsship_acq_run(gnsship_acq* a, const void* sig, int fmt, int sig
             }
         } else if (a->P) {
             HIP_TRY(ctx, launch_acq_fft_big(src, fmt, a->wipe, a->n_bins, a->P, a->plan, a->tw, a->X, 0, a->consumed, ctx->stream));
-            HIP_TRY(ctx, launch_acq_search_big(a->X, a->codes_fft, n_prns, a->n_bins, a->P, a->plan, a->tw, rs, accumulate,
+            HIP_TRY(ctx, launch_acq_search_big(a->X, codes, n_prns, a->n_bins, a->P, a->plan, a->tw, rs, accumulate,
                              a->rowstat, keep_grid ? a->grid_dev : nullptr, ctx->stream));
         } else {
             HIP_TRY(ctx, launch_acq_fft_rows(src, fmt, a->wipe, a->n_bins, a->plan, a->tw, a->X, 0, a->consumed, ctx->stream));
-            HIP_TRY(ctx, launch_acq_search(a->X, a->codes_fft, n_prns, a->n_bins, a->plan, a->tw, rs, accumulate,
+            HIP_TRY(ctx, launch_acq_search(a->X, codes, n_prns, a->n_bins, a->plan, a->tw, rs, accumulate,
                              a->rowstat, keep_grid ? a->grid_dev : nullptr, ctx->stream));
         }
-        HIP_TRY(ctx, launch_acq_decide(a->rowstat, n_prns, a->n_bins, rs.row_len, a->conf.doppler_max, a->conf.doppler_step, a->conf.doppler_center,
+        HIP_TRY(ctx, launch_acq_decide(a->rowstat, n_decisions, dec_bins, rs.row_len, a->conf.doppler_max, a->conf.doppler_step, a->conf.doppler_center,
                          a->dwell_count, a->conf.use_cfar, a->conf.samples_per_code, a->conf.resampler_ratio > 0.0f ? a->conf.resampler_ratio : 1.0f,
                          a->conf.resampler_latency_samples, a->step2, a->res_dev, ctx->stream));
         return GNSSHIP_OK;
@@ -480,7 +533,8 @@ extern "C" int gnsship_acq_run(gnsship_acq* a, const void* sig, int fmt, int sig
     }();
     const bool graphs_on = graph_env < 0 ? a->huge : graph_env == 1;
     if (graphs_on && !a->graph_broken) {
-        const gnsship_acq::GraphKey key{src, fmt, n_prns, accumulate, keep_grid ? 1 : 0, a->dwell_count, keep_grid ? a->grid_dev : nullptr, a->step2};
+        const gnsship_acq::GraphKey key{src, fmt, n_prns, accumulate, keep_grid ? 1 : 0, a->dwell_count, slot0, n_decisions,
+            keep_grid ? a->grid_dev : nullptr, a->step2};
         const bool same = a->graph && std::memcmp(&key, &a->graph_key, sizeof(key)) == 0;
         if (!same) {
             acq_graph_reset(a);
@@ -509,7 +563,33 @@ extern "C" int gnsship_acq_run(gnsship_acq* a, const void* sig, int fmt, int sig
         HIP_TRY(ctx, hipMemcpyAsync(grid, a->grid_dev, sizeof(float) * static_cast<size_t>(n_prns) * a->n_bins * rs.row_len, hipMemcpyDeviceToHost,
                          ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::memcpy(results, a->res_host, sizeof(gnsship_acq_result) * n_prns);
+    std::memcpy(results, a->res_host, sizeof(gnsship_acq_result) * n_decisions);
     return GNSSHIP_OK;
+}
+
+extern "C" int gnsship_acq_run(gnsship_acq* a, const void* sig, int fmt, int sig_on_device, int n_prns, gnsship_acq_result* results,
+    float* grid)
+{
+    if (!a) return GNSSHIP_E_INVAL;
+    gnsship_ctx* ctx = a->ctx;
+    if (!sig || !results || n_prns < 1 || n_prns > a->conf.max_prns || fmt_bytes(fmt) == 0)
+        return fail(ctx, GNSSHIP_E_INVAL, "gnsship_acq_run: bad arguments");
+    if (a->fdma_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_acq_run: the grid is an FDMA grid (gnsship_acq_run_fdma, or gnsship_acq_set_grid)");
+    if (a->n_bins < 1) return fail(ctx, GNSSHIP_E_STATE, "gnsship_acq_run: no Doppler grid (the last set_grid failed)");
+    for (int p = 0; p < n_prns; p++)
+        if (!a->code_set[p]) return fail(ctx, GNSSHIP_E_STATE, "gnsship_acq_run: set_local_code missing for a prn slot");
+    return acq_run_rows(a, sig, fmt, sig_on_device, 0, n_prns, n_prns, a->n_bins, results, grid);
+}
+
+extern "C" int gnsship_acq_run_fdma(gnsship_acq* a, const void* sig, int fmt, int sig_on_device, int prn_slot, gnsship_acq_result* results,
+    float* grid)
+{
+    if (!a) return GNSSHIP_E_INVAL;
+    gnsship_ctx* ctx = a->ctx;
+    if (!sig || !results || prn_slot < 0 || prn_slot >= a->conf.max_prns || fmt_bytes(fmt) == 0)
+        return fail(ctx, GNSSHIP_E_INVAL, "gnsship_acq_run_fdma: bad arguments");
+    if (!a->fdma_channels || a->n_bins < 1) return fail(ctx, GNSSHIP_E_STATE, "gnsship_acq_run_fdma: gnsship_acq_set_grid_fdma first");
+    if (!a->code_set[prn_slot]) return fail(ctx, GNSSHIP_E_STATE, "gnsship_acq_run_fdma: set_local_code missing for the prn slot");
+    return acq_run_rows(a, sig, fmt, sig_on_device, prn_slot, 1, a->fdma_channels, a->n_bins / a->fdma_channels, results, grid);
 }
 static_assert(sizeof(gnsship_acq_conf) == 64, "gnsship_acq_conf layout (abi.AcqConf)");

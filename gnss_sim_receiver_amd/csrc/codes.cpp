@@ -17,6 +17,9 @@
 //                 (the ICD's two 14-stage registers multiplied out; E5a-I and E5a-Q share theirs) from the PRN's
 //                 first 28 chips (galileo_e5_tables.h; reference galileo_e5_signal_replica.cc:31-216 reads tables);
 //                 sampled with resampler()'s truncating float index (gnss_signal_replica.cc:275-290)
+//  GLONASS C/A  : one 9-stage maximal sequence (1 + x^5 + x^9, output stage 7), 511 chips, the same for every
+//                 satellite and for L1 and L2 (glonass_l1_signal_replica.cc:25-123), sampled as B1I; the
+//                 satellites differ by FDMA frequency channel (gnsship_glonass_freq_channel)
 //  sampled forms: the Borre-style upsampling with a float chip clock and the last sample forced
 //                 to the last chip  (gps_sdr_signal_replica.cc:145-185, beidou_b1i_signal_replica.cc:142-180)
 //
@@ -459,6 +462,73 @@ extern "C" int gnsship_gps_l2c_m_code_gen_complex_sampled(float* dest, uint32_t 
     static thread_local int8_t c[kL5Len];
     if (int rc = l2cm_chips(static_cast<int32_t>(prn), c)) return rc;
     return sample_code_ceil(c, kL5Len, 511500, fs, true, false, dest);
+}
+
+// GLONASS L1 / L2 C/A (glonass_l1_signal_replica.cc:25-77; the L2 generator is the same text): one 511-chip
+// maximal sequence for every satellite.  Nine cells, all ones at the start; the output is cell 2 (the
+// reference's G1_register[2], ICD stage 7 of 1 + x^5 + x^9), the feedback cells 4 ⊕ 0 enter at cell 8.
+static void glonass_chips(uint32_t chip_shift, int8_t* chips)
+{
+    constexpr int L = 511;
+    uint8_t g[L];
+    uint32_t s = 0x1FFu;
+    for (int i = 0; i < L; i++) {
+        g[i] = (s >> 2) & 1u;
+        const uint32_t fb = ((s >> 4) ^ s) & 1u;
+        s = (s >> 1) | (fb << 8);
+    }
+    for (int i = 0; i < L; i++) chips[i] = g[(i + chip_shift) % L] ? 1 : -1;
+}
+
+extern "C" int gnsship_glonass_l1_ca_code_gen_float(float* dest, uint32_t chip_shift)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    int8_t c[511];
+    glonass_chips(chip_shift, c);
+    for (int i = 0; i < 511; i++) dest[i] = static_cast<float>(c[i]);
+    return GNSSHIP_OK;
+}
+
+extern "C" int gnsship_glonass_l1_ca_code_gen_complex(float* dest, uint32_t chip_shift)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    int8_t c[511];
+    glonass_chips(chip_shift, c);
+    for (int i = 0; i < 511; i++) {
+        dest[2 * i] = static_cast<float>(c[i]);
+        dest[2 * i + 1] = 0.0F;
+    }
+    return GNSSHIP_OK;
+}
+
+// glonass_l1_ca_code_gen_complex_sampled (:83-123): tc = (float)(1.0 / (float)511000), the chip index
+// ceil(ts·(i+1)/tc) − 1 in float, the last sample forced to the last chip — the B1I sampling rule.
+extern "C" int gnsship_glonass_l1_ca_code_gen_complex_sampled(float* dest, int32_t fs, uint32_t chip_shift)
+{
+    if (!dest) return GNSSHIP_E_INVAL;
+    int8_t c[511];
+    glonass_chips(chip_shift, c);
+    return sample_code(c, 511, 511000, fs, false, true, dest);
+}
+
+extern "C" int gnsship_glonass_l2_ca_code_gen_float(float* dest, uint32_t chip_shift) { return gnsship_glonass_l1_ca_code_gen_float(dest, chip_shift); }
+extern "C" int gnsship_glonass_l2_ca_code_gen_complex(float* dest, uint32_t chip_shift)
+{
+    return gnsship_glonass_l1_ca_code_gen_complex(dest, chip_shift);
+}
+extern "C" int gnsship_glonass_l2_ca_code_gen_complex_sampled(float* dest, int32_t fs, uint32_t chip_shift)
+{
+    return gnsship_glonass_l1_ca_code_gen_complex_sampled(dest, fs, chip_shift);
+}
+
+// GLONASS_PRN (GLONASS_L1_L2_CA.h:134): the FDMA frequency channel k of orbital slot ("PRN") 0..24; entry 0
+// is the reference's test entry.
+extern "C" int gnsship_glonass_freq_channel(int32_t prn, int32_t* k)
+{
+    static constexpr int8_t kChannel[25] = {8, 1, -4, 5, 6, 1, -4, 5, 6, -2, -7, 0, -1, -2, -7, 0, -1, 4, -3, 3, -5, 4, -3, 3, 2};
+    if (!k || prn < 0 || prn > 24) return GNSSHIP_E_INVAL;
+    *k = kChannel[prn];
+    return GNSSHIP_OK;
 }
 
 extern "C" int gnsship_code_samples_per_code(int32_t chip_rate, int32_t code_len, int32_t fs)

@@ -296,6 +296,18 @@ bool build_params(const gnsship_trk_conf& c, TrkParams& p)
             p.single_code_bits = 1;
         }
     } break;
+    case GNSSHIP_SYS_GLO_L1CA:  // glonass_l1_ca_dll_pll_tracking_cc.cc; GLONASS_L1_L2_CA.h:68-81
+    case GNSSHIP_SYS_GLO_L2CA:  // glonass_l2_ca_dll_pll_tracking_cc.cc: the same block with the L2 constants
+        p.code_chip_rate = 0.511e6;
+        p.carrier_freq = c.system == GNSSHIP_SYS_GLO_L1CA ? 1.602e9 : 1.246e9;  // channel 0's; a channel's own is set by start
+        p.code_period = 0.001;
+        p.code_length_chips = 511;
+        p.code_samples_per_chip = 1;
+        g.symbols_per_bit = 1;
+        p.veml = 0;
+        p.track_pilot = 0;
+        g.secondary = 0;
+        break;
     default: return false;
     }
     p.n_taps = p.veml ? 5 : 3;
@@ -391,6 +403,21 @@ bool build_params(const gnsship_trk_conf& c, TrkParams& p)
     p.if_mod = p.fs_int > 0 ? ((ifi % p.fs_int) + p.fs_int) % p.fs_int : 0;
     p.inv_fs = 1.0 / c.fs_in;
     p.inv_carrier_freq = 1.0 / p.carrier_freq;
+    if (c.system == GNSSHIP_SYS_GLO_L1CA || c.system == GNSSHIP_SYS_GLO_L2CA) {
+        // Tracking_2nd_DLL_filter / Tracking_2nd_PLL_filter (tracking_2nd_DLL_filter.cc:27-59, tracking_2nd_PLL_filter.cc:26-63),
+        // float throughout: ζ = 0.7, k = 1 (code) / 0.25 (carrier), pdi = 1 ms; the two constants get_*_nco forms per
+        // call are formed once (trk_glo_loop.h)
+        auto coefficients = [](float lbw, float k, float& ratio, float& gain) {
+            const float zeta = 0.7F, pdi = 0.001F;
+            const float Wn = lbw * 8.0F * zeta / (4.0F * zeta * zeta + 1.0F);
+            const float tau1 = k / (Wn * Wn);
+            const float tau2 = 2.0F * zeta / Wn;
+            ratio = tau2 / tau1;
+            gain = pdi / (2.0F * tau1);
+        };
+        coefficients(c.dll_bw_hz, 1.0F, p.ls[0].lf_in[0], p.ls[0].lf_in[1]);
+        coefficients(c.pll_bw_hz, 0.25F, p.ls[0].lf_out[0], p.ls[0].lf_out[1]);
+    }
     return true;
 }
 
@@ -469,6 +496,17 @@ extern "C" int gnsship_trk_create(gnsship_ctx* ctx, const gnsship_trk_conf* conf
             return fail(ctx, GNSSHIP_E_INVAL, msg);
         }
     }
+    if (conf->system == GNSSHIP_SYS_GLO_L1CA || conf->system == GNSSHIP_SYS_GLO_L2CA) {
+        // Cpu_Multicorrelator's generic rotator equals the real-code generic kernel for a code with zero imaginary part;
+        // its SIMD forms (four chains, renormalised every 128 iterations) are not restated
+        if (t->params.conf.rotator != GNSSHIP_ROTATOR_GENERIC) {
+            delete t;
+            return fail(ctx, GNSSHIP_E_INVAL,
+                "gnsship_trk_create: GLONASS needs rotator = GNSSHIP_ROTATOR_GENERIC (the u_avx / a_avx forms of "
+                "volk_gnsssdr_32fc_x2_rotator_dot_prod_32fc_xn are not restated)");
+        }
+        t->params.conf.high_dyn = 0;  // the block has no high-dynamics form: ignored
+    }
     if (t->params.conf.high_dyn) t->params.conf.rotator = GNSSHIP_ROTATOR_GENERIC;  // only generic high-dynamics variants exist
     if (t->params.conf.rotator == GNSSHIP_ROTATOR_AVX && !trk_persist_supports(t->params)) {
         delete t;
@@ -521,7 +559,7 @@ extern "C" int gnsship_trk_create(gnsship_ctx* ctx, const gnsship_trk_conf* conf
     if (e == hipSuccess) e = hipMemset(t->anchors_dev, 0, sizeof(Anchor) * static_cast<size_t>(n_anchors + kAnchorPad));
     if (e == hipSuccess) e = hipMalloc(&t->partials_dev, sizeof(float) * 2 * kMaxTaps * static_cast<size_t>(t->n_chunks));
     if (e == hipSuccess) e = hipMalloc(&t->out_dev, sizeof(float) * 2 * kMaxTaps * static_cast<size_t>(t->n_jobs));
-    t->high_dyn = conf->high_dyn != 0;
+    t->high_dyn = t->params.conf.high_dyn != 0;
     t->serial_rounds = !t->high_dyn && (conf->system == GNSSHIP_SYS_GAL_E5A || conf->system == GNSSHIP_SYS_GAL_E5B);
     if (e == hipSuccess && t->serial_rounds) e = hipMalloc(&t->serial_dev, sizeof(SerialJob) * static_cast<size_t>(t->n_jobs));
     if (e == hipSuccess && t->high_dyn) {
@@ -550,6 +588,72 @@ extern "C" int gnsship_trk_create(gnsship_ctx* ctx, const gnsship_trk_conf* conf
     return GNSSHIP_OK;
 }
 
+// glonass_l1_ca_dll_pll_tracking_cc::start_tracking (:148-225) and the pull-in call of general_work (:507-524) with
+// d_sample_counter = first_sample; the members' places in TrkChannel are listed in trk_glo_loop.h.
+static int glo_start_state(gnsship_trk* t, int channel, const gnsship_trk_start_args* a, TrkChannel& c)
+{
+    gnsship_ctx* ctx = t->ctx;
+    const TrkParams& p = t->params;
+    const gnsship_trk_conf& k = p.conf;
+    int32_t freq_ch = 0;
+    if (gnsship_glonass_freq_channel(a->prn, &freq_ch) != GNSSHIP_OK)
+        return fail(ctx, GNSSHIP_E_INVAL, "gnsship_trk_start: GLONASS PRN outside the GLONASS_PRN table (0..24)");
+    const double dfrq = k.system == GNSSHIP_SYS_GLO_L1CA ? 0.56250e6 : 0.43750e6;
+    std::memset(&c, 0, sizeof(c));
+    c.code_id = a->code_id;
+    c.data_code_id = a->code_id;
+    c.prn = static_cast<uint32_t>(a->prn);
+    c.acq_sample_stamp = a->acq_samplestamp_samples;
+    const int64_t fs_in = static_cast<int64_t>(k.fs_in);  // d_fs_in is an int64_t
+    const int64_t acq_trk_diff_samples = static_cast<int64_t>(a->first_sample) - static_cast<int64_t>(a->acq_samplestamp_samples);
+    const double acq_trk_diff_seconds = static_cast<float>(acq_trk_diff_samples) / static_cast<float>(fs_in);
+    const int64_t glonass_freq_ch = static_cast<int64_t>(p.carrier_freq + (dfrq * freq_ch));  // d_glonass_freq_ch is an int64_t
+    const double radial_velocity = (static_cast<double>(glonass_freq_ch) + a->acq_doppler_hz) / static_cast<double>(glonass_freq_ch);
+    c.code_phase_rate_step_chips = static_cast<double>(glonass_freq_ch);
+    c.code_freq_chips = radial_velocity * p.code_chip_rate;
+    c.code_phase_step_chips = c.code_freq_chips / static_cast<double>(fs_in);
+    const double T_chip_mod_seconds = 1.0 / c.code_freq_chips;
+    const double T_prn_mod_seconds = T_chip_mod_seconds * 511.0;
+    const double T_prn_mod_samples = T_prn_mod_seconds * static_cast<double>(fs_in);
+    c.current_prn_length_samples = static_cast<int32_t>(std::round(T_prn_mod_samples));
+    const double T_prn_true_seconds = 511.0 / p.code_chip_rate;
+    const double T_prn_true_samples = T_prn_true_seconds * static_cast<double>(fs_in);
+    const double T_prn_diff_seconds = T_prn_true_seconds - T_prn_mod_seconds;
+    const double N_prn_diff = acq_trk_diff_seconds / T_prn_true_seconds;
+    double corrected_acq_phase_samples = std::fmod(a->acq_delay_samples + T_prn_diff_seconds * N_prn_diff * static_cast<double>(fs_in), T_prn_true_samples);
+    if (corrected_acq_phase_samples < 0) corrected_acq_phase_samples = T_prn_mod_samples + corrected_acq_phase_samples;
+    c.carrier_phase_rate_step_rad = a->acq_doppler_hz + (dfrq * freq_ch);  // d_carrier_frequency_hz
+    c.carrier_doppler_hz = a->acq_doppler_hz;
+    c.carrier_phase_step_rad = 6.2831853071796 * c.carrier_phase_rate_step_rad / static_cast<double>(fs_in);
+    const double carrier_doppler_phase_step_rad = 6.2831853071796 * c.carrier_doppler_hz / static_cast<double>(fs_in);
+    c.carrier_lock_test = 1.0F;  // the constructor's values; start_tracking leaves them
+    c.cn0_db_hz = 0.0F;
+    c.spc = k.early_late_space_chips;
+    // the pull-in (:507-524)
+    const int32_t acq_to_trk_delay_samples = static_cast<int32_t>(a->first_sample - a->acq_samplestamp_samples);
+    const double acq_trk_shif_correction_samples = static_cast<double>(c.current_prn_length_samples) -
+                                                   static_cast<double>(std::fmod(static_cast<float>(acq_to_trk_delay_samples), static_cast<float>(c.current_prn_length_samples)));
+    const int32_t samples_offset = static_cast<int32_t>(std::round(corrected_acq_phase_samples + acq_trk_shif_correction_samples));
+    c.nitems_read = a->first_sample + static_cast<uint64_t>(samples_offset);
+    c.acc_carrier_phase_rad -= carrier_doppler_phase_step_rad * samples_offset;
+    c.state = 4;  // the block has one tracking state; records carry 4
+    if (p.has_if) {
+        const uint64_t fsu = static_cast<uint64_t>(p.fs_int);
+        const unsigned __int128 prod = static_cast<unsigned __int128>(static_cast<uint64_t>(p.if_mod)) * (c.nitems_read % fsu);
+        c.if_num = static_cast<int64_t>(prod % fsu);
+        c.if_cyc = static_cast<double>(c.if_num) / static_cast<double>(p.fs_int);
+    }
+    const int job = channel;  // one job per channel
+    t->job_code[job] = c.code_id;
+    const CodeDesc& cd = ctx->codes_host[c.code_id];
+    for (int m = 0; m < p.chunks_per_job; m++) {
+        ChunkDesc& d = t->chunks_host[t->jobs_first_chunk[job] + m];
+        d.code = cd.ptr;
+        d.code_len = cd.len;
+    }
+    return GNSSHIP_OK;
+}
+
 // start_tracking (:643-883) and the state-1 pull-in (:1757-1788) at nitems_read = first_sample: the
 // channel's state on the host (validated), and the channel's jobs' code ids in the host tables.
 static int trk_start_state(gnsship_trk* t, int channel, const gnsship_trk_start_args* a, TrkChannel& c)
@@ -568,6 +672,7 @@ static int trk_start_state(gnsship_trk* t, int channel, const gnsship_trk_start_
         if (a->prn < 1 || a->prn > last)
             return fail(ctx, GNSSHIP_E_INVAL, "gnsship_trk_start: Galileo E5a / E5b PRN outside 1..50 (E5a pilot secondary codes: 1..47)");
     }
+    if (p.conf.system == GNSSHIP_SYS_GLO_L1CA || p.conf.system == GNSSHIP_SYS_GLO_L2CA) return glo_start_state(t, channel, a, c);
     std::memset(&c, 0, sizeof(c));
     const gnsship_trk_conf& k = p.conf;
     c.code_id = a->code_id;
@@ -844,6 +949,8 @@ static int trk_enqueue(gnsship_trk* t, const void* src, int fmt, uint64_t buffer
     const bool persist = !t->high_dyn && trk_persist_supports(t->params) && trk_persist_lds_bytes(t->params, code_cap, avx) <= kTrkPersistMaxLds &&
                          !(t->force_rounds && !avx);
     if (avx && !persist) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_trk_run: the AVX rotator needs the persistent loop (epoch too long for LDS)");
+    if (!persist && (t->params.conf.system == GNSSHIP_SYS_GLO_L1CA || t->params.conf.system == GNSSHIP_SYS_GLO_L2CA))
+        return fail(ctx, GNSSHIP_E_INVAL, "gnsship_trk_run: the GLONASS loop runs in the persistent loop only (codes too long for its LDS, or GNSSHIP_TRK_ROUNDS)");
     gnsship_trk_corr_trace* trace = nullptr;
     t->trace_n = 0;
     if (t->trace_on && persist) {

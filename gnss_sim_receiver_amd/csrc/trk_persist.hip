@@ -65,6 +65,7 @@ __device__ __forceinline__ void trk_prof_stamp(int e, int k)
 #endif
 
 #include "trk_loop.h"
+#include "trk_glo_loop.h"
 
 #pragma clang fp contract(off)
 
@@ -397,14 +398,14 @@ __device__ void chains_avx(PEpoch& ep, i4v span, int N, const float* code0, cons
 // generic lane factor needs arg/|inc| in double, the AVX path needs dz instead).
 // p0 / inc: (cos rem, −sin rem) and (cos −step, sin −step), evaluated by two lanes of wave 0 at once.
 template <bool AVX>
-__device__ void derive_epoch(PEpoch& ep, const TrkParams& k, const TrkChannel& c, int64_t off, int L, f2 p0, f2 inc)
+__device__ void derive_epoch(PEpoch& ep, const TrkParams& k, const TrkChannel& c, int64_t off, int L, f2 p0, f2 inc, int32_t n_samples)
 {
     const int NT = k.n_taps;
     const float* sh = c.narrow ? k.shifts_n : k.shifts;
     DevJob& j = ep.job;
     const float spcf = static_cast<float>(k.code_samples_per_chip);
     j.sample_offset = off;
-    j.n_samples = static_cast<int32_t>(k.conf.vector_length);
+    j.n_samples = n_samples;
     j.code_id = c.code_id;
     j.n_taps = NT;
     j.rot_avx = 0;  // (the batch path's flag: this kernel has its own replays)
@@ -449,7 +450,10 @@ __device__ void stage_code(float* dst, const CodeDesc& cd)
 template <bool THRU>
 constexpr int persist_waves_per_simd() { return THRU ? 4 : 1; }
 
-template <int FMT, int NT, bool DATA, bool AVX, bool THRU, bool SERIAL = avx_serial_layout(NT, DATA)>
+// GLO: the GLONASS L1 / L2 C/A block (trk_glo_loop.h) on the generic serial pipeline — the epoch is correlated over the
+// channel's current block length (not vector_length) and thread 0 runs glo_epoch_update in place of the five phases.
+// Every GLO branch is `if constexpr`: the other instantiations compile to what they were.
+template <int FMT, int NT, bool DATA, bool AVX, bool THRU, bool SERIAL = avx_serial_layout(NT, DATA), bool GLO = false>
 __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk_persist_kernel(const TrkParams* __restrict__ pk, TrkChannel* __restrict__ chans,
     const CodeDesc* __restrict__ codes, int n_codes, const void* __restrict__ samples, uint64_t buf_first, int64_t buf_len, int max_rounds,
     int n_chans, int code_cap_floats, int avx_g, gnsship_trk_epoch* __restrict__ rec, gnsship_trk_dump_record* __restrict__ dump,
@@ -507,12 +511,12 @@ __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk
             const f2 p0 = f2{__shfl(cf, 0, kWave), -__shfl(sf, 0, kWave)};
             const f2 inc = f2{__shfl(cf, 1, kWave), __shfl(sf, 1, kWave)};
             if (lane == 0) {
-                const uint64_t vl = k.conf.vector_length;
+                const uint64_t vl = GLO ? static_cast<uint64_t>(sc.current_prn_length_samples > 0 ? sc.current_prn_length_samples : 0) : k.conf.vector_length;
                 const bool runnable = (sc.state == 2 || sc.state == 3 || sc.state == 4) && sc.nitems_read >= buf_first &&
-                                      sc.nitems_read + vl <= buf_first + static_cast<uint64_t>(buf_len);
+                                      sc.nitems_read + vl <= buf_first + static_cast<uint64_t>(buf_len) && (!GLO || vl > 0);
                 ep.runnable = runnable ? 1 : 0;
                 if (runnable) {
-                    derive_epoch<AVX>(ep, k, sc, static_cast<int64_t>(sc.nitems_read - buf_first), L, p0, inc);
+                    derive_epoch<AVX>(ep, k, sc, static_cast<int64_t>(sc.nitems_read - buf_first), L, p0, inc, static_cast<int32_t>(vl));
                     sc.epoch_start = sc.nitems_read;
                 }
                 ep.published = 0;
@@ -529,7 +533,9 @@ __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk
         const uint64_t off64 = static_cast<uint64_t>(ep.job.sample_offset);
         const int64_t off_u = static_cast<int64_t>((static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(off64 >> 32)))) << 32) |
                                                    static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(off64 & 0xffffffffu))));
-        const i4v span = sample_span<FMT>(samples, off_u, N);
+        // the epoch's length: vector_length, or (GLO) the block length the previous epoch left, wave-uniform
+        const int Ne = GLO ? __builtin_amdgcn_readfirstlane(ep.job.n_samples) : N;
+        const i4v span = sample_span<FMT>(samples, off_u, Ne);
         f2 acc[NT + 1];
 #pragma unroll
         for (int t = 0; t <= NT; t++) acc[t] = f2{0.0f, 0.0f};
@@ -552,7 +558,7 @@ __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk
             else
                 consume_avx<FMT, NT, DATA, false, THRU ? 4 : 16>(ep, Z, T, span, N, avx_g, c0, c1, L, lane, wave, acc);
         } else {
-            serial_epoch<FMT, NT, DATA>(ep, anc, avx_g, span, N, c0, c1, L, lane, wave);  // avx_g = the ring's chunks
+            serial_epoch<FMT, NT, DATA>(ep, anc, avx_g, span, Ne, c0, c1, L, lane, wave);  // avx_g = the ring's chunks
             if (tid == 0) GNSSHIP_TRK_STAMP(e, 2);
         }
         if (lane == 0) GNSSHIP_TRK_STAMP(e, wave <= 1 ? 3 + wave : 14 + wave);  // waves 2, 3: slots 16, 17
@@ -585,7 +591,12 @@ __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk
             GNSSHIP_TRK_STAMP(e, 5);
             ep.rec = gnsship_trk_epoch{};
             ep.rec.flags = 8;
-            ep.coh = epoch_pre(k, sc, taps, pdata, ep.rec, nullptr, dr);
+            if constexpr (GLO) {
+                ep.coh = 0.0;  // no phases: the block's whole epoch, record and consume_each included
+                glo_epoch_update(k, sc, taps, ep.rec, dr);
+            } else {
+                ep.coh = epoch_pre(k, sc, taps, pdata, ep.rec, nullptr, dr);
+            }
         }
         __syncthreads();
         // the lock detectors (wave 1) beside the loop filters and NCO update (wave 0), which run
@@ -609,14 +620,14 @@ __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk
                 if (locked) store_regs(lr, sc);
                 epoch_post(k, sc, taps, pdata, ep.rec, locked, dr);
             }
-            epoch_finish(k, sc, ep.rec);
+            if constexpr (!GLO) epoch_finish(k, sc, ep.rec);
             const size_t slot = static_cast<size_t>(e) * n_chans + ch;
             if (rec) rec[slot] = ep.rec;
             if (dump && (ep.rec.flags & 16)) dump[slot] = ep.dump;
             if (trace) {
                 gnsship_trk_corr_trace tr{};
                 tr.sample_counter = sc.epoch_start;
-                tr.n_samples = N;
+                tr.n_samples = Ne;
                 tr.n_taps = NT;
                 tr.rem_carrier_phase_rad = ep.trace_rem_carr;
                 tr.phase_step_rad = ep.trace_step;
@@ -688,6 +699,8 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
     int avx_g = 0;
     const size_t lds = persist_lds(params, code_cap_floats, avx, &avx_g);
     const bool data = params.jobs_per_channel > 1;
+    const bool glo = params.conf.system == GNSSHIP_SYS_GLO_L1CA || params.conf.system == GNSSHIP_SYS_GLO_L2CA;
+    if (glo && (avx || data || params.n_taps != 3)) return hipErrorInvalidValue;
     // more channels than CUs: the throughput variant (GNSSHIP_TRK_THRU=0/1 overrides, for A/B runs)
     bool thru = n_chans > 256;
     if (const char* env = std::getenv("GNSSHIP_TRK_THRU")) thru = env[0] == '1';
@@ -702,9 +715,19 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
         hipLaunchKernelGGL(kfn, grid, block, lds, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans,  \
             code_cap_floats, avx_g, rec, dump, trace, ran_count);                                                                                     \
     } while (0)
+#define GNSSHIP_PERSIST_GLO(F)                                                                                                                \
+    do {                                                                                                                                      \
+        auto kfn = thru ? trk_persist_kernel<F, 3, false, false, true, false, true> : trk_persist_kernel<F, 3, false, false, false, false, true>; \
+        hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)); \
+        if (e0 != hipSuccess) return e0;                                                                                                      \
+        hipLaunchKernelGGL(kfn, grid, block, lds, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans, \
+            code_cap_floats, avx_g, rec, dump, trace, ran_count);                                                                             \
+    } while (0)
 #define GNSSHIP_PERSIST_F(F)                                                      \
     do {                                                                          \
-        if (nt == 3 && !data) {                                                   \
+        if (glo) {                                                                \
+            GNSSHIP_PERSIST_GLO(F);                                               \
+        } else if (nt == 3 && !data) {                                            \
             if (avx && params.single_code_bits) GNSSHIP_PERSIST_S(F, 3, false, true, true); /* B3I, L2C: chains_avx */ \
             else if (avx) GNSSHIP_PERSIST(F, 3, false, true);                     \
             else GNSSHIP_PERSIST(F, 3, false, false);                             \
@@ -728,6 +751,7 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
     default: return hipErrorInvalidValue;
     }
 #undef GNSSHIP_PERSIST_F
+#undef GNSSHIP_PERSIST_GLO
 #undef GNSSHIP_PERSIST_S
 #undef GNSSHIP_PERSIST
     return hipGetLastError();

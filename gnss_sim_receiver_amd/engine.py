@@ -355,12 +355,14 @@ class PcpsAcquisition:
         nb = ctypes.c_int()
         check(ctx.lib.gnsship_acq_num_bins(self.h, ctypes.byref(nb)), "gnsship_acq_num_bins", ctx.h)
         self.n_bins = nb.value
+        self.fdma_channels = 0  # > 0: the grid is an FDMA grid (set_grid_fdma)
 
     def set_grid(self, doppler_max: int, doppler_step: int, doppler_center: int = 0):
         check(self.ctx.lib.gnsship_acq_set_grid(self.h, doppler_max, doppler_step, doppler_center), "gnsship_acq_set_grid", self.ctx.h)
         nb = ctypes.c_int()
         check(self.ctx.lib.gnsship_acq_num_bins(self.h, ctypes.byref(nb)), "gnsship_acq_num_bins", self.ctx.h)
         self.n_bins = nb.value
+        self.fdma_channels = 0
 
     def set_grid_step2(self, doppler_center_step_two: float, doppler_step2: float, num_doppler_bins_step2: int,
                        step_one_input_power: float):
@@ -392,6 +394,34 @@ class PcpsAcquisition:
               "gnsship_acq_run", self.ctx.h)
         return list(res), grid
 
+    def set_grid_fdma(self, doppler_max: int, doppler_step: int, doppler_center: int, bias_hz):
+        """One Doppler grid per FDMA frequency channel (pcps_acquisition's d_doppler_bias, :211-229, :295-302):
+        channel g's rows are built from bias_hz[g] + the grid's Doppler.  set_grid returns to the ordinary grid."""
+        bias = np.ascontiguousarray(bias_hz, np.int32)
+        check(self.ctx.lib.gnsship_acq_set_grid_fdma(self.h, doppler_max, doppler_step, doppler_center, len(bias),
+                                                     bias.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "gnsship_acq_set_grid_fdma", self.ctx.h)
+        nb = ctypes.c_int()
+        check(self.ctx.lib.gnsship_acq_num_bins(self.h, ctypes.byref(nb)), "gnsship_acq_num_bins", self.ctx.h)
+        self.n_bins = nb.value
+        self.fdma_channels = len(bias)
+
+    def run_fdma(self, sig, prn_slot: int = 0, want_grid: bool = False, fmt: int = None):
+        """One dwell of the code in prn_slot under every channel of the FDMA grid: one result per channel (its
+        doppler_hz without the bias) and, with want_grid, the grid as (channels, n_bins, row_len)."""
+        nch = self.fdma_channels
+        if not nch:
+            raise ValueError("run_fdma needs set_grid_fdma first")
+        res = (abi.AcqResult * nch)()
+        grid = np.zeros((nch, self.n_bins, self.row_len), np.float32) if want_grid else None
+        if isinstance(sig, DeviceBuffer):
+            ptr, on_dev, f = sig.ptr, 1, FMT_CF32 if fmt is None else fmt
+        else:
+            sig = np.ascontiguousarray(sig)
+            ptr, on_dev, f = sig.ctypes.data, 0, sample_format(sig)
+        check(self.ctx.lib.gnsship_acq_run_fdma(self.h, ptr, f, on_dev, prn_slot, res, fptr(grid) if want_grid else None),
+              "gnsship_acq_run_fdma", self.ctx.h)
+        return list(res), grid
+
     def close(self):
         if self.h:
             self.ctx.lib.gnsship_acq_destroy(self.h)
@@ -403,6 +433,57 @@ class PcpsAcquisition:
                 self.close()
         except Exception:
             pass
+
+
+def _glonass_pcps_acquisition(signal, ctx, fs_in, doppler_max, doppler_step, freq_channels, sampled_ms, kw):
+    from . import codes
+    code_length = int(np.floor(fs_in / (codes.GLONASS_L1_CA_CODE_RATE_CPS / codes.GLONASS_L1_CA_CODE_LENGTH_CHIPS)))
+    acq = PcpsAcquisition(ctx, fs_in, sampled_ms * code_length, doppler_max, doppler_step, chip_rate=codes.GLONASS_L1_CA_CODE_RATE_CPS,
+                          ms_per_code=1, **kw)
+    acq.freq_channels = [int(k) for k in freq_channels]
+    # gnsship_acq_create has just built the ordinary grid's table and buffers; they are replaced here, once per handle
+    # (a few ms of host table per grid).  Kept so: a handle is always runnable, and creation is not on the dwell path.
+    acq.set_grid_fdma(doppler_max, doppler_step, kw.get("doppler_center", 0), [codes.glonass_doppler_bias_hz(signal, k) for k in acq.freq_channels])
+    acq.set_local_code(codes.glonass_l1_ca_acquisition_code(fs_in, sampled_ms))
+    return acq
+
+
+def glonass_l1_ca_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, doppler_step: int, freq_channels=range(-7, 7),
+                                   sampled_ms: int = 1, **kw) -> PcpsAcquisition:
+    """GlonassL1CaPcpsAcquisition's parameters (glonass_l1_ca_pcps_acquisition.cc:49-66): ms_per_code 1, the C/A chip
+    rate 511 kcps, code_length = floor(fs / 1000) samples and a search window of sampled_ms of them (an optimum
+    acquisition rate of 100e6: no resampler is ever designed).  Every satellite sends the same code, so the handle
+    comes back with that code in slot 0 and the FDMA grid of freq_channels set (bias (int32)(DFRQ1_GLO · k), as
+    is_fdma() computes it): run_fdma(sig) gives one result per entry of acq.freq_channels.  The channel of a PRN is
+    codes.glonass_freq_channel(prn).  Other PcpsAcquisition arguments pass through."""
+    return _glonass_pcps_acquisition("1G", ctx, fs_in, doppler_max, doppler_step, freq_channels, sampled_ms, kw)
+
+
+def glonass_l2_ca_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, doppler_step: int, freq_channels=range(-7, 7),
+                                   sampled_ms: int = 1, **kw) -> PcpsAcquisition:
+    """GlonassL2CaPcpsAcquisition (glonass_l2_ca_pcps_acquisition.cc:48-66): as L1 with the bias (int32)(DFRQ2_GLO · k)."""
+    return _glonass_pcps_acquisition("2G", ctx, fs_in, doppler_max, doppler_step, freq_channels, sampled_ms, kw)
+
+
+def _glonass_trk_conf(system: int, fs_in: float, kw) -> "abi.TrkConf":
+    from . import codes
+    vl = int(round(fs_in / (codes.GLONASS_L1_CA_CODE_RATE_CPS / codes.GLONASS_L1_CA_CODE_LENGTH_CHIPS)))
+    base = dict(pll_bw_hz=50.0, dll_bw_hz=2.0, early_late_space_chips=0.5, max_carrier_lock_fail=50, rotator=abi.ROTATOR_GENERIC)
+    base.update(kw)
+    return abi.TrkConf.defaults(system, fs_in, vl, **base)
+
+
+def glonass_l1_ca_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
+    """GlonassL1CaDllPllTracking's configuration (glonass_l1_ca_dll_pll_tracking.cc:44-62): vector_length = round(fs / 1000),
+    pll_bw_hz 50, dll_bw_hz 2, early_late_space_chips 0.5; max_carrier_lock_fail carries the block's gflag max_lock_fail (50),
+    carrier_lock_th and cn0_min theirs (0.7, 25).  The rotator is the generic one (the only one the engine has for this
+    block).  Tracking code: codes.glonass_l1_ca_code_gen_float(); start's prn selects the frequency channel."""
+    return _glonass_trk_conf(abi.SYS_GLO_L1CA, fs_in, kw)
+
+
+def glonass_l2_ca_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
+    """GlonassL2CaDllPllTracking (glonass_l2_ca_dll_pll_tracking.cc:44-62): as L1 on the L2 carrier and spacing."""
+    return _glonass_trk_conf(abi.SYS_GLO_L2CA, fs_in, kw)
 
 
 def gps_l5i_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, doppler_step: int, sampled_ms: int = 1, **kw) -> PcpsAcquisition:
@@ -889,15 +970,22 @@ class DllPllVemlTracking:
         return np.array([self.channel_state(ch)[0] for ch in range(self.max_channels)], np.int32)
 
     @staticmethod
-    def write_dump_files(prefix: str, records: np.ndarray, dumps: np.ndarray, append: bool = False) -> list:
+    def write_dump_files(prefix: str, records: np.ndarray, dumps: np.ndarray, append: bool = False, glonass: bool = False) -> list:
         """The reference's per-channel tracking dump files (<prefix><channel>.dat, dll_pll_veml_tracking.cc:
-        set_channel :1674-1700, log_data :1376-1466): the records log_data wrote, in round order."""
+        set_channel :1674-1700, log_data :1376-1466): the records log_data wrote, in round order.
+        glonass: the 88-byte record of glonass_l1_ca_dll_pll_tracking_cc (:641-701), which has no rate fields."""
         paths = []
         for ch in range(records.shape[1]):
             sel = (records[:, ch]["flags"] & abi.TRK_FLAG_DUMP) != 0
             path = f"{prefix}{ch}.dat"
+            rows = np.ascontiguousarray(dumps[sel, ch])
+            if glonass:
+                short = np.zeros(len(rows), abi.TRK_DUMP_GLONASS_DTYPE)
+                for name in abi.TRK_DUMP_GLONASS_DTYPE.names:
+                    short[name] = rows[name]
+                rows = short
             with open(path, "ab" if append else "wb") as f:
-                f.write(np.ascontiguousarray(dumps[sel, ch]).tobytes())
+                f.write(rows.tobytes())
             paths.append(path)
         return paths
 

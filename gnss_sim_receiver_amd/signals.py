@@ -36,7 +36,15 @@ SYSTEMS = {
     # Galileo E5a / E5b: the tracking code is the Q pilot, the data code the I component (dll_pll_veml_tracking.cc:699-746)
     "GAL_E5A": (C.GALILEO_E5A_CODE_CHIP_RATE_CPS, C.GALILEO_E5A_CODE_LENGTH_CHIPS, C.GALILEO_E5A_FREQ_HZ, C.galileo_e5a_q_code_gen_float),
     "GAL_E5B": (C.GALILEO_E5B_CODE_CHIP_RATE_CPS, C.GALILEO_E5B_CODE_LENGTH_CHIPS, C.GALILEO_E5B_FREQ_HZ, C.galileo_e5b_q_code_gen_float),
+    # GLONASS L1 / L2 C/A: FDMA — one code for every satellite; the carrier here is channel 0's, a satellite's own
+    # is carrier + freq_channel·FDMA_STEP_HZ (Satellite.carrier_hz), and it sits at that offset in the IF
+    "GLO_L1": (C.GLONASS_L1_CA_CODE_RATE_CPS, C.GLONASS_L1_CA_CODE_LENGTH_CHIPS, C.GLONASS_L1_CA_FREQ_HZ,
+               lambda prn: C.glonass_l1_ca_code_gen_float()),
+    "GLO_L2": (C.GLONASS_L2_CA_CODE_RATE_CPS, C.GLONASS_L2_CA_CODE_LENGTH_CHIPS, C.GLONASS_L2_CA_FREQ_HZ,
+               lambda prn: C.glonass_l2_ca_code_gen_float()),
 }
+# FDMA systems: carrier spacing between adjacent frequency channels
+FDMA_STEP_HZ = {"GLO_L1": C.DFRQ1_GLO, "GLO_L2": C.DFRQ2_GLO}
 DATA_CODES = {"GAL": lambda prn: C.galileo_e1_code_gen_sinboc11_float("1B", prn), "GPS_L5": C.gps_l5i_code_gen_float,
               "GAL_E5A": C.galileo_e5a_i_code_gen_float, "GAL_E5B": C.galileo_e5b_i_code_gen_float}
 # secondary codes a system's satellites carry unless the Satellite names its own, as a function of the PRN
@@ -80,8 +88,14 @@ class Satellite:
     doppler_rate_hz_s: float = 0.0
     # code periods per navigation bit when not the system default (BeiDou GEO D2: 2)
     symbols_per_bit: int = None
+    # FDMA frequency channel k (GLONASS, −7…+6): by default the GLONASS_PRN table's value for the PRN.  The
+    # satellite's carrier is the system's + k·FDMA_STEP_HZ, and its signal lies k·FDMA_STEP_HZ above f_if_hz
+    # (bits with symbols_per_bit=10 give the 10 ms meander half-bits of the GLONASS data)
+    freq_channel: int = None
 
     def __post_init__(self):
+        if self.freq_channel is None and self.system in FDMA_STEP_HZ:
+            self.freq_channel = C.glonass_freq_channel(self.prn)
         if self.code is None:
             self.code = SYSTEMS[self.system][3](self.prn)
         if self.code_data is None and self.system in DATA_CODES:
@@ -101,20 +115,27 @@ class Satellite:
     def code_len(self):
         return SYSTEMS[self.system][1]
 
+    def carrier_hz(self):
+        """The satellite's own carrier: the system's, plus the FDMA channel offset."""
+        fc = SYSTEMS[self.system][2]
+        return fc + self.freq_channel * FDMA_STEP_HZ[self.system] if self.system in FDMA_STEP_HZ else fc
+
+    def if_hz(self):
+        """Where the satellite's carrier lies in the IF stream at zero Doppler: f_if_hz, plus the FDMA channel offset."""
+        return self.f_if_hz + self.freq_channel * FDMA_STEP_HZ[self.system] if self.system in FDMA_STEP_HZ else self.f_if_hz
+
     def code_freq(self):
-        rate, _, fc, _ = SYSTEMS[self.system]
-        return rate * (1.0 + self.doppler_hz / fc)
+        return self.chip_rate * (1.0 + self.doppler_hz / self.carrier_hz())
 
     def chip_phase(self, n: np.ndarray, fs: float) -> np.ndarray:
         """Received code phase [chips] at sample n (unwrapped)."""
         ph = n / fs * self.code_freq() - self.code_delay_chips
         if self.doppler_rate_hz_s:
-            rate, _, fc, _ = SYSTEMS[self.system]
-            ph = ph + 0.5 * rate * self.doppler_rate_hz_s / fc * (n / fs) ** 2
+            ph = ph + 0.5 * self.chip_rate * self.doppler_rate_hz_s / self.carrier_hz() * (n / fs) ** 2
         return ph
 
     def carrier_phase(self, n: np.ndarray, fs: float) -> np.ndarray:
-        ph = 2.0 * np.pi * (self.f_if_hz + self.doppler_hz) * (n / fs) + self.carrier_phase_rad
+        ph = 2.0 * np.pi * (self.if_hz() + self.doppler_hz) * (n / fs) + self.carrier_phase_rad
         if self.doppler_rate_hz_s:
             ph = ph + np.pi * self.doppler_rate_hz_s * (n / fs) ** 2
         return ph
@@ -201,7 +222,7 @@ def truth_jobs(sat: Satellite, fs: float, n_epochs: int, vector_length: int, shi
         jobs[i]["code_id"] = code_id
         jobs[i]["n_taps"] = len(shifts_chips)
         jobs[i]["rem_carrier_phase_rad"] = np.float32(carr)
-        jobs[i]["phase_step_rad"] = np.float32(2 * np.pi * (sat.f_if_hz + sat.doppler_hz) / fs)
+        jobs[i]["phase_step_rad"] = np.float32(2 * np.pi * (sat.if_hz() + sat.doppler_hz) / fs)
         jobs[i]["rem_code_phase_chips"] = np.float32(-chip * samples_per_chip)
         jobs[i]["code_phase_step_chips"] = np.float32(fcode / fs * samples_per_chip)
         sh = np.zeros(MAX_TAPS, np.float32)
@@ -242,7 +263,7 @@ def generate_if_device(fs: float, n_samples: int, sats: list, seed: int = 0, sta
                               None if s.code_data is None else torch.as_tensor(np.asarray(s.code_data, np.float64), device=device))
             code, code_d = codes[key]
             amp = float(np.sqrt(2.0 * 10.0 ** (s.cn0_dbhz / 10.0) / fs))
-            rate, _, fc, _ = SYSTEMS[s.system]
+            rate, fc = s.chip_rate, s.carrier_hz()
             ph = n / fs * s.code_freq() - s.code_delay_chips
             if s.doppler_rate_hz_s:
                 ph = ph + 0.5 * rate * s.doppler_rate_hz_s / fc * (n / fs) ** 2
@@ -269,7 +290,7 @@ def generate_if_device(fs: float, n_samples: int, sats: list, seed: int = 0, sta
                 c = (sign * code_d[idx] - c) / np.sqrt(2.0)
             else:
                 c = c * sign
-            cp = 2.0 * np.pi * (s.f_if_hz + s.doppler_hz) * (n / fs) + s.carrier_phase_rad
+            cp = 2.0 * np.pi * (s.if_hz() + s.doppler_hz) * (n / fs) + s.carrier_phase_rad
             if s.doppler_rate_hz_s:
                 cp = cp + np.pi * s.doppler_rate_hz_s * (n / fs) ** 2
             cos_cp, sin_cp = torch.cos(cp), torch.sin(cp)

@@ -210,6 +210,21 @@ int gnsship_galileo_e5a_i_secondary_code(char* dest);
 int gnsship_galileo_e5b_i_secondary_code(char* dest);
 int gnsship_galileo_e5a_q_secondary_code(char* dest, int32_t prn);
 int gnsship_galileo_e5b_q_secondary_code(char* dest, int32_t prn);
+/* glonass_l1_ca_code_gen_complex (glonass_l1_signal_replica.cc:25-77): the one GLONASS C/A code, 511 chips ±1,
+ * rotated left by chip_shift.  _float: dest[511]; _complex: dest = 511 complex, the code in the real part. */
+int gnsship_glonass_l1_ca_code_gen_float(float* dest, uint32_t chip_shift);
+int gnsship_glonass_l1_ca_code_gen_complex(float* dest, uint32_t chip_shift);
+/* glonass_l1_ca_code_gen_complex_sampled (:83-123): dest = n = (int)(fs / 1000) complex (code in real), chip index
+ * ceil(ts·(i+1)/tc) − 1 in float, the last sample forced to the last chip; returns n or <0 */
+int gnsship_glonass_l1_ca_code_gen_complex_sampled(float* dest, int32_t sampling_freq, uint32_t chip_shift);
+/* glonass_l2_signal_replica.cc: the same code under the L2 names */
+int gnsship_glonass_l2_ca_code_gen_float(float* dest, uint32_t chip_shift);
+int gnsship_glonass_l2_ca_code_gen_complex(float* dest, uint32_t chip_shift);
+int gnsship_glonass_l2_ca_code_gen_complex_sampled(float* dest, int32_t sampling_freq, uint32_t chip_shift);
+/* GLONASS_PRN (GLONASS_L1_L2_CA.h:134): *k = the FDMA frequency channel (−7…+6) of PRN (orbital slot) 1..24, and 8 for
+ * the reference's test entry PRN 0; GNSSHIP_E_INVAL for any other PRN.  The carrier of channel k is
+ * 1602 MHz + k·562.5 kHz on L1 and 1246 MHz + k·437.5 kHz on L2. */
+int gnsship_glonass_freq_channel(int32_t prn, int32_t* k);
 /* samples per code period: (int)(fs / (chip_rate / code_len)) as the generators compute it */
 int gnsship_code_samples_per_code(int32_t chip_rate, int32_t code_len, int32_t fs);
 
@@ -342,6 +357,22 @@ int gnsship_acq_set_grid_step2(gnsship_acq* a, float doppler_center_step_two, fl
 int gnsship_acq_run(gnsship_acq* a, const void* sig, int fmt, int sig_on_device, int n_prns,
     gnsship_acq_result* results, float* grid);
 int gnsship_acq_num_bins(gnsship_acq* a, int* n_bins);
+/* FDMA sweep (GLONASS; pcps_acquisition's is_fdma() / d_doppler_bias, :175-229, :296-301): one code searched
+ * under n_channels Doppler grids in one pass.  The wipe-off table holds n_channels × n_bins rows, channel-major;
+ * row (g, i) is built from (float)(bias_hz[g] − doppler_max + doppler_center + doppler_step·i), as
+ * update_grid_doppler_wipeoffs builds a channel's row with d_doppler_bias = bias_hz[g].  1 ≤ n_channels ≤ 32 (GLONASS
+ * has 14) and n_channels·n_bins ≤ 4096, GNSSHIP_E_INVAL otherwise.  n_bins is the ordinary
+ * grid's, ceil(2·doppler_max / doppler_step), and what gnsship_acq_num_bins reports.  The buffers that scale with the
+ * row count are reallocated when n_channels·n_bins changes.  gnsship_acq_set_grid returns the handle to the ordinary
+ * grid; while the FDMA grid is set, gnsship_acq_run and gnsship_acq_set_grid_step2 return GNSSHIP_E_INVAL (two-step
+ * acquisition is not available on an FDMA grid). */
+int gnsship_acq_set_grid_fdma(gnsship_acq* a, int doppler_max, int doppler_step, int doppler_center, int n_channels, const int32_t* bias_hz);
+/* One dwell of the code in prn_slot under every frequency channel of the FDMA grid: the forward transforms and the
+ * search run once over all n_channels·n_bins rows; the decision (arg-max, the CFAR opposite-bin row, first against
+ * second peak) is taken per channel inside that channel's n_bins rows.  results[n_channels]: doppler_index within the
+ * channel, doppler_hz without the bias (as Acq_doppler_hz).  grid (optional, host): n_channels × n_bins × row
+ * floats, channel-major.  Non-coherent dwells, bit_transition_flag and zero padding act as in gnsship_acq_run. */
+int gnsship_acq_run_fdma(gnsship_acq* a, const void* sig, int fmt, int sig_on_device, int prn_slot, gnsship_acq_result* results, float* grid);
 /* Restart the non-coherent dwell accumulation (d_num_noncoherent_integrations_counter = 0 after a
  * decision, pcps_acquisition.cc:783,835,860-864): the next gnsship_acq_run is dwell 1. */
 int gnsship_acq_reset_dwells(gnsship_acq* a);
@@ -564,6 +595,25 @@ int gnsship_mit_destroy(gnsship_mit* m);
  *     capped at the I secondary length (20 / 4).  start's prn must be in 1..50. */
 #define GNSSHIP_SYS_GAL_E5A 6
 #define GNSSHIP_SYS_GAL_E5B 7
+/* GLONASS L1 / L2 C/A: not dll_pll_veml_tracking but glonass_l1_ca_dll_pll_tracking_cc (glonass_l2_…: the same block with
+ * the L2 constants) — 3 taps at ∓early_late_space_chips, two second-order float loop filters (Tracking_2nd_DLL_filter,
+ * Tracking_2nd_PLL_filter: ζ 0.7, pdi 1 ms, coefficients fixed at create from dll_bw_hz / pll_bw_hz), no bit or secondary
+ * synchronisation states, a lock test every CN0_ESTIMATION_SAMPLES + 1 = 11 epochs.  The carrier NCO carries the channel's
+ * FDMA offset DFRQ·k, k from start's PRN through gnsship_glonass_freq_channel (GNSSHIP_E_INVAL for a PRN outside the
+ * table); carrier_doppler_hz is reported without it.  Of gnsship_trk_conf the block reads fs_in, vector_length
+ * (round(fs / 1000)), pll_bw_hz, dll_bw_hz, early_late_space_chips, carrier_lock_th, cn0_min, max_carrier_lock_fail (the
+ * block's gflags carrier_lock_th / cn0_min / max_lock_fail), if_hz and rotator; cn0_samples only sizes the prompt buffer
+ * (the test length is 10).  Ignored: track_pilot, the FLL fields, the narrow spacings and bandwidths,
+ * very_early_late_space_chips, extend_correlation_symbols, high_dyn, the smoothers, slope / spc / y_intercept,
+ * max_code_lock_fail, pull_in_time_s, bit_synchronization_time_limit_s, carrier_aiding and the filter orders.  rotator must
+ * be GNSSHIP_ROTATOR_GENERIC (create: GNSSHIP_E_INVAL otherwise — the SIMD forms of the complex-code rotator are not
+ * restated).  The loop runs on the persistent generic pipeline only (gnsship_trk_last_engine: _PERSIST); a run that cannot
+ * use it returns GNSSHIP_E_INVAL.  Records: state 4; flags 8 every epoch, 1 Flag_valid_symbol_output, 2 on loss of lock (the
+ * channel stops), 16 with dump; prompt_i / prompt_q the epoch's prompt on every epoch; sample_counter the epoch's first
+ * sample.  The epoch is correlated over the block length the previous epoch left and consumes the new one, as the block
+ * does.  Dump records (:641-701): PRN_start_sample_count is the epoch's first sample, both rate fields 0. */
+#define GNSSHIP_SYS_GLO_L1CA 8
+#define GNSSHIP_SYS_GLO_L2CA 9
 
 typedef struct gnsship_trk_conf { /* Dll_Pll_Conf (dll_pll_conf.h:33-80), same names and units */
     double fs_in;

@@ -12,8 +12,10 @@
 #include <array>
 #include <cmath>
 #include <complex>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <atomic>
 #include <map>
 #include <memory>
@@ -645,6 +647,64 @@ public:
     void set_doppler_step(uint32_t doppler_step) { doppler_step_ = doppler_step; }
     void set_doppler_center(int32_t doppler_center) { doppler_center_ = doppler_center; }
     int consumed_samples() const { return consumed_; }
+    // is_fdma() (:211-229) for the satellite this block is to acquire, as set_gnss_synchro + set_local_code leave it:
+    // signal "1G" / "2G" gives d_doppler_bias = (int32)(DFRQ · GLONASS_PRN[prn]) and rebuilds the grid with it
+    // (update_grid_doppler_wipeoffs adds the bias to every wipeoff frequency, :295-302); any other signal clears the
+    // bias.  Acq_doppler_hz is reported without the bias, as the block reports it, and step two of make_2_steps is
+    // centred on that reported Doppler (update_grid_doppler_wipeoffs_step2, :305-312, adds no bias).  false: a PRN the
+    // GLONASS_PRN table does not hold (the reference's map::at throws there).
+    bool set_gnss_synchro(const char* signal, uint32_t prn)
+    {
+        int32_t bias = 0;
+        if (signal && (std::strcmp(signal, "1G") == 0 || std::strcmp(signal, "2G") == 0)) {
+            int32_t k = 0;
+            if (gnsship_glonass_freq_channel(static_cast<int32_t>(prn), &k) != GNSSHIP_OK) return false;
+            bias = static_cast<int32_t>((signal[0] == '1' ? 0.56250e6 : 0.43750e6) * k);
+        }
+        doppler_bias_ = bias;
+        fdma_channels_ = 0;
+        return init();
+    }
+    int32_t doppler_bias() const { return doppler_bias_; }
+    // The FDMA sweep (gnsship_acq_set_grid_fdma / gnsship_acq_run_fdma): the one GLONASS code under the grids of several
+    // frequency channels in one pass, in place of one block per channel.  init_fdma builds the channel-major grid for
+    // the current max / step / center; acquisition_core_fdma runs one dwell and fills one outcome per channel
+    // (Acq_doppler_hz without the bias; positive against the threshold).  No step two on this grid.  init() or
+    // set_gnss_synchro() returns the block to its own grid.  acquisition_core_fdma searches the code of slot 0 (the
+    // block's only one), keeps no grid, and stays outside the block's state machine: it touches neither the dwell
+    // counter nor general_work's state, so with max_dwells > 1 successive calls accumulate in the engine until
+    // max_dwells is reached and the caller decides when a series ends (init_fdma() or init() restarts it).
+    bool init_fdma(const std::vector<int32_t>& bias_hz)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        const int step = doppler_step_ ? static_cast<int>(doppler_step_) : static_cast<int>(conf_.doppler_step);
+        if (gnsship_acq_set_grid_fdma(h_, conf_.doppler_max, step, doppler_center_, static_cast<int>(bias_hz.size()), bias_hz.data()) != GNSSHIP_OK)
+            return false;
+        step_two_ = false;
+        fdma_channels_ = static_cast<int>(bias_hz.size());
+        calculate_threshold();
+        return true;
+    }
+    bool acquisition_core_fdma(const std::complex<float>* in, uint64_t samp_count, std::vector<Acq_Outcome>& out)
+    {
+        if (fdma_channels_ < 1) return false;
+        std::vector<gnsship_acq_result> r(static_cast<size_t>(fdma_channels_));
+        {
+            std::lock_guard<std::mutex> lk(dev_->mutex());
+            if (gnsship_acq_run_fdma(h_, in, GNSSHIP_FMT_CF32, 0, 0, r.data(), nullptr) != GNSSHIP_OK) return false;
+        }
+        out.assign(r.size(), Acq_Outcome{});
+        for (size_t g = 0; g < r.size(); g++) {
+            out[g].Acq_delay_samples = r[g].acq_delay_samples - static_cast<double>(resampler_latency_);
+            out[g].Acq_doppler_hz = static_cast<double>(r[g].doppler_hz);
+            out[g].Acq_samplestamp_samples = static_cast<uint64_t>(std::rint(static_cast<double>(samp_count) * conf_.resampler_ratio));
+            out[g].test_statistics = r[g].test_statistic;
+            out[g].input_power = r[g].input_power;
+            out[g].peak = r[g].peak;
+            out[g].positive = r[g].test_statistic > threshold_;
+        }
+        return true;
+    }
     // set_local_code (:175-208): FFT of the zero-padded sampled code + conjugate, on the device
     bool set_local_code(const std::complex<float>* code)
     {
@@ -656,8 +716,9 @@ public:
     {
         std::lock_guard<std::mutex> lk(dev_->mutex());
         const int step = doppler_step_ ? static_cast<int>(doppler_step_) : static_cast<int>(conf_.doppler_step);
-        if (gnsship_acq_set_grid(h_, conf_.doppler_max, step, doppler_center_) != GNSSHIP_OK) return false;
+        if (gnsship_acq_set_grid(h_, conf_.doppler_max, step, doppler_center_ + doppler_bias_) != GNSSHIP_OK) return false;
         step_two_ = false;
+        fdma_channels_ = 0;
         calculate_threshold();
         return true;
     }
@@ -685,6 +746,7 @@ public:
             std::lock_guard<std::mutex> lk(dev_->mutex());
             if (gnsship_acq_run(h_, in, GNSSHIP_FMT_CF32, 0, 1, &r, nullptr) != GNSSHIP_OK) return false;
         }
+        r.doppler_hz -= doppler_bias_;  // the grid's centre carried the FDMA bias; Acq_doppler_hz does not
         out.Acq_delay_samples = r.acq_delay_samples - static_cast<double>(resampler_latency_);  // :686-687
         out.Acq_doppler_hz = static_cast<double>(r.doppler_hz);
         out.Acq_samplestamp_samples = static_cast<uint64_t>(std::rint(static_cast<double>(samp_count) * conf_.resampler_ratio));  // :689
@@ -704,7 +766,7 @@ public:
                 step_two_ = true;
             } else if (step_two_) {
                 const int step = doppler_step_ ? static_cast<int>(doppler_step_) : static_cast<int>(conf_.doppler_step);
-                if (gnsship_acq_set_grid(h_, conf_.doppler_max, step, doppler_center_) != GNSSHIP_OK) return false;
+                if (gnsship_acq_set_grid(h_, conf_.doppler_max, step, doppler_center_ + doppler_bias_) != GNSSHIP_OK) return false;
                 step_two_ = false;
             }
         }
@@ -806,6 +868,7 @@ private:
             std::lock_guard<std::mutex> lk(dev_->mutex());
             if (gnsship_acq_run(h_, in, GNSSHIP_FMT_CF32, 0, 1, &r, nullptr) != GNSSHIP_OK) return;
         }
+        r.doppler_hz -= doppler_bias_;  // the grid's centre carried the FDMA bias; Acq_doppler_hz does not
         synchro_.Acq_delay_samples = r.acq_delay_samples - static_cast<double>(resampler_latency_);
         synchro_.Acq_doppler_hz = static_cast<double>(r.doppler_hz);
         synchro_.Acq_samplestamp_samples = static_cast<uint64_t>(std::rint(static_cast<double>(sample_counter_) * conf_.resampler_ratio));
@@ -819,7 +882,7 @@ private:
         auto to_step_one = [&]() {
             const int step = doppler_step_ ? static_cast<int>(doppler_step_) : static_cast<int>(conf_.doppler_step);
             std::lock_guard<std::mutex> lk(dev_->mutex());
-            gnsship_acq_set_grid(h_, conf_.doppler_max, step, doppler_center_);
+            gnsship_acq_set_grid(h_, conf_.doppler_max, step, doppler_center_ + doppler_bias_);
             step_two_ = false;
         };
         auto on_hit = [&]() {
@@ -901,6 +964,8 @@ private:
     float threshold_ = 0.0F;
     uint32_t doppler_step_ = 0;
     int32_t doppler_center_ = 0;
+    int32_t doppler_bias_ = 0;   // d_doppler_bias (is_fdma)
+    int fdma_channels_ = 0;      // > 0: the FDMA sweep's grid is set (init_fdma)
     uint32_t resampler_latency_ = 0;
 };
 
@@ -1013,6 +1078,60 @@ inline std::vector<std::complex<float>> acquisition_code_10230(uint32_t prn, con
 inline std::vector<std::complex<float>> beidou_b3i_acquisition_code(uint32_t prn, const Acq_Conf& conf) { return acquisition_code_10230(prn, conf, false); }
 inline std::vector<std::complex<float>> gps_l2c_m_acquisition_code(uint32_t prn, const Acq_Conf& conf) { return acquisition_code_10230(prn, conf, true); }
 
+// ---- GLONASS L1 / L2 C/A (glonass_l1_signal_replica.h, glonass_l2_signal_replica.h, GLONASS_L1_L2_CA.h, gnss_frequencies.h,
+// glonass_l1_ca_pcps_acquisition.cc:49-66 and its L2 twin) ----
+constexpr double FREQ1_GLO = 1.60200e9;
+constexpr double DFRQ1_GLO = 0.56250e6;
+constexpr double FREQ2_GLO = 1.24600e9;
+constexpr double DFRQ2_GLO = 0.43750e6;
+constexpr double GLONASS_L1_CA_FREQ_HZ = FREQ1_GLO;
+constexpr double GLONASS_L1_CA_DFREQ_HZ = DFRQ1_GLO;
+constexpr double GLONASS_L1_CA_CODE_RATE_CPS = 0.511e6;
+constexpr double GLONASS_L1_CA_CODE_LENGTH_CHIPS = 511.0;
+constexpr double GLONASS_L2_CA_FREQ_HZ = FREQ2_GLO;
+constexpr double GLONASS_L2_CA_DFREQ_HZ = DFRQ2_GLO;
+constexpr double GLONASS_L2_CA_CODE_RATE_CPS = 0.511e6;
+constexpr double GLONASS_L2_CA_CODE_LENGTH_CHIPS = 511.0;
+// The reference's generators under their names (dest: 511 complex; sampled: (int)(fs / 1000) complex, returns that count).
+inline void glonass_l1_ca_code_gen_complex(std::complex<float>* dest, uint32_t chip_shift) { gnsship_glonass_l1_ca_code_gen_complex(reinterpret_cast<float*>(dest), chip_shift); }
+inline int glonass_l1_ca_code_gen_complex_sampled(std::complex<float>* dest, int32_t sampling_freq, uint32_t chip_shift)
+{
+    return gnsship_glonass_l1_ca_code_gen_complex_sampled(reinterpret_cast<float*>(dest), sampling_freq, chip_shift);
+}
+inline void glonass_l2_ca_code_gen_complex(std::complex<float>* dest, uint32_t chip_shift) { gnsship_glonass_l2_ca_code_gen_complex(reinterpret_cast<float*>(dest), chip_shift); }
+inline int glonass_l2_ca_code_gen_complex_sampled(std::complex<float>* dest, int32_t sampling_freq, uint32_t chip_shift)
+{
+    return gnsship_glonass_l2_ca_code_gen_complex_sampled(reinterpret_cast<float*>(dest), sampling_freq, chip_shift);
+}
+// GLONASS_PRN.at(prn): the frequency channel of PRN 0..24; false for a PRN the table does not hold.
+inline bool glonass_freq_channel(uint32_t prn, int32_t* k) { return gnsship_glonass_freq_channel(static_cast<int32_t>(prn), k) == GNSSHIP_OK; }
+// is_fdma()'s d_doppler_bias of a frequency channel: (int32)(DFRQ · k), signal "1G" or "2G"
+inline int32_t glonass_doppler_bias_hz(const char* signal, int32_t k) { return static_cast<int32_t>((signal[0] == '1' ? DFRQ1_GLO : DFRQ2_GLO) * k); }
+// GlonassL1CaPcpsAcquisition's / GlonassL2CaPcpsAcquisition's Acq_Conf: ms_per_code 1, the C/A chip rate; the optimum
+// acquisition rate is 100e6, so no resampler is ever designed.  The caller's other fields are kept.
+inline Acq_Conf glonass_l1_ca_acq_conf(Acq_Conf conf)
+{
+    conf.ms_per_code = 1U;
+    conf.chips_per_second = static_cast<uint32_t>(GLONASS_L1_CA_CODE_RATE_CPS);
+    conf.SetDerivedParams();
+    conf.ConfigureAutomaticResampler(100e6);
+    return conf;
+}
+inline Acq_Conf glonass_l2_ca_acq_conf(Acq_Conf conf) { return glonass_l1_ca_acq_conf(conf); }
+// set_local_code of the two adapters: code_length = floor(fs / 1000) samples of the sampled code, copied sampled_ms
+// times into vector_length = floor(sampled_ms · samples_per_ms) samples (doubled with bit_transition_flag: the rest zero).
+inline std::vector<std::complex<float>> glonass_l1_ca_acquisition_code(const Acq_Conf& conf)
+{
+    const int64_t fs = conf.resampled_fs ? conf.resampled_fs : conf.fs_in;
+    const auto code_length = static_cast<size_t>(std::floor(static_cast<double>(fs) / (GLONASS_L1_CA_CODE_RATE_CPS / GLONASS_L1_CA_CODE_LENGTH_CHIPS)));
+    const auto vector_length = static_cast<size_t>(std::floor(conf.sampled_ms * (static_cast<float>(fs) * 0.001F)) * (conf.bit_transition_flag ? 2.0 : 1.0));
+    std::vector<std::complex<float>> one(code_length), out(std::max(vector_length, code_length * conf.sampled_ms));
+    if (glonass_l1_ca_code_gen_complex_sampled(one.data(), static_cast<int32_t>(fs), 0) < 0) return {};
+    for (uint32_t i = 0; i < conf.sampled_ms; i++) std::copy(one.begin(), one.end(), out.begin() + static_cast<size_t>(i) * code_length);
+    return out;
+}
+inline std::vector<std::complex<float>> glonass_l2_ca_acquisition_code(const Acq_Conf& conf) { return glonass_l1_ca_acquisition_code(conf); }
+
 // ---- Galileo E5a / E5b (galileo_e5_signal_replica.h, Galileo_E5a.h, Galileo_E5b.h, galileo_e5a_pcps_acquisition.cc:48-76,
 // :145-180 and its E5b twin) ----
 constexpr double GALILEO_E5A_FREQ_HZ = 1176.45e6;
@@ -1108,7 +1227,8 @@ struct Dll_Pll_Conf {
     bool carrier_aiding{true}, track_pilot{true};
     // 'G' GPS (signal "1C": L1 C/A, "L5": the L5Q pilot + L5I prompt, "2S": L2C, the L2 CM code), 'E' Galileo (signal
     // "5X": E5a, "7X": E5b — the Q pilot + the I prompt with track_pilot, the I component alone without — anything else:
-    // E1), 'C' BeiDou (signal "B3": B3I, anything else: B1I)
+    // E1), 'C' BeiDou (signal "B3": B3I, anything else: B1I), 'R' GLONASS (signal "1G": L1 C/A, "2G": L2 C/A — not this
+    // block but glonass_l1_ca / glonass_l2_ca_dll_pll_tracking_cc: glonass_l1_ca_trk_conf / glonass_l2_ca_trk_conf below)
     char system{'G'};
     char signal[3]{"1C"};
     // Not a Dll_Pll_Conf member: the reference's correlations follow the volk_gnsssdr rotator variant
@@ -1118,6 +1238,28 @@ struct Dll_Pll_Conf {
     // it ahead of the channels; here the correlator NCO wipes it off, gnsship.h if_hz).
     double if_hz{0.0};
 };
+
+// GlonassL1CaDllPllTracking / GlonassL2CaDllPllTracking's configuration (glonass_l1_ca_dll_pll_tracking.cc:44-62): system
+// 'R', signal "1G" / "2G", the adapters' defaults pll_bw_hz 50, dll_bw_hz 2, early_late_space_chips 0.5, vector_length =
+// round(fs / 1000); max_carrier_lock_fail carries the block's gflag max_lock_fail (50).  The rotator is the generic one:
+// the engine has no other for this block (gnsship_trk_create refuses the rest).  The caller's fs_in and if_hz are kept.
+inline Dll_Pll_Conf glonass_trk_conf(Dll_Pll_Conf conf, const char* signal)
+{
+    conf.system = 'R';
+    conf.signal[0] = signal[0];
+    conf.signal[1] = signal[1];
+    conf.signal[2] = '\0';
+    conf.pll_bw_hz = 50.0F;
+    conf.dll_bw_hz = 2.0F;
+    conf.early_late_space_chips = 0.5F;
+    conf.max_carrier_lock_fail = 50;
+    conf.track_pilot = false;
+    conf.rotator = GNSSHIP_ROTATOR_GENERIC;
+    conf.vector_length = static_cast<uint32_t>(std::round(conf.fs_in / (0.511e6 / 511.0)));
+    return conf;
+}
+inline Dll_Pll_Conf glonass_l1_ca_trk_conf(const Dll_Pll_Conf& conf) { return glonass_trk_conf(conf, "1G"); }
+inline Dll_Pll_Conf glonass_l2_ca_trk_conf(const Dll_Pll_Conf& conf) { return glonass_trk_conf(conf, "2G"); }
 
 // Mirror of dll_pll_veml_tracking (gnuradio_blocks/dll_pll_veml_tracking.cc) for many channels on one
 // device: start_tracking(:643-883) per channel, general_work over an IF buffer for all of them (the
@@ -1168,7 +1310,8 @@ public:
         const bool l2c = conf.system == 'G' && conf.signal[0] == '2' && conf.signal[1] == 'S';  // GpsL2MDllPllTracking
         const bool e5a = conf.system == 'E' && conf.signal[0] == '5' && conf.signal[1] == 'X';  // GalileoE5aDllPllTracking
         const bool e5b = conf.system == 'E' && conf.signal[0] == '7' && conf.signal[1] == 'X';  // GalileoE5bDllPllTracking
-        c.system = e5a ? GNSSHIP_SYS_GAL_E5A : e5b ? GNSSHIP_SYS_GAL_E5B : conf.system == 'E' ? GNSSHIP_SYS_GAL_E1 : b3 ? GNSSHIP_SYS_BDS_B3I : conf.system == 'C' ? GNSSHIP_SYS_BDS_B1I
+        const bool glo = conf.system == 'R' && conf.signal[1] == 'G' && (conf.signal[0] == '1' || conf.signal[0] == '2');  // GlonassL1Ca / L2CaDllPllTracking
+        c.system = glo ? (conf.signal[0] == '1' ? GNSSHIP_SYS_GLO_L1CA : GNSSHIP_SYS_GLO_L2CA) : e5a ? GNSSHIP_SYS_GAL_E5A : e5b ? GNSSHIP_SYS_GAL_E5B : conf.system == 'E' ? GNSSHIP_SYS_GAL_E1 : b3 ? GNSSHIP_SYS_BDS_B3I : conf.system == 'C' ? GNSSHIP_SYS_BDS_B1I
                    : l5 ? GNSSHIP_SYS_GPS_L5 : l2c ? GNSSHIP_SYS_GPS_L2C : GNSSHIP_SYS_GPS_L1CA;
         // gps_l5_dll_pll_tracking.cc:49-53 (track_pilot = false — the block's interchange_iq — is refused by gnsship_trk_create)
         if (l5 && c.extend_correlation_symbols < 1) c.extend_correlation_symbols = 1;
@@ -1184,11 +1327,16 @@ public:
                 c.extend_correlation_symbols = std::min(c.extend_correlation_symbols,
                     e5a ? GALILEO_E5A_I_SECONDARY_CODE_LENGTH : GALILEO_E5B_I_SECONDARY_CODE_LENGTH);
         }
+        if (glo) {  // glonass_l1_ca_dll_pll_tracking.cc:44-62: vector_length alone is derived; the block has no pilot
+            c.vector_length = static_cast<uint32_t>(std::round(conf.fs_in / (0.511e6 / 511.0)));
+            c.track_pilot = 0;
+        }
         if (l2c) {  // gps_l2_m_dll_pll_tracking.cc:47-59: one 20 ms code per epoch, no extension, no pilot
             c.vector_length = static_cast<uint32_t>(std::round(conf.fs_in / (GPS_L2_M_CODE_RATE_CPS / GPS_L2_M_CODE_LENGTH_CHIPS)));
             c.extend_correlation_symbols = 1;
             c.track_pilot = 0;
         }
+        glonass_ = glo;
         code_base_ = 1024 + 2 * max_channels * next_engine_id();
         std::lock_guard<std::mutex> lk(dev_->mutex());
         if (gnsship_trk_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
@@ -1264,7 +1412,17 @@ public:
         bool ok = true;
         for (int r = 0; r < rounds && ok; r++) {
             const size_t i = static_cast<size_t>(r) * channels_ + channel;
-            if (records[i].flags & 16) ok = std::fwrite(&dumps[i], sizeof(gnsship_trk_dump_record), 1, f) == 1;
+            if (!(records[i].flags & 16)) continue;
+            if (!glonass_) {
+                ok = std::fwrite(&dumps[i], sizeof(gnsship_trk_dump_record), 1, f) == 1;
+                continue;
+            }
+            // glonass_l1_ca_dll_pll_tracking_cc's record (:641-701): 88 bytes, the same without the two rate fields
+            const char* d = reinterpret_cast<const char*>(&dumps[i]);
+            const size_t r1 = offsetof(gnsship_trk_dump_record, carrier_doppler_rate_hz), c1 = offsetof(gnsship_trk_dump_record, code_freq_chips);
+            const size_t r2 = offsetof(gnsship_trk_dump_record, code_freq_rate_chips), c2 = offsetof(gnsship_trk_dump_record, carr_error_hz);
+            ok = std::fwrite(d, r1, 1, f) == 1 && std::fwrite(d + c1, r2 - c1, 1, f) == 1 &&
+                 std::fwrite(d + c2, sizeof(gnsship_trk_dump_record) - c2, 1, f) == 1;
         }
         return std::fclose(f) == 0 && ok;
     }
@@ -1287,6 +1445,7 @@ private:
     gnsship_trk* h_ = nullptr;
     int channels_ = 0;
     int code_base_ = 0;
+    bool glonass_ = false;  // the GLONASS block: its dump file has the 88-byte record
 };
 
 }  // namespace gnsship

@@ -100,7 +100,8 @@ private:
 // The configuration keys of the 1C channels (conf/gnss-sdr_GPS_L1_gr_complex.conf); with trk.signal = "L5"
 // the same keys of the L5 channels (Channels_L5, Acquisition_L5, Tracking_L5), with "2S" of the L2C channels
 // (Channels_2S, ...; vector_length = round(fs / 50)), with trk.system 'C' and trk.signal "B3" of the BeiDou B3I ones,
-// with trk.system 'E' and trk.signal "5X" / "7X" of the Galileo E5a / E5b ones.
+// with trk.system 'E' and trk.signal "5X" / "7X" of the Galileo E5a / E5b ones, with trk.system 'R' and trk.signal "1G" / "2G"
+// (trk = glonass_l1_ca_trk_conf / glonass_l2_ca_trk_conf) of the GLONASS L1 / L2 C/A ones.
 struct Receiver_Conf {
     int channels{1};                     // Channels_1C.count
     int in_acquisition{1};               // Channels.in_acquisition (capped at channels)
@@ -163,6 +164,11 @@ public:
         e5a_ = conf_.trk.system == 'E' && conf_.trk.signal[0] == '5' && conf_.trk.signal[1] == 'X';
         e5b_ = conf_.trk.system == 'E' && conf_.trk.signal[0] == '7' && conf_.trk.signal[1] == 'X';
         if (e5a_ || e5b_) conf_.acq = galileo_e5_acq_conf(conf_.acq);
+        // Channels_1G / Channels_2G (system 'R', signal "1G" / "2G"): one code for every satellite; each channel's
+        // acquisition searches under its satellite's FDMA bias (pcps_acquisition::is_fdma), as the reference's channels do,
+        // and the tracker takes the frequency channel from the PRN
+        glo_ = conf_.trk.system == 'R' && conf_.trk.signal[1] == 'G' && (conf_.trk.signal[0] == '1' || conf_.trk.signal[0] == '2');
+        if (glo_) conf_.acq = glonass_l1_ca_acq_conf(conf_.acq);
         n_ = std::max(1, conf_.channels);
         max_acq_ = std::min(std::max(0, conf_.in_acquisition), n_);
         conf_.satellite.resize(static_cast<size_t>(n_), 0U);
@@ -187,7 +193,7 @@ public:
         else if (!conf_.mitigation.empty())
             throw std::invalid_argument("Gnss_Receiver_Hip: mitigation must be Pulse_Blanking_Filter, Notch_Filter or Notch_Filter_Lite");
         // set_signals_list (GPS: 1-32, BeiDou: 1-63, Galileo: 1-36)
-        for (uint32_t p = 1; p <= (b3_ ? 63U : (e5a_ || e5b_) ? 36U : 32U); p++) available_.push_back(p);
+        for (uint32_t p = 1; p <= (glo_ ? 24U : b3_ ? 63U : (e5a_ || e5b_) ? 36U : 32U); p++) available_.push_back(p);
         prn_.assign(static_cast<size_t>(n_), 0U);
         apos_.assign(static_cast<size_t>(n_), 0U);
         fsm_.resize(static_cast<size_t>(n_));
@@ -311,6 +317,14 @@ private:
                 if (!ok || !trk_->start_tracking(c, pilot ? q_code.data() : i_code.data(), pilot ? i_code.data() : nullptr, 10230, s.Acq_delay_samples,
                                s.Acq_doppler_hz, s.Acq_samplestamp_samples, now_, static_cast<int>(prn)))
                     error_ = true;
+            } else if (glo_) {  // glonass_l1_ca_dll_pll_tracking_cc::start_tracking :198-200: the one code from chip 1
+                std::vector<std::complex<float>> z(511);
+                std::vector<float> code(511);
+                glonass_l1_ca_code_gen_complex(z.data(), 0);
+                for (size_t i = 0; i < z.size(); i++) code[i] = z[i].real();
+                if (!trk_->start_tracking(c, code.data(), nullptr, 511, s.Acq_delay_samples, s.Acq_doppler_hz, s.Acq_samplestamp_samples, now_,
+                        static_cast<int>(prn)))
+                    error_ = true;
             } else if (b3_ || l2c_) {  // start_tracking :666-668, :799-801: one replica, no data prompt
                 std::vector<float> code(10230);
                 if (!(b3_ ? beidou_b3i_code_gen_float(code.data(), static_cast<int32_t>(prn), 0) : gps_l2c_m_code_gen_float(code.data(), prn)) ||
@@ -343,6 +357,13 @@ private:
         if (e5a_ || e5b_) {  // GalileoE5aPcpsAcquisition / GalileoE5bPcpsAcquisition::set_local_code: the search runs on the I component
             const std::vector<std::complex<float>> code = galileo_e5_acquisition_code(prn, conf_.acq, e5b_);
             if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
+            return;
+        }
+        if (glo_) {  // GlonassL1CaPcpsAcquisition::set_local_code, and set_gnss_synchro's PRN → is_fdma()'s bias and grid
+            const std::vector<std::complex<float>> code = glonass_l1_ca_acquisition_code(conf_.acq);
+            const char sig[3] = {conf_.trk.signal[0], 'G', '\0'};
+            if (code.empty() || !acq_[static_cast<size_t>(c)]->set_gnss_synchro(sig, prn) || !acq_[static_cast<size_t>(c)]->set_local_code(code.data()))
+                error_ = true;
             return;
         }
         if (b3_ || l2c_) {  // BeidouB3iPcpsAcquisition / GpsL2MPcpsAcquisition::set_local_code
@@ -586,6 +607,7 @@ private:
     bool l5_ = false;  // GPS L5 channels (acquisition L5I, tracking L5Q pilot + L5I prompt)
     bool b3_ = false, l2c_ = false;  // BeiDou B3I / GPS L2C channels (acquisition and tracking on one code)
     bool e5a_ = false, e5b_ = false;  // Galileo E5a / E5b channels (acquisition on the I component, tracking on the Q pilot)
+    bool glo_ = false;  // GLONASS L1 / L2 C/A channels (one code, each satellite under its FDMA bias)
 };
 
 }  // namespace gnsship

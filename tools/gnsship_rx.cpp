@@ -8,7 +8,7 @@
 // component on the data prompt; the records' symbols have I and Q exchanged, as the block hands them to telemetry).
 //
 //   gnsship_rx --file F [--item gr_complex|ishort|ibyte|float|short|byte|2bit|nsr|2bit-cpx|4bit-cpx]
-//              [--sample-type real|iq|qi] [--big-endian-bytes] [--fs 4000000] [--seconds S] [--signal 1C|L5|2S|B3|5X|7X]
+//              [--sample-type real|iq|qi] [--big-endian-bytes] [--fs 4000000] [--seconds S] [--signal 1C|L5|2S|B3|5X|7X|1G|2G]
 //              [--channels 5] [--in-acquisition 1] [--satellite CH:PRN ...] [--repeat-satellite]
 //              [--pfa 0.01] [--doppler-max 10000] [--doppler-step 250]
 //              [--pll-bw 40] [--dll-bw 4] [--order 3] [--pull-in-time-s 10] [--rotator auto|generic|avx]
@@ -175,11 +175,12 @@ int main(int argc, char** argv)
     if (real_items && !conditioner) usage("real-sampled items need the conditioner (--if-hz / --decimation)");
     const int64_t sample_bits = gnsship_cond_fmt_bits(fmt);
     const int64_t per_byte = sample_bits < 8 ? 8 / sample_bits : 1;  // samples per byte of a packed item
-    if (signal != "1C" && signal != "L5" && signal != "2S" && signal != "B3" && signal != "5X" && signal != "7X")
-        usage("--signal must be 1C, L5, 2S, B3, 5X or 7X");
+    if (signal != "1C" && signal != "L5" && signal != "2S" && signal != "B3" && signal != "5X" && signal != "7X" && signal != "1G" && signal != "2G")
+        usage("--signal must be 1C, L5, 2S, B3, 5X, 7X, 1G or 2G");
     std::snprintf(rc.trk.signal, sizeof(rc.trk.signal), "%s", signal.c_str());
     if (signal == "B3") rc.trk.system = 'C';  // otherwise 'G'
     if (signal == "5X" || signal == "7X") rc.trk.system = 'E';
+    if (signal == "1G" || signal == "2G") rc.trk.system = 'R';  // GLONASS: each PRN acquired under its own channel's bias
     const double fs_file = fs;  // the rate the file is read at; fs from here on is the channels' rate
     if (conditioner) {
         if (decimation < 1 || std::fmod(fs, static_cast<double>(decimation)) != 0.0) usage("--decimation must divide --fs");
@@ -216,6 +217,8 @@ int main(int argc, char** argv)
     // gps_l1_ca_dll_pll_tracking.cc:47, gps_l5_dll_pll_tracking.cc:47, beidou_b3i_dll_pll_tracking.cc:47; gps_l2_m_dll_pll_tracking.cc:47
     rc.trk.vector_length = static_cast<uint32_t>(std::lround(fs / (signal == "2S" ? 50.0 : 1000.0)));
     rc.trk.rotator = rotator == "generic" ? GNSSHIP_ROTATOR_GENERIC : rotator == "avx" ? GNSSHIP_ROTATOR_AVX : GNSSHIP_ROTATOR_AUTO;
+    // the GLONASS block's correlator has the generic rotator only: "auto" means that one here, "avx" is refused by the engine
+    if ((signal == "1G" || signal == "2G") && rotator == "auto") rc.trk.rotator = GNSSHIP_ROTATOR_GENERIC;
     rc.block_samples = static_cast<int64_t>(fs * block_ms / 1000.0);
     rc.dump_filename = dump;
     rc.satellite.assign(static_cast<size_t>(rc.channels), 0U);
