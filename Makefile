@@ -98,6 +98,12 @@ $(GLONASS_MIRROR_TEST): tests/cpp/glonass_mirror_test.cpp include/gnsship_cpp.hp
 	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/glonass_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
 all: $(GLONASS_MIRROR_TEST)
 
+# The Viterbi decoder mirrors (tests/test_cpp_mirror_viterbi.py)
+VITERBI_MIRROR_TEST := tests/cpp/viterbi_mirror_test
+$(VITERBI_MIRROR_TEST): tests/cpp/viterbi_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
+	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/viterbi_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
+all: $(VITERBI_MIRROR_TEST)
+
 # Profiling variant (workgroup phase timestamps in corr_batch_kernel; scripts/corr_wg_profile.py)
 PROF_LIB := scripts/libgnsship_prof.so
 PROF_OBJS := $(patsubst $(CSRC)/%.hip,$(PROF_OBJDIR)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(PROF_OBJDIR)/%.cpp.o,$(CPP_SRCS))

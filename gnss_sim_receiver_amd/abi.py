@@ -159,6 +159,18 @@ class MitState(ctypes.Structure):
                 ("chunks_replayed", ctypes.c_uint64)]
 
 
+VIT_MODE_REFERENCE, VIT_MODE_FULL = 0, 1
+VIT_MAX_FRAME_SYMBOLS = 1024
+
+
+class VitConf(ctypes.Structure):
+    """gnsship_vit_conf — Viterbi_Decoder(KK, nn, LL, g) (viterbi_decoder.cc:21-44), the page's interleaver
+    (galileo_telemetry_decoder_gs.cc:342-351), the G2 flip (:362-368) and the decoding mode."""
+    _fields_ = [("constraint_length", ctypes.c_int32), ("rate_n", ctypes.c_int32), ("g", ctypes.c_int32 * 2),
+                ("data_length", ctypes.c_int32), ("interleaver_rows", ctypes.c_int32), ("interleaver_cols", ctypes.c_int32),
+                ("invert_g2", ctypes.c_int32), ("mode", ctypes.c_int32)]
+
+
 SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5, SYS_BDS_B3I, SYS_GPS_L2C = 0, 1, 2, 3, 4, 5
 SYS_GAL_E5A, SYS_GAL_E5B = 6, 7
 SYS_GLO_L1CA, SYS_GLO_L2CA = 8, 9  # glonass_l1_ca / glonass_l2_ca_dll_pll_tracking_cc (include/gnsship.h)
@@ -357,6 +369,12 @@ _SIGNATURES = {
     "gnsship_mit_reset": ([_vp], _i),
     "gnsship_mit_state_get": ([_vp, ctypes.POINTER(MitState)], _i),
     "gnsship_mit_destroy": ([_vp], _i),
+    "gnsship_vit_create": ([_vp, ctypes.POINTER(VitConf), ctypes.c_int32, _vpp], _i),
+    "gnsship_vit_run": ([_vp, _vp, _i, ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8),
+                         ctypes.POINTER(ctypes.c_uint8), _vp], _i),
+    "gnsship_vit_reset_channel": ([_vp, ctypes.c_int32], _i),
+    "gnsship_vit_state_get": ([_vp, ctypes.c_int32, _f32p], _i),
+    "gnsship_vit_destroy": ([_vp], _i),
     "gnsship_trk_create": ([_vp, ctypes.POINTER(TrkConf), _i, _vpp], _i),
     "gnsship_trk_start": ([_vp, _i, ctypes.POINTER(TrkStartArgs)], _i),
     "gnsship_trk_start_many": ([_vp, _i, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(TrkStartArgs)], _i),

@@ -846,6 +846,106 @@ class InterferenceMitigation:
             pass
 
 
+class ViterbiDecoder:
+    """The K = 7, rate-1/2 Viterbi decoder of the Galileo telemetry block with its de-interleaver and G2 flip
+    (galileo_telemetry_decoder_gs.cc:342-371, viterbi_decoder.cc:47-120) for up to ``max_channels`` channels, one
+    Viterbi_Decoder object per channel.  mode: "reference" (the decoder as written: first symbol of each pair only,
+    metrics carried from frame to frame) | "full" (both symbols, every frame from state 0) or abi.VIT_MODE_*."""
+
+    MODES = {"reference": abi.VIT_MODE_REFERENCE, "full": abi.VIT_MODE_FULL}
+
+    def __init__(self, ctx: Context, max_channels: int, data_length: int, interleaver_rows: int = 0, interleaver_cols: int = 0,
+                 invert_g2: bool = False, mode="reference", g=(121, 91), constraint_length: int = 7, rate_n: int = 2):
+        self.ctx = ctx
+        self.h = None
+        self.mode = self.MODES[mode] if isinstance(mode, str) else int(mode)
+        self.conf = abi.VitConf(constraint_length=constraint_length, rate_n=rate_n, g=(ctypes.c_int32 * 2)(int(g[0]), int(g[1])),
+                                data_length=data_length, interleaver_rows=interleaver_rows, interleaver_cols=interleaver_cols,
+                                invert_g2=int(bool(invert_g2)), mode=self.mode)
+        self.max_channels = int(max_channels)
+        self.data_length = int(data_length)
+        self.frame_symbols = 2 * (self.data_length + 6)
+        h = ctypes.c_void_p()
+        check(ctx.lib.gnsship_vit_create(ctx.h, ctypes.byref(self.conf), self.max_channels, ctypes.byref(h)), "gnsship_vit_create", ctx.h)
+        self.h = h
+
+    def run(self, symbols, channels, negate=None, on_device: bool = False, n_frames: int = None, bits_dev=None, host: bool = True):
+        """Decode frames: a host float32 array [n_frames, frame_symbols] as received, or a device pointer with
+        on_device=True; channels int32[n_frames]; negate uint8[n_frames] or None.  Returns uint8[n_frames,
+        data_length] (0 / 1) when host, else None (the bits are at bits_dev, asynchronously)."""
+        channels = np.ascontiguousarray(channels, np.int32).ravel()
+        n_frames = channels.size if n_frames is None else int(n_frames)
+        if channels.size != n_frames:
+            raise ValueError("one channel per frame")
+        if on_device:
+            ptr = ctypes.c_void_p(symbols)
+        else:
+            symbols = np.ascontiguousarray(symbols, np.float32)
+            if symbols.size != n_frames * self.frame_symbols:
+                raise ValueError(f"{n_frames} frames of {self.frame_symbols} symbols expected, got {symbols.size} symbols")
+            ptr = ctypes.c_void_p(symbols.ctypes.data) if symbols.size else None
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        if negate is not None:
+            negate = np.ascontiguousarray(negate, np.uint8).ravel()
+            if negate.size != n_frames:
+                raise ValueError("one negate flag per frame")
+        out = np.zeros((n_frames, self.data_length), np.uint8) if host else None
+        self._in_flight = (symbols, channels, negate)  # a run without a host copy returns before the stream has read them
+        check(self.ctx.lib.gnsship_vit_run(self.h, ptr, int(on_device), n_frames, channels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                           negate.ctypes.data_as(u8p) if negate is not None else None,
+                                           out.ctypes.data_as(u8p) if host and out.size else None,
+                                           ctypes.c_void_p(bits_dev) if bits_dev else None),
+              "gnsship_vit_run", self.ctx.h)
+        return out
+
+    def state(self, channel: int) -> np.ndarray:
+        """The channel's 64 carried path metrics (d_prev_section)."""
+        sec = np.zeros(64, np.float32)
+        check(self.ctx.lib.gnsship_vit_state_get(self.h, channel, fptr(sec)), "gnsship_vit_state_get", self.ctx.h)
+        return sec
+
+    def reset_channel(self, channel: int):
+        """A new Viterbi_Decoder object on this channel."""
+        check(self.ctx.lib.gnsship_vit_reset_channel(self.h, channel), "gnsship_vit_reset_channel", self.ctx.h)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.gnsship_vit_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.close()
+        except Exception:
+            pass
+
+
+# (interleaver rows, interleaver columns, data length) of the Galileo page types: 8 rows each, frames of 240, 488
+# and 984 symbols (an I/NAV page part, an F/NAV page, a C/NAV page without their preambles), 6 tail bits per frame
+GALILEO_INAV_PAGE, GALILEO_FNAV_PAGE, GALILEO_CNAV_PAGE = (8, 30, 114), (8, 61, 238), (8, 123, 486)
+
+
+def _galileo_page_decoder(ctx, max_channels, page, mode):
+    rows, cols, data_length = page
+    return ViterbiDecoder(ctx, max_channels, data_length, rows, cols, invert_g2=True, mode=mode)
+
+
+def galileo_inav_page_decoder(ctx: Context, max_channels: int, mode="reference") -> ViterbiDecoder:
+    """decode_INAV_word's first two steps (galileo_telemetry_decoder_gs.cc:354-371): one 240-symbol page part → 114 bits."""
+    return _galileo_page_decoder(ctx, max_channels, GALILEO_INAV_PAGE, mode)
+
+
+def galileo_fnav_page_decoder(ctx: Context, max_channels: int, mode="reference") -> ViterbiDecoder:
+    """decode_FNAV_word's first two steps (:585-599): one 488-symbol page → 238 bits."""
+    return _galileo_page_decoder(ctx, max_channels, GALILEO_FNAV_PAGE, mode)
+
+
+def galileo_cnav_page_decoder(ctx: Context, max_channels: int, mode="reference") -> ViterbiDecoder:
+    """decode_CNAV_word's first two steps (:684-697): one 984-symbol page → 486 bits."""
+    return _galileo_page_decoder(ctx, max_channels, GALILEO_CNAV_PAGE, mode)
+
+
 class DllPllVemlTracking:
     """dll_pll_veml_tracking (dll_pll_veml_tracking.cc) for up to ``max_channels`` channels, the
     per-epoch loop resident on the device: ``start_tracking`` → :meth:`start`, ``general_work``

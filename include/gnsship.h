@@ -551,6 +551,64 @@ int gnsship_mit_state_get(gnsship_mit* m, gnsship_mit_state* st);
 int gnsship_mit_destroy(gnsship_mit* m);
 
 /* ---------------------------------------------------------------------------------------------
+ * Viterbi decoding of Galileo pages: the first thing galileo_telemetry_decoder_gs does to an I/NAV, F/NAV or
+ * C/NAV page (decode_INAV_word / decode_FNAV_word / decode_CNAV_word, galileo_telemetry_decoder_gs.cc:354-371,
+ * :585-599, :684-697): de-interleave (:342-351, out[c*rows + r] = in[r*cols + c]), undo the NOT gate of G2
+ * (:362-368, every second de-interleaved symbol negated), Viterbi_Decoder::decode (telemetry_decoder/libs/
+ * viterbi_decoder.cc:47-120), here for many channels' frames in one launch, one wavefront per frame.
+ * A frame is 2*(data_length + 6) soft symbols as received (interleaved, preamble removed), a one positive.
+ *   GNSSHIP_VIT_MODE_REFERENCE reproduces Viterbi_Decoder::decode as written, one object per channel:
+ *     1. only the first symbol of each pair enters the metric (:61 copies d_nn - 1 = 1 value, d_rec_array[1]
+ *        stays 0): Gamma = {0, 0 + 0, 0 + r0, (0 + 0) + r0} (:151-166);
+ *     2. the 64 path metrics carry over from one decode to the next (:56 sets entry 0 alone; -1e7 only in a new
+ *        object; reset() does not touch them);
+ *     3. d_next_section starts at -1e7, states ascend with a strict > (:70-93): for next state s' the first
+ *        predecessor (s' & 31) << 1 wins a tie against the second, and an entry neither lifts above -1e7 is
+ *        not stored;
+ *     4. the section maximum is subtracted (:96-103); the traceback starts at state 0, skips the 6 tail steps
+ *        and emits data_length bits (:107-119).
+ *     Bits and carried metrics are bit-equal to the reference's, with one case left out: where the traceback
+ *     visits an entry nothing stored in this call, the reference reads what an earlier call left there and this
+ *     library reads predecessor 0, bit 0, which is what a new object holds.
+ *   GNSSHIP_VIT_MODE_FULL: both symbols in the metric and every frame starts from state 0 alone (the decoder the
+ *     code was designed for); the carried metrics are neither read nor written.
+ * Inputs are finite by contract; with NaN / Inf the bits are unspecified. */
+#define GNSSHIP_VIT_MODE_REFERENCE 0
+#define GNSSHIP_VIT_MODE_FULL 1
+#define GNSSHIP_VIT_MAX_FRAME_SYMBOLS 1024
+#define GNSSHIP_VIT_MAX_CHANNELS (1 << 20)
+#define GNSSHIP_VIT_MAX_FRAMES (1 << 22)
+typedef struct gnsship_vit gnsship_vit;
+typedef struct gnsship_vit_conf {
+    int32_t constraint_length;  /* 7; anything else E_INVAL                                          */
+    int32_t rate_n;             /* 2; anything else E_INVAL                                          */
+    int32_t g[2];               /* generator words, {121, 91} for Galileo; any two 7-bit words       */
+    int32_t data_length;        /* LL >= 1; frame = 2*(LL + 6) symbols <= GNSSHIP_VIT_MAX_FRAME_SYMBOLS */
+    int32_t interleaver_rows;   /* 0, 0 = none; else rows*cols == 2*(LL + 6)                         */
+    int32_t interleaver_cols;
+    int32_t invert_g2;          /* != 0: negate every second de-interleaved symbol                   */
+    int32_t mode;               /* GNSSHIP_VIT_MODE_*                                                */
+} gnsship_vit_conf;
+/* One decoder for channels 0..max_channels-1 (1..GNSSHIP_VIT_MAX_CHANNELS), each channel a new
+ * Viterbi_Decoder object.  E_INVAL (gnsship_last_error says why) for anything the conf comments exclude. */
+int gnsship_vit_create(gnsship_ctx* ctx, const gnsship_vit_conf* conf, int32_t max_channels, gnsship_vit** out);
+/* Decode n_frames frames (0..GNSSHIP_VIT_MAX_FRAMES).  symbols: n_frames*frame floats on the host or (on_device)
+ * on the device; channels: host int32[n_frames], frame i belongs to channel channels[i]; negate: host
+ * uint8[n_frames] or NULL, != 0 negates frame i (d_flag_PLL_180_deg_phase_locked, :1026-1029).  Bits are bytes
+ * of 0 / 1, data_length per frame: to bits_dev (a caller's device buffer) or, where NULL, to the handle's own
+ * buffer; bits_host (may be NULL): also copied to the host before returning; asynchronous on the context stream
+ * otherwise (the host arrays then stay the caller's until the stream has passed the run).  In reference mode a channel's frames are ordered through its carried metrics, so a channel may
+ * appear once per call; a duplicate or a channel out of range is E_INVAL and nothing runs.  Full mode checks
+ * the channel range only. */
+int gnsship_vit_run(gnsship_vit* v, const float* symbols, int on_device, int32_t n_frames, const int32_t* channels,
+    const uint8_t* negate, uint8_t* bits_host, void* bits_dev);
+/* A new Viterbi_Decoder object on this channel: all 64 metrics -1e7. */
+int gnsship_vit_reset_channel(gnsship_vit* v, int32_t channel);
+/* d_prev_section of a channel after everything run so far (waits for the context stream). */
+int gnsship_vit_state_get(gnsship_vit* v, int32_t channel, float* section /* [64] */);
+int gnsship_vit_destroy(gnsship_vit* v);
+
+/* ---------------------------------------------------------------------------------------------
  * Closed-loop tracking engine: the per-epoch DLL/PLL of dll_pll_veml_tracking
  * resident on the device.  Replaces, for N channels at once, the general_work loop of
  * src/algorithms/tracking/gnuradio_blocks/dll_pll_veml_tracking.cc:1728-2094 around

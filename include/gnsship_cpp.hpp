@@ -559,6 +559,117 @@ private:
     std::unique_ptr<Freq_Xlating_Fir_Filter_Hip> xlat_;
 };
 
+// Mirror of Viterbi_Decoder (src/algorithms/telemetry_decoder/libs/viterbi_decoder.h:34-57): one object, one
+// channel of a gnsship_vit in reference mode, so decode() after decode() carries the 64 path metrics as the
+// reference's object does; reset() leaves them alone, as there (viterbi_decoder.cc:123-131 rebuilds the transition
+// tables only).  KK and nn other than 7 and 2 throw std::invalid_argument.
+class Viterbi_Decoder_Hip {
+public:
+    Viterbi_Decoder_Hip(int32_t KK, int32_t nn, int32_t LL, const std::array<int32_t, 2>& g, int device = 0) : dev_(Device::get(device)), LL_(LL)
+    {
+        const gnsship_vit_conf c{KK, nn, {g[0], g[1]}, LL, 0, 0, 0, GNSSHIP_VIT_MODE_REFERENCE};
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        if (gnsship_vit_create(dev_->ctx(), &c, 1, &h_) != GNSSHIP_OK)
+            throw std::invalid_argument(std::string("gnsship_vit_create: ") + gnsship_last_error(dev_->ctx()));
+    }
+    ~Viterbi_Decoder_Hip()
+    {
+        if (h_) gnsship_vit_destroy(h_);
+    }
+    Viterbi_Decoder_Hip(const Viterbi_Decoder_Hip&) = delete;
+    Viterbi_Decoder_Hip& operator=(const Viterbi_Decoder_Hip&) = delete;
+    // output_u_int[0 .. LL) = the hard decisions; input_c = 2·(LL + 6) soft symbols (throws std::invalid_argument on
+    // other sizes, where the reference would read or write out of bounds)
+    void decode(std::vector<int32_t>& output_u_int, const std::vector<float>& input_c)
+    {
+        if (input_c.size() != static_cast<size_t>(2 * (LL_ + 6)) || output_u_int.size() < static_cast<size_t>(LL_))
+            throw std::invalid_argument("Viterbi_Decoder_Hip::decode: 2*(LL + 6) symbols in, LL bits out");
+        const int32_t channel = 0;
+        bits_.resize(static_cast<size_t>(LL_));
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        if (gnsship_vit_run(h_, input_c.data(), 0, 1, &channel, nullptr, bits_.data(), nullptr) != GNSSHIP_OK)
+            throw std::runtime_error(std::string("gnsship_vit_run: ") + gnsship_last_error(dev_->ctx()));
+        for (int32_t i = 0; i < LL_; i++) output_u_int[static_cast<size_t>(i)] = bits_[static_cast<size_t>(i)];
+    }
+    void reset() {}
+    // d_prev_section
+    std::array<float, 64> section() const
+    {
+        std::array<float, 64> s{};
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        gnsship_vit_state_get(h_, 0, s.data());
+        return s;
+    }
+
+private:
+    std::shared_ptr<Device> dev_;
+    gnsship_vit* h_ = nullptr;
+    int32_t LL_;
+    std::vector<uint8_t> bits_;
+};
+
+// The page formats of galileo_telemetry_decoder_gs (its constructor, :149-213, and decode_*_word): K = 7, rate 1/2,
+// G1 = 171o, G2 = 133o with its output inverted, an 8-row block interleaver and 6 tail bits per frame:
+//   I/NAV page part 240 symbols = 8 × 30 → 114 bits, F/NAV page 488 = 8 × 61 → 238, C/NAV page 984 = 8 × 123 → 486.
+inline gnsship_vit_conf galileo_vit_conf(int32_t rows, int32_t cols, int mode)
+{
+    return gnsship_vit_conf{7, 2, {121, 91}, rows * cols / 2 - 6, rows, cols, 1, mode};
+}
+inline gnsship_vit_conf galileo_inav_vit_conf(int mode = GNSSHIP_VIT_MODE_REFERENCE) { return galileo_vit_conf(8, 30, mode); }
+inline gnsship_vit_conf galileo_fnav_vit_conf(int mode = GNSSHIP_VIT_MODE_REFERENCE) { return galileo_vit_conf(8, 61, mode); }
+inline gnsship_vit_conf galileo_cnav_vit_conf(int mode = GNSSHIP_VIT_MODE_REFERENCE) { return galileo_vit_conf(8, 123, mode); }
+
+// The first two steps of decode_INAV_word / decode_FNAV_word / decode_CNAV_word for many channels at once: frames as
+// received (interleaved, preamble removed) in, data bits out, one Viterbi_Decoder object per channel.
+class Galileo_Page_Decoder_Hip {
+public:
+    Galileo_Page_Decoder_Hip(const gnsship_vit_conf& c, int32_t max_channels, int device = 0) : dev_(Device::get(device)), conf_(c)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        if (gnsship_vit_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
+            throw std::invalid_argument(std::string("gnsship_vit_create: ") + gnsship_last_error(dev_->ctx()));
+    }
+    ~Galileo_Page_Decoder_Hip()
+    {
+        if (h_) gnsship_vit_destroy(h_);
+    }
+    Galileo_Page_Decoder_Hip(const Galileo_Page_Decoder_Hip&) = delete;
+    Galileo_Page_Decoder_Hip& operator=(const Galileo_Page_Decoder_Hip&) = delete;
+    int32_t frame_symbols() const { return 2 * (conf_.data_length + 6); }
+    int32_t data_length() const { return conf_.data_length; }
+    // symbols: channels.size() frames of frame_symbols() floats; negate: empty, or one flag per frame (the block's
+    // d_flag_PLL_180_deg_phase_locked); bits: resized to channels.size() · data_length() bytes of 0 / 1.  In reference
+    // mode a channel may appear once per call.
+    bool decode_frames(const std::vector<float>& symbols, const std::vector<int32_t>& channels, const std::vector<uint8_t>& negate,
+        std::vector<uint8_t>& bits)
+    {
+        const size_t n = channels.size();
+        if (symbols.size() != n * static_cast<size_t>(frame_symbols()) || (!negate.empty() && negate.size() != n)) return false;
+        bits.resize(n * static_cast<size_t>(conf_.data_length));
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_vit_run(h_, symbols.data(), 0, static_cast<int32_t>(n), channels.data(), negate.empty() ? nullptr : negate.data(), bits.data(),
+                   nullptr) == GNSSHIP_OK;
+    }
+    bool reset_channel(int32_t channel)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_vit_reset_channel(h_, channel) == GNSSHIP_OK;
+    }
+    std::array<float, 64> section(int32_t channel) const
+    {
+        std::array<float, 64> s{};
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        gnsship_vit_state_get(h_, channel, s.data());
+        return s;
+    }
+    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
+
+private:
+    std::shared_ptr<Device> dev_;
+    gnsship_vit_conf conf_;
+    gnsship_vit* h_ = nullptr;
+};
+
 // What acquisition_core writes into Gnss_Synchro (gnss_synchro.h:52-55; pcps_acquisition.cc:683-696).
 struct Acq_Outcome {
     double Acq_delay_samples{0.0};
