@@ -127,6 +127,20 @@ class AcqResult(ctypes.Structure):
     ]
 
 
+class AcqLayout(ctypes.Structure):
+    """gnsship_acq_layout — the transform layout a handle chose (gnsship_acq_layout_get)."""
+    _fields_ = [
+        ("kind", ctypes.c_int32),
+        ("P", ctypes.c_int32),
+        ("row_len", ctypes.c_int32),
+        ("n_passes", ctypes.c_int32),
+        ("radix", ctypes.c_int32 * 16),
+        ("ct_rows", ctypes.c_int32),
+    ]
+
+
+assert ctypes.sizeof(AcqLayout) == 84
+
 COND_MAX_BANDS, COND_MAX_TAPS = 4, 4096
 
 
@@ -346,6 +360,7 @@ _SIGNATURES = {
     "gnsship_acq_set_local_code": ([_vp, _i, _f32p], _i),
     "gnsship_acq_run": ([_vp, _vp, _i, _i, _i, ctypes.POINTER(AcqResult), _f32p], _i),
     "gnsship_acq_num_bins": ([_vp, ctypes.POINTER(_i)], _i),
+    "gnsship_acq_layout_get": ([_vp, ctypes.POINTER(AcqLayout)], _i),
     "gnsship_acq_set_grid_fdma": ([_vp, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_int32)], _i),
     "gnsship_acq_run_fdma": ([_vp, _vp, _i, _i, _i, ctypes.POINTER(AcqResult), _f32p], _i),
     "gnsship_acq_reset_dwells": ([_vp], _i),

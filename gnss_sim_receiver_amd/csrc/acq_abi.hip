@@ -432,6 +432,21 @@ extern "C" int gnsship_acq_num_bins(gnsship_acq* a, int* n_bins)
     return GNSSHIP_OK;
 }
 
+extern "C" int gnsship_acq_layout_get(gnsship_acq* a, gnsship_acq_layout* out)
+{
+    if (!a || !out) return GNSSHIP_E_INVAL;
+    static_assert(sizeof(out->radix) / sizeof(out->radix[0]) == kMaxPasses, "gnsship_acq_layout::radix holds a whole FftPlan");
+    *out = gnsship_acq_layout{};
+    out->kind = a->huge ? 2 : (a->P ? 1 : 0);
+    out->P = a->P;
+    out->row_len = a->plan.n;
+    out->n_passes = a->plan.n_passes;
+    for (int p = 0; p < a->plan.n_passes; p++) out->radix[p] = a->plan.radix[p];
+    // the sizes launch_acq_fft_big / launch_acq_search_big and the huge launchers give a compile-time row kernel
+    out->ct_rows = a->huge ? (huge_ct_rows(a->plan.n) ? 1 : 0) : ((a->P && (a->plan.n == 250 || a->plan.n == 1000)) ? 1 : 0);
+    return GNSSHIP_OK;
+}
+
 // pcps_acquisition::set_local_code (:175-208), sampled_ms == ms_per_code, no bit-transition padding:
 // FFT of the code, then volk_32fc_conjugate_32fc.
 extern "C" int gnsship_acq_set_local_code(gnsship_acq* a, int prn_slot, const float* code)
@@ -593,3 +608,4 @@ extern "C" int gnsship_acq_run_fdma(gnsship_acq* a, const void* sig, int fmt, in
     return acq_run_rows(a, sig, fmt, sig_on_device, prn_slot, 1, a->fdma_channels, a->n_bins / a->fdma_channels, results, grid);
 }
 static_assert(sizeof(gnsship_acq_conf) == 64, "gnsship_acq_conf layout (abi.AcqConf)");
+static_assert(sizeof(gnsship_acq_layout) == 84, "gnsship_acq_layout layout (abi.AcqLayout)");

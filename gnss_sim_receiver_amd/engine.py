@@ -14,6 +14,7 @@ All compute runs in ``libgnsship.so`` (HIP, gfx950).  These wrappers only move a
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 
@@ -320,6 +321,15 @@ def correlate_host(ctx: Context, samples: np.ndarray, jobs: np.ndarray, codes: l
         buf.free()
 
 
+class AcqLayout(NamedTuple):
+    """The transform layout of an acquisition handle (gnsship_acq_layout): N = P × row_len."""
+    kind: str       # "lds" (one workgroup, P = 0), "four_step" or "huge"
+    P: int          # register points per column; 0 for "lds"
+    row_len: int    # M, the LDS transform's length (N for "lds")
+    radix: tuple    # Stockham radices of the row plan, in pass order
+    ct_rows: bool   # the rows run a kernel with a compile-time plan
+
+
 class PcpsAcquisition:
     """pcps_acquisition (pcps_acquisition.cc) over up to ``max_prns`` local codes at once."""
 
@@ -356,6 +366,13 @@ class PcpsAcquisition:
         check(ctx.lib.gnsship_acq_num_bins(self.h, ctypes.byref(nb)), "gnsship_acq_num_bins", ctx.h)
         self.n_bins = nb.value
         self.fdma_channels = 0  # > 0: the grid is an FDMA grid (set_grid_fdma)
+
+    @property
+    def layout(self) -> AcqLayout:
+        """The transform layout the handle chose at create (gnsship_acq_layout_get)."""
+        lay = abi.AcqLayout()
+        check(self.ctx.lib.gnsship_acq_layout_get(self.h, ctypes.byref(lay)), "gnsship_acq_layout_get", self.ctx.h)
+        return AcqLayout(("lds", "four_step", "huge")[lay.kind], lay.P, lay.row_len, tuple(lay.radix[: lay.n_passes]), bool(lay.ct_rows))
 
     def set_grid(self, doppler_max: int, doppler_step: int, doppler_center: int = 0):
         check(self.ctx.lib.gnsship_acq_set_grid(self.h, doppler_max, doppler_step, doppler_center), "gnsship_acq_set_grid", self.ctx.h)

@@ -357,6 +357,20 @@ int gnsship_acq_set_grid_step2(gnsship_acq* a, float doppler_center_step_two, fl
 int gnsship_acq_run(gnsship_acq* a, const void* sig, int fmt, int sig_on_device, int n_prns,
     gnsship_acq_result* results, float* grid);
 int gnsship_acq_num_bins(gnsship_acq* a, int* n_bins);
+/* The transform layout the handle chose at create for its fft_size N (read-only; for tests and tooling
+ * that must know which kernels a size runs). */
+typedef struct gnsship_acq_layout {
+    int32_t kind;       /* 0: one-workgroup LDS transform, 1: four-step, 2: huge                */
+    int32_t P;          /* register points per column, N = P x row_len (0 for kind 0)           */
+    int32_t row_len;    /* M, the LDS row transform's length (N for kind 0)                     */
+    int32_t n_passes;   /* Stockham passes of the row plan                                      */
+    int32_t radix[16];  /* their radices in order; entries past n_passes are 0                  */
+    int32_t ct_rows;    /* 1: the rows run a kernel with a compile-time plan (four-step M in
+                           {250, 1000}, huge M in {10000, 12500}), whose passes take radix 10
+                           where it divides, then 5, 3, 8, 4, 2, instead of radix[]; the four-step
+                           search (inverse) rows do so only at 25 x 1000 and 16 x 250           */
+} gnsship_acq_layout;
+int gnsship_acq_layout_get(gnsship_acq* a, gnsship_acq_layout* out);
 /* FDMA sweep (GLONASS; pcps_acquisition's is_fdma() / d_doppler_bias, :175-229, :296-301): one code searched
  * under n_channels Doppler grids in one pass.  The wipe-off table holds n_channels × n_bins rows, channel-major;
  * row (g, i) is built from (float)(bias_hz[g] − doppler_max + doppler_center + doppler_step·i), as

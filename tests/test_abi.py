@@ -58,3 +58,4 @@ def test_job_layout_matches_header(built):
     assert abi.JOB_DTYPE.itemsize == 80
     assert ctypes.sizeof(abi.AcqResult) == 32
     assert ctypes.sizeof(abi.AcqConf) == 64
+    assert ctypes.sizeof(abi.AcqLayout) == 84

@@ -138,9 +138,11 @@ def test_bad_configuration_rejected(ctx):
 
 # ---- large transforms (four-step, N = P·M > 16384): SURVEY §8 C3, 25 Msps, 1 ms GPS code ----
 
-def _acq_big_case(ctx, fs, n, prns, present, dmax, step, cfar, seed, want_grid=False):
+def _acq_big_case(ctx, fs, n, prns, present, dmax, step, cfar, seed, want_grid=False, layout=None):
     sig = signals.generate_if(fs, n, present, seed=seed)
     acq = engine.PcpsAcquisition(ctx, fs, n, dmax, step, 0, cfar, max_prns=len(prns))
+    if layout is not None:  # (kind, P, row_len, row radices, compile-time rows): the path the test is written for
+        assert acq.layout == layout
     for k, p in enumerate(prns):
         acq.set_local_code(codes.gps_l1_ca_code_gen_complex_sampled(p, fs), k)
     res, grid = acq.run(sig, n_prns=len(prns), want_grid=want_grid)
@@ -193,7 +195,8 @@ def test_four_step_forced_at_small_size_first_vs_second(ctx, monkeypatch):
     monkeypatch.setenv("GNSSHIP_ACQ_FORCE_BIG", "1")
     fs, n = 4000000, 4000
     sat = signals.Satellite(prn=22, doppler_hz=-620.0, code_delay_chips=432.1, cn0_dbhz=47.0)
-    sig, (r,), grid = _acq_big_case(ctx, fs, n, [22], [sat], 5000, 250, False, seed=5, want_grid=True)
+    sig, (r,), grid = _acq_big_case(ctx, fs, n, [22], [sat], 5000, 250, False, seed=5, want_grid=True,
+                                    layout=("four_step", 16, 250, (5, 5, 5, 2), True))
     ref, rgrid = O.pcps_acquisition_core(sig, codes.gps_l1_ca_code_gen_complex_sampled(22, fs), fs, 5000, 250, 0, False)
     assert np.max(np.abs(grid[0] - rgrid)) / rgrid.max() < 1e-5
     assert (r.doppler_index, r.code_index) == (ref.doppler_index, ref.code_index)
@@ -222,7 +225,8 @@ def test_four_step_max_size_and_limit(ctx):
     # 32768 = 32 × 1024: the largest four-step transform; a 1 ms code at 32.768 Msps
     fs, n = 32768000, 32768
     sat = signals.Satellite(prn=2, doppler_hz=-1000.0, code_delay_chips=55.5, cn0_dbhz=50.0)
-    sig, (r,), grid = _acq_big_case(ctx, fs, n, [2], [sat], 2000, 500, True, seed=3, want_grid=True)
+    sig, (r,), grid = _acq_big_case(ctx, fs, n, [2], [sat], 2000, 500, True, seed=3, want_grid=True,
+                                    layout=("four_step", 32, 1024, (8, 8, 8, 2), False))
     ref, rgrid = O.pcps_acquisition_core(sig, codes.gps_l1_ca_code_gen_complex_sampled(2, fs), fs, 2000, 500, 0, True)
     assert np.max(np.abs(grid[0] - rgrid)) / rgrid.max() < 1e-5
     assert (r.doppler_index, r.code_index) == (ref.doppler_index, ref.code_index)
@@ -238,7 +242,8 @@ def test_huge_forced_at_small_size_matches_oracle(ctx, monkeypatch):
     fs, n = 4000000, 4000
     sat = signals.Satellite(prn=14, doppler_hz=1380.0, code_delay_chips=702.6, cn0_dbhz=47.0)
     for cfar in (False, True):
-        sig, (r,), grid = _acq_big_case(ctx, fs, n, [14], [sat], 5000, 250, cfar, seed=15, want_grid=True)
+        sig, (r,), grid = _acq_big_case(ctx, fs, n, [14], [sat], 5000, 250, cfar, seed=15, want_grid=True,
+                                        layout=("huge", 4, 1000, (8, 5, 5, 5), False))
         ref, rgrid = O.pcps_acquisition_core(sig, codes.gps_l1_ca_code_gen_complex_sampled(14, fs), fs, 5000, 250, 0, cfar)
         assert np.max(np.abs(grid[0] - rgrid)) / rgrid.max() < 1e-5
         assert (r.doppler_index, r.code_index) == (ref.doppler_index, ref.code_index)
@@ -247,11 +252,13 @@ def test_huge_forced_at_small_size_matches_oracle(ctx, monkeypatch):
 
 
 def test_huge_gps_50msps_multi_prn(ctx):
-    """1 ms GPS L1 C/A at 50 Msps (SURVEY §8d C5 rate): N = 50000 = 4 × 12500."""
+    """1 ms GPS L1 C/A at 50 Msps (SURVEY §8d C5 rate): N = 50000 = 5 × 10000, the huge layout with the
+    compile-time 10000-point rows (the chooser takes them before 4 × 12500)."""
     fs, n, dmax, step = 50000000, 50000, 2000, 500
     present = [signals.Satellite(prn=p, doppler_hz=d, code_delay_chips=c, cn0_dbhz=47.0) for p, d, c in [(6, 1200.0, 333.3), (21, -800.0, 40.9)]]
     prns = [6, 21, 2]
-    sig, res, grid = _acq_big_case(ctx, fs, n, prns, present, dmax, step, True, seed=61, want_grid=True)
+    sig, res, grid = _acq_big_case(ctx, fs, n, prns, present, dmax, step, True, seed=61, want_grid=True,
+                                   layout=("huge", 5, 10000, (8, 5, 5, 5, 5, 2), True))
     for k, p in enumerate(prns):
         ref, rgrid = O.pcps_acquisition_core(sig, codes.gps_l1_ca_code_gen_complex_sampled(p, fs), fs, dmax, step, 0, True)
         assert np.max(np.abs(grid[k] - rgrid)) / rgrid.max() < 1e-5, p
@@ -263,7 +270,7 @@ def test_huge_gps_50msps_multi_prn(ctx):
 @pytest.mark.parametrize("cboc", [False, True])
 def test_huge_galileo_e1_25msps(ctx, cboc):
     """Galileo E1 acquisition (GalileoE1PcpsAmbiguousAcquisition: ms_per_code 4,
-    galileo_e1_pcps_ambiguous_acquisition.cc:51): 4 ms at 25 Msps, N = 100000 = 8 × 12500, E1-B
+    galileo_e1_pcps_ambiguous_acquisition.cc:51): 4 ms at 25 Msps, N = 100000 = 10 × 10000, E1-B
     replica from galileo_e1_code_gen_complex_sampled, against the oracle core."""
     fs, n, dmax, step = 25000000, 100000, 1000, 250
     present = [signals.Satellite(prn=p, doppler_hz=d, code_delay_chips=c, cn0_dbhz=45.0, system="GAL")
@@ -271,6 +278,7 @@ def test_huge_galileo_e1_25msps(ctx, cboc):
     prns = [11, 30, 4]
     sig = signals.generate_if(fs, n, present, seed=91)
     acq = engine.PcpsAcquisition(ctx, fs, n, dmax, step, 0, False, max_prns=3, ms_per_code=4)
+    assert acq.layout == ("huge", 10, 10000, (8, 5, 5, 5, 5, 2), True)
     lc = [codes.galileo_e1_code_gen_complex_sampled("1B", cboc, p, fs) for p in prns]
     for k in range(3):
         acq.set_local_code(lc[k], k)
@@ -303,6 +311,7 @@ def test_huge_galileo_e1_all_sky_prn_batches(ctx):
     sats = signals.random_sky(6, seed=0x6E550007, system="GAL", prns=present_prns)
     sig = signals.generate_if(fs, n, sats, seed=0x6E550007)
     acq = engine.PcpsAcquisition(ctx, fs, n, dmax, step, 0, False, max_prns=32, ms_per_code=4)
+    assert acq.layout == ("huge", 10, 10000, (8, 5, 5, 5, 5, 2), True)
     lc = [codes.galileo_e1_code_gen_complex_sampled("1B", False, p, fs) for p in range(1, 33)]
     for k in range(32):
         acq.set_local_code(lc[k], k)
@@ -364,7 +373,7 @@ def test_zero_padded_input_sampled_ms_ne_ms_per_code(ctx, cfar):
 
 
 def test_bit_transition_four_step_and_huge(ctx, monkeypatch):
-    _variant_case(ctx, 25000000, 50000, 0, True, True, 9, 43)              # huge layout (4 × 12500)
+    _variant_case(ctx, 25000000, 50000, 0, True, True, 9, 43)              # huge layout (5 × 10000)
     _variant_case(ctx, 8000000, 16000, 0, True, False, 9, 44, monkeypatch, "GNSSHIP_ACQ_FORCE_BIG")  # four-step (16 × 1000)
 
 
