@@ -104,11 +104,16 @@ bool derive_job(const gnsship_corr_job& in, int code_len, DevJob& out)
     for (int t = 0; t < kMaxTaps; t++) out.shifts[t] = (t < in.n_taps) ? in.shifts_chips[t] : 0.0f;
     // Range of floor(step·n + shift − rem) over the job, bounded in double with 2 chips of slack
     // (each float rounding moves a value < 2^15 by far less than one chip): inside the padded
-    // LDS replica the kernel skips the modulo.
+    // LDS replica the kernel skips the modulo.  A tap count below its tap class (2, 4, 6, 7) runs the wider
+    // kernel with the surplus shifts zeroed: those taps read the replica too, so shift 0 is part of the proof.
     double smin = in.shifts_chips[0], smax = in.shifts_chips[0];
     for (int t = 1; t < in.n_taps; t++) {
         smin = std::min(smin, static_cast<double>(in.shifts_chips[t]));
         smax = std::max(smax, static_cast<double>(in.shifts_chips[t]));
+    }
+    if (in.n_taps == 2 || in.n_taps == 4 || in.n_taps == 6 || in.n_taps == 7) {
+        smin = std::min(smin, 0.0);
+        smax = std::max(smax, 0.0);
     }
     const double span = static_cast<double>(in.code_phase_step_chips) * static_cast<double>(in.n_samples > 0 ? in.n_samples - 1 : 0);
     const double lo = std::min(0.0, span) + smin - in.rem_code_phase_chips - 2.0;
@@ -481,6 +486,9 @@ extern "C" int gnsship_batch_set_jobs(gnsship_batch* b, const gnsship_corr_job* 
             return fail(ctx, GNSSHIP_E_INVAL, "gnsship_batch_set_jobs: job refers to an unset code id");
         if (in.flags & ~(GNSSHIP_JOB_HIGH_DYN | GNSSHIP_JOB_ROTATOR_AVX | GNSSHIP_JOB_ROTATOR_TREE))
             return fail(ctx, GNSSHIP_E_INVAL, "gnsship_batch_set_jobs: unknown job flags");
+        // every job's code counts, the empty slots of high-dynamics and serial jobs too: their workgroups stage the
+        // replica like any other, into the LDS the launch sizes by this length
+        if (ctx->codes_host[in.code_id].len > max_len) max_len = ctx->codes_host[in.code_id].len;
         if ((in.flags & GNSSHIP_JOB_ROTATOR_AVX) && (in.flags & GNSSHIP_JOB_ROTATOR_TREE))
             return fail(ctx, GNSSHIP_E_INVAL, "gnsship_batch_set_jobs: GNSSHIP_JOB_ROTATOR_AVX and _TREE are exclusive");
         if (in.flags & 1) {  // high-dynamics resampler/rotator: its own plan, an empty slot here
@@ -506,7 +514,6 @@ extern "C" int gnsship_batch_set_jobs(gnsship_batch* b, const gnsship_corr_job* 
             derive_job(empty, cd.len, b->jobs_host[j]);
             continue;
         }
-        if (ctx->codes_host[in.code_id].len > max_len) max_len = ctx->codes_host[in.code_id].len;
     }
     b->max_code_len = max_len;
     b->replay_lanes = 1;
