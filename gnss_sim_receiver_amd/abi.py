@@ -197,6 +197,18 @@ ROTATOR_GENERIC, ROTATOR_AVX, ROTATOR_AUTO = 0, 1, -1
 JOB_HIGH_DYN, JOB_ROTATOR_AVX, JOB_ROTATOR_TREE = 1, 2, 4
 
 
+class TrkPlan(ctypes.Structure):
+    """gnsship_trk_plan — gnsship_trk_last_plan: the kernel variant and LDS plan the last run's launch function chose."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("engine", "format", "n_taps", "data_prompt", "packed", "sring", "rs", "rg", "lds_bytes", "thru",
+                                              "long_plan", "avx", "lane_waves")] + [("reserved", ctypes.c_int32 * 3)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+assert ctypes.sizeof(TrkPlan) == 64
+
+
 class TrkConf(ctypes.Structure):
     """gnsship_trk_conf — Dll_Pll_Conf (dll_pll_conf.h:33-80), same names/units; defaults as there
     with the gnss_sdr_flags defaults for cn0_samples/cn0_min/max_*lock_fail/carrier_lock_th.  The
@@ -403,6 +415,7 @@ _SIGNATURES = {
     "gnsship_trk_trace_records": ([_vp, _vp, _i], _i),
     "gnsship_trk_channel_state": ([_vp, _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_uint64)], _i),
     "gnsship_trk_last_engine": ([_vp, ctypes.POINTER(_i)], _i),
+    "gnsship_trk_last_plan": ([_vp, ctypes.POINTER(TrkPlan)], _i),
     "gnsship_trk_destroy": ([_vp], _i),
     "gnsship_comm_unique_id": ([_vp], _i),
     "gnsship_comm_create": ([_vp, _i, _i, _vp, _vpp], _i),

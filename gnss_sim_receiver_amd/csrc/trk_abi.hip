@@ -88,6 +88,7 @@ struct gnsship_trk {
     // gnsship_trk_set_trace: per channel-epoch correlation trace of the last run
     bool trace_on = false;
     int last_engine = GNSSHIP_TRK_ENGINE_NONE;  // the engine the last run / launch used
+    gnsship_trk_plan last_plan{};               // and the variant its launch function chose (gnsship_trk_last_plan)
     gnsship_trk_corr_trace* trace_dev = nullptr;
     size_t trace_cap = 0;
     size_t trace_n = 0;  // records of the last run (max_rounds × max_channels)
@@ -447,6 +448,14 @@ extern "C" int gnsship_trk_last_engine(gnsship_trk* t, int* engine)
 {
     if (!t || !engine) return GNSSHIP_E_INVAL;
     *engine = t->last_engine;
+    return GNSSHIP_OK;
+}
+
+extern "C" int gnsship_trk_last_plan(gnsship_trk* t, gnsship_trk_plan* plan)
+{
+    if (!t || !plan) return GNSSHIP_E_INVAL;
+    *plan = t->last_plan;
+    plan->engine = t->last_engine;
     return GNSSHIP_OK;
 }
 
@@ -981,21 +990,28 @@ static int trk_enqueue(gnsship_trk* t, const void* src, int fmt, uint64_t buffer
         const bool lanes = avx && !no_fast && trk_lane_supported(t->params, code_cap, nc, fmt, n_buffer_samples, binary);
         const bool fast = avx && !lanes && trk_fast_supported(t->params, code_cap, nc, binary);
         t->last_engine = GNSSHIP_TRK_ENGINE_NONE;
+        t->last_plan = gnsship_trk_plan{};
+        gnsship_trk_plan plan{};
         if (lanes)
             e = launch_trk_lane(t->params_dev, t->params, t->chans_dev, nc, ctx->codes_dev, n_codes, code_cap, src, fmt, buffer_first_sample,
-                n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, ctx->stream);
+                n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, ctx->stream, &plan);
         else if (fast)
             e = launch_trk_fast(t->params_dev, t->params, t->chans_dev, nc, ctx->codes_dev, n_codes, code_cap, src, fmt, buffer_first_sample,
-                n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, binary, ctx->stream);
+                n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, binary, ctx->stream, &plan);
         else
             e = launch_trk_persist(t->params_dev, t->params, t->chans_dev, nc, ctx->codes_dev, n_codes, code_cap, src, fmt, buffer_first_sample,
-                n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, avx, ctx->stream);
+                n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, avx, ctx->stream, &plan);
         if (e != hipSuccess) return hip_fail(ctx, e, lanes ? "launch_trk_lane" : fast ? "launch_trk_fast" : "launch_trk_persist");
         t->last_engine = lanes  ? GNSSHIP_TRK_ENGINE_LANES
                          : fast ? (trk_fast_thru(nc) ? GNSSHIP_TRK_ENGINE_FAST_THROUGHPUT : GNSSHIP_TRK_ENGINE_FAST_LATENCY)
                                 : GNSSHIP_TRK_ENGINE_PERSIST;
+        t->last_plan = plan;
     }
-    if (!persist) t->last_engine = GNSSHIP_TRK_ENGINE_ROUNDS;
+    if (!persist) {
+        t->last_engine = GNSSHIP_TRK_ENGINE_ROUNDS;
+        t->last_plan = gnsship_trk_plan{};
+        t->last_plan.format = fmt;
+    }
     for (int r = 0; r <= max_rounds && !persist; r++) {
         const int consume = r > 0 ? 1 : 0, emit = r < max_rounds ? 1 : 0;
         gnsship_trk_epoch* rec = (out && r > 0) ? t->rec_dev + static_cast<size_t>(r - 1) * nc : nullptr;

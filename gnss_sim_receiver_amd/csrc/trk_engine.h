@@ -151,7 +151,8 @@ inline bool trk_persist_supports(const TrkParams& p)
 constexpr size_t kTrkPersistMaxLds = 150 * 1024;  // of the 160 KiB per CU, beside the static state
 hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes,
     int n_codes, int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool avx, hipStream_t stream);
+    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool avx, hipStream_t stream, gnsship_trk_plan* plan = nullptr);
+// Every launch function fills `plan` (when given) with the variant it chose: gnsship_trk_last_plan.
 // The latency-optimised persistent loop for the AVX rotator (trk_fast.hip): register-resident loop
 // state, flagless phasor slots, lock detectors beside the loop update.
 // codes_binary: every chip of the channels' codes is ±1 (the GPS L5 tap layout holds its replicas as sign
@@ -165,9 +166,10 @@ int trk_device_cus();             // compute units of the current device
 bool trk_lane_supported(const TrkParams& p, int code_cap_floats, int n_chans, int fmt, int64_t buf_len, bool codes_binary);
 hipError_t launch_trk_lane(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes, int n_codes,
     int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, hipStream_t stream);
+    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, hipStream_t stream, gnsship_trk_plan* plan = nullptr);
 hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes, int n_codes,
     int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool codes_binary, hipStream_t stream);
+    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool codes_binary, hipStream_t stream,
+    gnsship_trk_plan* plan = nullptr);
 
 }  // namespace gnsship

@@ -1864,6 +1864,11 @@ static FastPlan fast_plan(const TrkParams& p, int code_cap_floats, int n_chans, 
 {
     FastPlan f;
     f.packed = fast_packed_layout(p, codes_binary);
+    // Five taps (Galileo E1: 8184-float replicas, one or two) have no throughput form: beside 32 KiB of replica the
+    // 72 KiB budget holds one product group of its 23 KiB, and a plan needs two.  The form is not instantiated for
+    // them (launch_trk_fast), so whatever the code bank holds there is no plan: the run goes to trk_lane or trk_persist.
+    // (This also drops the one-group plan of epochs under 528 samples, which no E1 rate reaches.)
+    if (p.n_taps == 5 && fast_thru(n_chans)) return f;
     const int N = static_cast<int>(p.conf.vector_length);
     const int M = N / kAvxLanes;
     const int G = kFastG;
@@ -1920,13 +1925,25 @@ bool trk_fast_supported(const TrkParams& p, int code_cap_floats, int n_chans, bo
         if (env[0] == '1') return fast_plan(p, code_cap_floats, n_chans, codes_binary).bytes > 0;
     }
     // every channel count: with more channels than CUs the throughput form (fast_thru), which keeps
-    // u_avx's accumulation order as the latency form does (trk_persist.hip's tree sums do not)
+    // u_avx's accumulation order as the latency form does
     return fast_plan(p, code_cap_floats, n_chans, codes_binary).bytes > 0;
+}
+
+// The instantiation of a form (0 latency, 1 throughput, 2 long epochs); THRU_FORM false: the layout has no throughput
+// form, which is then not instantiated (null for form 1).
+template <int F, int NTV, bool DV, bool SR, bool PK, bool THRU_FORM>
+static auto fast_kernel_of(int form) -> decltype(&trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWaves, PK>)
+{
+    if (form == 1) {
+        if constexpr (THRU_FORM) return trk_fast_kernel<F, NTV, DV, kFastG, true, SR, GNSSHIP_THRU_WAVES, PK>;
+        else return nullptr;
+    }
+    return form == 2 ? trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWavesLong, PK> : trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWaves, PK>;
 }
 
 hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes, int n_codes,
     int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool codes_binary, hipStream_t stream)
+    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool codes_binary, hipStream_t stream, gnsship_trk_plan* plan)
 {
     const FastPlan f = fast_plan(params, code_cap_floats, n_chans, codes_binary);
     if (f.bytes == 0) return hipErrorInvalidValue;
@@ -1940,10 +1957,10 @@ hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params,
     const int form = thru ? 1 : (N >= kLongEpoch ? 2 : 0);
     const int waves = form == 1 ? GNSSHIP_THRU_WAVES : form == 2 ? kFWavesLong : kFWaves;
     dim3 grid(n_chans), block(waves * kWave);
-#define GNSSHIP_FAST(F, NTV, DV, SR, PK)                                                                                                             \
+#define GNSSHIP_FAST(F, NTV, DV, SR, PK)                                                                                                         \
     do {                                                                                                                                         \
-        auto kfn = form == 1 ? trk_fast_kernel<F, NTV, DV, kFastG, true, SR, GNSSHIP_THRU_WAVES, PK>                                              \
-                             : form == 2 ? trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWavesLong, PK> : trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWaves, PK>; \
+        auto kfn = fast_kernel_of<F, NTV, DV, SR, PK, (NTV) == 3>(form); /* five taps: no throughput form (fast_plan) */                          \
+        if (!kfn) return hipErrorInvalidValue;                                                                                                   \
         hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.bytes)); \
         if (e0 != hipSuccess) return e0;                                                                                                         \
         hipLaunchKernelGGL(kfn, grid, block, f.bytes, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans, \
@@ -1972,6 +1989,20 @@ hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params,
 #undef GNSSHIP_FAST_F
 #undef GNSSHIP_FAST_R
 #undef GNSSHIP_FAST
+    if (plan) {
+        *plan = gnsship_trk_plan{};
+        plan->engine = thru ? GNSSHIP_TRK_ENGINE_FAST_THROUGHPUT : GNSSHIP_TRK_ENGINE_FAST_LATENCY;
+        plan->format = fmt;
+        plan->n_taps = nt;
+        plan->data_prompt = data ? 1 : 0;
+        plan->packed = f.packed ? 1 : 0;
+        plan->sring = sring ? 1 : 0;
+        plan->rs = f.rs;
+        plan->rg = f.rg;
+        plan->lds_bytes = static_cast<int32_t>(f.bytes);
+        plan->thru = thru ? 1 : 0;
+        plan->long_plan = form == 2 ? 1 : 0;
+    }
     return hipGetLastError();
 }
 

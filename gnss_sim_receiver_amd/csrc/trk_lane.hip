@@ -357,7 +357,7 @@ bool trk_lane_supported(const TrkParams& p, int code_cap_floats, int n_chans, in
 
 hipError_t launch_trk_lane(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes, int n_codes,
     int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, hipStream_t stream)
+    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, hipStream_t stream, gnsship_trk_plan* plan)
 {
     const bool data = params.jobs_per_channel > 1;
     const int nt = params.n_taps;
@@ -391,6 +391,15 @@ hipError_t launch_trk_lane(const TrkParams* params_dev, const TrkParams& params,
     }
 #undef GNSSHIP_LANE_F
 #undef GNSSHIP_LANE
+    if (plan) {
+        *plan = gnsship_trk_plan{};
+        plan->engine = GNSSHIP_TRK_ENGINE_LANES;
+        plan->format = fmt;
+        plan->n_taps = nt;
+        plan->data_prompt = data ? 1 : 0;
+        plan->lds_bytes = static_cast<int32_t>(lds);
+        plan->lane_waves = nw;
+    }
     return hipGetLastError();
 }
 

@@ -8,13 +8,11 @@
 // inside one launch: no kernel boundary, no host round trip and no grid-wide synchronisation
 // between epochs.  Per epoch:
 //   1. thread 0 derives the correlator arguments from the channel state (do_correlation_step);
-//   2. wave 0 replays the reference's rotator recursion and publishes its anchors to LDS block by
-//      block, while waves 1-3 correlate every block whose anchor is published, in a static order
-//      (wave w takes work items w − 1 mod 3): the replay — the serial floor of the epoch — overlaps
-//      the correlation, and every sum is formed in the same order on every run (the results are
-//      bit-reproducible, independent of wave scheduling and of the other channels in the launch);
-//   3. the tap sums are reduced in LDS and thread 0 runs the loop update on the channel state,
-//      which lives in LDS for the whole run, and writes the epoch's record.
+//   2. the epoch is correlated in the reference's own order of operations, per rotator variant (below): every
+//      sum is formed in the same order on every run (the results are bit-reproducible, independent of wave
+//      scheduling and of the other channels in the launch) and equals the reference's bit for bit;
+//   3. thread 0 runs the loop update on the channel state, which lives in LDS for the whole run, and
+//      writes the epoch's record.
 //
 // Rotator variants (include/gnsship.h GNSSHIP_ROTATOR_*):
 //  * generic (volk_gnsssdr_32fc_32f_rotator_dot_prod_32fc_xn.h:66-98): one phasor, N dependent
@@ -25,14 +23,13 @@
 //    products with every tap's chip; wave 3's lane j < 2·taps (+2 for the data prompt) adds tap
 //    component j's products serially in sample order — the reference's own float sum.
 //  * AVX (…:155-316, what volk_gnsssdr dispatches on AVX hosts): 16 phasors z_l advanced by
-//    dz = normalise(inc^16), renormalised every 64 iterations.  The replay is 16 lanes × N/16 steps
-//    (16× shorter than the generic chain); it publishes z_l at every renormalisation, and the
-//    correlating lane of (segment, l) continues that lane's chain itself — the same float products
-//    in the same order, so every phasor is bit-identical to the reference's (the sums are trees;
-//    the exact AVX engines are trk_fast.hip and trk_lane.hip).  The GPS L5 tap layout (3 taps + data
-//    prompt) instead runs u_avx's sixteen chains on sixteen lanes, serial sums and all (chains_avx):
-//    bit-exact here too.  So do BeiDou B3I and GPS L2C (TrkParams::single_code_bits), chosen at launch:
-//    GPS L1 and BeiDou B1I, which share their tap layout, keep the tree form.
+//    dz = normalise(inc^16), renormalised every 64 iterations, sixteen accumulators per tap.  Sixteen lanes
+//    of one wave ARE those sixteen chains, serial sums and all (chains_avx): one dependent chain of N/16
+//    iterations per epoch, the reference's own single-core latency.  This is the fallback behind trk_fast.hip
+//    and trk_lane.hip (GNSSHIP_TRK_FAST=0, codes that are not ±1, no trk_fast plan).  An earlier form cut the
+//    epoch into tasks spread over three waves and summed them as a tree: faster, and one ulp off the
+//    reference's taps in every epoch; it was removed when every engine was held to bit equality, and what
+//    the chains cost against it has not been measured.
 //
 // High-dynamics tracking and epochs too long for LDS stay on the round-based path (trk_kernel.hip).
 #include <cstdlib>
@@ -44,7 +41,7 @@
 // Epoch phase timestamps for the profiling build only (make prof → scripts/libgnsship_prof.so,
 // scripts/trk_wg_profile.py): slot [(channel·kProfEpochs + epoch)·16 + k] = wall_clock64() at phase
 // k (0-6 and 16-21 in the kernel, 8-12 inside the loop update — trk_loop.h GNSSHIP_TRK_LOOP_STAMP —
-// 13-15 inside the AVX replay; slot 7 holds the replay's shader cycles).
+// 13-15 and 7 unused).
 #ifdef GNSSHIP_CORR_PROFILE
 namespace gnsship {
 constexpr int kProfEpochs = 64;
@@ -74,7 +71,7 @@ namespace {
 
 constexpr int kPThreads = 256;
 constexpr int kPWaves = kPThreads / kWave;
-constexpr int kAvxSeg = 64;    // its renormalisation period in 16-sample iterations (:265-272)
+constexpr int kAvxSeg = 64;    // the AVX rotator's renormalisation period in 16-sample iterations (:265-272)
 
 // The epoch being correlated (LDS): the reference's call arguments as a DevJob plus the AVX step.
 struct PEpoch {
@@ -82,37 +79,14 @@ struct PEpoch {
     float dz_re, dz_im;  // normalise(inc^16) (AVX)
     int32_t runnable;
     int32_t in_margin;   // every chip index of the epoch lies in the padded LDS replica
-    int32_t published;   // AVX: segments whose anchors are ready (S + 1 = all, tail included)
     SerialSync sync;     // generic: the serial pipeline's ring counters
     int32_t locked;      // lock_status outcome (wave 1) for the loop update (wave 0)
     double coh;          // epoch_pre's coherent integration time (0: no lock test this epoch)
     float trace_rem_carr, trace_step;  // the carrier arguments as passed (IF folded in)
-    float red[kPWaves][2 * (kMaxTaps + 1)];
     float taps[2 * kMaxTaps + 2];  // the epoch's tap sums (+ the data prompt), as epoch_update reads them
     gnsship_trk_epoch rec;
     gnsship_trk_dump_record dump;
 };
-
-// The publishing wave's LDS operations complete in program order, so a counter stored after the
-// data it announces lands after it: a relaxed store behind a wavefront-scope fence (which only
-// keeps the compiler from reordering) needs no wait for the data store, and a reader that acquires
-// the counter then sees the data.
-__device__ __forceinline__ void publish(int32_t* p, int v)
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-__device__ __forceinline__ void wait_published(int32_t* p, int need)
-{
-    while (__hip_atomic_load(p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < need) __builtin_amdgcn_s_sleep(1);
-}
-
-// AVX geometry of an N-sample epoch: M = N/16 iterations, cut into tasks of G iterations (G = 16,
-// 32 or 64, a divisor of the renormalisation period, chosen by the LDS budget): task 0 = iteration 0,
-// task t ≥ 1 = iterations [G(t−1)+1, Gt] ∩ [0, M).  Renormalisations (after iterations ≡ 0 mod 64)
-// then only ever fall after a task's last iteration.  The N mod 16 tail runs serially after them.
-__host__ __device__ __forceinline__ int avx_tasks(int M, int G) { return M <= 1 ? 1 : 1 + (M - 1 + G - 1) / G; }
 
 // ---- the generic rotator: serial pipeline (serial_rotator.h) ---------------------------------------
 // Ring of RC chunks in the dynamic LDS after the codes: phases, then 2·(taps + data prompt) product
@@ -145,178 +119,13 @@ __device__ void serial_epoch(PEpoch& ep, float* anc, int RC, i4v span, int N, co
     }
 }
 
-// AVX (lanes 0..15 = phasor l): Z[t·16 + l] = the phasor lane l starts task t with; T[j] = the
-// tail phasor of sample 16M + j.  The initial phasors are the generic chain phase·inc^l (:204-208);
-// dz = normalise(inc^16) (:215-225); after iteration m's update, renormalise when m ≡ 0 mod 64.
-// Whole renormalisation periods (iterations 64s+1 … 64(s+1), tasks 1 + P·s … P·(s+1) for P = 64/G)
-// run as one unrolled block each — G steps, store and publish the next task's start, per task; the
-// renormalisation after the block — with no per-task bookkeeping on the chain; the < 64 iterations
-// after the last whole period hold no renormalisation.
-template <int G>
-__device__ void replay_avx(const PEpoch& ep, f2* Z, f2* T, int N, int lane, int32_t* published)
-{
-    constexpr int kPer = kAvxSeg / G;
-    const int M = N / kAvxLanes, S = avx_tasks(M, G);
-    const f2 inc = f2{ep.job.inc_re, ep.job.inc_im};
-    const f2 dz = f2{ep.dz_re, ep.dz_im};
-    f2 z = f2{ep.job.p0_re, ep.job.p0_im};
-    for (int i = 0; i < kAvxLanes - 1; i++)
-        if (i < lane) z = cmul_exact(z, inc);
-    Z[lane] = z;
-    if (lane == 0) publish(published, 1);
-    if (M > 0) {  // iteration 0 (task 0), renormalised after its update
-        z = normalise_avx(cmul_exact(z, dz));
-        if (S > 1) {
-            Z[kAvxLanes + lane] = z;
-            if (lane == 0) publish(published, 2);
-        }
-    }
-    if (lane == 0) GNSSHIP_TRK_LOOP_STAMP(13);
-#ifdef GNSSHIP_CORR_PROFILE
-    const long long c13 = clock64();  // shader cycles of the task loop → slot 7 (not a timestamp)
-#endif
-    const int n_per = M > 0 ? (M - 1) / kAvxSeg : 0;
-    for (int sg = 0; sg < n_per; sg++) {
-#pragma unroll
-        for (int u = 0; u < kPer; u++) {
-#pragma unroll
-            for (int i = 0; i < G; i++) z = cmul_exact(z, dz);
-            if (u == kPer - 1) z = normalise_avx(z);
-            const int t = 1 + kPer * sg + u;  // the task just run
-            if (t + 1 < S) {
-                Z[(t + 1) * kAvxLanes + lane] = z;
-                if (lane == 0) publish(published, t + 2);
-            }
-        }
-    }
-    for (int t = 1 + kPer * n_per; t < S; t++) {
-        const int cnt = min(G * t, M - 1) - G * (t - 1);
-        if (cnt == G) {
-#pragma unroll
-            for (int i = 0; i < G; i++) z = cmul_exact(z, dz);
-        } else {
-            for (int i = 0; i < cnt; i++) z = cmul_exact(z, dz);
-        }
-        if (t + 1 < S) {
-            Z[(t + 1) * kAvxLanes + lane] = z;
-            if (lane == 0) publish(published, t + 2);
-        }
-    }
-    if (lane == 0) {  // z0 = normalise(z0) after the loop, then the serial tail (:286-304)
-        GNSSHIP_TRK_LOOP_STAMP(14);
-#ifdef GNSSHIP_CORR_PROFILE
-        if (g_trk_prof && g_prof_epoch < kProfEpochs)
-            g_trk_prof[(static_cast<size_t>(blockIdx.x) * kProfEpochs + g_prof_epoch) * kProfSlots + 7] = static_cast<unsigned long long>(clock64() - c13);
-#endif
-        f2 t = normalise_avx(z);
-        for (int j = 0; j < N - kAvxLanes * M; j++) {
-            T[j] = t;
-            t = cmul_exact(t, inc);
-        }
-        publish(published, S + 1);
-        GNSSHIP_TRK_LOOP_STAMP(15);
-    }
-}
-
-// ---- correlation (AVX) ---------------------------------------------------------------------------
-// AVX: wave step g = tasks 4g..4g+3 × the 16 phasors (64 lanes: lane = 16·(t − 4g) + l), each lane
-// continuing its phasor's chain over the task's ≤ G iterations (sample 16m + l at iteration m), 16
-// iterations per step with the next 16 samples in flight (the first 16 are loaded before the
-// task's anchors are awaited); the step after the last correlates the N mod 16 tail samples.
-template <int FMT, int NT, bool DATA, bool IN_MARGIN, int kB>
-__device__ void consume_avx(PEpoch& ep, const f2* Z, const f2* T, i4v span, int N, int G, const float* code0, const float* code1, int L,
-    int lane, int wave, f2 (&acc)[NT + 1])
-{
-    const DevJob& job = ep.job;
-    const int M = N / kAvxLanes, S = avx_tasks(M, G);
-    const int n_groups = (S + 3) / 4, tail = N - kAvxLanes * M;
-    const int n_steps = n_groups + (tail > 0 ? 1 : 0);
-    const f2 dz = f2{ep.dz_re, ep.dz_im};
-    const float step = job.code_step, rem = job.rem_code;
-    float shifts[NT];
-#pragma unroll
-    for (int t = 0; t < NT; t++) shifts[t] = job.shifts[t];
-    constexpr int SB = sample_bytes<FMT>();
-    if (wave == 0) return;  // the replay wave
-    for (int g = wave - 1; g < n_steps; g += kPWaves - 1) {  // static: wave w ≥ 1 takes steps w − 1 (mod 3)
-        if (g == n_groups) {  // the serial tail (:292-304)
-            wait_published(&ep.published, S + 1);
-            if (lane < tail) {
-                const int n = kAvxLanes * M + lane;
-                const f2 x = load_sample<FMT>(span, n * SB, 0);
-                const f2 r = cmul_pk2(x, T[lane]);
-                const float sn = __fmul_rn(step, static_cast<float>(n));
-#pragma unroll
-                for (int t = 0; t < NT; t++) {
-                    const float c = code_at<IN_MARGIN>(code0, L, sn, shifts[t], rem);
-                    acc[t] = __builtin_elementwise_fma(r, f2{c, c}, acc[t]);
-                }
-                if constexpr (DATA) {
-                    const float c = code_at<IN_MARGIN>(code1, L, sn, 0.0f, rem);
-                    acc[NT] = __builtin_elementwise_fma(r, f2{c, c}, acc[NT]);
-                }
-            }
-            continue;
-        }
-        const int t = 4 * g + (lane >> 4), l = lane & (kAvxLanes - 1);
-        const bool active = t < S;
-        const int m_lo = t == 0 ? 0 : G * (t - 1) + 1;
-        int cnt = 0;
-        if (active) cnt = t == 0 ? (M > 0 ? 1 : 0) : min(G * t, M - 1) - m_lo + 1;
-        int cmax = cnt;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) cmax = max(cmax, __shfl_xor(cmax, o, kWave));
-        cmax = __builtin_amdgcn_readfirstlane(cmax);
-        // sample n = 16m + l: the lane's voffset advances by 16 samples per iteration
-        const int v0 = (kAvxLanes * m_lo + l) * SB;
-        f2 xa[kB], xb[kB];
-#pragma unroll
-        for (int u = 0; u < kB; u++) xa[u] = load_sample<FMT>(span, v0 + u * kAvxLanes * SB, 0);
-        wait_published(&ep.published, (4 * g + 4 < S ? 4 * g + 4 : S));
-        f2 z = active ? Z[(active ? t : 0) * kAvxLanes + l] : f2{0.0f, 0.0f};
-        for (int i0 = 0; i0 < cmax; i0 += kB) {
-            if (i0 + kB < cmax) {
-#pragma unroll
-                for (int u = 0; u < kB; u++) xb[u] = load_sample<FMT>(span, v0 + (i0 + kB + u) * kAvxLanes * SB, 0);
-            }
-#pragma unroll
-            for (int u = 0; u < kB; u++) {
-                const int i = i0 + u;
-                // past the task: weight 0, and the chip index of a sample inside the epoch (the
-                // padded replica covers [0, N) only; a product 0·code[far] could meet a NaN)
-                const bool on = i < cnt;
-                const f2 r = on ? cmul_pk2(xa[u], z) : f2{0.0f, 0.0f};
-                z = cmul_exact(z, dz);
-                const int n = on ? kAvxLanes * (m_lo + i) + l : 0;
-                const float sn = __fmul_rn(step, static_cast<float>(n));
-#pragma unroll
-                for (int q = 0; q < NT; q++) {
-                    const float c = code_at<IN_MARGIN>(code0, L, sn, shifts[q], rem);
-                    acc[q] = __builtin_elementwise_fma(r, f2{c, c}, acc[q]);
-                }
-                if constexpr (DATA) {
-                    const float c = code_at<IN_MARGIN>(code1, L, sn, 0.0f, rem);
-                    acc[NT] = __builtin_elementwise_fma(r, f2{c, c}, acc[NT]);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < kB; u++) xa[u] = xb[u];
-        }
-    }
-}
-
 // ---- correlation (AVX, u_avx's own accumulation order) -------------------------------------------
-// The tap layout of GPS L5 (3 taps + data prompt) is held to the reference's sums bit for bit on every
-// engine, this one included, so its AVX form does not use the task tree above: the sixteen lanes of one
-// wave ARE u_avx's sixteen chains (trk_lane.hip's scheme with float replicas).  Lane l starts at
-// phase·inc^l, takes the samples 16m + l, forms a = x·z_l (_mm256_complexmul_ps rounding), advances
+// The sixteen lanes of one wave ARE u_avx's sixteen chains (trk_lane.hip's scheme with float replicas).  Lane l
+// starts at phase·inc^l, takes the samples 16m + l, forms a = x·z_l (_mm256_complexmul_ps rounding), advances
 // z_l·dz (renormalised after iteration m ≡ 0 mod 64, :266-272) and adds a·code to its own accumulators
 // in iteration order (_mm256_mul_ps, _mm256_add_ps, :252-260); the chains combine as :279-291, the
 // N mod 16 tail runs on lane 0 (:294-308).  One dependent chain of N/16 iterations per epoch: the
 // reference's own single-core latency — this engine is the fallback behind trk_fast and trk_lane.
-// (the default of trk_persist_kernel's SERIAL argument; launch_trk_persist also sets it for 3 taps without a
-// data prompt when TrkParams::single_code_bits is set — BeiDou B3I, GPS L2C)
-constexpr bool avx_serial_layout(int nt, bool data) { return nt == 3 && data; }
 
 // ((d_k + d_{k+4}) + d_{k+8}) + d_{k+12} for k = 0..3, then (((0 + s_0) + s_1) + s_2) + s_3, valid at
 // lane 0 of the 16-lane row (as trk_lane.hip's avx_chain_sum_row)
@@ -453,10 +262,10 @@ constexpr int persist_waves_per_simd() { return THRU ? 4 : 1; }
 // GLO: the GLONASS L1 / L2 C/A block (trk_glo_loop.h) on the generic serial pipeline — the epoch is correlated over the
 // channel's current block length (not vector_length) and thread 0 runs glo_epoch_update in place of the five phases.
 // Every GLO branch is `if constexpr`: the other instantiations compile to what they were.
-template <int FMT, int NT, bool DATA, bool AVX, bool THRU, bool SERIAL = avx_serial_layout(NT, DATA), bool GLO = false>
+template <int FMT, int NT, bool DATA, bool AVX, bool THRU, bool GLO = false>
 __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk_persist_kernel(const TrkParams* __restrict__ pk, TrkChannel* __restrict__ chans,
     const CodeDesc* __restrict__ codes, int n_codes, const void* __restrict__ samples, uint64_t buf_first, int64_t buf_len, int max_rounds,
-    int n_chans, int code_cap_floats, int avx_g, gnsship_trk_epoch* __restrict__ rec, gnsship_trk_dump_record* __restrict__ dump,
+    int n_chans, int code_cap_floats, int ring_chunks, gnsship_trk_epoch* __restrict__ rec, gnsship_trk_dump_record* __restrict__ dump,
     gnsship_trk_corr_trace* __restrict__ trace, int* __restrict__ ran_count)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -491,8 +300,6 @@ __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk
     const float* c0 = code0 + kCodeMargin;
     const float* c1 = code1 + kCodeMargin;
     const int N = static_cast<int>(k.conf.vector_length);
-    f2* Z = reinterpret_cast<f2*>(anc);
-    f2* T = AVX ? Z + (avx_tasks(N / kAvxLanes, avx_g) + 1) * kAvxLanes : nullptr;
     for (int e = 0; e < max_rounds; e++) {
         if (wave == 0) {
             if (lane == 0) GNSSHIP_TRK_STAMP(e, 0);
@@ -519,7 +326,6 @@ __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk
                     derive_epoch<AVX>(ep, k, sc, static_cast<int64_t>(sc.nitems_read - buf_first), L, p0, inc, static_cast<int32_t>(vl));
                     sc.epoch_start = sc.nitems_read;
                 }
-                ep.published = 0;
                 ep.sync = SerialSync{};
                 if constexpr (!AVX)
                     for (int i = 0; i < 2 * kMaxTaps + 2; i++) ep.taps[i] = 0.0f;
@@ -536,53 +342,17 @@ __global__ __launch_bounds__(kPThreads, persist_waves_per_simd<THRU>()) void trk
         // the epoch's length: vector_length, or (GLO) the block length the previous epoch left, wave-uniform
         const int Ne = GLO ? __builtin_amdgcn_readfirstlane(ep.job.n_samples) : N;
         const i4v span = sample_span<FMT>(samples, off_u, Ne);
-        f2 acc[NT + 1];
-#pragma unroll
-        for (int t = 0; t <= NT; t++) acc[t] = f2{0.0f, 0.0f};
-        constexpr bool kSerialAvx = AVX && SERIAL;
-        if constexpr (kSerialAvx) {
+        if constexpr (AVX) {
             if (wave == 1 && lane < kAvxLanes) {
                 if (ep.in_margin) chains_avx<FMT, NT, DATA, true>(ep, span, N, c0, c1, L, lane);
                 else chains_avx<FMT, NT, DATA, false>(ep, span, N, c0, c1, L, lane);
             }
             if (tid == 0) GNSSHIP_TRK_STAMP(e, 2);
-        } else if constexpr (AVX) {
-            if (wave == 0 && lane < kAvxLanes) {
-                if (avx_g == 16) replay_avx<16>(ep, Z, T, N, lane, &ep.published);
-                else if (avx_g == 32) replay_avx<32>(ep, Z, T, N, lane, &ep.published);
-                else replay_avx<64>(ep, Z, T, N, lane, &ep.published);
-            }
-            if (tid == 0) GNSSHIP_TRK_STAMP(e, 2);
-            if (ep.in_margin)
-                consume_avx<FMT, NT, DATA, true, THRU ? 4 : 16>(ep, Z, T, span, N, avx_g, c0, c1, L, lane, wave, acc);
-            else
-                consume_avx<FMT, NT, DATA, false, THRU ? 4 : 16>(ep, Z, T, span, N, avx_g, c0, c1, L, lane, wave, acc);
         } else {
-            serial_epoch<FMT, NT, DATA>(ep, anc, avx_g, span, Ne, c0, c1, L, lane, wave);  // avx_g = the ring's chunks
+            serial_epoch<FMT, NT, DATA>(ep, anc, ring_chunks, span, Ne, c0, c1, L, lane, wave);
             if (tid == 0) GNSSHIP_TRK_STAMP(e, 2);
         }
         if (lane == 0) GNSSHIP_TRK_STAMP(e, wave <= 1 ? 3 + wave : 14 + wave);  // waves 2, 3: slots 16, 17
-        if constexpr (AVX && !kSerialAvx) {
-            constexpr int kOut = NT + (DATA ? 1 : 0);
-#pragma unroll
-            for (int t = 0; t < kOut; t++) {
-                const float sr = wave_sum(acc[t].x), si = wave_sum(acc[t].y);
-                if (lane == 0) {
-                    ep.red[wave][2 * t] = sr;
-                    ep.red[wave][2 * t + 1] = si;
-                }
-            }
-            if (lane == 0) GNSSHIP_TRK_STAMP(e, 18 + wave);  // wave sums stored: slots 18-21
-            __syncthreads();
-            // tap sums over the waves (each in the serial order w = 0..3), the data prompt at 2·kMaxTaps
-            if (tid < 2 * kMaxTaps + 2) {
-                const int v = tid < 2 * kMaxTaps ? tid : 2 * NT + (tid - 2 * kMaxTaps);
-                float s = 0.0f;
-                if (tid < 2 * NT || (DATA && tid >= 2 * kMaxTaps))
-                    for (int w = 0; w < kPWaves; w++) s += ep.red[w][v];
-                ep.taps[tid] = s;
-            }
-        }
         __syncthreads();
         const float* taps = ep.taps;
         const float* pdata = DATA ? ep.taps + 2 * kMaxTaps : ep.taps;
@@ -664,27 +434,19 @@ extern "C" int gnsship_debug_trk_profile(void* dev_buf)
 namespace gnsship {
 #endif
 
-// LDS bytes of the persistent kernel's dynamic region (codes + rings) and, for the AVX rotator, the
-// task granularity G (16 iterations where the anchors fit, else 32 or 64), for the generic rotator the
-// serial pipeline's ring chunks.
+// LDS bytes of the persistent kernel's dynamic region: the code replica(s) and, for the generic rotator, the serial
+// pipeline's rings — 16 chunks where they fit, else 8 or 4 (g_out = RC).  The AVX form (chains_avx) keeps its
+// chains in registers: the replicas alone.
 static size_t persist_lds(const TrkParams& p, int code_cap_floats, bool avx, int* g_out)
 {
-    const int N = static_cast<int>(p.conf.vector_length);
     const size_t codes = static_cast<size_t>(p.jobs_per_channel > 1 ? 2 : 1) * code_cap_floats * sizeof(float);
-    if (!avx) {  // the serial pipeline's rings: 16 chunks where they fit, else 8 or 4 (g_out = RC)
-        const int na = 2 * (p.n_taps + (p.jobs_per_channel > 1 ? 1 : 0));
-        size_t bytes = 0;
-        for (int rc = 16; rc >= 4; rc /= 2) {
-            bytes = codes + serial_ring_bytes(rc, na);
-            if (g_out) *g_out = rc;
-            if (bytes <= kTrkPersistMaxLds) break;
-        }
-        return bytes;
-    }
+    if (g_out) *g_out = 0;
+    if (avx) return codes;
+    const int na = 2 * (p.n_taps + (p.jobs_per_channel > 1 ? 1 : 0));
     size_t bytes = 0;
-    for (int G = 16; G <= kAvxSeg; G *= 2) {
-        bytes = codes + static_cast<size_t>(avx_tasks(N / kAvxLanes, G) + 2) * kAvxLanes * sizeof(f2);
-        if (g_out) *g_out = G;
+    for (int rc = 16; rc >= 4; rc /= 2) {
+        bytes = codes + serial_ring_bytes(rc, na);
+        if (g_out) *g_out = rc;
         if (bytes <= kTrkPersistMaxLds) break;
     }
     return bytes;
@@ -694,10 +456,10 @@ size_t trk_persist_lds_bytes(const TrkParams& p, int code_cap_floats, bool avx) 
 
 hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes,
     int n_codes, int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool avx, hipStream_t stream)
+    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool avx, hipStream_t stream, gnsship_trk_plan* plan)
 {
-    int avx_g = 0;
-    const size_t lds = persist_lds(params, code_cap_floats, avx, &avx_g);
+    int ring_chunks = 0;  // the generic rotator's ring (0 for the AVX form)
+    const size_t lds = persist_lds(params, code_cap_floats, avx, &ring_chunks);
     const bool data = params.jobs_per_channel > 1;
     const bool glo = params.conf.system == GNSSHIP_SYS_GLO_L1CA || params.conf.system == GNSSHIP_SYS_GLO_L2CA;
     if (glo && (avx || data || params.n_taps != 3)) return hipErrorInvalidValue;
@@ -706,30 +468,28 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
     if (const char* env = std::getenv("GNSSHIP_TRK_THRU")) thru = env[0] == '1';
     const int nt = params.n_taps;
     dim3 grid(n_chans), block(kPThreads);
-#define GNSSHIP_PERSIST(F, NTV, DV, AV) GNSSHIP_PERSIST_S(F, NTV, DV, AV, avx_serial_layout(NTV, DV))
-#define GNSSHIP_PERSIST_S(F, NTV, DV, AV, SV)                                                                                                  \
+#define GNSSHIP_PERSIST(F, NTV, DV, AV)                                                                                                  \
     do {                                                                                                                                       \
-        auto kfn = thru ? trk_persist_kernel<F, NTV, DV, AV, true, SV> : trk_persist_kernel<F, NTV, DV, AV, false, SV>;                         \
+        auto kfn = thru ? trk_persist_kernel<F, NTV, DV, AV, true> : trk_persist_kernel<F, NTV, DV, AV, false>;                             \
         hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)); \
         if (e0 != hipSuccess) return e0;                                                                                                       \
         hipLaunchKernelGGL(kfn, grid, block, lds, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans,  \
-            code_cap_floats, avx_g, rec, dump, trace, ran_count);                                                                                     \
+            code_cap_floats, ring_chunks, rec, dump, trace, ran_count);                                                                                     \
     } while (0)
 #define GNSSHIP_PERSIST_GLO(F)                                                                                                                \
     do {                                                                                                                                      \
-        auto kfn = thru ? trk_persist_kernel<F, 3, false, false, true, false, true> : trk_persist_kernel<F, 3, false, false, false, false, true>; \
+        auto kfn = thru ? trk_persist_kernel<F, 3, false, false, true, true> : trk_persist_kernel<F, 3, false, false, false, true>;               \
         hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)); \
         if (e0 != hipSuccess) return e0;                                                                                                      \
         hipLaunchKernelGGL(kfn, grid, block, lds, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans, \
-            code_cap_floats, avx_g, rec, dump, trace, ran_count);                                                                             \
+            code_cap_floats, ring_chunks, rec, dump, trace, ran_count);                                                                             \
     } while (0)
 #define GNSSHIP_PERSIST_F(F)                                                      \
     do {                                                                          \
         if (glo) {                                                                \
             GNSSHIP_PERSIST_GLO(F);                                               \
         } else if (nt == 3 && !data) {                                            \
-            if (avx && params.single_code_bits) GNSSHIP_PERSIST_S(F, 3, false, true, true); /* B3I, L2C: chains_avx */ \
-            else if (avx) GNSSHIP_PERSIST(F, 3, false, true);                     \
+            if (avx) GNSSHIP_PERSIST(F, 3, false, true);                          \
             else GNSSHIP_PERSIST(F, 3, false, false);                             \
         } else if (nt == 3 && data) { /* GPS L5: pilot taps + the L5I prompt */    \
             if (avx) GNSSHIP_PERSIST(F, 3, true, true);                           \
@@ -752,8 +512,17 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
     }
 #undef GNSSHIP_PERSIST_F
 #undef GNSSHIP_PERSIST_GLO
-#undef GNSSHIP_PERSIST_S
 #undef GNSSHIP_PERSIST
+    if (plan) {
+        *plan = gnsship_trk_plan{};
+        plan->engine = GNSSHIP_TRK_ENGINE_PERSIST;
+        plan->format = fmt;
+        plan->n_taps = nt;
+        plan->data_prompt = data ? 1 : 0;
+        plan->lds_bytes = static_cast<int32_t>(lds);
+        plan->thru = thru ? 1 : 0;
+        plan->avx = avx ? 1 : 0;
+    }
     return hipGetLastError();
 }
 

@@ -1082,6 +1082,12 @@ class DllPllVemlTracking:
         check(self.ctx.lib.gnsship_trk_last_engine(self.h, ctypes.byref(v)), "gnsship_trk_last_engine", self.ctx.h)
         return v.value
 
+    def last_plan(self) -> dict:
+        """gnsship_trk_last_plan: the variant the last run's launch function chose (abi.TrkPlan's members by name)."""
+        p = abi.TrkPlan()
+        check(self.ctx.lib.gnsship_trk_last_plan(self.h, ctypes.byref(p)), "gnsship_trk_last_plan", self.ctx.h)
+        return p.as_dict()
+
     def states(self) -> np.ndarray:
         """Tracking state (0 idle/lost, 2, 3, 4) of every channel."""
         return np.array([self.channel_state(ch)[0] for ch in range(self.max_channels)], np.int32)

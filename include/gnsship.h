@@ -856,6 +856,25 @@ int gnsship_trk_trace_records(gnsship_trk* t, gnsship_trk_corr_trace* out, int m
 #define GNSSHIP_TRK_ENGINE_ROUNDS 4
 #define GNSSHIP_TRK_ENGINE_LANES 5
 int gnsship_trk_last_engine(gnsship_trk* t, int* engine);
+/* What the last gnsship_trk_run / _launch decided beyond the engine: the kernel variant and its LDS plan, as the
+ * launch function chose them (a member that does not apply to the engine is 0; everything but `engine` and `format`
+ * is 0 for _ROUNDS and _NONE).  A query only: it changes nothing and reads no environment variable. */
+typedef struct gnsship_trk_plan {
+    int32_t engine;       /* GNSSHIP_TRK_ENGINE_* (what gnsship_trk_last_engine returns) */
+    int32_t format;       /* GNSSHIP_FMT_* of the run's samples */
+    int32_t n_taps;       /* 3 or 5 */
+    int32_t data_prompt;  /* 1: a second replica for the data prompt (track_pilot) */
+    int32_t packed;       /* trk_fast: the replicas held as sign bits (trk_lane always holds them so: 0 there) */
+    int32_t sring;        /* trk_fast: the phasor slots in a ring (rs tasks) instead of one per task of the epoch */
+    int32_t rs, rg;       /* trk_fast: phasor slots (tasks) and product groups held in LDS */
+    int32_t lds_bytes;    /* dynamic LDS of the launch */
+    int32_t thru;         /* trk_fast: the throughput form (3-tap layouts only); trk_persist: the variant at 4 waves per SIMD */
+    int32_t long_plan;    /* trk_fast's latency form: the wave-role plan of long epochs (vector_length >= 10000) */
+    int32_t avx;          /* trk_persist: the AVX rotator's form, u_avx's sixteen chains on sixteen lanes (else the generic serial pipeline) */
+    int32_t lane_waves;   /* trk_lane: waves per workgroup (4 channels each) */
+    int32_t reserved[3];
+} gnsship_trk_plan; /* 64 bytes */
+int gnsship_trk_last_plan(gnsship_trk* t, gnsship_trk_plan* plan);
 int gnsship_trk_destroy(gnsship_trk* t);
 
 /* ------------------------------------------------------------------------------------------ */

@@ -59,3 +59,4 @@ def test_job_layout_matches_header(built):
     assert ctypes.sizeof(abi.AcqResult) == 32
     assert ctypes.sizeof(abi.AcqConf) == 64
     assert ctypes.sizeof(abi.AcqLayout) == 84
+    assert ctypes.sizeof(abi.TrkPlan) == 64

@@ -113,7 +113,7 @@ def test_lanes(ctx, monkeypatch):
 
 def test_persist_avx(ctx, monkeypatch):
     """GNSSHIP_TRK_FAST=0: trk_persist.hip with the AVX rotator, which for B3I runs u_avx's sixteen chains on
-    sixteen lanes with serial sums (chains_avx), not the task tree GPS L1 and B1I keep."""
+    sixteen lanes with serial sums (chains_avx), as every AVX layout of trk_persist now does."""
     monkeypatch.setenv("GNSSHIP_TRK_FAST", "0")
     sc = scenario(FS_A, EPOCHS_A)
     (rec, rounds), eng = run_one(ctx, sc)

@@ -93,8 +93,9 @@ def test_sync_to_state_4_lanes(ctx, monkeypatch):
 
 def test_sync_to_state_4_persist_avx(ctx, monkeypatch):
     """(d) GNSSHIP_TRK_FAST=0: trk_persist.hip with the AVX rotator.  For this tap layout its AVX form runs
-    u_avx's sixteen chains on sixteen lanes with serial sums (chains_avx), not the task tree it keeps for
-    the other layouts (which differed from the oracle by one ulp of the prompt in 42 of these 120 epochs)."""
+    u_avx's sixteen chains on sixteen lanes with serial sums (chains_avx), not the task tree it once ran
+    (which differed from the oracle by one ulp of the prompt in 42 of these 120 epochs; the tree is gone
+    for every layout since)."""
     monkeypatch.setenv("GNSSHIP_TRK_FAST", "0")
     sc = scenario(FS_A, EPOCHS_A)
     (rec, rounds), eng = run_one(ctx, sc)
