@@ -104,6 +104,12 @@ $(VITERBI_MIRROR_TEST): tests/cpp/viterbi_mirror_test.cpp include/gnsship_cpp.hp
 	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/viterbi_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
 all: $(VITERBI_MIRROR_TEST)
 
+# The telemetry decoder mirror (tests/test_cpp_mirror_tlm.py)
+TLM_MIRROR_TEST := tests/cpp/tlm_mirror_test
+$(TLM_MIRROR_TEST): tests/cpp/tlm_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
+	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/tlm_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
+all: $(TLM_MIRROR_TEST)
+
 # Profiling variant (workgroup phase timestamps in corr_batch_kernel; scripts/corr_wg_profile.py)
 PROF_LIB := scripts/libgnsship_prof.so
 PROF_OBJS := $(patsubst $(CSRC)/%.hip,$(PROF_OBJDIR)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(PROF_OBJDIR)/%.cpp.o,$(CPP_SRCS))

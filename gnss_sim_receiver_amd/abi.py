@@ -185,6 +185,36 @@ class VitConf(ctypes.Structure):
                 ("invert_g2", ctypes.c_int32), ("mode", ctypes.c_int32)]
 
 
+TLM_INAV, TLM_FNAV, TLM_CNAV = 1, 2, 3
+# gnsship_tlm_page.flags
+TLM_CRC_OK, TLM_CRC_EVALUATED, TLM_PLL_180, TLM_ODD, TLM_FRAME_SYNC, TLM_SYNC_LOST = 1, 2, 4, 8, 16, 32
+# (preamble length, period, required symbols, data length LL) of the three frame types
+TLM_GEOMETRY = {TLM_INAV: (10, 250, 510, 114), TLM_FNAV: (12, 500, 512, 238), TLM_CNAV: (16, 1000, 1016, 486)}
+
+
+class TlmConf(ctypes.Structure):
+    """gnsship_tlm_conf — the frame type of galileo_telemetry_decoder_gs (:167-213), the Viterbi mode and the most
+    symbols per channel one run may carry."""
+    _fields_ = [("frame_type", ctypes.c_int32), ("vit_mode", ctypes.c_int32), ("max_rounds", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class TlmState(ctypes.Structure):
+    """gnsship_tlm_state — the block's members of one channel."""
+    _fields_ = [("symbol_counter", ctypes.c_uint64), ("preamble_index", ctypes.c_uint64), ("last_valid_preamble", ctypes.c_uint64),
+                ("stat", ctypes.c_int32), ("crc_error_counter", ctypes.c_int32), ("history_size", ctypes.c_int32),
+                ("pll_180", ctypes.c_uint8), ("frame_sync", ctypes.c_uint8), ("even_word_arrived", ctypes.c_uint8),
+                ("flag_crc_test", ctypes.c_uint8), ("sent_tlm_failed", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "pad"}
+
+
+assert ctypes.sizeof(TlmState) == 48
+
+TLM_PAGE_DTYPE = np.dtype([("symbol_counter", "<u8"), ("sample_counter", "<u8"), ("channel", "<i4"), ("flags", "<i4"),
+                           ("crc_error_counter", "<i4"), ("pad", "<i4")])
+assert TLM_PAGE_DTYPE.itemsize == 32
+
 SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5, SYS_BDS_B3I, SYS_GPS_L2C = 0, 1, 2, 3, 4, 5
 SYS_GAL_E5A, SYS_GAL_E5B = 6, 7
 SYS_GLO_L1CA, SYS_GLO_L2CA = 8, 9  # glonass_l1_ca / glonass_l2_ca_dll_pll_tracking_cc (include/gnsship.h)
@@ -411,6 +441,17 @@ _SIGNATURES = {
     "gnsship_trk_run_dump": ([_vp, _vp, _i, _i, ctypes.c_uint64, ctypes.c_int64, _i, _vp, _vp, ctypes.POINTER(_i)], _i),
     "gnsship_trk_launch": ([_vp, _vp, _i, ctypes.c_uint64, ctypes.c_int64, _i, _i, _i], _i),
     "gnsship_trk_collect": ([_vp, _vp, _vp, ctypes.POINTER(_i)], _i),
+    "gnsship_trk_records_device": ([_vp, _vpp, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)], _i),
+    "gnsship_tlm_create": ([_vp, ctypes.POINTER(TlmConf), ctypes.c_int32, _vpp], _i),
+    "gnsship_tlm_run_symbols": ([_vp, _vp, _vp, _i, ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
+    "gnsship_tlm_run_records": ([_vp, _vp, _i, ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
+    "gnsship_tlm_run_trk": ([_vp, _vp, _vp, _vp, _vp, _vp], _i),
+    "gnsship_tlm_outputs_device": ([_vp, _vpp, _vpp, _vpp, _vpp, ctypes.POINTER(ctypes.c_int32)], _i),
+    "gnsship_tlm_reset_channel": ([_vp, ctypes.c_int32], _i),
+    "gnsship_tlm_set_satellite": ([_vp, ctypes.c_int32], _i),
+    "gnsship_tlm_new_channel": ([_vp, ctypes.c_int32], _i),
+    "gnsship_tlm_state_get": ([_vp, ctypes.c_int32, ctypes.POINTER(TlmState)], _i),
+    "gnsship_tlm_destroy": ([_vp], _i),
     "gnsship_trk_set_trace": ([_vp, _i], _i),
     "gnsship_trk_trace_records": ([_vp, _vp, _i], _i),
     "gnsship_trk_channel_state": ([_vp, _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_uint64)], _i),

@@ -85,6 +85,7 @@ struct gnsship_trk {
     // gnsship_trk_launch → gnsship_trk_collect: the enqueued run's rounds (−1: none pending)
     int pending_rounds = -1;
     bool pending_out = false, pending_dump = false;
+    int rec_rounds = 0;  // rounds of records the last run / launch left in rec_dev (gnsship_trk_records_device), 0: none
     // gnsship_trk_set_trace: per channel-epoch correlation trace of the last run
     bool trace_on = false;
     int last_engine = GNSSHIP_TRK_ENGINE_NONE;  // the engine the last run / launch used
@@ -1045,6 +1046,7 @@ static int trk_enqueue(gnsship_trk* t, const void* src, int fmt, uint64_t buffer
     }
     t->pending_rounds = max_rounds;
     t->pending_out = out;
+    t->rec_rounds = out ? max_rounds : 0;
     t->pending_dump = dump;
     return GNSSHIP_OK;
 }
@@ -1136,6 +1138,22 @@ extern "C" int gnsship_trk_collect(gnsship_trk* t, gnsship_trk_epoch* out, gnssh
     if (int rc = set_device(t->ctx)) return rc;
     return trk_finish(t, out, dump, rounds_done);
 }
+
+extern "C" int gnsship_trk_records_device(gnsship_trk* t, const gnsship_trk_epoch** dev_ptr, int32_t* rounds, int32_t* max_channels)
+{
+    if (!t) return GNSSHIP_E_INVAL;
+    if (!dev_ptr || !rounds || !max_channels) return fail(t->ctx, GNSSHIP_E_INVAL, "gnsship_trk_records_device: null argument");
+    if (t->rec_rounds < 1 || !t->rec_dev) return fail(t->ctx, GNSSHIP_E_STATE, "gnsship_trk_records_device: the last run kept no records on the device");
+    *dev_ptr = t->rec_dev;
+    *rounds = t->rec_rounds;
+    *max_channels = t->max_channels;
+    return GNSSHIP_OK;
+}
+
+// the context the records above are ordered on (tlm_galileo.hip: gnsship_tlm_run_trk requires its own)
+namespace gnsship {
+gnsship_ctx* trk_context(const gnsship_trk* t) { return t->ctx; }
+}  // namespace gnsship
 
 extern "C" int gnsship_trk_set_trace(gnsship_trk* t, int enable)
 {

@@ -18,6 +18,7 @@
 //              the subtraction.
 //   traceback  serial, one lane, out of LDS: from state 0, the 6 tail steps skipped, LL bytes of 0 / 1.  An entry
 //              nothing stored reads as predecessor 0, bit 0 (a new object's content; include/gnsship.h).
+// Trellis and traceback are vit_wave.h's, shared with the telemetry framing kernel (tlm_galileo.hip).
 //
 // REFERENCE mode reproduces Viterbi_Decoder::decode as written: only the first symbol of each pair enters the
 // metric (:61 copies d_nn − 1 = 1 value; Gamma = {0, 0 + 0, 0 + r0, (0 + 0) + r0}, :151-166) and the 64 metrics
@@ -32,6 +33,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "vit_wave.h"
 
 #pragma clang fp contract(off)
 
@@ -46,9 +48,6 @@ using namespace gnsship;
 namespace {
 
 constexpr int kVitFramesPerWg = 4;  // waves per workgroup: 4 · 24 · 512 = 48 KiB of LDS at the longest frame
-constexpr int kVitStates = 64;
-constexpr int kVitTail = 6;         // K − 1
-constexpr float kVitMaxLog = 1e7f;  // d_MAXLOG
 
 struct VitArgs {
     const float* sym;         // n_frames × 2·steps, as received
@@ -63,45 +62,6 @@ struct VitArgs {
     int32_t invert_g2, mode;
     int32_t g0, g1;
 };
-
-// 16-byte words of LDS per wave: T survivor words and 2·T symbols
-__host__ __device__ constexpr int vit_wave_lds_words(int steps) { return steps + (steps + 1) / 2; }
-
-__device__ __forceinline__ int vit_parity7(int x) { return __popc(x & 127) & 1; }
-
-// nsc_enc_bit (viterbi_decoder.cc:183-204): the output symbol of the branch from state p with information bit `bit`
-__device__ __forceinline__ int vit_branch(const VitArgs& a, int bit, int p)
-{
-    const int w = (bit << 6) ^ p;
-    return (vit_parity7(w & a.g0) << 1) | vit_parity7(w & a.g1);
-}
-
-// The order of finite floats as the order of signed integers: negative values get their magnitude bits inverted.
-// Its own inverse.  (−0 would sort below +0; no operand here is ever −0.)
-__device__ __forceinline__ int vit_order_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
-
-template <int kCtrl>
-__device__ __forceinline__ int vit_dpp(int v)
-{
-    return __builtin_amdgcn_update_dpp(0, v, kCtrl, 0xF, 0xF, true);  // every lane has a source lane in these patterns
-}
-
-// The maximum of a value over the wave, in every lane; all 64 lanes must be active and the values finite.  Taken on
-// the integer keys, where a DPP operand folds into the max instruction and the last three maxima are scalar: four
-// steps leave each row of 16 lanes with its own maximum (lane ^ 1, lane ^ 2 by quad_perm, then row_half_mirror and
-// row_mirror), four lane reads join the rows.  The maximum of a set does not depend on the order it is taken in.
-__device__ __forceinline__ float vit_wave_max(float x)
-{
-    constexpr int kQuadXor1 = 0xB1, kQuadXor2 = 0x4E, kRowHalfMirror = 0x141, kRowMirror = 0x140;
-    int v = vit_order_key(__float_as_int(x));
-    v = max(v, vit_dpp<kQuadXor1>(v));
-    v = max(v, vit_dpp<kQuadXor2>(v));
-    v = max(v, vit_dpp<kRowHalfMirror>(v));
-    v = max(v, vit_dpp<kRowMirror>(v));
-    const int r0 = __builtin_amdgcn_readlane(v, 0), r1 = __builtin_amdgcn_readlane(v, 16);
-    const int r2 = __builtin_amdgcn_readlane(v, 32), r3 = __builtin_amdgcn_readlane(v, 48);
-    return __int_as_float(vit_order_key(max(max(r0, r1), max(r2, r3))));
-}
 
 // kFull: GNSSHIP_VIT_MODE_FULL (both symbols in the metric, nothing carried)
 template <bool kFull>
@@ -121,66 +81,20 @@ __global__ __launch_bounds__(kVitFramesPerWg * 64) void vit_decode_kernel(const 
         const bool neg = a.negate != nullptr && a.negate[f] != 0;
         for (int i = lane; i < 2 * T; i += 64) {
             float v = in[i];
-            int j = i;
-            if (a.rows > 0) {  // rows · cols == 2·T (checked by create), so r < rows and j < 2·T
-                const int r = i / a.cols, c = i - r * a.cols;
-                j = c * a.rows + r;
-            }
-            if (neg) v = -v;
-            if (a.invert_g2 && (j & 1)) v = -v;
+            const int j = vit_place(i, a.rows, a.cols, neg, a.invert_g2 != 0, v);  // rows · cols == 2·T (checked by create), so j < 2·T
             sym[j] = v;
         }
     }
     __syncthreads();
 
     if (active) {
-        const int p0 = (lane & 31) << 1, p1 = p0 | 1, bit = lane >> 5;
-        const int out0 = vit_branch(a, bit, p0), out1 = vit_branch(a, bit, p1);
         const int64_t sec = static_cast<int64_t>(a.channels[f]) * kVitStates + lane;
-        // the branch symbols' two bits select the terms of Gamma (:157-164)
-        const bool a_lo = out0 & 1, a_hi = out0 & 2, b_lo = out1 & 1, b_hi = out1 & 2;
-        float prev = kFull ? -kVitMaxLog : a.sections[sec];
-        if (lane == 0) prev = 0.0f;  // :56
-        float2 next = reinterpret_cast<const float2*>(sym)[0];
-        for (int t = 0; t < T; t++) {
-            const float2 r = next;
-            next = reinterpret_cast<const float2*>(sym)[min(t + 1, T - 1)];  // ahead of the step that needs it
-            // Gamma(0) = 0, Gamma(1) = 0 + rec[1], Gamma(2) = 0 + rec[0], Gamma(3) = (0 + rec[1]) + rec[0]; rec[1] stays 0
-            // in reference mode, where Gamma(1) = 0 and Gamma(3) = (0 + 0) + rec[0] = Gamma(2)
-            const float gm2 = 0.0f + r.x;
-            float ga, gb;
-            if (kFull) {
-                const float gm1 = 0.0f + r.y, gm3 = gm1 + r.x;
-                ga = a_hi ? (a_lo ? gm3 : gm2) : (a_lo ? gm1 : 0.0f);
-                gb = b_hi ? (b_lo ? gm3 : gm2) : (b_lo ? gm1 : 0.0f);
-            } else {
-                ga = a_hi ? gm2 : 0.0f;
-                gb = b_hi ? gm2 : 0.0f;
-            }
-            const float m0 = __shfl(prev, p0) + ga;
-            const float m1 = __shfl(prev, p1) + gb;
-            float cur = -kVitMaxLog;
-            const bool s0 = m0 > cur;
-            cur = s0 ? m0 : cur;
-            const bool s1 = m1 > cur;
-            cur = s1 ? m1 : cur;
-            const unsigned long long d = __ballot(s1), s = __ballot(s0 || s1);
-            if (lane == 0) surv[t] = make_ulonglong2(d, s);
-            prev = cur - vit_wave_max(cur);
-        }
+        const float prev = vit_wave_trellis<kFull>(surv, sym, T, kFull ? -kVitMaxLog : a.sections[sec], lane, a.g0, a.g1);
         if (!kFull) a.sections[sec] = prev;
     }
     __syncthreads();
 
-    if (active && lane == 0) {
-        int state = 0;
-        for (int t = T - 1; t >= 0; t--) {
-            const ulonglong2 w = surv[t];
-            const bool st = (w.y >> state) & 1ull;
-            if (t < LL) obits[t] = st ? static_cast<uint8_t>(state >> 5) : 0;
-            state = st ? (((state & 31) << 1) | static_cast<int>((w.x >> state) & 1ull)) : 0;
-        }
-    }
+    if (active && lane == 0) vit_wave_traceback(surv, obits, T, LL);
     __syncthreads();
 
     if (active)

@@ -963,6 +963,135 @@ def galileo_cnav_page_decoder(ctx: Context, max_channels: int, mode="reference")
     return _galileo_page_decoder(ctx, max_channels, GALILEO_CNAV_PAGE, mode)
 
 
+class TlmResult(NamedTuple):
+    """One gnsship_tlm run: pages [max_channels, pages_per_run] (abi.TLM_PAGE_DTYPE), bits uint8[max_channels,
+    pages_per_run, LL], counts int32[max_channels], faults uint8[max_channels]; slots k >= counts[c] are unspecified."""
+    pages: np.ndarray
+    bits: np.ndarray
+    counts: np.ndarray
+    faults: np.ndarray
+
+
+class GalileoTelemetryDecoder:
+    """The frame handling of galileo_telemetry_decoder_gs::general_work (:872-1094) for up to ``max_channels`` channels
+    on the device, one block object per channel: preamble synchronisation, page parts, Viterbi, CRC-24Q, the CRC-error
+    counter and check_tlm_separation (include/gnsship.h, gnsship_tlm_*).  frame_type abi.TLM_INAV / _FNAV / _CNAV;
+    mode "reference" | "full" as ViterbiDecoder; max_rounds: the most symbols per channel one run may carry."""
+
+    def __init__(self, ctx: Context, frame_type: int, max_channels: int, max_rounds: int, mode="reference"):
+        self.ctx = ctx
+        self.h = None
+        self.frame_type = int(frame_type)
+        self.mode = ViterbiDecoder.MODES[mode] if isinstance(mode, str) else int(mode)
+        self.max_channels, self.max_rounds = int(max_channels), int(max_rounds)
+        self.conf = abi.TlmConf(frame_type=self.frame_type, vit_mode=self.mode, max_rounds=self.max_rounds, reserved=0)
+        h = ctypes.c_void_p()
+        check(ctx.lib.gnsship_tlm_create(ctx.h, ctypes.byref(self.conf), self.max_channels, ctypes.byref(h)), "gnsship_tlm_create", ctx.h)
+        self.h = h
+        self.preamble_symbols, self.period, self.required, self.data_length = abi.TLM_GEOMETRY[self.frame_type]
+        ppr = ctypes.c_int32()
+        check(ctx.lib.gnsship_tlm_outputs_device(self.h, None, None, None, None, ctypes.byref(ppr)), "gnsship_tlm_outputs_device", ctx.h)
+        self.pages_per_run = ppr.value
+
+    def _outputs(self, host: bool):
+        if not host:
+            return None, (None, None, None, None)
+        res = TlmResult(np.zeros((self.max_channels, self.pages_per_run), abi.TLM_PAGE_DTYPE),
+                        np.zeros((self.max_channels, self.pages_per_run, self.data_length), np.uint8),
+                        np.zeros(self.max_channels, np.int32), np.zeros(self.max_channels, np.uint8))
+        return res, tuple(ctypes.c_void_p(x.ctypes.data) for x in res)
+
+    def run_symbols(self, symbols, valid=None, on_device: bool = False, n_rounds: int = None, host: bool = True):
+        """symbols float32[n_rounds, max_channels] (or a device pointer with on_device and n_rounds), valid uint8 of the
+        same shape (and place) or None.  Returns a TlmResult, or None when not host (asynchronous)."""
+        if on_device:
+            sp, vp = ctypes.c_void_p(symbols), ctypes.c_void_p(valid) if valid else None
+        else:
+            symbols = np.ascontiguousarray(symbols, np.float32).reshape(-1, self.max_channels)
+            n_rounds = symbols.shape[0] if n_rounds is None else int(n_rounds)
+            sp = ctypes.c_void_p(symbols.ctypes.data) if symbols.size else None
+            vp = None
+            if valid is not None:
+                valid = np.ascontiguousarray(valid, np.uint8).reshape(-1, self.max_channels)
+                if valid.shape != symbols.shape:
+                    raise ValueError("valid must have the symbols' shape")
+                vp = ctypes.c_void_p(valid.ctypes.data) if valid.size else None
+        res, ptrs = self._outputs(host)
+        self._in_flight = (symbols, valid)  # a run without a host copy returns before the stream has read them
+        check(self.ctx.lib.gnsship_tlm_run_symbols(self.h, sp, vp, int(on_device), int(n_rounds), *ptrs), "gnsship_tlm_run_symbols", self.ctx.h)
+        return res
+
+    def run_records(self, records, on_device: bool = False, n_rounds: int = None, host: bool = True):
+        """records: abi.TRK_EPOCH_DTYPE[n_rounds, max_channels] on the host, or a device pointer with on_device and n_rounds."""
+        if on_device:
+            rp = ctypes.c_void_p(records)
+        else:
+            records = np.ascontiguousarray(records, abi.TRK_EPOCH_DTYPE).reshape(-1, self.max_channels)
+            n_rounds = records.shape[0] if n_rounds is None else int(n_rounds)
+            rp = ctypes.c_void_p(records.ctypes.data) if records.size else None
+        res, ptrs = self._outputs(host)
+        self._in_flight = (records,)
+        check(self.ctx.lib.gnsship_tlm_run_records(self.h, rp, int(on_device), int(n_rounds), *ptrs), "gnsship_tlm_run_records", self.ctx.h)
+        return res
+
+    def run_trk(self, trk: "DllPllVemlTracking", host: bool = True):
+        """Consume, in place, the records the tracker's last run left on the device."""
+        res, ptrs = self._outputs(host)
+        check(self.ctx.lib.gnsship_tlm_run_trk(self.h, trk.h, *ptrs), "gnsship_tlm_run_trk", self.ctx.h)
+        return res
+
+    def outputs_device(self):
+        """Device pointers (pages, bits, counts, faults) of the handle's output buffers."""
+        p = [ctypes.c_void_p() for _ in range(4)]
+        check(self.ctx.lib.gnsship_tlm_outputs_device(self.h, *[ctypes.byref(x) for x in p], None), "gnsship_tlm_outputs_device", self.ctx.h)
+        return tuple(x.value for x in p)
+
+    def state(self, channel: int) -> dict:
+        """The channel's block members (gnsship_tlm_state) by name."""
+        st = abi.TlmState()
+        check(self.ctx.lib.gnsship_tlm_state_get(self.h, channel, ctypes.byref(st)), "gnsship_tlm_state_get", self.ctx.h)
+        return st.as_dict()
+
+    def reset_channel(self, channel: int):
+        """The block's reset()."""
+        check(self.ctx.lib.gnsship_tlm_reset_channel(self.h, channel), "gnsship_tlm_reset_channel", self.ctx.h)
+
+    def set_satellite(self, channel: int):
+        """The block's set_satellite()."""
+        check(self.ctx.lib.gnsship_tlm_set_satellite(self.h, channel), "gnsship_tlm_set_satellite", self.ctx.h)
+
+    def new_channel(self, channel: int):
+        """A new block object on this channel."""
+        check(self.ctx.lib.gnsship_tlm_new_channel(self.h, channel), "gnsship_tlm_new_channel", self.ctx.h)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.gnsship_tlm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.close()
+        except Exception:
+            pass
+
+
+def galileo_inav_telemetry(ctx: Context, max_channels: int, max_rounds: int, mode="reference") -> GalileoTelemetryDecoder:
+    """I/NAV (E1-B, E5b-I): 250-symbol page parts, even + odd joined for the CRC."""
+    return GalileoTelemetryDecoder(ctx, abi.TLM_INAV, max_channels, max_rounds, mode)
+
+
+def galileo_fnav_telemetry(ctx: Context, max_channels: int, max_rounds: int, mode="reference") -> GalileoTelemetryDecoder:
+    """F/NAV (E5a-I): 500-symbol pages."""
+    return GalileoTelemetryDecoder(ctx, abi.TLM_FNAV, max_channels, max_rounds, mode)
+
+
+def galileo_cnav_telemetry(ctx: Context, max_channels: int, max_rounds: int, mode="reference") -> GalileoTelemetryDecoder:
+    """C/NAV frame geometry (E6-B): 1000-symbol pages."""
+    return GalileoTelemetryDecoder(ctx, abi.TLM_CNAV, max_channels, max_rounds, mode)
+
+
 class DllPllVemlTracking:
     """dll_pll_veml_tracking (dll_pll_veml_tracking.cc) for up to ``max_channels`` channels, the
     per-epoch loop resident on the device: ``start_tracking`` → :meth:`start`, ``general_work``

@@ -824,6 +824,10 @@ int gnsship_trk_run_dump(gnsship_trk* t, const void* sig, int fmt, int sig_on_de
 int gnsship_trk_launch(gnsship_trk* t, const void* dev_sig, int fmt, uint64_t buffer_first_sample, int64_t n_buffer_samples, int max_rounds,
     int want_records, int want_dump);
 int gnsship_trk_collect(gnsship_trk* t, gnsship_trk_epoch* out, gnsship_trk_dump_record* dump, int* rounds_done);
+/* Where the last gnsship_trk_run / _launch that kept records left them on the device: rounds × max_channels records,
+ * round-major, written in context-stream order (valid until the handle's next run or its destruction; before or after
+ * gnsship_trk_collect).  A query only.  GNSSHIP_E_STATE when the last run kept none. */
+int gnsship_trk_records_device(gnsship_trk* t, const gnsship_trk_epoch** dev_ptr, int32_t* rounds, int32_t* max_channels);
 int gnsship_trk_channel_state(gnsship_trk* t, int channel, int* state, uint64_t* next_sample);
 /* Correlation trace: each channel-epoch's do_correlation_step call (dll_pll_veml_tracking.cc:1037-1062)
  * as the engine ran it — the float arguments of Carrier_wipeoff_multicorrelator_resampler
@@ -876,6 +880,97 @@ typedef struct gnsship_trk_plan {
 } gnsship_trk_plan; /* 64 bytes */
 int gnsship_trk_last_plan(gnsship_trk* t, gnsship_trk_plan* plan);
 int gnsship_trk_destroy(gnsship_trk* t);
+
+/* ---------------------------------------------------------------------------------------------
+ * Galileo telemetry framing on the device: the frame handling of galileo_telemetry_decoder_gs::general_work
+ * (galileo_telemetry_decoder_gs.cc:872-1094) for I/NAV (E1-B, E5b-I), F/NAV (E5a-I) and C/NAV frame geometry, one
+ * block object per channel, one wavefront per channel.  Per symbol, in the block's order: push_back into the symbol
+ * history (capacity required + 1, :884), d_symbol_counter++ (:886), check_tlm_separation (:856-869), then the switch on
+ * d_stat: states 0 / 1 correlate the P oldest history entries with the preamble once the history is full (an entry is
+ * negative only when `< 0.0`; |corr| >= P is a hit; state 1 accepts a hit exactly one period after the last, falls back
+ * to 0 on a later one and ignores an earlier one), state 2 decodes when counter == preamble_index + period: the frame is
+ * history[P .. P + frame), negated under the 180° flag, de-interleaved, G2-flipped and Viterbi-decoded as gnsship_vit
+ * does (same modes, the carried metrics per channel), then the page handling of decode_INAV/FNAV/CNAV_word up to the
+ * CRC and the CRC-error counter (more than 6 consecutive failures: loss of sync, back to state 0).
+ *   geometry        preamble          P   period  required  frame  rows x cols   LL   fault after
+ *   I/NAV           0101100000        10   250     510       240    8 x 30       114  15000 symbols
+ *   F/NAV           101101110000      12   500     512       488    8 x 61       238   2500
+ *   C/NAV           1011011101110000  16  1000    1016       984    8 x 123      486  60000
+ * I/NAV: an even part (first bit 0) is stored and tests nothing; an odd part joins the stored even part, CRC-24Q over
+ * bits [0, 196) of the joined string against [196, 220), and clears the stored flag; an odd part with no stored even
+ * part tests nothing.  flag_CRC_test is sticky (written only at a joined odd part, cleared by nothing), so crc_ok after
+ * an even part is the previous odd part's verdict and the first part after sync counts as an error — as the block.
+ * F/NAV: CRC over [0, 214) against [214, 238), C/NAV: [0, 462) against [462, 486), on every page.  The block decodes a
+ * C/NAV page only when the symbol's sampling rate is non-zero (:1040); here it is taken as non-zero always.
+ * A page part is emitted required + 1 + 2*period symbols after its preamble's first symbol at the earliest: the
+ * correlation looks at the oldest end of a full history.
+ * Not here: TOW and everything below :1096, page_jk_decoder / ephemeris fields, Reed-Solomon, HAS header parsing and the
+ * dummy-page test, time tags, the nav-data monitor, the CRC statistics file, the .dat dump, other systems' telemetry.
+ * Symbols are finite by contract; with NaN / Inf the decoded bits are unspecified (nothing is read or written out of
+ * bounds: every index comes from lane numbers, sizes and ballot bits). */
+#define GNSSHIP_TLM_INAV 1
+#define GNSSHIP_TLM_FNAV 2
+#define GNSSHIP_TLM_CNAV 3
+#define GNSSHIP_TLM_MAX_CHANNELS (1 << 20)
+#define GNSSHIP_TLM_MAX_ROUNDS (1 << 20)
+typedef struct gnsship_tlm gnsship_tlm;
+typedef struct gnsship_tlm_conf {
+    int32_t frame_type;      /* GNSSHIP_TLM_*                                                  */
+    int32_t vit_mode;        /* GNSSHIP_VIT_MODE_REFERENCE (default, parity) or _FULL          */
+    int32_t max_rounds;      /* most symbols per channel in one run, >= 1                      */
+    int32_t reserved;        /* 0 */
+} gnsship_tlm_conf;
+typedef struct gnsship_tlm_page {   /* one decoded page part, 32 bytes */
+    uint64_t symbol_counter;        /* d_symbol_counter at the part's last symbol              */
+    uint64_t sample_counter;        /* the completing epoch's record.sample_counter; 0 for run_symbols */
+    int32_t channel;
+    int32_t flags;                  /* 1 crc_ok as the block computes it (sticky for I/NAV), 2 a CRC was evaluated on
+                                       this part, 4 PLL 180°, 8 I/NAV odd part, 16 frame sync after this part,
+                                       32 sync lost at this part (d_stat back to 0)            */
+    int32_t crc_error_counter;      /* after this part */
+    int32_t pad;
+} gnsship_tlm_page;
+typedef struct gnsship_tlm_state { /* the block's members, for tests and diagnosis */
+    uint64_t symbol_counter, preamble_index, last_valid_preamble;
+    int32_t stat, crc_error_counter, history_size;
+    uint8_t pll_180, frame_sync, even_word_arrived, flag_crc_test, sent_tlm_failed, pad[3];
+} gnsship_tlm_state;
+/* Channels 0..max_channels-1 (1..GNSSHIP_TLM_MAX_CHANNELS), each a new block object: empty history, counters 0,
+ * d_stat 0, all 64 Viterbi metrics -1e7.  A run emits at most pages_per_run = max_rounds / period + 1 parts per
+ * channel.  Device memory per channel: the history ring (required + 1 floats: 2 KiB I/NAV, 4 KiB C/NAV), 64 bytes of
+ * members, 256 of metrics, and pages_per_run slots of 32 + LL bytes. */
+int gnsship_tlm_create(gnsship_ctx* ctx, const gnsship_tlm_conf* conf, int32_t max_channels, gnsship_tlm** out);
+/* symbols[r*max_channels + c], r < n_rounds (0..max_rounds), float on the host or (on_device) on the device; valid:
+ * uint8 of the same shape and place, or NULL for all valid.  Channel c consumes its valid entries in order of r.
+ * Outputs, in the handle's own device buffers (gnsship_tlm_outputs_device) and copied to whichever host pointers are
+ * given: pages[c][k] and bits[c][k][LL] (bytes of 0 / 1) for k < counts[c], the parts channel c emitted in this run in
+ * order (slots beyond counts[c] are unspecified); counts int32[c]; faults uint8[c], 1 where check_tlm_separation fired
+ * in this run.  With no host pointer the call is asynchronous on the context stream (host inputs then stay the
+ * caller's until the stream has passed the run). */
+int gnsship_tlm_run_symbols(gnsship_tlm* t, const float* symbols, const uint8_t* valid, int on_device, int32_t n_rounds,
+    gnsship_tlm_page* pages_host, uint8_t* bits_host, int32_t* counts_host, uint8_t* faults_host);
+/* The same over tracking records of that shape: an entry is a symbol when flags & 1, the symbol is (float)prompt_i
+ * (as :884 narrows the double), the page's sample_counter the completing record's. */
+int gnsship_tlm_run_records(gnsship_tlm* t, const gnsship_trk_epoch* records, int on_device, int32_t n_rounds,
+    gnsship_tlm_page* pages_host, uint8_t* bits_host, int32_t* counts_host, uint8_t* faults_host);
+/* The same over the records the tracker's last run left on the device (gnsship_trk_records_device), in place, ordered
+ * on the context stream; before or after gnsship_trk_collect.  E_STATE if there are none; E_INVAL if the handles are
+ * on different contexts, their max_channels differ or the run had more rounds than max_rounds. */
+int gnsship_tlm_run_trk(gnsship_tlm* t, gnsship_trk* trk, gnsship_tlm_page* pages_host, uint8_t* bits_host, int32_t* counts_host,
+    uint8_t* faults_host);
+/* The handle's output buffers (any pointer may be NULL) and pages_per_run. */
+int gnsship_tlm_outputs_device(gnsship_tlm* t, gnsship_tlm_page** pages, uint8_t** bits, int32_t** counts, uint8_t** faults,
+    int32_t* pages_per_run);
+/* The block's reset() (:792-820): d_flag_frame_sync false, d_stat 0, d_last_valid_preamble = d_symbol_counter, the
+ * fault flag cleared.  History, counters, 180° flag, the stored even part, flag_CRC_test and the Viterbi metrics stay. */
+int gnsship_tlm_reset_channel(gnsship_tlm* t, int32_t channel);
+/* set_satellite() (:771-789): d_last_valid_preamble = d_symbol_counter, the fault flag cleared. */
+int gnsship_tlm_set_satellite(gnsship_tlm* t, int32_t channel);
+/* A new block object on this channel. */
+int gnsship_tlm_new_channel(gnsship_tlm* t, int32_t channel);
+/* The channel's members after everything run so far (waits for the context stream). */
+int gnsship_tlm_state_get(gnsship_tlm* t, int32_t channel, gnsship_tlm_state* st);
+int gnsship_tlm_destroy(gnsship_tlm* t);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Multi-GPU fan-out: one process per GPU, one RCCL communicator per context.  */

@@ -1545,6 +1545,8 @@ public:
         return st;
     }
     const char* last_error() const { return gnsship_last_error(dev_->ctx()); }
+    gnsship_trk* handle() const { return h_; }  // for Galileo_Telemetry_Decoder_Hip::work_trk
+    int channels() const { return channels_; }
 
 private:
     static int next_engine_id()
@@ -1557,6 +1559,114 @@ private:
     int channels_ = 0;
     int code_base_ = 0;
     bool glonass_ = false;  // the GLONASS block: its dump file has the 88-byte record
+};
+
+// The frame types of galileo_telemetry_decoder_gs (:167-213) as gnsship_tlm_conf: max_rounds is the most symbols per
+// channel one work_* call may carry.
+inline gnsship_tlm_conf galileo_tlm_conf(int32_t frame_type, int32_t max_rounds, int mode)
+{
+    return gnsship_tlm_conf{frame_type, mode, max_rounds, 0};
+}
+inline gnsship_tlm_conf galileo_inav_tlm_conf(int32_t max_rounds, int mode = GNSSHIP_VIT_MODE_REFERENCE)
+{
+    return galileo_tlm_conf(GNSSHIP_TLM_INAV, max_rounds, mode);
+}
+inline gnsship_tlm_conf galileo_fnav_tlm_conf(int32_t max_rounds, int mode = GNSSHIP_VIT_MODE_REFERENCE)
+{
+    return galileo_tlm_conf(GNSSHIP_TLM_FNAV, max_rounds, mode);
+}
+inline gnsship_tlm_conf galileo_cnav_tlm_conf(int32_t max_rounds, int mode = GNSSHIP_VIT_MODE_REFERENCE)
+{
+    return galileo_tlm_conf(GNSSHIP_TLM_CNAV, max_rounds, mode);
+}
+
+// The frame handling of galileo_telemetry_decoder_gs::general_work (:872-1094) for many channels at once, one block
+// object per channel (include/gnsship.h, gnsship_tlm_*): symbols or tracking records in, CRC-checked page parts and
+// check_tlm_separation faults out.  After a work_* call, pages() / bits() / counts() / faults() hold that call's outputs.
+class Galileo_Telemetry_Decoder_Hip {
+public:
+    Galileo_Telemetry_Decoder_Hip(const gnsship_tlm_conf& c, int32_t max_channels, int device = 0)
+        : dev_(Device::get(device)), conf_(c), channels_(max_channels)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        if (gnsship_tlm_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
+            throw std::invalid_argument(std::string("gnsship_tlm_create: ") + gnsship_last_error(dev_->ctx()));
+        gnsship_tlm_outputs_device(h_, nullptr, nullptr, nullptr, nullptr, &pages_per_run_);
+        data_length_ = c.frame_type == GNSSHIP_TLM_INAV ? 114 : c.frame_type == GNSSHIP_TLM_FNAV ? 238 : 486;
+        const size_t slots = static_cast<size_t>(max_channels) * pages_per_run_;
+        pages_.resize(slots);
+        bits_.resize(slots * data_length_);
+        counts_.resize(static_cast<size_t>(max_channels));
+        faults_.resize(static_cast<size_t>(max_channels));
+    }
+    ~Galileo_Telemetry_Decoder_Hip()
+    {
+        if (h_) gnsship_tlm_destroy(h_);
+    }
+    Galileo_Telemetry_Decoder_Hip(const Galileo_Telemetry_Decoder_Hip&) = delete;
+    Galileo_Telemetry_Decoder_Hip& operator=(const Galileo_Telemetry_Decoder_Hip&) = delete;
+    int32_t data_length() const { return data_length_; }
+    int32_t pages_per_run() const { return pages_per_run_; }
+    // the block's set_satellite() (:771-789) and reset() (:792-820) on one channel; new_channel: a new block object
+    bool set_satellite(int32_t channel)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_tlm_set_satellite(h_, channel) == GNSSHIP_OK;
+    }
+    bool reset(int32_t channel)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_tlm_reset_channel(h_, channel) == GNSSHIP_OK;
+    }
+    bool new_channel(int32_t channel)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_tlm_new_channel(h_, channel) == GNSSHIP_OK;
+    }
+    // symbols[r · max_channels + c], r < n_rounds; valid: the same shape, or null for all valid
+    bool work_symbols(const float* symbols, const uint8_t* valid, int32_t n_rounds, bool on_device = false)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_tlm_run_symbols(h_, symbols, valid, on_device ? 1 : 0, n_rounds, pages_.data(), bits_.data(), counts_.data(), faults_.data()) ==
+               GNSSHIP_OK;
+    }
+    // tracking records of that shape: an entry is a symbol when flags & 1, the symbol is (float)prompt_i
+    bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_tlm_run_records(h_, records, on_device ? 1 : 0, n_rounds, pages_.data(), bits_.data(), counts_.data(), faults_.data()) ==
+               GNSSHIP_OK;
+    }
+    // the records the tracker's last work() left on the device, in place
+    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_tlm_run_trk(h_, trk.handle(), pages_.data(), bits_.data(), counts_.data(), faults_.data()) == GNSSHIP_OK;
+    }
+    // the last work_* call's outputs: part k < counts()[c] of channel c is pages()[c · pages_per_run() + k], its bits
+    // (bytes of 0 / 1) start at bits()[(c · pages_per_run() + k) · data_length()]
+    const std::vector<gnsship_tlm_page>& pages() const { return pages_; }
+    const std::vector<uint8_t>& bits() const { return bits_; }
+    const std::vector<int32_t>& counts() const { return counts_; }
+    const std::vector<uint8_t>& faults() const { return faults_; }
+    gnsship_tlm_state state(int32_t channel) const
+    {
+        gnsship_tlm_state st{};
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        gnsship_tlm_state_get(h_, channel, &st);
+        return st;
+    }
+    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
+
+private:
+    std::shared_ptr<Device> dev_;
+    gnsship_tlm_conf conf_;
+    gnsship_tlm* h_ = nullptr;
+    int32_t channels_ = 0, pages_per_run_ = 0, data_length_ = 0;
+    std::vector<gnsship_tlm_page> pages_;
+    std::vector<uint8_t> bits_;
+    std::vector<int32_t> counts_;
+    std::vector<uint8_t> faults_;
 };
 
 }  // namespace gnsship

@@ -127,6 +127,12 @@ struct Receiver_Conf {
     Pulse_Blanking_Filter_Conf pulse_blanking;
     Notch_Filter_Conf notch;
     Notch_Filter_Lite_Conf notch_lite;
+    // Optional telemetry framing on the device (galileo_telemetry_decoder_gs up to the CRC; Galileo_Telemetry_Decoder_Hip),
+    // Galileo channels only: "5X" decodes F/NAV pages, "7X" I/NAV page parts.  Each tracking block's records go through
+    // the decoder where tracking left them on the device; a channel whose check_tlm_separation fires gets the fault message
+    // of msg_handler_telemetry_to_trk.  Off (the default): exactly the receiver above, every output byte for byte.
+    bool telemetry{false};
+    int telemetry_mode{GNSSHIP_VIT_MODE_REFERENCE};  // GNSSHIP_VIT_MODE_*
 };
 
 // One control event, in stream order.
@@ -143,6 +149,13 @@ struct Receiver_Event {
 struct Receiver_Record {
     uint32_t prn;
     gnsship_trk_epoch e;
+};
+
+// One decoded page part of a channel with the satellite it was tracking.
+struct Receiver_Page {
+    uint32_t prn;
+    gnsship_tlm_page page;
+    std::vector<uint8_t> bits;  // bytes of 0 / 1: 114 (I/NAV part) or 238 (F/NAV page)
 };
 
 class Gnss_Receiver_Hip {
@@ -177,6 +190,12 @@ public:
         block_ = conf_.block_samples > 0 ? conf_.block_samples : static_cast<int64_t>(conf_.trk.fs_in / 10.0);
         tail_ = 2 * vl_;
         trk_ = std::make_unique<Dll_Pll_Veml_Tracking_Hip>(conf_.trk, n_, conf_.device);
+        if (conf_.telemetry) {
+            if (!e5a_ && !e5b_) throw std::invalid_argument("Gnss_Receiver_Hip: telemetry decodes Galileo channels (signal 5X or 7X)");
+            const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
+            tlm_ = std::make_unique<Galileo_Telemetry_Decoder_Hip>(
+                e5a_ ? galileo_fnav_tlm_conf(max_ep, conf_.telemetry_mode) : galileo_inav_tlm_conf(max_ep, conf_.telemetry_mode), n_, conf_.device);
+        }
         if (conf_.use_conditioner) {
             const double fs_out = conf_.input_filter.sampling_frequency / std::max(1, conf_.input_filter.decimation_factor);
             if (fs_out != conf_.trk.fs_in || static_cast<int64_t>(fs_out) != conf_.acq.fs_in)
@@ -278,6 +297,8 @@ public:
     const std::vector<Receiver_Event>& events() const { return events_; }
     // Every tracking epoch record in stream order per channel (the Gnss_Synchro stream).
     const std::vector<std::vector<Receiver_Record>>& records() const { return recs_; }
+    // With conf.telemetry: every decoded page part in the order the blocks emitted them (channel by channel within a block).
+    const std::vector<Receiver_Page>& pages() const { return pages_; }
     uint64_t position() const { return pos_; }
     unsigned channel_fsm_state(int c) const { return fsm_[static_cast<size_t>(c)].state(); }
     uint32_t channel_prn(int c) const { return prn_[static_cast<size_t>(c)]; }
@@ -349,6 +370,7 @@ private:
     void set_signal(int c, uint32_t prn)
     {
         prn_[static_cast<size_t>(c)] = prn;
+        if (tlm_ && !tlm_->set_satellite(c)) error_ = true;  // nav_->set_satellite (channel.cc:237)
         if (l5_) {  // GpsL5iPcpsAcquisition::set_local_code: the search runs on L5I
             const std::vector<std::complex<float>> code = gps_l5i_acquisition_code(prn, conf_.acq);
             if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
@@ -531,6 +553,18 @@ private:
         const int rounds = trk_->work_dump(reinterpret_cast<const std::complex<float>*>(dev_buf_), win_first_, wn, max_ep, rec_buf_.data(),
             dump ? dump_buf_.data() : nullptr, true);
         if (rounds < 0) return false;
+        if (tlm_) {  // the records where tracking left them; a fault goes back to the channel's tracking (telemetry_to_trk)
+            if (!tlm_->work_trk(*trk_)) return false;
+            const size_t LL = static_cast<size_t>(tlm_->data_length()), ppr = static_cast<size_t>(tlm_->pages_per_run());
+            for (int c = 0; c < n_; c++) {
+                for (int k = 0; k < tlm_->counts()[static_cast<size_t>(c)]; k++) {
+                    const size_t slot = static_cast<size_t>(c) * ppr + static_cast<size_t>(k);
+                    const uint8_t* b = tlm_->bits().data() + slot * LL;
+                    pages_.push_back({prn_[static_cast<size_t>(c)], tlm_->pages()[slot], std::vector<uint8_t>(b, b + LL)});
+                }
+                if (tlm_->faults()[static_cast<size_t>(c)] && !trk_->msg_handler_telemetry_to_trk(c, 1)) return false;
+            }
+        }
         recs_.resize(static_cast<size_t>(n_));
         for (int c = 0; c < n_; c++) {
             bool lost = false;
@@ -577,6 +611,8 @@ private:
     int n_ = 1, max_acq_ = 1, acq_count_ = 0;
     int64_t vl_ = 0, block_ = 0, tail_ = 0;
     std::unique_ptr<Dll_Pll_Veml_Tracking_Hip> trk_;
+    std::unique_ptr<Galileo_Telemetry_Decoder_Hip> tlm_;  // the optional telemetry framing
+    std::vector<Receiver_Page> pages_;
     std::unique_ptr<Freq_Xlating_Fir_Filter_Hip> cond_;  // the optional conditioner stage
     int64_t cond_block_ = 0;                             // its run size, in input samples
     std::vector<std::complex<float>> cond_host_;

@@ -14,9 +14,15 @@
 //              [--pll-bw 40] [--dll-bw 4] [--order 3] [--pull-in-time-s 10] [--rotator auto|generic|avx]
 //              [--max-carrier-lock-fail 5000] [--max-code-lock-fail 50] [--cn0-min 25]
 //              [--block-ms 100] [--acq-piece 8192] [--dump PREFIX] [--events CSV] [--records BIN]
+//              [--telemetry] [--telemetry-mode reference|full]
 //              [--if-hz 0] [--decimation 1] [--filter-bw 0] [--filter-tw 0]
 //              [--input-filter pulse-blanking|notch|notch-lite] [--input-filter-pfa P] [--segment-length 32]
 //              [--segments-est 12500] [--segments-reset 5000000] [--p-c-factor 0.9] [--coeff-rate R]
+//
+// --telemetry (with --signal 5X or 7X) sends each tracking block's records through the device telemetry framing
+// (F/NAV pages on 5X, I/NAV page parts on 7X) and prints, ahead of the summary, one line per page part: channel, PRN,
+// symbol counter, even / odd, the CRC verdict as the block computes it, the bits as hex.  A telemetry fault goes back to
+// the channel's tracking.  --telemetry-mode picks the Viterbi metric (reference: as the block; full: both symbols).
 //
 // --input-filter puts the interference mitigation (InputFilter.implementation = Pulse_Blanking_Filter, Notch_Filter or
 // Notch_Filter_Lite; pfa, length, segments_est, segments_reset, p_c_factor, coeff_rate: 0 = the adapter's defaults)
@@ -143,6 +149,12 @@ int main(int argc, char** argv)
         else if (a == "--dump") dump = val();
         else if (a == "--events") events_csv = val();
         else if (a == "--records") records_bin = val();
+        else if (a == "--telemetry") rc.telemetry = true;
+        else if (a == "--telemetry-mode") {
+            const std::string m = val();
+            if (m != "reference" && m != "full") usage("--telemetry-mode must be reference or full");
+            rc.telemetry_mode = m == "full" ? GNSSHIP_VIT_MODE_FULL : GNSSHIP_VIT_MODE_REFERENCE;
+        }
         else usage(("unknown option " + a).c_str());
     }
     if (file.empty()) usage("--file is required");
@@ -316,6 +328,17 @@ int main(int argc, char** argv)
                     }
             std::fclose(r);
         }
+    }
+    // --telemetry: one line per page part — channel, PRN, symbol counter, even / odd / page, CRC verdict, the bits as hex
+    for (const auto& pg : rx.pages()) {
+        std::string hex;
+        for (size_t i = 0; i < pg.bits.size(); i += 4) {
+            int v = 0;
+            for (size_t j = 0; j < 4; j++) v = (v << 1) | (i + j < pg.bits.size() ? pg.bits[i + j] : 0);
+            hex += "0123456789abcdef"[v];
+        }
+        std::printf("page channel %d prn %u symbol %llu %s crc %s %s\n", pg.page.channel, pg.prn, static_cast<unsigned long long>(pg.page.symbol_counter),
+            signal == "7X" ? ((pg.page.flags & 8) ? "odd" : "even") : "page", (pg.page.flags & 1) ? "ok" : "fail", hex.c_str());
     }
     int n_pos = 0, n_neg = 0, n_lost = 0;
     for (const auto& ev : rx.events()) {
