@@ -110,6 +110,12 @@ $(TLM_MIRROR_TEST): tests/cpp/tlm_mirror_test.cpp include/gnsship_cpp.hpp includ
 	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/tlm_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
 all: $(TLM_MIRROR_TEST)
 
+# The GPS L1 C/A telemetry decoder mirror (tests/test_cpp_mirror_lnav.py)
+LNAV_MIRROR_TEST := tests/cpp/lnav_mirror_test
+$(LNAV_MIRROR_TEST): tests/cpp/lnav_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
+	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/lnav_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
+all: $(LNAV_MIRROR_TEST)
+
 # Profiling variant (workgroup phase timestamps in corr_batch_kernel; scripts/corr_wg_profile.py)
 PROF_LIB := scripts/libgnsship_prof.so
 PROF_OBJS := $(patsubst $(CSRC)/%.hip,$(PROF_OBJDIR)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(PROF_OBJDIR)/%.cpp.o,$(CPP_SRCS))

@@ -215,6 +215,41 @@ TLM_PAGE_DTYPE = np.dtype([("symbol_counter", "<u8"), ("sample_counter", "<u8"),
                            ("crc_error_counter", "<i4"), ("pad", "<i4")])
 assert TLM_PAGE_DTYPE.itemsize == 32
 
+# gnsship_lnav_subframe.flags
+LNAV_OK, LNAV_PARITY_OK, LNAV_PLL_180, LNAV_STATE1, LNAV_FRAME_SYNC, LNAV_SYNC_LOST = 1, 2, 4, 8, 16, 32
+# sflags of an entry (GNSSHIP_LNAV_S_*)
+LNAV_S_OUTPUT, LNAV_S_PLL_180, LNAV_S_SUBFRAME = 1, 2, 4
+
+
+def lnav_subframes_per_run(max_rounds: int) -> int:
+    """GNSSHIP_LNAV_SUBFRAMES_PER_RUN."""
+    return max_rounds // 300 + max_rounds // 900 + 2
+
+
+class LnavConf(ctypes.Structure):
+    """gnsship_lnav_conf — the most entries per channel one run may carry."""
+    _fields_ = [("max_rounds", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class LnavState(ctypes.Structure):
+    """gnsship_lnav_state — the members of one channel's gps_l1_ca_telemetry_decoder_gs object."""
+    _fields_ = [("symbol_counter", ctypes.c_uint64), ("preamble_index", ctypes.c_uint64), ("last_valid_preamble", ctypes.c_uint64),
+                ("subframes_tried", ctypes.c_uint64), ("prev_word", ctypes.c_uint32), ("tow_at_preamble_ms", ctypes.c_uint32),
+                ("tow_at_current_symbol_ms", ctypes.c_uint32), ("nav_tow_s", ctypes.c_uint32), ("stat", ctypes.c_int32),
+                ("crc_error_counter", ctypes.c_int32), ("history_size", ctypes.c_int32), ("pll_180", ctypes.c_uint8),
+                ("frame_sync", ctypes.c_uint8), ("tow_set", ctypes.c_uint8), ("sent_tlm_failed", ctypes.c_uint8)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+assert ctypes.sizeof(LnavState) == 64
+
+LNAV_SUBFRAME_DTYPE = np.dtype([("symbol_counter", "<u8"), ("sample_counter", "<u8"), ("words", "<u4", (10,)), ("channel", "<i4"),
+                                ("subframe_id", "<i4"), ("tow_s", "<u4"), ("crc_error_counter", "<i4"), ("parity_fail_mask", "<u4"),
+                                ("flags", "<i4")])
+assert LNAV_SUBFRAME_DTYPE.itemsize == 80
+
 SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5, SYS_BDS_B3I, SYS_GPS_L2C = 0, 1, 2, 3, 4, 5
 SYS_GAL_E5A, SYS_GAL_E5B = 6, 7
 SYS_GLO_L1CA, SYS_GLO_L2CA = 8, 9  # glonass_l1_ca / glonass_l2_ca_dll_pll_tracking_cc (include/gnsship.h)
@@ -452,6 +487,16 @@ _SIGNATURES = {
     "gnsship_tlm_new_channel": ([_vp, ctypes.c_int32], _i),
     "gnsship_tlm_state_get": ([_vp, ctypes.c_int32, ctypes.POINTER(TlmState)], _i),
     "gnsship_tlm_destroy": ([_vp], _i),
+    "gnsship_lnav_create": ([_vp, ctypes.POINTER(LnavConf), ctypes.c_int32, _vpp], _i),
+    "gnsship_lnav_run_symbols": ([_vp, _vp, _vp, _vp, _i, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp], _i),
+    "gnsship_lnav_run_records": ([_vp, _vp, _i, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp], _i),
+    "gnsship_lnav_run_trk": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int32)], _i),
+    "gnsship_lnav_outputs_device": ([_vp, _vpp, _vpp, _vpp, _vpp, _vpp, ctypes.POINTER(ctypes.c_int32)], _i),
+    "gnsship_lnav_reset_channel": ([_vp, ctypes.c_int32], _i),
+    "gnsship_lnav_set_satellite": ([_vp, ctypes.c_int32], _i),
+    "gnsship_lnav_new_channel": ([_vp, ctypes.c_int32], _i),
+    "gnsship_lnav_state_get": ([_vp, ctypes.c_int32, ctypes.POINTER(LnavState)], _i),
+    "gnsship_lnav_destroy": ([_vp], _i),
     "gnsship_trk_set_trace": ([_vp, _i], _i),
     "gnsship_trk_trace_records": ([_vp, _vp, _i], _i),
     "gnsship_trk_channel_state": ([_vp, _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_uint64)], _i),

@@ -905,7 +905,7 @@ int gnsship_trk_destroy(gnsship_trk* t);
  * A page part is emitted required + 1 + 2*period symbols after its preamble's first symbol at the earliest: the
  * correlation looks at the oldest end of a full history.
  * Not here: TOW and everything below :1096, page_jk_decoder / ephemeris fields, Reed-Solomon, HAS header parsing and the
- * dummy-page test, time tags, the nav-data monitor, the CRC statistics file, the .dat dump, other systems' telemetry.
+ * dummy-page test, time tags, the nav-data monitor, the CRC statistics file, the .dat dump, other systems' telemetry (GPS L1 C/A LNAV: gnsship_lnav_* below).
  * Symbols are finite by contract; with NaN / Inf the decoded bits are unspecified (nothing is read or written out of
  * bounds: every index comes from lane numbers, sizes and ballot bits). */
 #define GNSSHIP_TLM_INAV 1
@@ -971,6 +971,122 @@ int gnsship_tlm_new_channel(gnsship_tlm* t, int32_t channel);
 /* The channel's members after everything run so far (waits for the context stream). */
 int gnsship_tlm_state_get(gnsship_tlm* t, int32_t channel, gnsship_tlm_state* st);
 int gnsship_tlm_destroy(gnsship_tlm* t);
+
+/* ---------------------------------------------------------------------------------------------
+ * GPS L1 C/A telemetry on the device: gps_l1_ca_telemetry_decoder_gs (gps_l1_ca_telemetry_decoder_gs.cc) up to the
+ * time of week, one block object per channel, one wavefront per channel, no float arithmetic.  Per symbol, in the
+ * block's order (general_work, :564-707):
+ *   seeding     an empty history (a new object, or after reset) first receives the 8 preamble values 10001011 ('1' -> +1,
+ *               '0' -> -1), negated when the incoming symbol carries the 180° flag, and the counter grows by 8 (:573-590).
+ *   push        (float)Prompt_I into a history of capacity 300, counter++, d_flag_preamble = false.
+ *   separation  check_tlm_separation (:448-460) fires once, until reset, when counter - last_valid_preamble > 6000.
+ *   state 0     on a full history the 8 oldest entries are correlated with the preamble (an entry is negative only when
+ *               `< 0.0`); |corr| >= 8 is a hit: preamble_index = counter, the 180° flag becomes corr < 0 and stays so
+ *               even if the decode fails, d_prev_GPS_frame_4bytes = 0, decode_subframe.  On success the error counter is
+ *               0, last_valid_preamble = counter, frame sync, state 1.  Hit or not, state 0 ends with flag_TOW_set false.
+ *   state 1     when counter >= preamble_index + 300: preamble_index = counter and decode under the stored 180° flag; the
+ *               previous word is NOT cleared, it carries over from the last decode, failed or not.  A failure counts; more
+ *               than 2 in a row: frame sync false, state 0, both TOW members 0, the error counter 0, flag_TOW_set false.
+ *   decode      (:261-433) over the 300 entries, oldest first: a bit is 1 when the symbol is > 0 (inverted: < 0), so a
+ *               zero, a -0 or a NaN is a 0 bit under both polarities and counts as positive in the correlation — exactly,
+ *               this is part of the contract.  Every 30 bits: bits 30 / 31 of the word are bits 0 / 1 of the previous word
+ *               as stored; with bit 30 set the word is XORed with 0x3FFFFFC0; the parity check of :191-214; the word
+ *               becomes the previous word.  Any failing word fails the subframe but all ten are processed.  After ten
+ *               good parities the subframe ID is (word2 >> 8) & 7; for 1..5 the navigation object's TOW becomes
+ *               6 * ((word2 >> 13) & 0x1FFFF) (gps_navigation_message.cc:98-273) and the decode returns true; any other
+ *               ID leaves the TOW alone and the decode returns false.
+ *   stamp       (:605-629) a valid subframe with a non-zero navigation TOW sets both TOW members to TOW * 1000 and
+ *               flag_TOW_set; with a zero TOW nothing happens, not even the increment (a stale value may be output);
+ *               any other symbol adds 20 ms if flag_TOW_set.  The block outputs the symbol only when flag_TOW_set.
+ * Not here: ephemeris, iono, UTC and almanac fields and their messages, hybrid mode, the nav-data monitor, the CRC
+ * statistics file, dumps, time tags, and the pi added to the carrier phase (the 180° flag is in the output instead). */
+#define GNSSHIP_LNAV_MAX_CHANNELS (1 << 20)
+#define GNSSHIP_LNAV_MAX_ROUNDS (1 << 20)
+/* The most records one run of max_rounds symbols can emit.  Every record sets preamble_index, so the next state-1 decode
+ * is 300 symbols later: consecutive records are >= 300 symbols apart, except a state-0 success, which may follow a loss
+ * of sync by one symbol.  A loss needs three consecutive state-1 failures after the last success (the first loss of a
+ * run may find the error counter at 2 already), so losses are >= 901 symbols apart: with L losses in n symbols,
+ * n >= 1 + 300 (R - 1 - L) + L and L <= (n - 1) / 901 + 1, hence R <= n / 300 + n / 900 + 2.  (n / 300 + 2 holds for
+ * n < 900 only: 1, 2, 302, 602, 902, 903 are six records in 903 symbols.) */
+#define GNSSHIP_LNAV_SUBFRAMES_PER_RUN(max_rounds) ((max_rounds) / 300 + (max_rounds) / 900 + 2)
+typedef struct gnsship_lnav gnsship_lnav;
+typedef struct gnsship_lnav_conf {
+    int32_t max_rounds;      /* most entries per channel in one run, >= 1 */
+    int32_t reserved;        /* 0 */
+} gnsship_lnav_conf;
+typedef struct gnsship_lnav_subframe { /* one decode_subframe call that was emitted, 80 bytes */
+    uint64_t symbol_counter;        /* d_sample_counter at the subframe's last symbol */
+    uint64_t sample_counter;        /* the completing epoch's record.sample_counter; 0 for run_symbols */
+    uint32_t words[10];             /* as the block stores them: data bits un-inverted, bits 30 / 31 = D30* / D29* */
+    int32_t channel;
+    int32_t subframe_id;            /* (words[1] >> 8) & 7, whatever the parities */
+    uint32_t tow_s;                 /* the navigation object's TOW after this decode */
+    int32_t crc_error_counter;      /* after this decode */
+    uint32_t parity_fail_mask;      /* bit i: word i failed */
+    int32_t flags;                  /* 1 decode_subframe returned true, 2 all ten parities passed, 4 PLL 180°,
+                                       8 decoded in state 1, 16 frame sync after it, 32 sync lost here */
+} gnsship_lnav_subframe;
+#ifdef __cplusplus
+static_assert(sizeof(gnsship_lnav_subframe) == 80, "gnsship_lnav_subframe");
+#else
+_Static_assert(sizeof(gnsship_lnav_subframe) == 80, "gnsship_lnav_subframe");
+#endif
+typedef struct gnsship_lnav_state { /* the block's members, for tests and diagnosis, 64 bytes */
+    uint64_t symbol_counter, preamble_index, last_valid_preamble;
+    uint64_t subframes_tried;       /* a diagnostic: every decode_subframe call, failed state-0 attempts included */
+    uint32_t prev_word;             /* d_prev_GPS_frame_4bytes */
+    uint32_t tow_at_preamble_ms, tow_at_current_symbol_ms;
+    uint32_t nav_tow_s;             /* d_nav.get_TOW() */
+    int32_t stat, crc_error_counter, history_size;
+    uint8_t pll_180, frame_sync, tow_set, sent_tlm_failed;
+} gnsship_lnav_state;
+/* sflags of an entry */
+#define GNSSHIP_LNAV_S_OUTPUT 1     /* the block output this symbol (flag_TOW_set) */
+#define GNSSHIP_LNAV_S_PLL_180 2    /* d_flag_PLL_180_deg_phase_locked after this symbol */
+#define GNSSHIP_LNAV_S_SUBFRAME 4   /* this symbol completed a valid subframe (d_flag_preamble) */
+/* Channels 0..max_channels-1 (1..GNSSHIP_LNAV_MAX_CHANNELS), each a new block object.  Device memory per channel: 144
+ * bytes of members (64 and the history as two 300-bit strings: was it < 0, was it > 0), subframes_per_run =
+ * GNSSHIP_LNAV_SUBFRAMES_PER_RUN(max_rounds) slots of 80 bytes, and 5 bytes per entry of a run (max_rounds of them). */
+int gnsship_lnav_create(gnsship_ctx* ctx, const gnsship_lnav_conf* conf, int32_t max_channels, gnsship_lnav** out);
+/* symbols[r*max_channels + c], r < n_rounds (0..max_rounds), float on the host or (on_device) on the device; valid and
+ * flags180: uint8 of the same shape and place, or NULL for all valid / all false.  flags180 is read only where the block
+ * seeds.  Channel c consumes its valid entries in order of r.  Outputs, in the handle's own device buffers
+ * (gnsship_lnav_outputs_device) and copied to whichever host pointers are given:
+ *   subframes[c][k], k < counts[c]   one record per successful decode and per failed state-1 decode, in order (failed
+ *                                    state-0 attempts, one for about every 126 symbols of noise, are only counted in
+ *                                    subframes_tried); slots beyond counts[c] are unspecified
+ *   counts int32[c], faults uint8[c] faults: 1 where check_tlm_separation fired in this run
+ *   tow_ms uint32[r*max_channels+c], sflags uint8[...]  r < n_rounds: the block's output stream — d_TOW_at_current_symbol_ms
+ *                                    after the symbol and GNSSHIP_LNAV_S_*; both 0 for entries that are not symbols
+ * With no host pointer the call is asynchronous on the context stream (host inputs then stay the caller's until the
+ * stream has passed the run). */
+int gnsship_lnav_run_symbols(gnsship_lnav* t, const float* symbols, const uint8_t* valid, const uint8_t* flags180, int on_device,
+    int32_t n_rounds, gnsship_lnav_subframe* subframes_host, int32_t* counts_host, uint8_t* faults_host, uint32_t* tow_ms_host,
+    uint8_t* sflags_host);
+/* The same over tracking records of that shape: an entry is a symbol when flags & 1, the symbol is (float)prompt_i, the
+ * 180° input is flags & 4, the subframe's sample_counter the completing record's. */
+int gnsship_lnav_run_records(gnsship_lnav* t, const gnsship_trk_epoch* records, int on_device, int32_t n_rounds,
+    gnsship_lnav_subframe* subframes_host, int32_t* counts_host, uint8_t* faults_host, uint32_t* tow_ms_host, uint8_t* sflags_host);
+/* The same over the records the tracker's last run left on the device (gnsship_trk_records_device), in place, ordered
+ * on the context stream; before or after gnsship_trk_collect.  n_rounds_out (may be NULL): the rounds of that run, the
+ * first dimension of tow_ms / sflags.  E_STATE if there are no records; E_INVAL if the handles are on different
+ * contexts, their max_channels differ or the run had more rounds than max_rounds. */
+int gnsship_lnav_run_trk(gnsship_lnav* t, gnsship_trk* trk, gnsship_lnav_subframe* subframes_host, int32_t* counts_host,
+    uint8_t* faults_host, uint32_t* tow_ms_host, uint8_t* sflags_host, int32_t* n_rounds_out);
+/* The handle's output buffers (any pointer may be NULL) and subframes_per_run. */
+int gnsship_lnav_outputs_device(gnsship_lnav* t, gnsship_lnav_subframe** subframes, int32_t** counts, uint8_t** faults,
+    uint32_t** tow_ms, uint8_t** sflags, int32_t* subframes_per_run);
+/* The block's reset() (:436-445): d_last_valid_preamble = d_sample_counter, the fault flag cleared, flag_TOW_set false,
+ * the history cleared (the next symbol seeds again), d_stat 0.  The error counter, d_flag_frame_sync, the 180° flag, the
+ * previous word, both TOW members and the navigation TOW stay. */
+int gnsship_lnav_reset_channel(gnsship_lnav* t, int32_t channel);
+/* set_satellite() (:217-224): a new navigation object — its TOW becomes 0, nothing else changes. */
+int gnsship_lnav_set_satellite(gnsship_lnav* t, int32_t channel);
+/* A new block object on this channel. */
+int gnsship_lnav_new_channel(gnsship_lnav* t, int32_t channel);
+/* The channel's members after everything run so far (waits for the context stream). */
+int gnsship_lnav_state_get(gnsship_lnav* t, int32_t channel, gnsship_lnav_state* st);
+int gnsship_lnav_destroy(gnsship_lnav* t);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Multi-GPU fan-out: one process per GPU, one RCCL communicator per context.  */

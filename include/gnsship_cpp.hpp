@@ -1669,6 +1669,108 @@ private:
     std::vector<uint8_t> faults_;
 };
 
+// gps_l1_ca_telemetry_decoder_gs as gnsship_lnav_conf: max_rounds is the most entries per channel one work_* call may carry.
+inline gnsship_lnav_conf gps_l1_ca_tlm_conf(int32_t max_rounds)
+{
+    return gnsship_lnav_conf{max_rounds, 0};
+}
+
+// gps_l1_ca_telemetry_decoder_gs up to the time of week for many channels at once, one block object per channel
+// (include/gnsship.h, gnsship_lnav_*): symbols or tracking records in; subframes, the TOW stamp of every entry and
+// check_tlm_separation faults out.  After a work_* call, subframes() / counts() / faults() / tow_ms() / sflags() hold that
+// call's outputs.
+class Gps_L1_Ca_Telemetry_Decoder_Hip {
+public:
+    Gps_L1_Ca_Telemetry_Decoder_Hip(const gnsship_lnav_conf& c, int32_t max_channels, int device = 0)
+        : dev_(Device::get(device)), conf_(c), channels_(max_channels)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        if (gnsship_lnav_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
+            throw std::invalid_argument(std::string("gnsship_lnav_create: ") + gnsship_last_error(dev_->ctx()));
+        gnsship_lnav_outputs_device(h_, nullptr, nullptr, nullptr, nullptr, nullptr, &subframes_per_run_);
+        const size_t nc = static_cast<size_t>(max_channels);
+        subframes_.resize(nc * subframes_per_run_);
+        counts_.resize(nc);
+        faults_.resize(nc);
+        tow_ms_.resize(nc * c.max_rounds);
+        sflags_.resize(nc * c.max_rounds);
+    }
+    ~Gps_L1_Ca_Telemetry_Decoder_Hip()
+    {
+        if (h_) gnsship_lnav_destroy(h_);
+    }
+    Gps_L1_Ca_Telemetry_Decoder_Hip(const Gps_L1_Ca_Telemetry_Decoder_Hip&) = delete;
+    Gps_L1_Ca_Telemetry_Decoder_Hip& operator=(const Gps_L1_Ca_Telemetry_Decoder_Hip&) = delete;
+    int32_t subframes_per_run() const { return subframes_per_run_; }
+    // the block's set_satellite() (:217-224) and reset() (:436-445) on one channel; new_channel: a new block object
+    bool set_satellite(int32_t channel)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_lnav_set_satellite(h_, channel) == GNSSHIP_OK;
+    }
+    bool reset(int32_t channel)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_lnav_reset_channel(h_, channel) == GNSSHIP_OK;
+    }
+    bool new_channel(int32_t channel)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_lnav_new_channel(h_, channel) == GNSSHIP_OK;
+    }
+    // symbols[r · max_channels + c], r < n_rounds; valid, flags180: the same shape, or null for all valid / all false
+    bool work_symbols(const float* symbols, const uint8_t* valid, const uint8_t* flags180, int32_t n_rounds, bool on_device = false)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = n_rounds;
+        return gnsship_lnav_run_symbols(h_, symbols, valid, flags180, on_device ? 1 : 0, n_rounds, subframes_.data(), counts_.data(), faults_.data(),
+                   tow_ms_.data(), sflags_.data()) == GNSSHIP_OK;
+    }
+    // tracking records of that shape: a symbol when flags & 1, the symbol is (float)prompt_i, the 180° input flags & 4
+    bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = n_rounds;
+        return gnsship_lnav_run_records(h_, records, on_device ? 1 : 0, n_rounds, subframes_.data(), counts_.data(), faults_.data(), tow_ms_.data(),
+                   sflags_.data()) == GNSSHIP_OK;
+    }
+    // the records the tracker's last work() left on the device, in place
+    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = 0;
+        return gnsship_lnav_run_trk(h_, trk.handle(), subframes_.data(), counts_.data(), faults_.data(), tow_ms_.data(), sflags_.data(), &rounds_) ==
+               GNSSHIP_OK;
+    }
+    // the last work_* call's outputs: subframe k < counts()[c] of channel c is subframes()[c · subframes_per_run() + k];
+    // entry (r, c), r < rounds(), is tow_ms()[r · max_channels + c] and sflags()[r · max_channels + c]
+    const std::vector<gnsship_lnav_subframe>& subframes() const { return subframes_; }
+    const std::vector<int32_t>& counts() const { return counts_; }
+    const std::vector<uint8_t>& faults() const { return faults_; }
+    const std::vector<uint32_t>& tow_ms() const { return tow_ms_; }
+    const std::vector<uint8_t>& sflags() const { return sflags_; }
+    int32_t rounds() const { return rounds_; }
+    gnsship_lnav_state state(int32_t channel) const
+    {
+        gnsship_lnav_state st{};
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        gnsship_lnav_state_get(h_, channel, &st);
+        return st;
+    }
+    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
+
+private:
+    std::shared_ptr<Device> dev_;
+    gnsship_lnav_conf conf_;
+    gnsship_lnav* h_ = nullptr;
+    int32_t channels_ = 0, subframes_per_run_ = 0, rounds_ = 0;
+    std::vector<gnsship_lnav_subframe> subframes_;
+    std::vector<int32_t> counts_;
+    std::vector<uint8_t> faults_;
+    std::vector<uint32_t> tow_ms_;
+    std::vector<uint8_t> sflags_;
+};
+
 }  // namespace gnsship
 
 #endif  // GNSSHIP_CPP_HPP

@@ -133,6 +133,12 @@ struct Receiver_Conf {
     // of msg_handler_telemetry_to_trk.  Off (the default): exactly the receiver above, every output byte for byte.
     bool telemetry{false};
     int telemetry_mode{GNSSHIP_VIT_MODE_REFERENCE};  // GNSSHIP_VIT_MODE_*
+    // Optional GPS L1 C/A telemetry on the device (gps_l1_ca_telemetry_decoder_gs up to the time of week;
+    // Gps_L1_Ca_Telemetry_Decoder_Hip), 1C channels only.  Each tracking block's records go through the decoder where
+    // tracking left them on the device; a channel that is assigned a satellite gets a new block object; a channel whose
+    // check_tlm_separation fires gets the fault message of msg_handler_telemetry_to_trk.  Off (the default): exactly the
+    // receiver above, every output byte for byte.
+    bool lnav{false};
 };
 
 // One control event, in stream order.
@@ -156,6 +162,12 @@ struct Receiver_Page {
     uint32_t prn;
     gnsship_tlm_page page;
     std::vector<uint8_t> bits;  // bytes of 0 / 1: 114 (I/NAV part) or 238 (F/NAV page)
+};
+
+// One LNAV subframe of a channel with the satellite it was tracking.
+struct Receiver_Subframe {
+    uint32_t prn;
+    gnsship_lnav_subframe subframe;
 };
 
 class Gnss_Receiver_Hip {
@@ -195,6 +207,12 @@ public:
             const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
             tlm_ = std::make_unique<Galileo_Telemetry_Decoder_Hip>(
                 e5a_ ? galileo_fnav_tlm_conf(max_ep, conf_.telemetry_mode) : galileo_inav_tlm_conf(max_ep, conf_.telemetry_mode), n_, conf_.device);
+        }
+        if (conf_.lnav) {
+            if (l5_ || b3_ || l2c_ || e5a_ || e5b_ || glo_ || conf_.trk.system != 'G')
+                throw std::invalid_argument("Gnss_Receiver_Hip: lnav decodes GPS L1 C/A channels (signal 1C)");
+            const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
+            lnav_ = std::make_unique<Gps_L1_Ca_Telemetry_Decoder_Hip>(gps_l1_ca_tlm_conf(max_ep), n_, conf_.device);
         }
         if (conf_.use_conditioner) {
             const double fs_out = conf_.input_filter.sampling_frequency / std::max(1, conf_.input_filter.decimation_factor);
@@ -299,6 +317,8 @@ public:
     const std::vector<std::vector<Receiver_Record>>& records() const { return recs_; }
     // With conf.telemetry: every decoded page part in the order the blocks emitted them (channel by channel within a block).
     const std::vector<Receiver_Page>& pages() const { return pages_; }
+    // With conf.lnav: every emitted subframe record in the order the blocks emitted them (channel by channel within a block).
+    const std::vector<Receiver_Subframe>& subframes() const { return subframes_; }
     uint64_t position() const { return pos_; }
     unsigned channel_fsm_state(int c) const { return fsm_[static_cast<size_t>(c)].state(); }
     uint32_t channel_prn(int c) const { return prn_[static_cast<size_t>(c)]; }
@@ -371,6 +391,7 @@ private:
     {
         prn_[static_cast<size_t>(c)] = prn;
         if (tlm_ && !tlm_->set_satellite(c)) error_ = true;  // nav_->set_satellite (channel.cc:237)
+        if (lnav_ && !lnav_->new_channel(c)) error_ = true;  // the channel starts on its satellite with a new block object
         if (l5_) {  // GpsL5iPcpsAcquisition::set_local_code: the search runs on L5I
             const std::vector<std::complex<float>> code = gps_l5i_acquisition_code(prn, conf_.acq);
             if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
@@ -565,6 +586,15 @@ private:
                 if (tlm_->faults()[static_cast<size_t>(c)] && !trk_->msg_handler_telemetry_to_trk(c, 1)) return false;
             }
         }
+        if (lnav_) {  // likewise for the GPS L1 C/A decoder
+            if (!lnav_->work_trk(*trk_)) return false;
+            const size_t spr = static_cast<size_t>(lnav_->subframes_per_run());
+            for (int c = 0; c < n_; c++) {
+                for (int k = 0; k < lnav_->counts()[static_cast<size_t>(c)]; k++)
+                    subframes_.push_back({prn_[static_cast<size_t>(c)], lnav_->subframes()[static_cast<size_t>(c) * spr + static_cast<size_t>(k)]});
+                if (lnav_->faults()[static_cast<size_t>(c)] && !trk_->msg_handler_telemetry_to_trk(c, 1)) return false;
+            }
+        }
         recs_.resize(static_cast<size_t>(n_));
         for (int c = 0; c < n_; c++) {
             bool lost = false;
@@ -613,6 +643,8 @@ private:
     std::unique_ptr<Dll_Pll_Veml_Tracking_Hip> trk_;
     std::unique_ptr<Galileo_Telemetry_Decoder_Hip> tlm_;  // the optional telemetry framing
     std::vector<Receiver_Page> pages_;
+    std::unique_ptr<Gps_L1_Ca_Telemetry_Decoder_Hip> lnav_;  // the optional GPS L1 C/A telemetry
+    std::vector<Receiver_Subframe> subframes_;
     std::unique_ptr<Freq_Xlating_Fir_Filter_Hip> cond_;  // the optional conditioner stage
     int64_t cond_block_ = 0;                             // its run size, in input samples
     std::vector<std::complex<float>> cond_host_;

@@ -14,7 +14,7 @@
 //              [--pll-bw 40] [--dll-bw 4] [--order 3] [--pull-in-time-s 10] [--rotator auto|generic|avx]
 //              [--max-carrier-lock-fail 5000] [--max-code-lock-fail 50] [--cn0-min 25]
 //              [--block-ms 100] [--acq-piece 8192] [--dump PREFIX] [--events CSV] [--records BIN]
-//              [--telemetry] [--telemetry-mode reference|full]
+//              [--telemetry] [--telemetry-mode reference|full] [--lnav]
 //              [--if-hz 0] [--decimation 1] [--filter-bw 0] [--filter-tw 0]
 //              [--input-filter pulse-blanking|notch|notch-lite] [--input-filter-pfa P] [--segment-length 32]
 //              [--segments-est 12500] [--segments-reset 5000000] [--p-c-factor 0.9] [--coeff-rate R]
@@ -23,6 +23,10 @@
 // (F/NAV pages on 5X, I/NAV page parts on 7X) and prints, ahead of the summary, one line per page part: channel, PRN,
 // symbol counter, even / odd, the CRC verdict as the block computes it, the bits as hex.  A telemetry fault goes back to
 // the channel's tracking.  --telemetry-mode picks the Viterbi metric (reference: as the block; full: both symbols).
+//
+// --lnav (with --signal 1C) sends each tracking block's records through the device GPS L1 C/A telemetry decoder and
+// prints, ahead of the summary, one line per emitted subframe: channel, PRN, symbol counter, subframe ID, TOW in seconds,
+// ok / fail, the ten words as the block stores them in hex.  A telemetry fault goes back to the channel's tracking.
 //
 // --input-filter puts the interference mitigation (InputFilter.implementation = Pulse_Blanking_Filter, Notch_Filter or
 // Notch_Filter_Lite; pfa, length, segments_est, segments_reset, p_c_factor, coeff_rate: 0 = the adapter's defaults)
@@ -150,6 +154,7 @@ int main(int argc, char** argv)
         else if (a == "--events") events_csv = val();
         else if (a == "--records") records_bin = val();
         else if (a == "--telemetry") rc.telemetry = true;
+        else if (a == "--lnav") rc.lnav = true;
         else if (a == "--telemetry-mode") {
             const std::string m = val();
             if (m != "reference" && m != "full") usage("--telemetry-mode must be reference or full");
@@ -189,6 +194,7 @@ int main(int argc, char** argv)
     const int64_t per_byte = sample_bits < 8 ? 8 / sample_bits : 1;  // samples per byte of a packed item
     if (signal != "1C" && signal != "L5" && signal != "2S" && signal != "B3" && signal != "5X" && signal != "7X" && signal != "1G" && signal != "2G")
         usage("--signal must be 1C, L5, 2S, B3, 5X, 7X, 1G or 2G");
+    if (rc.lnav && signal != "1C") usage("--lnav decodes GPS L1 C/A channels (--signal 1C)");
     std::snprintf(rc.trk.signal, sizeof(rc.trk.signal), "%s", signal.c_str());
     if (signal == "B3") rc.trk.system = 'C';  // otherwise 'G'
     if (signal == "5X" || signal == "7X") rc.trk.system = 'E';
@@ -339,6 +345,13 @@ int main(int argc, char** argv)
         }
         std::printf("page channel %d prn %u symbol %llu %s crc %s %s\n", pg.page.channel, pg.prn, static_cast<unsigned long long>(pg.page.symbol_counter),
             signal == "7X" ? ((pg.page.flags & 8) ? "odd" : "even") : "page", (pg.page.flags & 1) ? "ok" : "fail", hex.c_str());
+    }
+    // --lnav: one line per emitted subframe — channel, PRN, symbol counter, ID, TOW, the decode's verdict, the ten words
+    for (const auto& sf : rx.subframes()) {
+        std::printf("subframe channel %d prn %u symbol %llu id %d tow %u %s", sf.subframe.channel, sf.prn,
+            static_cast<unsigned long long>(sf.subframe.symbol_counter), sf.subframe.subframe_id, sf.subframe.tow_s, (sf.subframe.flags & 1) ? "ok" : "fail");
+        for (int w = 0; w < 10; w++) std::printf(" %08x", sf.subframe.words[w]);
+        std::printf("\n");
     }
     int n_pos = 0, n_neg = 0, n_lost = 0;
     for (const auto& ev : rx.events()) {
