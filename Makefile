@@ -114,6 +114,11 @@ all: $(TLM_MIRROR_TEST)
 LNAV_MIRROR_TEST := tests/cpp/lnav_mirror_test
 $(LNAV_MIRROR_TEST): tests/cpp/lnav_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
 	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/lnav_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
+
+# The GPS CNAV telemetry decoder mirror (tests/test_cpp_mirror_cnav.py)
+CNAV_MIRROR_TEST := tests/cpp/cnav_mirror_test
+$(CNAV_MIRROR_TEST): tests/cpp/cnav_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
+	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/cnav_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
 all: $(LNAV_MIRROR_TEST)
 
 # Profiling variant (workgroup phase timestamps in corr_batch_kernel; scripts/corr_wg_profile.py)

@@ -250,6 +250,41 @@ LNAV_SUBFRAME_DTYPE = np.dtype([("symbol_counter", "<u8"), ("sample_counter", "<
                                 ("flags", "<i4")])
 assert LNAV_SUBFRAME_DTYPE.itemsize == 80
 
+# gnsship_cnav_conf.signal
+CNAV_L2C, CNAV_L5 = 0, 1
+# gnsship_cnav_message.flags
+CNAV_CRC_OK, CNAV_INVERTED, CNAV_LOCK = 1, 2, 4
+# sflags of an entry (GNSSHIP_CNAV_S_*)
+CNAV_S_VALID_WORD, CNAV_S_PLL_180, CNAV_S_MESSAGE = 1, 2, 4
+
+
+def cnav_messages_per_run(max_rounds: int) -> int:
+    """GNSSHIP_CNAV_MESSAGES_PER_RUN."""
+    return max_rounds // 300 + 4
+
+
+class CnavConf(ctypes.Structure):
+    """gnsship_cnav_conf — the most entries per channel one run may carry, and the signal (CNAV_L2C / CNAV_L5)."""
+    _fields_ = [("max_rounds", ctypes.c_int32), ("signal", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+CNAV_MESSAGE_DTYPE = np.dtype([("symbol_counter", "<u8"), ("sample_counter", "<u8"), ("channel", "<i4"), ("tow", "<u4"), ("delay", "<u4"),
+                               ("prn", "u1"), ("msg_id", "u1"), ("alert", "u1"), ("part", "u1"), ("raw", "u1", (38,)), ("flags", "u1"),
+                               ("reserved", "u1")])
+assert CNAV_MESSAGE_DTYPE.itemsize == 72
+
+# gnsship_cnav_part / gnsship_cnav_state: every member of one channel's block object, as numpy records so that a state
+# read from one handle can be written to another unchanged
+CNAV_PART_DTYPE = np.dtype([("metrics", "<u4", (2, 64)), ("decisions", "<u4", (64, 2)), ("symbols", "u1", (128,)), ("decoded", "u1", (64,)),
+                            ("n_symbols", "<u4"), ("n_decoded", "<u4"), ("n_crc_fail", "<u4"), ("decisions_index", "<u4"),
+                            ("old_is_metrics2", "u1"), ("preamble_seen", "u1"), ("invert", "u1"), ("message_lock", "u1"), ("crc_ok", "u1"),
+                            ("init", "u1"), ("reserved", "u1", (2,))])
+assert CNAV_PART_DTYPE.itemsize == 1240
+CNAV_STATE_DTYPE = np.dtype([("part", CNAV_PART_DTYPE, (2,)), ("symbol_counter", "<u8"), ("last_valid_preamble", "<u8"), ("tow_s", "<f8"),
+                             ("tow_ms", "<u4"), ("tow_at_preamble", "<u4"), ("pll_180", "u1"), ("valid_word", "u1"), ("sent_tlm_failed", "u1"),
+                             ("reserved", "u1"), ("reserved2", "<u4")])
+assert CNAV_STATE_DTYPE.itemsize == 2520
+
 SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5, SYS_BDS_B3I, SYS_GPS_L2C = 0, 1, 2, 3, 4, 5
 SYS_GAL_E5A, SYS_GAL_E5B = 6, 7
 SYS_GLO_L1CA, SYS_GLO_L2CA = 8, 9  # glonass_l1_ca / glonass_l2_ca_dll_pll_tracking_cc (include/gnsship.h)
@@ -497,6 +532,16 @@ _SIGNATURES = {
     "gnsship_lnav_new_channel": ([_vp, ctypes.c_int32], _i),
     "gnsship_lnav_state_get": ([_vp, ctypes.c_int32, ctypes.POINTER(LnavState)], _i),
     "gnsship_lnav_destroy": ([_vp], _i),
+    "gnsship_cnav_create": ([_vp, ctypes.POINTER(CnavConf), ctypes.c_int32, _vpp], _i),
+    "gnsship_cnav_run_symbols": ([_vp, _vp, _vp, _vp, _i, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp], _i),
+    "gnsship_cnav_run_records": ([_vp, _vp, _i, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp], _i),
+    "gnsship_cnav_run_trk": ([_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int32)], _i),
+    "gnsship_cnav_outputs_device": ([_vp, _vpp, _vpp, _vpp, _vpp, _vpp, ctypes.POINTER(ctypes.c_int32)], _i),
+    "gnsship_cnav_reset_channel": ([_vp, ctypes.c_int32], _i),
+    "gnsship_cnav_new_channel": ([_vp, ctypes.c_int32], _i),
+    "gnsship_cnav_state_get": ([_vp, ctypes.c_int32, _vp], _i),
+    "gnsship_cnav_state_set": ([_vp, ctypes.c_int32, _vp], _i),
+    "gnsship_cnav_destroy": ([_vp], _i),
     "gnsship_trk_set_trace": ([_vp, _i], _i),
     "gnsship_trk_trace_records": ([_vp, _vp, _i], _i),
     "gnsship_trk_channel_state": ([_vp, _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_uint64)], _i),

@@ -905,7 +905,7 @@ int gnsship_trk_destroy(gnsship_trk* t);
  * A page part is emitted required + 1 + 2*period symbols after its preamble's first symbol at the earliest: the
  * correlation looks at the oldest end of a full history.
  * Not here: TOW and everything below :1096, page_jk_decoder / ephemeris fields, Reed-Solomon, HAS header parsing and the
- * dummy-page test, time tags, the nav-data monitor, the CRC statistics file, the .dat dump, other systems' telemetry (GPS L1 C/A LNAV: gnsship_lnav_* below).
+ * dummy-page test, time tags, the nav-data monitor, the CRC statistics file, the .dat dump, other systems' telemetry (GPS L1 C/A LNAV: gnsship_lnav_*, GPS CNAV: gnsship_cnav_*, both below).
  * Symbols are finite by contract; with NaN / Inf the decoded bits are unspecified (nothing is read or written out of
  * bounds: every index comes from lane numbers, sizes and ballot bits). */
 #define GNSSHIP_TLM_INAV 1
@@ -1087,6 +1087,154 @@ int gnsship_lnav_new_channel(gnsship_lnav* t, int32_t channel);
 /* The channel's members after everything run so far (waits for the context stream). */
 int gnsship_lnav_state_get(gnsship_lnav* t, int32_t channel, gnsship_lnav_state* st);
 int gnsship_lnav_destroy(gnsship_lnav* t);
+
+/* ---------------------------------------------------------------------------------------------
+ * GPS CNAV telemetry (L2C and L5) on the device: gps_l2c_telemetry_decoder_gs / gps_l5_telemetry_decoder_gs over
+ * libswiftcnav (telemetry_decoder/libs/libswiftcnav: cnav_msg.c, viterbi27.c, bits.c, edc.c) up to the time of week, one
+ * block object per channel, one wavefront per channel, integer arithmetic only (but for the L2C block's TOW, a double).
+ * The library, restated and not repaired — all of this is part of the contract:
+ *   parts       two K=7 rate-1/2 Viterbi decoders one symbol apart (cnav_msg.c:374-390: cnav_msg_decoder_init feeds
+ *               part 2 one symbol of 0x80).  Each part buffers symbols, waits for 128 of them before its first decode and
+ *               for 64 afterwards (:162-184), updates its decoder over all of them, chains back 64 bits and appends the
+ *               oldest 32 to its 512-bit decode buffer (:194-199).
+ *   update      viterbi27.c:85-189.  The symbol metric is (c0 ^ sym0) + (c1 ^ sym1) over the tables v27_poly_init makes of
+ *               0x4F / 0x6D; the two candidates of a state are formed in uint32 arithmetic, modulo 2^32, the decision is
+ *               (int32)(m0 - m1) > 0; bit j of the step's decision words w[0..1] is state j's.  Normalisation runs only
+ *               when new_metrics[0] > 2^30 — state 0 alone is tested — and subtracts min(2^31, minimum over the states).
+ *               The buffers are swapped at the end of every step.
+ *   chain-back  v27_chainback_likely (:232-249) reads new_metrics, which after the swap holds the metrics of the step
+ *               BEFORE the last; the start state is the first minimum of that stale buffer (ties: the lowest state), the
+ *               walk still starts at the current decision index.  Both metric buffers are state.
+ *   rescan      cnav_rescan_preamble_ (:117-145) looks for 0x8B / 0x74 from bit 1 (never bit 0) to n_decoded - 9; a hit
+ *               sets `invert` and shifts the buffer to it; a miss leaves 7 bits.
+ *   check       with a preamble and >= 300 bits, CRC-24Q over 276 bits against the last 24 (:227-275).  Without lock: a
+ *               match locks, a mismatch drops the preamble and rescans the same buffer (the retry loop).  With lock: a
+ *               mismatch counts, more than 10 in a row drop lock and preamble and rescan.
+ *   dispose     cnav_msg_decode_ (:323-361) runs on every symbol while a part is locked and disposes of 300 bits whether
+ *               the CRC held or not; crc_ok is whatever the last check left.  It returns true, with PRN, ID, TOW, alert,
+ *               the un-inverted 64-byte buffer and delay = (n_decoded - 300 + 32) * 2 + n_symbols, only when crc_ok.
+ *   precedence  (:415-439) part 1 locked: part 2's n_decoded and n_symbols are zeroed on every symbol (its buffers are
+ *               not) and part 1 decodes; else the same with the parts exchanged.
+ * The blocks, per symbol (L2C: gps_l2c_telemetry_decoder_gs.cc:189-344, L5: gps_l5_telemetry_decoder_gs.cc:191-360):
+ *   symbol      (Prompt_I > 0) * 255 for L2C, (Prompt_Q > 0) * 255 for L5: a NaN or a zero of either sign is 0.
+ *   watchdog    counter++, and once until reset() a fault when counter - last_valid_preamble > 3000 (L2C) / 6000 (L5).
+ *               (L2C runs it after the decoder, L5 before; both before a message moves last_valid_preamble.)
+ *   message     the 180° flag becomes part1.invert || part2.invert — including the stale `invert` of the part that is not
+ *               locked.  L2C: last_valid_preamble = counter, the TOW, a double, becomes tow * 6.0 + delay * 0.02 +
+ *               12 * 0.02 in that order, unfused, valid_word true.  L5: the TOW, integer ms, becomes tow * 6000 +
+ *               (delay + 12) * 10; if the previous value is non-zero and differs by more than 10 ms, TOW and valid_word
+ *               become 0; otherwise last_valid_preamble = counter and valid_word true.
+ *   otherwise   L2C: TOW += 0.02, one addition per symbol (never k * 0.02), and valid_word drops on an entry whose
+ *               output-valid flag is false.  L5: only while valid_word: TOW += 10, then the same drop.
+ *   output      L2C: round(TOW * 1000) as uint32, valid_word and the 180° flag on every symbol.  L5: TOW and the 180° flag
+ *               only while valid_word, else 0.
+ *   reset()     L2C (:181-186): last_valid_preamble = counter, the fault flag cleared.  L5 (:181-188): also TOW and
+ *               valid_word 0.  Neither touches the CNAV decoder.
+ * Not here: Gps_CNAV_Navigation_Message::decode_page and the ephemeris, iono and UTC messages, the nav-data monitor, dumps,
+ * the CRC-statistics option (which clears message_lock; it counts as off), and the pi added to the carrier phase (the
+ * 180° flag is in the output instead). */
+#define GNSSHIP_CNAV_MAX_CHANNELS (1 << 20)
+#define GNSSHIP_CNAV_MAX_ROUNDS (1 << 20)
+#define GNSSHIP_CNAV_L2C 0
+#define GNSSHIP_CNAV_L5 1
+/* The most records one run of max_rounds symbols can emit.  Every record disposes of 300 bits of a part's decode buffer.
+ * A part gains 32 bits per decode; its decodes are 64 symbols apart, the first of a run at its first symbol at the
+ * earliest (127 symbols held), so n symbols bring at most n / 64 + 2 decodes; and a part starts a run with at most 480
+ * bits (331 in operation; 480 is what gnsship_cnav_state_set admits).  Both parts: 2 * (480 + 32 * (n / 64 + 2)) =
+ * n + 1088 bits at most, hence R <= n / 300 + 4. */
+#define GNSSHIP_CNAV_MESSAGES_PER_RUN(max_rounds) ((max_rounds) / 300 + 4)
+typedef struct gnsship_cnav gnsship_cnav;
+typedef struct gnsship_cnav_conf {
+    int32_t max_rounds;      /* most entries per channel in one run, >= 1 */
+    int32_t signal;          /* GNSSHIP_CNAV_L2C or GNSSHIP_CNAV_L5 */
+    int32_t reserved;        /* 0 */
+} gnsship_cnav_conf;
+typedef struct gnsship_cnav_message { /* one 300-bit buffer a locked part disposed of, CRC good or not, 72 bytes */
+    uint64_t symbol_counter;        /* d_sample_counter at the completing symbol */
+    uint64_t sample_counter;        /* the completing epoch's record.sample_counter; 0 for run_symbols */
+    int32_t channel;
+    uint32_t tow;                   /* 17 bits, in 6-second units */
+    uint32_t delay;                 /* (n_decoded - 300 + 32) * 2 + n_symbols */
+    uint8_t prn, msg_id, alert;     /* bits 8..13, 14..19 and 37 of the un-inverted message */
+    uint8_t part;                   /* 0: part 1, 1: part 2 */
+    uint8_t raw[38];                /* the first 38 bytes of the un-inverted decode buffer: the 300 bits, MSB first */
+    uint8_t flags;                  /* 1 crc_ok (the library returned true), 2 inverted, 4 message_lock after it */
+    uint8_t reserved;
+} gnsship_cnav_message;
+typedef struct gnsship_cnav_part { /* cnav_v27_part_t with its v27_t, 1240 bytes */
+    uint32_t metrics[2][64];        /* metrics1, metrics2 */
+    uint32_t decisions[64][2];      /* v27_decision_t w[0..1] */
+    uint8_t symbols[128];
+    uint8_t decoded[64];
+    uint32_t n_symbols, n_decoded, n_crc_fail, decisions_index;
+    uint8_t old_is_metrics2;        /* old_metrics points at metrics2 (new_metrics at the other) */
+    uint8_t preamble_seen, invert, message_lock, crc_ok, init;
+    uint8_t reserved[2];
+} gnsship_cnav_part;
+typedef struct gnsship_cnav_state { /* every member of one block object, 2520 bytes */
+    gnsship_cnav_part part[2];
+    uint64_t symbol_counter, last_valid_preamble;
+    double tow_s;                   /* L2C: d_TOW_at_current_symbol */
+    uint32_t tow_ms;                /* L5: d_TOW_at_current_symbol_ms */
+    uint32_t tow_at_preamble;       /* L2C: msg.tow; L5: msg.tow * 6000 */
+    uint8_t pll_180, valid_word, sent_tlm_failed, reserved;
+    uint32_t reserved2;
+} gnsship_cnav_state;
+#ifdef __cplusplus
+static_assert(sizeof(gnsship_cnav_message) == 72, "gnsship_cnav_message");
+static_assert(sizeof(gnsship_cnav_part) == 1240, "gnsship_cnav_part");
+static_assert(sizeof(gnsship_cnav_state) == 2520, "gnsship_cnav_state");
+#else
+_Static_assert(sizeof(gnsship_cnav_message) == 72, "gnsship_cnav_message");
+_Static_assert(sizeof(gnsship_cnav_part) == 1240, "gnsship_cnav_part");
+_Static_assert(sizeof(gnsship_cnav_state) == 2520, "gnsship_cnav_state");
+#endif
+/* sflags of an entry */
+#define GNSSHIP_CNAV_S_VALID_WORD 1 /* d_flag_valid_word after this symbol */
+#define GNSSHIP_CNAV_S_PLL_180 2    /* the 180° flag as output with this symbol */
+#define GNSSHIP_CNAV_S_MESSAGE 4    /* cnav_msg_decoder_add_symbol returned true here */
+/* Channels 0..max_channels-1 (1..GNSSHIP_CNAV_MAX_CHANNELS), each a new block object: cnav_msg_decoder_init and zeroed
+ * members.  Device memory per channel: 2520 bytes of members, messages_per_run =
+ * GNSSHIP_CNAV_MESSAGES_PER_RUN(max_rounds) slots of 72 bytes, and 5 bytes per entry of a run (max_rounds of them). */
+int gnsship_cnav_create(gnsship_ctx* ctx, const gnsship_cnav_conf* conf, int32_t max_channels, gnsship_cnav** out);
+/* symbols[r*max_channels + c], r < n_rounds (0..max_rounds), float on the host or (on_device) on the device; valid and
+ * out_valid: uint8 of the same shape and place, or NULL for all valid / all true (out_valid is the entry's
+ * Flag_valid_symbol_output).  Channel c consumes its valid entries in order of r.  Outputs, in the handle's own device
+ * buffers (gnsship_cnav_outputs_device) and copied to whichever host pointers are given:
+ *   messages[c][k], k < counts[c]    one record per disposal, in order; slots beyond counts[c] are unspecified
+ *   counts int32[c], faults uint8[c] faults: 1 where the watchdog fired in this run
+ *   tow_ms uint32[r*max_channels+c], sflags uint8[...]  r < n_rounds: the block's output stream — the TOW in ms after the
+ *                                    symbol and GNSSHIP_CNAV_S_*; both 0 for entries that are not symbols
+ * With no host pointer the call is asynchronous on the context stream (host inputs then stay the caller's until the
+ * stream has passed the run). */
+int gnsship_cnav_run_symbols(gnsship_cnav* t, const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int on_device,
+    int32_t n_rounds, gnsship_cnav_message* messages_host, int32_t* counts_host, uint8_t* faults_host, uint32_t* tow_ms_host,
+    uint8_t* sflags_host);
+/* The same over tracking records of that shape: an entry is a symbol when flags & 1 and its output-valid flag is then
+ * true; the symbol is prompt_i > 0 (L2C) or prompt_q > 0 (L5), asked of the double itself, not narrowed to float; the
+ * message's sample_counter is the completing record's. */
+int gnsship_cnav_run_records(gnsship_cnav* t, const gnsship_trk_epoch* records, int on_device, int32_t n_rounds,
+    gnsship_cnav_message* messages_host, int32_t* counts_host, uint8_t* faults_host, uint32_t* tow_ms_host, uint8_t* sflags_host);
+/* The same over the records the tracker's last run left on the device (gnsship_trk_records_device), in place, ordered
+ * on the context stream; before or after gnsship_trk_collect.  n_rounds_out (may be NULL): the rounds of that run, the
+ * first dimension of tow_ms / sflags.  E_STATE if there are no records; E_INVAL if the handles are on different
+ * contexts, their max_channels differ or the run had more rounds than max_rounds. */
+int gnsship_cnav_run_trk(gnsship_cnav* t, gnsship_trk* trk, gnsship_cnav_message* messages_host, int32_t* counts_host,
+    uint8_t* faults_host, uint32_t* tow_ms_host, uint8_t* sflags_host, int32_t* n_rounds_out);
+/* The handle's output buffers (any pointer may be NULL) and messages_per_run. */
+int gnsship_cnav_outputs_device(gnsship_cnav* t, gnsship_cnav_message** messages, int32_t** counts, uint8_t** faults,
+    uint32_t** tow_ms, uint8_t** sflags, int32_t* messages_per_run);
+/* The block's reset(): last_valid_preamble = counter, the fault flag cleared; L5 also TOW and valid_word 0. */
+int gnsship_cnav_reset_channel(gnsship_cnav* t, int32_t channel);
+/* A new block object on this channel. */
+int gnsship_cnav_new_channel(gnsship_cnav* t, int32_t channel);
+/* The channel's members after everything run so far (waits for the context stream). */
+int gnsship_cnav_state_get(gnsship_cnav* t, int32_t channel, gnsship_cnav_state* st);
+/* The channel's members become *st (ordered on the context stream; *st is copied before the call returns): a channel
+ * moves between handles, or starts from a state the stream would take hours to reach.  E_INVAL unless, per part,
+ * n_symbols < 128 (init) or 64, n_decoded <= 480, decisions_index < 64 and the flags are 0 or 1. */
+int gnsship_cnav_state_set(gnsship_cnav* t, int32_t channel, const gnsship_cnav_state* st);
+int gnsship_cnav_destroy(gnsship_cnav* t);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Multi-GPU fan-out: one process per GPU, one RCCL communicator per context.  */

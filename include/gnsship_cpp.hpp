@@ -1771,6 +1771,140 @@ private:
     std::vector<uint8_t> sflags_;
 };
 
+// gps_l2c_telemetry_decoder_gs / gps_l5_telemetry_decoder_gs as gnsship_cnav_conf: max_rounds is the most entries per
+// channel one work_* call may carry.
+inline gnsship_cnav_conf gps_l2c_tlm_conf(int32_t max_rounds)
+{
+    return gnsship_cnav_conf{max_rounds, GNSSHIP_CNAV_L2C, 0};
+}
+inline gnsship_cnav_conf gps_l5_tlm_conf(int32_t max_rounds)
+{
+    return gnsship_cnav_conf{max_rounds, GNSSHIP_CNAV_L5, 0};
+}
+
+// The GPS CNAV telemetry decoders up to the time of week for many channels at once, one block object per channel
+// (include/gnsship.h, gnsship_cnav_*): symbols or tracking records in; messages, the TOW stamp of every entry and
+// watchdog faults out.  After a work_* call, messages() / counts() / faults() / tow_ms() / sflags() hold that call's
+// outputs.  The two blocks differ in the configuration's signal only.
+class Gps_Cnav_Telemetry_Decoder_Hip {
+public:
+    Gps_Cnav_Telemetry_Decoder_Hip(const gnsship_cnav_conf& c, int32_t max_channels, int device = 0)
+        : dev_(Device::get(device)), conf_(c), channels_(max_channels)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        if (gnsship_cnav_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
+            throw std::invalid_argument(std::string("gnsship_cnav_create: ") + gnsship_last_error(dev_->ctx()));
+        gnsship_cnav_outputs_device(h_, nullptr, nullptr, nullptr, nullptr, nullptr, &messages_per_run_);
+        const size_t nc = static_cast<size_t>(max_channels);
+        messages_.resize(nc * messages_per_run_);
+        counts_.resize(nc);
+        faults_.resize(nc);
+        tow_ms_.resize(nc * c.max_rounds);
+        sflags_.resize(nc * c.max_rounds);
+    }
+    ~Gps_Cnav_Telemetry_Decoder_Hip()
+    {
+        if (h_) gnsship_cnav_destroy(h_);
+    }
+    Gps_Cnav_Telemetry_Decoder_Hip(const Gps_Cnav_Telemetry_Decoder_Hip&) = delete;
+    Gps_Cnav_Telemetry_Decoder_Hip& operator=(const Gps_Cnav_Telemetry_Decoder_Hip&) = delete;
+    const gnsship_cnav_conf& conf() const { return conf_; }
+    int32_t messages_per_run() const { return messages_per_run_; }
+    // the block's reset() on one channel; new_channel: a new block object
+    bool reset(int32_t channel)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_cnav_reset_channel(h_, channel) == GNSSHIP_OK;
+    }
+    bool new_channel(int32_t channel)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_cnav_new_channel(h_, channel) == GNSSHIP_OK;
+    }
+    // symbols[r · max_channels + c], r < n_rounds; valid, out_valid: the same shape, or null for all valid / all true
+    bool work_symbols(const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int32_t n_rounds, bool on_device = false)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = n_rounds;
+        return gnsship_cnav_run_symbols(h_, symbols, valid, out_valid, on_device ? 1 : 0, n_rounds, messages_.data(), counts_.data(), faults_.data(),
+                   tow_ms_.data(), sflags_.data()) == GNSSHIP_OK;
+    }
+    // tracking records of that shape: a symbol when flags & 1; the symbol is prompt_i > 0 (L2C) or prompt_q > 0 (L5)
+    bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = n_rounds;
+        return gnsship_cnav_run_records(h_, records, on_device ? 1 : 0, n_rounds, messages_.data(), counts_.data(), faults_.data(), tow_ms_.data(),
+                   sflags_.data()) == GNSSHIP_OK;
+    }
+    // the records the tracker's last work() left on the device, in place
+    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = 0;
+        return gnsship_cnav_run_trk(h_, trk.handle(), messages_.data(), counts_.data(), faults_.data(), tow_ms_.data(), sflags_.data(), &rounds_) ==
+               GNSSHIP_OK;
+    }
+    // the last work_* call's outputs: message k < counts()[c] of channel c is messages()[c · messages_per_run() + k];
+    // entry (r, c), r < rounds(), is tow_ms()[r · max_channels + c] and sflags()[r · max_channels + c]
+    const std::vector<gnsship_cnav_message>& messages() const { return messages_; }
+    const std::vector<int32_t>& counts() const { return counts_; }
+    const std::vector<uint8_t>& faults() const { return faults_; }
+    const std::vector<uint32_t>& tow_ms() const { return tow_ms_; }
+    const std::vector<uint8_t>& sflags() const { return sflags_; }
+    int32_t rounds() const { return rounds_; }
+    gnsship_cnav_state state(int32_t channel) const
+    {
+        gnsship_cnav_state st{};
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        gnsship_cnav_state_get(h_, channel, &st);
+        return st;
+    }
+    bool set_state(int32_t channel, const gnsship_cnav_state& st)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_cnav_state_set(h_, channel, &st) == GNSSHIP_OK;
+    }
+    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
+
+protected:
+    // for the two block classes: the configuration must be their signal's
+    static const gnsship_cnav_conf& require(const gnsship_cnav_conf& c, int32_t signal)
+    {
+        if (c.signal != signal) throw std::invalid_argument("the configuration's signal is not this block's");
+        return c;
+    }
+
+private:
+    std::shared_ptr<Device> dev_;
+    gnsship_cnav_conf conf_;
+    gnsship_cnav* h_ = nullptr;
+    int32_t channels_ = 0, messages_per_run_ = 0, rounds_ = 0;
+    std::vector<gnsship_cnav_message> messages_;
+    std::vector<int32_t> counts_;
+    std::vector<uint8_t> faults_;
+    std::vector<uint32_t> tow_ms_;
+    std::vector<uint8_t> sflags_;
+};
+
+// gps_l2c_telemetry_decoder_gs: construct with gps_l2c_tlm_conf(max_rounds)
+class Gps_L2c_Telemetry_Decoder_Hip : public Gps_Cnav_Telemetry_Decoder_Hip {
+public:
+    Gps_L2c_Telemetry_Decoder_Hip(const gnsship_cnav_conf& c, int32_t max_channels, int device = 0)
+        : Gps_Cnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_CNAV_L2C), max_channels, device)
+    {
+    }
+};
+
+// gps_l5_telemetry_decoder_gs: construct with gps_l5_tlm_conf(max_rounds)
+class Gps_L5_Telemetry_Decoder_Hip : public Gps_Cnav_Telemetry_Decoder_Hip {
+public:
+    Gps_L5_Telemetry_Decoder_Hip(const gnsship_cnav_conf& c, int32_t max_channels, int device = 0)
+        : Gps_Cnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_CNAV_L5), max_channels, device)
+    {
+    }
+};
+
 }  // namespace gnsship
 
 #endif  // GNSSHIP_CPP_HPP

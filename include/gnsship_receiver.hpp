@@ -139,6 +139,12 @@ struct Receiver_Conf {
     // check_tlm_separation fires gets the fault message of msg_handler_telemetry_to_trk.  Off (the default): exactly the
     // receiver above, every output byte for byte.
     bool lnav{false};
+    // Optional GPS CNAV telemetry on the device (gps_l2c_telemetry_decoder_gs / gps_l5_telemetry_decoder_gs up to the time
+    // of week; Gps_L2c_Telemetry_Decoder_Hip / Gps_L5_Telemetry_Decoder_Hip), 2S and L5 channels only.  Each tracking
+    // block's records go through the decoder where tracking left them on the device; a channel that is assigned a
+    // satellite gets a new block object; a channel whose watchdog fires gets the fault message of
+    // msg_handler_telemetry_to_trk.  Off (the default): exactly the receiver above, every output byte for byte.
+    bool cnav{false};
 };
 
 // One control event, in stream order.
@@ -168,6 +174,12 @@ struct Receiver_Page {
 struct Receiver_Subframe {
     uint32_t prn;
     gnsship_lnav_subframe subframe;
+};
+
+// One CNAV message of a channel (every 300-bit buffer a locked part disposed of) with the satellite it was tracking.
+struct Receiver_Cnav_Message {
+    uint32_t prn;
+    gnsship_cnav_message message;
 };
 
 class Gnss_Receiver_Hip {
@@ -213,6 +225,12 @@ public:
                 throw std::invalid_argument("Gnss_Receiver_Hip: lnav decodes GPS L1 C/A channels (signal 1C)");
             const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
             lnav_ = std::make_unique<Gps_L1_Ca_Telemetry_Decoder_Hip>(gps_l1_ca_tlm_conf(max_ep), n_, conf_.device);
+        }
+        if (conf_.cnav) {
+            if (!l2c_ && !l5_) throw std::invalid_argument("Gnss_Receiver_Hip: cnav decodes GPS L2C or L5 channels (signal 2S or L5)");
+            const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
+            if (l5_) cnav_ = std::make_unique<Gps_L5_Telemetry_Decoder_Hip>(gps_l5_tlm_conf(max_ep), n_, conf_.device);
+            else cnav_ = std::make_unique<Gps_L2c_Telemetry_Decoder_Hip>(gps_l2c_tlm_conf(max_ep), n_, conf_.device);
         }
         if (conf_.use_conditioner) {
             const double fs_out = conf_.input_filter.sampling_frequency / std::max(1, conf_.input_filter.decimation_factor);
@@ -319,6 +337,11 @@ public:
     const std::vector<Receiver_Page>& pages() const { return pages_; }
     // With conf.lnav: every emitted subframe record in the order the blocks emitted them (channel by channel within a block).
     const std::vector<Receiver_Subframe>& subframes() const { return subframes_; }
+    // With conf.cnav: every message record in the order the blocks emitted them (channel by channel within a block), and
+    // a channel's decoder members after everything processed so far.
+    const std::vector<Receiver_Cnav_Message>& cnav_messages() const { return cnav_messages_; }
+    bool has_cnav() const { return cnav_ != nullptr; }
+    gnsship_cnav_state cnav_state(int c) const { return cnav_ ? cnav_->state(c) : gnsship_cnav_state{}; }
     uint64_t position() const { return pos_; }
     unsigned channel_fsm_state(int c) const { return fsm_[static_cast<size_t>(c)].state(); }
     uint32_t channel_prn(int c) const { return prn_[static_cast<size_t>(c)]; }
@@ -392,6 +415,7 @@ private:
         prn_[static_cast<size_t>(c)] = prn;
         if (tlm_ && !tlm_->set_satellite(c)) error_ = true;  // nav_->set_satellite (channel.cc:237)
         if (lnav_ && !lnav_->new_channel(c)) error_ = true;  // the channel starts on its satellite with a new block object
+        if (cnav_ && !cnav_->new_channel(c)) error_ = true;  // likewise
         if (l5_) {  // GpsL5iPcpsAcquisition::set_local_code: the search runs on L5I
             const std::vector<std::complex<float>> code = gps_l5i_acquisition_code(prn, conf_.acq);
             if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
@@ -595,6 +619,15 @@ private:
                 if (lnav_->faults()[static_cast<size_t>(c)] && !trk_->msg_handler_telemetry_to_trk(c, 1)) return false;
             }
         }
+        if (cnav_) {  // and for the GPS CNAV decoder
+            if (!cnav_->work_trk(*trk_)) return false;
+            const size_t mpr = static_cast<size_t>(cnav_->messages_per_run());
+            for (int c = 0; c < n_; c++) {
+                for (int k = 0; k < cnav_->counts()[static_cast<size_t>(c)]; k++)
+                    cnav_messages_.push_back({prn_[static_cast<size_t>(c)], cnav_->messages()[static_cast<size_t>(c) * mpr + static_cast<size_t>(k)]});
+                if (cnav_->faults()[static_cast<size_t>(c)] && !trk_->msg_handler_telemetry_to_trk(c, 1)) return false;
+            }
+        }
         recs_.resize(static_cast<size_t>(n_));
         for (int c = 0; c < n_; c++) {
             bool lost = false;
@@ -645,6 +678,8 @@ private:
     std::vector<Receiver_Page> pages_;
     std::unique_ptr<Gps_L1_Ca_Telemetry_Decoder_Hip> lnav_;  // the optional GPS L1 C/A telemetry
     std::vector<Receiver_Subframe> subframes_;
+    std::unique_ptr<Gps_Cnav_Telemetry_Decoder_Hip> cnav_;  // the optional GPS CNAV telemetry (L2C or L5)
+    std::vector<Receiver_Cnav_Message> cnav_messages_;
     std::unique_ptr<Freq_Xlating_Fir_Filter_Hip> cond_;  // the optional conditioner stage
     int64_t cond_block_ = 0;                             // its run size, in input samples
     std::vector<std::complex<float>> cond_host_;

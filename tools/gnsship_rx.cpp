@@ -14,7 +14,7 @@
 //              [--pll-bw 40] [--dll-bw 4] [--order 3] [--pull-in-time-s 10] [--rotator auto|generic|avx]
 //              [--max-carrier-lock-fail 5000] [--max-code-lock-fail 50] [--cn0-min 25]
 //              [--block-ms 100] [--acq-piece 8192] [--dump PREFIX] [--events CSV] [--records BIN]
-//              [--telemetry] [--telemetry-mode reference|full] [--lnav]
+//              [--telemetry] [--telemetry-mode reference|full] [--lnav] [--cnav]
 //              [--if-hz 0] [--decimation 1] [--filter-bw 0] [--filter-tw 0]
 //              [--input-filter pulse-blanking|notch|notch-lite] [--input-filter-pfa P] [--segment-length 32]
 //              [--segments-est 12500] [--segments-reset 5000000] [--p-c-factor 0.9] [--coeff-rate R]
@@ -27,6 +27,12 @@
 // --lnav (with --signal 1C) sends each tracking block's records through the device GPS L1 C/A telemetry decoder and
 // prints, ahead of the summary, one line per emitted subframe: channel, PRN, symbol counter, subframe ID, TOW in seconds,
 // ok / fail, the ten words as the block stores them in hex.  A telemetry fault goes back to the channel's tracking.
+//
+// --cnav (with --signal 2S or L5) sends each tracking block's records through the device GPS CNAV telemetry decoder and
+// prints, ahead of the summary, one line per message (every 300-bit buffer a locked part disposed of): channel, PRN,
+// symbol counter, the message's PRN, ID, TOW in 6-second units, alert, delay, part, ok / fail, the 38 bytes in hex; then per
+// channel one "cnav-state" line with the decoder's members (the arrays as weighted sums, as tests/cpp/cnav_mirror_test
+// prints them).  A telemetry fault goes back to the channel's tracking.
 //
 // --input-filter puts the interference mitigation (InputFilter.implementation = Pulse_Blanking_Filter, Notch_Filter or
 // Notch_Filter_Lite; pfa, length, segments_est, segments_reset, p_c_factor, coeff_rate: 0 = the adapter's defaults)
@@ -155,6 +161,7 @@ int main(int argc, char** argv)
         else if (a == "--records") records_bin = val();
         else if (a == "--telemetry") rc.telemetry = true;
         else if (a == "--lnav") rc.lnav = true;
+        else if (a == "--cnav") rc.cnav = true;
         else if (a == "--telemetry-mode") {
             const std::string m = val();
             if (m != "reference" && m != "full") usage("--telemetry-mode must be reference or full");
@@ -195,6 +202,7 @@ int main(int argc, char** argv)
     if (signal != "1C" && signal != "L5" && signal != "2S" && signal != "B3" && signal != "5X" && signal != "7X" && signal != "1G" && signal != "2G")
         usage("--signal must be 1C, L5, 2S, B3, 5X, 7X, 1G or 2G");
     if (rc.lnav && signal != "1C") usage("--lnav decodes GPS L1 C/A channels (--signal 1C)");
+    if (rc.cnav && signal != "2S" && signal != "L5") usage("--cnav decodes GPS L2C or L5 channels (--signal 2S or L5)");
     std::snprintf(rc.trk.signal, sizeof(rc.trk.signal), "%s", signal.c_str());
     if (signal == "B3") rc.trk.system = 'C';  // otherwise 'G'
     if (signal == "5X" || signal == "7X") rc.trk.system = 'E';
@@ -351,6 +359,34 @@ int main(int argc, char** argv)
         std::printf("subframe channel %d prn %u symbol %llu id %d tow %u %s", sf.subframe.channel, sf.prn,
             static_cast<unsigned long long>(sf.subframe.symbol_counter), sf.subframe.subframe_id, sf.subframe.tow_s, (sf.subframe.flags & 1) ? "ok" : "fail");
         for (int w = 0; w < 10; w++) std::printf(" %08x", sf.subframe.words[w]);
+        std::printf("\n");
+    }
+    // --cnav: one line per message — channel, PRN, symbol counter, the message's fields, the CRC verdict, the 38 bytes;
+    // then each channel's decoder members
+    for (const auto& cm : rx.cnav_messages()) {
+        const gnsship_cnav_message& m = cm.message;
+        std::printf("message channel %d prn %u symbol %llu msg_prn %u id %u tow %u alert %u delay %u part %u %s ", m.channel, cm.prn,
+            static_cast<unsigned long long>(m.symbol_counter), m.prn, m.msg_id, m.tow, m.alert, m.delay, m.part, (m.flags & 1) ? "ok" : "fail");
+        for (int b = 0; b < 38; b++) std::printf("%02x", m.raw[b]);
+        std::printf("\n");
+    }
+    for (int c = 0; rx.has_cnav() && c < rc.channels; c++) {
+        const gnsship_cnav_state s = rx.cnav_state(c);
+        std::printf("cnav-state %d %llu %llu %.17g %u %u %d %d %d", c, static_cast<unsigned long long>(s.symbol_counter),
+            static_cast<unsigned long long>(s.last_valid_preamble), s.tow_s, s.tow_ms, s.tow_at_preamble, s.pll_180, s.valid_word, s.sent_tlm_failed);
+        for (int k = 0; k < 2; k++) {
+            const gnsship_cnav_part& p = s.part[k];
+            uint64_t metrics = 0, decisions = 0, symbols = 0, decoded = 0;
+            for (int i = 0; i < 64; i++) {
+                metrics += static_cast<uint64_t>(p.metrics[0][i]) * (i + 1) + static_cast<uint64_t>(p.metrics[1][i]) * (i + 65);
+                decisions += static_cast<uint64_t>(p.decisions[i][0]) * (2 * i + 1) + static_cast<uint64_t>(p.decisions[i][1]) * (2 * i + 2);
+                decoded += static_cast<uint64_t>(p.decoded[i]) * (i + 1);
+            }
+            for (int i = 0; i < 128; i++) symbols += static_cast<uint64_t>(p.symbols[i]) * (i + 1);
+            std::printf(" %u %u %u %u %d %d %d %d %d %d %llu %llu %llu %llu", p.n_symbols, p.n_decoded, p.n_crc_fail, p.decisions_index,
+                p.old_is_metrics2, p.preamble_seen, p.invert, p.message_lock, p.crc_ok, p.init, static_cast<unsigned long long>(metrics),
+                static_cast<unsigned long long>(decisions), static_cast<unsigned long long>(symbols), static_cast<unsigned long long>(decoded));
+        }
         std::printf("\n");
     }
     int n_pos = 0, n_neg = 0, n_lost = 0;
