@@ -285,6 +285,44 @@ CNAV_STATE_DTYPE = np.dtype([("part", CNAV_PART_DTYPE, (2,)), ("symbol_counter",
                              ("reserved", "u1"), ("reserved2", "<u4")])
 assert CNAV_STATE_DTYPE.itemsize == 2520
 
+# gnsship_dnav_conf.signal
+DNAV_B1I, DNAV_B3I = 0, 1
+# gnsship_dnav_subframe.flags
+DNAV_INVERTED, DNAV_STATE1, DNAV_NEW_SOW, DNAV_D2_DECODER, DNAV_D2_TIMING, DNAV_TOW_ZEROED = 1, 2, 4, 8, 16, 32
+# sflags of an entry (GNSSHIP_DNAV_S_*)
+DNAV_S_VALID_WORD, DNAV_S_SUBFRAME, DNAV_S_INVERTED = 1, 2, 4
+
+
+def dnav_subframes_per_run(max_rounds: int) -> int:
+    """GNSSHIP_DNAV_SUBFRAMES_PER_RUN."""
+    return max_rounds // 300 + 1
+
+
+class DnavConf(ctypes.Structure):
+    """gnsship_dnav_conf — the most entries per channel one run may carry, and the signal (DNAV_B1I / DNAV_B3I)."""
+    _fields_ = [("max_rounds", ctypes.c_int32), ("signal", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+class DnavState(ctypes.Structure):
+    """gnsship_dnav_state — the members of one channel's beidou_b1i / beidou_b3i_telemetry_decoder_gs object."""
+    _fields_ = [("symbol_counter", ctypes.c_uint64), ("preamble_index", ctypes.c_uint64), ("last_valid_preamble", ctypes.c_uint64),
+                ("tow_at_preamble_ms", ctypes.c_uint32), ("tow_at_current_symbol_ms", ctypes.c_uint32), ("sow", ctypes.c_uint32),
+                ("symbol_duration_ms", ctypes.c_uint32), ("stat", ctypes.c_int32), ("crc_error_counter", ctypes.c_int32),
+                ("history_size", ctypes.c_int32), ("prn", ctypes.c_int32), ("sow_set", ctypes.c_uint8), ("frame_sync", ctypes.c_uint8),
+                ("valid_word", ctypes.c_uint8), ("new_sow_available", ctypes.c_uint8), ("sent_tlm_failed", ctypes.c_uint8),
+                ("d2_decoder", ctypes.c_uint8), ("d2_timing", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+assert ctypes.sizeof(DnavState) == 64
+
+DNAV_SUBFRAME_DTYPE = np.dtype([("symbol_counter", "<u8"), ("sample_counter", "<u8"), ("words", "<u4", (10,)), ("channel", "<i4"),
+                                ("fra_id", "<i4"), ("pnum", "<i4"), ("sow", "<u4"), ("corrected_mask", "<u4"),
+                                ("tow_at_current_symbol_ms", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert DNAV_SUBFRAME_DTYPE.itemsize == 88
+
 SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5, SYS_BDS_B3I, SYS_GPS_L2C = 0, 1, 2, 3, 4, 5
 SYS_GAL_E5A, SYS_GAL_E5B = 6, 7
 SYS_GLO_L1CA, SYS_GLO_L2CA = 8, 9  # glonass_l1_ca / glonass_l2_ca_dll_pll_tracking_cc (include/gnsship.h)
@@ -542,6 +580,16 @@ _SIGNATURES = {
     "gnsship_cnav_state_get": ([_vp, ctypes.c_int32, _vp], _i),
     "gnsship_cnav_state_set": ([_vp, ctypes.c_int32, _vp], _i),
     "gnsship_cnav_destroy": ([_vp], _i),
+    "gnsship_dnav_create": ([_vp, ctypes.POINTER(DnavConf), ctypes.c_int32, _vpp], _i),
+    "gnsship_dnav_run_symbols": ([_vp, _vp, _vp, _vp, _i, ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
+    "gnsship_dnav_run_records": ([_vp, _vp, _i, ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
+    "gnsship_dnav_run_trk": ([_vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int32)], _i),
+    "gnsship_dnav_outputs_device": ([_vp, _vpp, _vpp, _vpp, _vpp, ctypes.POINTER(ctypes.c_int32)], _i),
+    "gnsship_dnav_reset_channel": ([_vp, ctypes.c_int32], _i),
+    "gnsship_dnav_set_satellite": ([_vp, ctypes.c_int32, ctypes.c_int32], _i),
+    "gnsship_dnav_new_channel": ([_vp, ctypes.c_int32, ctypes.c_int32], _i),
+    "gnsship_dnav_state_get": ([_vp, ctypes.c_int32, ctypes.POINTER(DnavState)], _i),
+    "gnsship_dnav_destroy": ([_vp], _i),
     "gnsship_trk_set_trace": ([_vp, _i], _i),
     "gnsship_trk_trace_records": ([_vp, _vp, _i], _i),
     "gnsship_trk_channel_state": ([_vp, _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_uint64)], _i),

@@ -1354,6 +1354,137 @@ def gps_l5_telemetry(ctx: Context, max_channels: int, max_rounds: int) -> GpsCna
     return GpsCnavTelemetryDecoder(ctx, abi.CNAV_L5, max_channels, max_rounds)
 
 
+class DnavResult(NamedTuple):
+    """One gnsship_dnav run: subframes [max_channels, subframes_per_run] (abi.DNAV_SUBFRAME_DTYPE; slots k >= counts[c] are
+    unspecified), counts int32[max_channels], and the block's output stream per entry: tow_ms uint32[n_rounds, max_channels],
+    sflags uint8[n_rounds, max_channels] (abi.DNAV_S_*), both 0 where the entry is no symbol."""
+    subframes: np.ndarray
+    counts: np.ndarray
+    tow_ms: np.ndarray
+    sflags: np.ndarray
+
+
+class BeidouDnavTelemetryDecoder:
+    """beidou_b1i_telemetry_decoder_gs (signal abi.DNAV_B1I) or beidou_b3i_telemetry_decoder_gs (abi.DNAV_B3I) up to the time
+    of week for up to ``channels`` channels on the device, one block object per channel: the 311-symbol history, preamble
+    correlation, three-state frame sync, BCH(15,11,1) with its de-interleaver, the D1 / D2 FraID, Pnum and SOW, and the TOW
+    stamp with valid_word (include/gnsship.h, gnsship_dnav_*).  max_rounds: the most entries per channel one run may carry."""
+
+    def __init__(self, ctx: Context, channels: int, max_rounds: int, signal: int):
+        self.ctx = ctx
+        self.h = None
+        self.signal, self.max_channels, self.max_rounds = int(signal), int(channels), int(max_rounds)
+        self.conf = abi.DnavConf(max_rounds=self.max_rounds, signal=self.signal, reserved=0)
+        h = ctypes.c_void_p()
+        check(ctx.lib.gnsship_dnav_create(ctx.h, ctypes.byref(self.conf), self.max_channels, ctypes.byref(h)), "gnsship_dnav_create", ctx.h)
+        self.h = h
+        spr = ctypes.c_int32()
+        check(ctx.lib.gnsship_dnav_outputs_device(self.h, None, None, None, None, ctypes.byref(spr)), "gnsship_dnav_outputs_device", ctx.h)
+        self.subframes_per_run = spr.value
+
+    def _outputs(self, host: bool, n_rounds: int):
+        if not host:
+            return None, (None, None, None, None)
+        res = DnavResult(np.zeros((self.max_channels, self.subframes_per_run), abi.DNAV_SUBFRAME_DTYPE), np.zeros(self.max_channels, np.int32),
+                         np.zeros((n_rounds, self.max_channels), np.uint32), np.zeros((n_rounds, self.max_channels), np.uint8))
+        return res, tuple(ctypes.c_void_p(x.ctypes.data) for x in res)
+
+    def run_symbols(self, symbols, valid=None, out_valid=None, on_device: bool = False, n_rounds: int = None, host: bool = True):
+        """symbols float32[n_rounds, max_channels] (or a device pointer with on_device and n_rounds); valid and out_valid
+        uint8 of the same shape (and place) or None.  Returns a DnavResult, or None when not host (asynchronous)."""
+        if on_device:
+            sp = ctypes.c_void_p(symbols)
+            vp, op = (ctypes.c_void_p(x) if x else None for x in (valid, out_valid))
+        else:
+            symbols = np.ascontiguousarray(symbols, np.float32).reshape(-1, self.max_channels)
+            n_rounds = symbols.shape[0] if n_rounds is None else int(n_rounds)
+            sp = ctypes.c_void_p(symbols.ctypes.data) if symbols.size else None
+            masks = []
+            for m, name in ((valid, "valid"), (out_valid, "out_valid")):
+                if m is not None:
+                    m = np.ascontiguousarray(m, np.uint8).reshape(-1, self.max_channels)
+                    if m.shape != symbols.shape:
+                        raise ValueError(f"{name} must have the symbols' shape")
+                masks.append(m)
+            valid, out_valid = masks
+            vp, op = (ctypes.c_void_p(m.ctypes.data) if m is not None and m.size else None for m in masks)
+        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
+        self._in_flight = (symbols, valid, out_valid)  # a run without a host copy returns before the stream has read them
+        check(self.ctx.lib.gnsship_dnav_run_symbols(self.h, sp, vp, op, int(on_device), int(n_rounds), *ptrs), "gnsship_dnav_run_symbols", self.ctx.h)
+        return res
+
+    def run_records(self, records, on_device: bool = False, n_rounds: int = None, host: bool = True):
+        """records: abi.TRK_EPOCH_DTYPE[n_rounds, max_channels] on the host, or a device pointer with on_device and n_rounds."""
+        if on_device:
+            rp = ctypes.c_void_p(records)
+        else:
+            records = np.ascontiguousarray(records, abi.TRK_EPOCH_DTYPE).reshape(-1, self.max_channels)
+            n_rounds = records.shape[0] if n_rounds is None else int(n_rounds)
+            rp = ctypes.c_void_p(records.ctypes.data) if records.size else None
+        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
+        self._in_flight = (records,)
+        check(self.ctx.lib.gnsship_dnav_run_records(self.h, rp, int(on_device), int(n_rounds), *ptrs), "gnsship_dnav_run_records", self.ctx.h)
+        return res
+
+    def run_trk(self, trk: "DllPllVemlTracking", host: bool = True):
+        """Consume, in place, the records the tracker's last run left on the device."""
+        res, ptrs = self._outputs(host, self.max_rounds)
+        rounds = ctypes.c_int32()
+        check(self.ctx.lib.gnsship_dnav_run_trk(self.h, trk.h, *ptrs, ctypes.byref(rounds)), "gnsship_dnav_run_trk", self.ctx.h)
+        if res is None:
+            return None
+        n = rounds.value  # the copies are dense over the run's rounds
+        flat = self.max_rounds * self.max_channels
+        return res._replace(tow_ms=res.tow_ms.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels),
+                            sflags=res.sflags.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels))
+
+    def outputs_device(self):
+        """Device pointers (subframes, counts, tow_ms, sflags) of the handle's output buffers."""
+        p = [ctypes.c_void_p() for _ in range(4)]
+        check(self.ctx.lib.gnsship_dnav_outputs_device(self.h, *[ctypes.byref(x) for x in p], None), "gnsship_dnav_outputs_device", self.ctx.h)
+        return tuple(x.value for x in p)
+
+    def state(self, channel: int) -> dict:
+        """The channel's block members (gnsship_dnav_state) by name."""
+        st = abi.DnavState()
+        check(self.ctx.lib.gnsship_dnav_state_get(self.h, channel, ctypes.byref(st)), "gnsship_dnav_state_get", self.ctx.h)
+        return st.as_dict()
+
+    def reset_channel(self, channel: int):
+        """The block's reset()."""
+        check(self.ctx.lib.gnsship_dnav_reset_channel(self.h, channel), "gnsship_dnav_reset_channel", self.ctx.h)
+
+    def set_satellite(self, channel: int, prn: int):
+        """The block's set_satellite(): timing and decoder choice only."""
+        check(self.ctx.lib.gnsship_dnav_set_satellite(self.h, channel, int(prn)), "gnsship_dnav_set_satellite", self.ctx.h)
+
+    def new_channel(self, channel: int, prn: int):
+        """A new block object on this channel, constructed on this PRN."""
+        check(self.ctx.lib.gnsship_dnav_new_channel(self.h, channel, int(prn)), "gnsship_dnav_new_channel", self.ctx.h)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.gnsship_dnav_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.close()
+        except Exception:
+            pass
+
+
+def beidou_b1i_telemetry(ctx: Context, max_channels: int, max_rounds: int) -> BeidouDnavTelemetryDecoder:
+    """BeiDou B1I D1/D2 (beidou_b1i_telemetry_decoder_gs)."""
+    return BeidouDnavTelemetryDecoder(ctx, max_channels, max_rounds, abi.DNAV_B1I)
+
+
+def beidou_b3i_telemetry(ctx: Context, max_channels: int, max_rounds: int) -> BeidouDnavTelemetryDecoder:
+    """BeiDou B3I D1/D2 (beidou_b3i_telemetry_decoder_gs): a PRN above 58 takes the D1 decoder with the D2 timing."""
+    return BeidouDnavTelemetryDecoder(ctx, max_channels, max_rounds, abi.DNAV_B3I)
+
+
 class DllPllVemlTracking:
     """dll_pll_veml_tracking (dll_pll_veml_tracking.cc) for up to ``max_channels`` channels, the
     per-epoch loop resident on the device: ``start_tracking`` → :meth:`start`, ``general_work``

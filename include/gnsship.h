@@ -905,7 +905,7 @@ int gnsship_trk_destroy(gnsship_trk* t);
  * A page part is emitted required + 1 + 2*period symbols after its preamble's first symbol at the earliest: the
  * correlation looks at the oldest end of a full history.
  * Not here: TOW and everything below :1096, page_jk_decoder / ephemeris fields, Reed-Solomon, HAS header parsing and the
- * dummy-page test, time tags, the nav-data monitor, the CRC statistics file, the .dat dump, other systems' telemetry (GPS L1 C/A LNAV: gnsship_lnav_*, GPS CNAV: gnsship_cnav_*, both below).
+ * dummy-page test, time tags, the nav-data monitor, the CRC statistics file, the .dat dump, other systems' telemetry (GPS L1 C/A LNAV: gnsship_lnav_*, GPS CNAV: gnsship_cnav_*, BeiDou D1/D2: gnsship_dnav_*, all below).
  * Symbols are finite by contract; with NaN / Inf the decoded bits are unspecified (nothing is read or written out of
  * bounds: every index comes from lane numbers, sizes and ballot bits). */
 #define GNSSHIP_TLM_INAV 1
@@ -1235,6 +1235,148 @@ int gnsship_cnav_state_get(gnsship_cnav* t, int32_t channel, gnsship_cnav_state*
  * n_symbols < 128 (init) or 64, n_decoded <= 480, decisions_index < 64 and the flags are 0 or 1. */
 int gnsship_cnav_state_set(gnsship_cnav* t, int32_t channel, const gnsship_cnav_state* st);
 int gnsship_cnav_destroy(gnsship_cnav* t);
+
+/* ---------------------------------------------------------------------------------------------
+ * BeiDou D1/D2 telemetry (B1I and B3I) on the device: beidou_b1i_telemetry_decoder_gs / beidou_b3i_telemetry_decoder_gs
+ * with what they use of Beidou_Dnav_Navigation_Message (d1_subframe_decoder, d2_subframe_decoder) up to the time of week,
+ * one block object per channel, one wavefront per channel, no float arithmetic beyond the sign tests.  The two blocks are
+ * one algorithm with a signal mode.  Restated and not repaired — all of this is part of the contract:
+ *   history      a circular buffer of 311 (300 + 11) floats; every symbol is pushed as (float)Prompt_I and d_sample_counter
+ *                grows by one.  reset() and set_satellite() keep its contents.
+ *   correlation  only when the history holds 311 entries: over the 11 oldest against "11100010010", -preamble where the
+ *                entry is < 0 and +preamble otherwise, so +0, -0 and NaN count as positive.  A hit is |corr| >= 11.
+ *   state 0      a hit sets preamble_index = counter and state 1.
+ *   state 1      on a hit only, with diff = (int32)(counter - preamble_index): diff == 300 decodes and the outcome is
+ *                state 2; diff > 300 goes back to state 0 and this hit is thrown away; diff < 300 does nothing.  Without a
+ *                hit state 1 never times out.
+ *   state 2      when counter == preamble_index + 300: decode, hit or not.
+ *   polarity     in both decodes normal when corr > 0, inverted otherwise: a state-2 subframe whose preamble did not match
+ *                (corr 0, -3, ...) is decoded inverted.  The 300 symbols decoded are the 300 oldest history entries.
+ *   decode       a bit is +1 when the (possibly negated) float is > 0, else -1: zero and NaN are -1 under both polarities.
+ *                Word 1 is taken as it is.  Words 2..10 are de-interleaved (enc[c*2 + r] to row r, column c), each row goes
+ *                through decode_bch15_11_01 (a syndrome of 1..15 flips one bit, whatever the true error was), and the word
+ *                is 11 + 11 information bits, then 4 + 4 parity bits.
+ *   D1 / D2      the blocks differ.  B1I uses the D2 decoder and the D2 timing (2 ms per symbol) for PRN 1..5 or > 58.  B3I
+ *                uses the D2 decoder for PRN 1..5 only, but the D2 timing for PRN 1..5 or > 58: a B3I PRN > 58 runs the
+ *                D1 decoder with 2 ms symbols.  Otherwise D1 and 20 ms.
+ *   nav object   flag_crc_test is always true (the CRC is "tbd" in the source), so d_CRC_error_counter stays 0, frame sync
+ *                is never lost and an object in state 2 stays there; the branch behind `> CRC_ERROR_LIMIT` is unreachable
+ *                and is not here.  D1: FraID is bits 16..18, read whatever the preamble; for FraID 1..5 d_SOW becomes bits
+ *                19..26 ‖ 31..42 and flag_new_SOW_available is set, any other FraID leaves both alone.  D2: only FraID 1
+ *                with Pnum (bits 43..46) in 1..10 does so.  The block clears the flag when it uses it.
+ *   stamp        on a decode with the flag set: tow_at_preamble_ms = (SOW + 14) * 1000, tow_at_current_symbol_ms = that +
+ *                311 * symbol_duration_ms; if the previous current-symbol value was non-zero and differs from the new one
+ *                by more than one symbol duration (int64 arithmetic) the result is TOW 0 and valid_word false, otherwise
+ *                last_valid_preamble = counter and valid_word true.  On every other symbol, while valid_word: the TOW
+ *                grows by one symbol duration, and valid_word falls if the entry's output-valid flag is false.  The block
+ *                outputs the symbol only while valid_word.
+ *   reset()      last_valid_preamble = counter, TOW 0, valid_word false, the fault flag cleared; nothing else: state,
+ *                preamble_index and history stay.
+ *   faults       the blocks never publish on telemetry_to_trk: there is no fault output.
+ * Not here: ephemeris, almanac, iono and UTC fields and their messages, the nav-data monitor, CRC statistics, dumps. */
+#define GNSSHIP_DNAV_MAX_CHANNELS (1 << 20)
+#define GNSSHIP_DNAV_MAX_ROUNDS (1 << 20)
+#define GNSSHIP_DNAV_B1I 0
+#define GNSSHIP_DNAV_B3I 1
+/* The most records one run of max_rounds symbols can emit.  A record is a decode.  Every decode sets preamble_index =
+ * counter and leaves state 2, which is never left; in state 2 the only decode is the one at counter == preamble_index +
+ * 300.  So a run's decodes after its first are exactly 300 symbols apart, and the first (a state-1 hit, or the due symbol
+ * of state 2) falls on the run's first symbol at the earliest: n symbols hold at most (n - 1) / 300 + 1 <= n / 300 + 1
+ * decodes, and n = 300 k + 1 symbols starting on a due symbol hold exactly k + 1. */
+#define GNSSHIP_DNAV_SUBFRAMES_PER_RUN(max_rounds) ((max_rounds) / 300 + 1)
+typedef struct gnsship_dnav gnsship_dnav;
+typedef struct gnsship_dnav_conf {
+    int32_t max_rounds;      /* most entries per channel in one run, >= 1 */
+    int32_t signal;          /* GNSSHIP_DNAV_B1I or GNSSHIP_DNAV_B3I */
+    int32_t reserved;        /* 0 */
+} gnsship_dnav_conf;
+/* gnsship_dnav_subframe.flags */
+#define GNSSHIP_DNAV_INVERTED 1    /* decoded under the inverted polarity (corr <= 0) */
+#define GNSSHIP_DNAV_STATE1 2      /* decoded in state 1 (a hit 300 symbols after a hit); otherwise in state 2 */
+#define GNSSHIP_DNAV_NEW_SOW 4     /* flag_new_SOW_available was set: the stamp ran here */
+#define GNSSHIP_DNAV_D2_DECODER 8  /* d2_subframe_decoder; otherwise d1_subframe_decoder */
+#define GNSSHIP_DNAV_D2_TIMING 16  /* 2 ms per symbol; otherwise 20 ms */
+#define GNSSHIP_DNAV_TOW_ZEROED 32 /* the TOW consistency check failed here: TOW 0, valid_word false */
+typedef struct gnsship_dnav_subframe { /* one decode, 88 bytes */
+    uint64_t symbol_counter;        /* d_sample_counter at the completing symbol */
+    uint64_t sample_counter;        /* the completing epoch's record.sample_counter; 0 for run_symbols */
+    uint32_t words[10];             /* the ten decoded 30-bit words, bit 1 of the word in bit 29 */
+    int32_t channel;
+    int32_t fra_id;                 /* bits 16..18 */
+    int32_t pnum;                   /* bits 43..46 under the D2 decoder, bits 44..50 under D1, whatever the ID */
+    uint32_t sow;                   /* the navigation object's d_SOW after the decode */
+    uint32_t corrected_mask;        /* bit 2(w-2)+r: the syndrome of row r of word w (2..10) was non-zero */
+    uint32_t tow_at_current_symbol_ms; /* after the stamp */
+    uint32_t flags;                 /* GNSSHIP_DNAV_* above */
+    uint32_t reserved;
+} gnsship_dnav_subframe;
+typedef struct gnsship_dnav_state { /* every member of one block object that the above names, 64 bytes */
+    uint64_t symbol_counter;        /* d_sample_counter */
+    uint64_t preamble_index;
+    uint64_t last_valid_preamble;
+    uint32_t tow_at_preamble_ms, tow_at_current_symbol_ms;
+    uint32_t sow;                   /* the navigation object's d_SOW (a double there; always an integer below 2^20) */
+    uint32_t symbol_duration_ms;    /* 20 or 2 */
+    int32_t stat;
+    int32_t crc_error_counter;      /* always 0 */
+    int32_t history_size;           /* 0..311 */
+    int32_t prn;
+    uint8_t sow_set, frame_sync, valid_word;
+    uint8_t new_sow_available;      /* the navigation object's flag between symbols: always 0, the block uses it at once */
+    uint8_t sent_tlm_failed;        /* never set; reset() clears it */
+    uint8_t d2_decoder, d2_timing;  /* what set_satellite chose for the PRN */
+    uint8_t reserved;
+} gnsship_dnav_state;
+#ifdef __cplusplus
+static_assert(sizeof(gnsship_dnav_subframe) == 88, "gnsship_dnav_subframe");
+static_assert(sizeof(gnsship_dnav_state) == 64, "gnsship_dnav_state");
+#else
+_Static_assert(sizeof(gnsship_dnav_subframe) == 88, "gnsship_dnav_subframe");
+_Static_assert(sizeof(gnsship_dnav_state) == 64, "gnsship_dnav_state");
+#endif
+/* sflags of an entry */
+#define GNSSHIP_DNAV_S_VALID_WORD 1 /* d_flag_valid_word after this symbol: the block outputs it */
+#define GNSSHIP_DNAV_S_SUBFRAME 2   /* a subframe was decoded at this symbol */
+#define GNSSHIP_DNAV_S_INVERTED 4   /* ... under the inverted polarity */
+/* Channels 0..max_channels-1 (1..GNSSHIP_DNAV_MAX_CHANNELS), each a new block object on PRN 0 (D1, 20 ms).  Device memory
+ * per channel: 144 bytes of members and history (two 311-bit strings: "was < 0", "was > 0"), subframes_per_run =
+ * GNSSHIP_DNAV_SUBFRAMES_PER_RUN(max_rounds) slots of 88 bytes, and 5 bytes per entry of a run (max_rounds of them). */
+int gnsship_dnav_create(gnsship_ctx* ctx, const gnsship_dnav_conf* conf, int32_t max_channels, gnsship_dnav** out);
+/* symbols[r*max_channels + c], r < n_rounds (0..max_rounds), float on the host or (on_device) on the device; valid and
+ * out_valid: uint8 of the same shape and place, or NULL for all valid / all true (out_valid is the entry's
+ * Flag_valid_symbol_output).  Channel c consumes its valid entries in order of r.  Outputs, in the handle's own device
+ * buffers (gnsship_dnav_outputs_device) and copied to whichever host pointers are given:
+ *   subframes[c][k], k < counts[c]   one record per decode, in order; slots beyond counts[c] are unspecified
+ *   counts int32[c]
+ *   tow_ms uint32[r*max_channels+c], sflags uint8[...]  r < n_rounds: d_TOW_at_current_symbol_ms after the symbol (the
+ *                                    block outputs it only with GNSSHIP_DNAV_S_VALID_WORD) and GNSSHIP_DNAV_S_*; both 0
+ *                                    for entries that are not symbols
+ * With no host pointer the call is asynchronous on the context stream (host inputs then stay the caller's until the
+ * stream has passed the run). */
+int gnsship_dnav_run_symbols(gnsship_dnav* t, const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int on_device,
+    int32_t n_rounds, gnsship_dnav_subframe* subframes_host, int32_t* counts_host, uint32_t* tow_ms_host, uint8_t* sflags_host);
+/* The same over tracking records of that shape: an entry is a symbol when flags & 1, the symbol is (float)prompt_i and
+ * its output-valid flag is then true; the subframe's sample_counter is the completing record's. */
+int gnsship_dnav_run_records(gnsship_dnav* t, const gnsship_trk_epoch* records, int on_device, int32_t n_rounds,
+    gnsship_dnav_subframe* subframes_host, int32_t* counts_host, uint32_t* tow_ms_host, uint8_t* sflags_host);
+/* The same over the records the tracker's last run left on the device (gnsship_trk_records_device), in place, ordered
+ * on the context stream; before or after gnsship_trk_collect.  n_rounds_out (may be NULL): the rounds of that run, the
+ * first dimension of tow_ms / sflags.  E_STATE if there are no records; E_INVAL if the handles are on different
+ * contexts, their max_channels differ or the run had more rounds than max_rounds. */
+int gnsship_dnav_run_trk(gnsship_dnav* t, gnsship_trk* trk, gnsship_dnav_subframe* subframes_host, int32_t* counts_host,
+    uint32_t* tow_ms_host, uint8_t* sflags_host, int32_t* n_rounds_out);
+/* The handle's output buffers (any pointer may be NULL) and subframes_per_run. */
+int gnsship_dnav_outputs_device(gnsship_dnav* t, gnsship_dnav_subframe** subframes, int32_t** counts, uint32_t** tow_ms,
+    uint8_t** sflags, int32_t* subframes_per_run);
+/* The block's reset(). */
+int gnsship_dnav_reset_channel(gnsship_dnav* t, int32_t channel);
+/* The block's set_satellite(): the PRN (0..63), the symbol duration and the decoder choice; nothing else moves. */
+int gnsship_dnav_set_satellite(gnsship_dnav* t, int32_t channel, int32_t prn);
+/* A new block object on this channel, constructed on this PRN. */
+int gnsship_dnav_new_channel(gnsship_dnav* t, int32_t channel, int32_t prn);
+/* The channel's members after everything run so far (waits for the context stream). */
+int gnsship_dnav_state_get(gnsship_dnav* t, int32_t channel, gnsship_dnav_state* st);
+int gnsship_dnav_destroy(gnsship_dnav* t);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Multi-GPU fan-out: one process per GPU, one RCCL communicator per context.  */

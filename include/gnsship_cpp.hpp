@@ -1905,6 +1905,136 @@ public:
     }
 };
 
+// beidou_b1i_telemetry_decoder_gs / beidou_b3i_telemetry_decoder_gs as gnsship_dnav_conf: max_rounds is the most entries
+// per channel one work_* call may carry.
+inline gnsship_dnav_conf beidou_b1i_tlm_conf(int32_t max_rounds)
+{
+    return gnsship_dnav_conf{max_rounds, GNSSHIP_DNAV_B1I, 0};
+}
+inline gnsship_dnav_conf beidou_b3i_tlm_conf(int32_t max_rounds)
+{
+    return gnsship_dnav_conf{max_rounds, GNSSHIP_DNAV_B3I, 0};
+}
+
+// The BeiDou D1/D2 telemetry decoders up to the time of week for many channels at once, one block object per channel
+// (include/gnsship.h, gnsship_dnav_*): symbols or tracking records in; subframes and the TOW stamp of every entry out.
+// After a work_* call, subframes() / counts() / tow_ms() / sflags() hold that call's outputs.  The two blocks differ in
+// the configuration's signal only: which PRNs take the D2 decoder.
+class Beidou_Dnav_Telemetry_Decoder_Hip {
+public:
+    Beidou_Dnav_Telemetry_Decoder_Hip(const gnsship_dnav_conf& c, int32_t max_channels, int device = 0)
+        : dev_(Device::get(device)), conf_(c), channels_(max_channels)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        if (gnsship_dnav_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
+            throw std::invalid_argument(std::string("gnsship_dnav_create: ") + gnsship_last_error(dev_->ctx()));
+        gnsship_dnav_outputs_device(h_, nullptr, nullptr, nullptr, nullptr, &subframes_per_run_);
+        const size_t nc = static_cast<size_t>(max_channels);
+        subframes_.resize(nc * subframes_per_run_);
+        counts_.resize(nc);
+        tow_ms_.resize(nc * c.max_rounds);
+        sflags_.resize(nc * c.max_rounds);
+    }
+    ~Beidou_Dnav_Telemetry_Decoder_Hip()
+    {
+        if (h_) gnsship_dnav_destroy(h_);
+    }
+    Beidou_Dnav_Telemetry_Decoder_Hip(const Beidou_Dnav_Telemetry_Decoder_Hip&) = delete;
+    Beidou_Dnav_Telemetry_Decoder_Hip& operator=(const Beidou_Dnav_Telemetry_Decoder_Hip&) = delete;
+    const gnsship_dnav_conf& conf() const { return conf_; }
+    int32_t subframes_per_run() const { return subframes_per_run_; }
+    // the block's reset() and set_satellite() on one channel; new_channel: a new block object constructed on this PRN
+    bool reset(int32_t channel)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_dnav_reset_channel(h_, channel) == GNSSHIP_OK;
+    }
+    bool set_satellite(int32_t channel, int32_t prn)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_dnav_set_satellite(h_, channel, prn) == GNSSHIP_OK;
+    }
+    bool new_channel(int32_t channel, int32_t prn)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_dnav_new_channel(h_, channel, prn) == GNSSHIP_OK;
+    }
+    // symbols[r · max_channels + c], r < n_rounds; valid, out_valid: the same shape, or null for all valid / all true
+    bool work_symbols(const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int32_t n_rounds, bool on_device = false)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = n_rounds;
+        return gnsship_dnav_run_symbols(h_, symbols, valid, out_valid, on_device ? 1 : 0, n_rounds, subframes_.data(), counts_.data(), tow_ms_.data(),
+                   sflags_.data()) == GNSSHIP_OK;
+    }
+    // tracking records of that shape: a symbol when flags & 1; the symbol is (float)prompt_i
+    bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = n_rounds;
+        return gnsship_dnav_run_records(h_, records, on_device ? 1 : 0, n_rounds, subframes_.data(), counts_.data(), tow_ms_.data(), sflags_.data()) ==
+               GNSSHIP_OK;
+    }
+    // the records the tracker's last work() left on the device, in place
+    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = 0;
+        return gnsship_dnav_run_trk(h_, trk.handle(), subframes_.data(), counts_.data(), tow_ms_.data(), sflags_.data(), &rounds_) == GNSSHIP_OK;
+    }
+    // the last work_* call's outputs: subframe k < counts()[c] of channel c is subframes()[c · subframes_per_run() + k];
+    // entry (r, c), r < rounds(), is tow_ms()[r · max_channels + c] and sflags()[r · max_channels + c]
+    const std::vector<gnsship_dnav_subframe>& subframes() const { return subframes_; }
+    const std::vector<int32_t>& counts() const { return counts_; }
+    const std::vector<uint32_t>& tow_ms() const { return tow_ms_; }
+    const std::vector<uint8_t>& sflags() const { return sflags_; }
+    int32_t rounds() const { return rounds_; }
+    gnsship_dnav_state state(int32_t channel) const
+    {
+        gnsship_dnav_state st{};
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        gnsship_dnav_state_get(h_, channel, &st);
+        return st;
+    }
+    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
+
+protected:
+    // for the two block classes: the configuration must be their signal's
+    static const gnsship_dnav_conf& require(const gnsship_dnav_conf& c, int32_t signal)
+    {
+        if (c.signal != signal) throw std::invalid_argument("the configuration's signal is not this block's");
+        return c;
+    }
+
+private:
+    std::shared_ptr<Device> dev_;
+    gnsship_dnav_conf conf_;
+    gnsship_dnav* h_ = nullptr;
+    int32_t channels_ = 0, subframes_per_run_ = 0, rounds_ = 0;
+    std::vector<gnsship_dnav_subframe> subframes_;
+    std::vector<int32_t> counts_;
+    std::vector<uint32_t> tow_ms_;
+    std::vector<uint8_t> sflags_;
+};
+
+// beidou_b1i_telemetry_decoder_gs: construct with beidou_b1i_tlm_conf(max_rounds)
+class Beidou_B1i_Telemetry_Decoder_Hip : public Beidou_Dnav_Telemetry_Decoder_Hip {
+public:
+    Beidou_B1i_Telemetry_Decoder_Hip(const gnsship_dnav_conf& c, int32_t max_channels, int device = 0)
+        : Beidou_Dnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_DNAV_B1I), max_channels, device)
+    {
+    }
+};
+
+// beidou_b3i_telemetry_decoder_gs: construct with beidou_b3i_tlm_conf(max_rounds)
+class Beidou_B3i_Telemetry_Decoder_Hip : public Beidou_Dnav_Telemetry_Decoder_Hip {
+public:
+    Beidou_B3i_Telemetry_Decoder_Hip(const gnsship_dnav_conf& c, int32_t max_channels, int device = 0)
+        : Beidou_Dnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_DNAV_B3I), max_channels, device)
+    {
+    }
+};
+
 }  // namespace gnsship
 
 #endif  // GNSSHIP_CPP_HPP

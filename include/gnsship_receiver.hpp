@@ -145,6 +145,12 @@ struct Receiver_Conf {
     // satellite gets a new block object; a channel whose watchdog fires gets the fault message of
     // msg_handler_telemetry_to_trk.  Off (the default): exactly the receiver above, every output byte for byte.
     bool cnav{false};
+    // Optional BeiDou D1/D2 telemetry on the device (beidou_b3i_telemetry_decoder_gs up to the time of week;
+    // Beidou_B3i_Telemetry_Decoder_Hip), B3 channels only (the receiver has no B1I channels).  Each tracking block's
+    // records go through the decoder where tracking left them on the device; a channel that is assigned a satellite gets a
+    // new block object on that PRN.  The blocks publish nothing to tracking, so nothing goes back.  Off (the default):
+    // exactly the receiver above, every output byte for byte.
+    bool dnav{false};
 };
 
 // One control event, in stream order.
@@ -180,6 +186,12 @@ struct Receiver_Subframe {
 struct Receiver_Cnav_Message {
     uint32_t prn;
     gnsship_cnav_message message;
+};
+
+// One BeiDou D1/D2 subframe of a channel (every decode) with the satellite it was tracking.
+struct Receiver_Dnav_Subframe {
+    uint32_t prn;
+    gnsship_dnav_subframe subframe;
 };
 
 class Gnss_Receiver_Hip {
@@ -231,6 +243,11 @@ public:
             const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
             if (l5_) cnav_ = std::make_unique<Gps_L5_Telemetry_Decoder_Hip>(gps_l5_tlm_conf(max_ep), n_, conf_.device);
             else cnav_ = std::make_unique<Gps_L2c_Telemetry_Decoder_Hip>(gps_l2c_tlm_conf(max_ep), n_, conf_.device);
+        }
+        if (conf_.dnav) {
+            if (!b3_) throw std::invalid_argument("Gnss_Receiver_Hip: dnav decodes BeiDou B3I channels (signal B3)");
+            const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
+            dnav_ = std::make_unique<Beidou_B3i_Telemetry_Decoder_Hip>(beidou_b3i_tlm_conf(max_ep), n_, conf_.device);
         }
         if (conf_.use_conditioner) {
             const double fs_out = conf_.input_filter.sampling_frequency / std::max(1, conf_.input_filter.decimation_factor);
@@ -341,6 +358,8 @@ public:
     // a channel's decoder members after everything processed so far.
     const std::vector<Receiver_Cnav_Message>& cnav_messages() const { return cnav_messages_; }
     bool has_cnav() const { return cnav_ != nullptr; }
+    // With conf.dnav: every subframe record in the order the blocks emitted them (channel by channel within a block).
+    const std::vector<Receiver_Dnav_Subframe>& dnav_subframes() const { return dnav_subframes_; }
     gnsship_cnav_state cnav_state(int c) const { return cnav_ ? cnav_->state(c) : gnsship_cnav_state{}; }
     uint64_t position() const { return pos_; }
     unsigned channel_fsm_state(int c) const { return fsm_[static_cast<size_t>(c)].state(); }
@@ -416,6 +435,7 @@ private:
         if (tlm_ && !tlm_->set_satellite(c)) error_ = true;  // nav_->set_satellite (channel.cc:237)
         if (lnav_ && !lnav_->new_channel(c)) error_ = true;  // the channel starts on its satellite with a new block object
         if (cnav_ && !cnav_->new_channel(c)) error_ = true;  // likewise
+        if (dnav_ && !dnav_->new_channel(c, static_cast<int32_t>(prn))) error_ = true;  // likewise, constructed on the PRN
         if (l5_) {  // GpsL5iPcpsAcquisition::set_local_code: the search runs on L5I
             const std::vector<std::complex<float>> code = gps_l5i_acquisition_code(prn, conf_.acq);
             if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
@@ -628,6 +648,13 @@ private:
                 if (cnav_->faults()[static_cast<size_t>(c)] && !trk_->msg_handler_telemetry_to_trk(c, 1)) return false;
             }
         }
+        if (dnav_) {  // and for the BeiDou D1/D2 decoder, which has no fault to hand back
+            if (!dnav_->work_trk(*trk_)) return false;
+            const size_t spr = static_cast<size_t>(dnav_->subframes_per_run());
+            for (int c = 0; c < n_; c++)
+                for (int k = 0; k < dnav_->counts()[static_cast<size_t>(c)]; k++)
+                    dnav_subframes_.push_back({prn_[static_cast<size_t>(c)], dnav_->subframes()[static_cast<size_t>(c) * spr + static_cast<size_t>(k)]});
+        }
         recs_.resize(static_cast<size_t>(n_));
         for (int c = 0; c < n_; c++) {
             bool lost = false;
@@ -680,6 +707,8 @@ private:
     std::vector<Receiver_Subframe> subframes_;
     std::unique_ptr<Gps_Cnav_Telemetry_Decoder_Hip> cnav_;  // the optional GPS CNAV telemetry (L2C or L5)
     std::vector<Receiver_Cnav_Message> cnav_messages_;
+    std::unique_ptr<Beidou_B3i_Telemetry_Decoder_Hip> dnav_;  // the optional BeiDou D1/D2 telemetry (B3I)
+    std::vector<Receiver_Dnav_Subframe> dnav_subframes_;
     std::unique_ptr<Freq_Xlating_Fir_Filter_Hip> cond_;  // the optional conditioner stage
     int64_t cond_block_ = 0;                             // its run size, in input samples
     std::vector<std::complex<float>> cond_host_;

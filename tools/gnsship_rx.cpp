@@ -14,7 +14,7 @@
 //              [--pll-bw 40] [--dll-bw 4] [--order 3] [--pull-in-time-s 10] [--rotator auto|generic|avx]
 //              [--max-carrier-lock-fail 5000] [--max-code-lock-fail 50] [--cn0-min 25]
 //              [--block-ms 100] [--acq-piece 8192] [--dump PREFIX] [--events CSV] [--records BIN]
-//              [--telemetry] [--telemetry-mode reference|full] [--lnav] [--cnav]
+//              [--telemetry] [--telemetry-mode reference|full] [--lnav] [--cnav] [--dnav]
 //              [--if-hz 0] [--decimation 1] [--filter-bw 0] [--filter-tw 0]
 //              [--input-filter pulse-blanking|notch|notch-lite] [--input-filter-pfa P] [--segment-length 32]
 //              [--segments-est 12500] [--segments-reset 5000000] [--p-c-factor 0.9] [--coeff-rate R]
@@ -33,6 +33,10 @@
 // symbol counter, the message's PRN, ID, TOW in 6-second units, alert, delay, part, ok / fail, the 38 bytes in hex; then per
 // channel one "cnav-state" line with the decoder's members (the arrays as weighted sums, as tests/cpp/cnav_mirror_test
 // prints them).  A telemetry fault goes back to the channel's tracking.
+//
+// --dnav (with --signal B3) sends each tracking block's records through the device BeiDou D1/D2 telemetry decoder and
+// prints, ahead of the summary, one line per decoded subframe: channel, PRN, symbol counter, FraID, Pnum, SOW, the TOW in
+// ms after the stamp, the corrected-rows mask and the flags in hex, the ten words in hex.
 //
 // --input-filter puts the interference mitigation (InputFilter.implementation = Pulse_Blanking_Filter, Notch_Filter or
 // Notch_Filter_Lite; pfa, length, segments_est, segments_reset, p_c_factor, coeff_rate: 0 = the adapter's defaults)
@@ -162,6 +166,7 @@ int main(int argc, char** argv)
         else if (a == "--telemetry") rc.telemetry = true;
         else if (a == "--lnav") rc.lnav = true;
         else if (a == "--cnav") rc.cnav = true;
+        else if (a == "--dnav") rc.dnav = true;
         else if (a == "--telemetry-mode") {
             const std::string m = val();
             if (m != "reference" && m != "full") usage("--telemetry-mode must be reference or full");
@@ -203,6 +208,7 @@ int main(int argc, char** argv)
         usage("--signal must be 1C, L5, 2S, B3, 5X, 7X, 1G or 2G");
     if (rc.lnav && signal != "1C") usage("--lnav decodes GPS L1 C/A channels (--signal 1C)");
     if (rc.cnav && signal != "2S" && signal != "L5") usage("--cnav decodes GPS L2C or L5 channels (--signal 2S or L5)");
+    if (rc.dnav && signal != "B3") usage("--dnav decodes BeiDou B3I channels (--signal B3)");
     std::snprintf(rc.trk.signal, sizeof(rc.trk.signal), "%s", signal.c_str());
     if (signal == "B3") rc.trk.system = 'C';  // otherwise 'G'
     if (signal == "5X" || signal == "7X") rc.trk.system = 'E';
@@ -387,6 +393,14 @@ int main(int argc, char** argv)
                 p.old_is_metrics2, p.preamble_seen, p.invert, p.message_lock, p.crc_ok, p.init, static_cast<unsigned long long>(metrics),
                 static_cast<unsigned long long>(decisions), static_cast<unsigned long long>(symbols), static_cast<unsigned long long>(decoded));
         }
+        std::printf("\n");
+    }
+    // --dnav: one line per decoded subframe
+    for (const auto& ds : rx.dnav_subframes()) {
+        const gnsship_dnav_subframe& f = ds.subframe;
+        std::printf("dnav-subframe channel %d prn %u symbol %llu fraid %d pnum %d sow %u tow_ms %u corrected %05x flags %02x", f.channel, ds.prn,
+            static_cast<unsigned long long>(f.symbol_counter), f.fra_id, f.pnum, f.sow, f.tow_at_current_symbol_ms, f.corrected_mask, f.flags);
+        for (int w = 0; w < 10; w++) std::printf(" %08x", f.words[w]);
         std::printf("\n");
     }
     int n_pos = 0, n_neg = 0, n_lost = 0;
