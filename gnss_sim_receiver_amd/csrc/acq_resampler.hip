@@ -18,7 +18,14 @@
 //
 // Device form: one 256-lane workgroup per tile of up to 256 outputs; the tile's input span
 // ((outputs − 1)·D + ntaps samples, converted from the IF format in the load) and the reversed
-// taps are staged in LDS once, then lane j forms output j serially.  HBM traffic is one read of
+// taps are staged in LDS once, then lane j forms output j serially.  The tile has
+// opb = min(256, (8192 − ntaps)/D + 1) outputs, so the span holds at most 8192 float2 (64 KiB); the
+// taps lie beside it, padded to a float2 ((ntaps + 1)/2 float2, up to 16 KiB).  Dynamic LDS is
+// 8·((ntaps + 1)/2 + (opb − 1)·D + ntaps) B: 81 920 B at most (4096 taps, D = 4096), and above
+// 64 KiB already for the automatic design at 100 Msps (241 taps, D = 50: 66 496 B); a gfx950
+// workgroup has 160 KiB and the launches run as they are
+// (tests/test_gpu_acq_resampler_coverage.py runs every tile shape and size).  A tile's
+// shape changes no bit: every output is a serial sum over its own window.  HBM traffic is one read of
 // the input plus the decimated output (2 or 8 B in, 8/D B out per input sample) — a streaming
 // kernel far below the HBM roofline at receiver rates; it runs once per acquisition dwell.
 #include <cmath>
@@ -43,7 +50,7 @@ namespace {
 
 constexpr int kFirThreads = 256;
 constexpr int kFirMaxTaps = 4096;
-constexpr int kFirSpanMax = 8192;  // float2 samples of input span staged per workgroup (64 KiB)
+constexpr int kFirSpanMax = 8192;  // float2 samples of input span staged per workgroup (64 KiB; the taps, up to 16 KiB, lie beside it)
 
 template <int FMT>
 __device__ __forceinline__ float2 fir_load(const void* in, int64_t i)
@@ -186,8 +193,8 @@ extern "C" int gnsship_acq_resampler_create(gnsship_ctx* ctx, const float* taps,
     *out = nullptr;
     if (!taps || n_taps < 1 || n_taps > kFirMaxTaps || decimation < 1 || max_in_samples < decimation)
         return fail(ctx, GNSSHIP_E_INVAL, "gnsship_acq_resampler_create: 1 <= n_taps <= 4096, decimation >= 1, max_in_samples >= decimation");
+    // >= 1: n_taps <= kFirMaxTaps < kFirSpanMax, so one output's window always fits the span
     const int opb = static_cast<int>(std::min<int64_t>(kFirThreads, (kFirSpanMax - n_taps) / decimation + 1));
-    if (opb < 1) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_acq_resampler_create: decimation x taps exceed the LDS span");
     if (int rc = set_device(ctx)) return rc;
     gnsship_acq_resampler* r = new (std::nothrow) gnsship_acq_resampler();
     if (!r) return GNSSHIP_E_NOMEM;

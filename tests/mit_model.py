@@ -138,6 +138,7 @@ class Model:
         self.samples_in = self.samples_out = 0
         self.chunks_speculated = self.chunks_replayed = 0
         self.codes, self.ratios = [], []  # per segment since reset: code, E/(noise·thres) of detection segments
+        self.n_trace = []                 # per segment since reset: n_segments_ on entry
         self.est_err = 0.0                # largest relative error of the float32 noise estimate against float64
 
     @property
@@ -168,6 +169,7 @@ class Model:
         zseg = [None] * nseg
         for s in range(nseg):
             n = self.n_segments
+            self.n_trace.append(n)
             if n < self.n_est and not self.flag:
                 if notch:
                     lin, lin64 = estimate32(cur[s]), estimate64(cur[s])

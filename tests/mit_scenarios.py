@@ -152,3 +152,151 @@ def long_case(kind, n_coeff):
         return x, th, m, y
     return cached(("long", kind, n_coeff), make)
 
+
+
+# ---- coverage scenarios (tests/test_gpu_mit_coverage.py; conditions asserted in tests/test_mit_model.py) ----
+
+# Segment lengths beside the strides of the kernels: no whole group of 8 in mit_chain (2), whole groups and a remainder
+# (13, 255, 257), one below and one above the 256-lane strides of the DFT and the LDS loads (255, 257).
+COV_LENGTHS = (2, 13, 255, 257)
+COV_N_COEFF = 3
+
+
+# Lengths 2 and 13: the adapters' pfa = 0.001.  Lengths 255 and 257: as at 1024 the pfa threshold (614, 619) lies
+# below noise alone — the model's E/noise is 565 to 1060 on noise, 3200 and more where the tone covers part of a
+# segment, 11 800 and more where it covers all of it — so 2000 lets the tone decide.
+def cov_notch_thres(length):
+    return 2000.0 if length >= 255 else thres_pfa(0.001, length)
+
+
+# seeds at which every detection segment has E/(noise·thres) outside [1 − 1e-3, 1 + 1e-3], picked as NOTCH_SEEDS was:
+# the first from 101 on (tests/test_mit_model.py::test_coverage_lengths_keep_clear_of_the_threshold)
+COV_NOTCH_SEEDS = {(M.NOTCH, 2): 101, (M.NOTCH, 13): 101, (M.NOTCH, 255): 101, (M.NOTCH, 257): 101,
+                   (M.NOTCH_LITE, 2): 101, (M.NOTCH_LITE, 13): 101, (M.NOTCH_LITE, 255): 101, (M.NOTCH_LITE, 257): 101}
+
+
+def run_cut_sample(length, n):
+    """The cut of the two-run tests: RUN_CUT_SEG on the (compressed) pattern of cw_gated, inside a tone span."""
+    scale = min(1.0, (n / length) / 300.0)
+    return int(RUN_CUT_SEG * scale * length)
+
+
+def cov_length_case(kind, length):
+    """(stream, threshold, model after one whole run, model output) for a coverage length."""
+    def make():
+        if kind == M.PULSE_BLANKING:
+            x, th = pulsed(length), thres_pfa(0.04, length)
+        else:
+            x, th = cw_gated(length, COV_NOTCH_SEEDS[(kind, length)]), cov_notch_thres(length)
+        m = M.Model(kind, th, length, N_EST, N_RESET, p_c=0.9, n_coeff=COV_N_COEFF)
+        y = m.run(x)
+        return x, th, m, y
+    return cached(("cov-length", kind, length), make)
+
+
+COV_CHAIN_LENGTHS = (13, 257)
+
+
+def cov_chain_case(length, p_c, chunk_samples, warmup_samples):
+    """cw_continuous through the notch at a coverage length, the speculative form emulated."""
+    def make():
+        x = cw_continuous(CHAIN_N, CHAIN_SEED)
+        th = cov_notch_thres(length)
+        m = M.Model(M.NOTCH, th, length, N_EST, 5000000, p_c=p_c, chunk_samples=chunk_samples, warmup_samples=warmup_samples)
+        y = m.run(x)
+        return x, th, m, y
+    return cached(("cov-chain", length, p_c, chunk_samples, warmup_samples), make)
+
+
+def segs_to_samples(kind, seg_counts):
+    """Run lengths in samples that emit the given numbers of segments run after run: the notch emits a segment one
+    sample late (its one-sample advance), so its first run takes one sample more."""
+    out = [c * LONG_LENGTH for c in seg_counts]
+    if kind == M.NOTCH and out:
+        out[0] += 1
+    return out
+
+
+def gated_by_segment(kind, on_segments, seed=LONG_SEED, amp=8.0):
+    """8192 segments of 8 samples, the tone on over exactly the block's segments named by the boolean array: the notch's
+    segment s holds input samples s·8 + 1 .. s·8 + 8, the other blocks' s·8 .. s·8 + 7."""
+    x = noise(LONG_N, seed)
+    t = np.arange(LONG_N)
+    shift = 1 if kind == M.NOTCH else 0
+    seg = (t - shift) // LONG_LENGTH
+    on = np.where(seg >= 0, np.asarray(on_segments, bool)[np.clip(seg, 0, None)], False)
+    return (x + on * amp * np.exp(2j * np.pi * 0.0731 * t)).astype(np.complex64)
+
+
+# Runs of filtered segments against the scan's tiles of 1024: one tile exactly; across an edge; a single segment last
+# in a tile ("a") or first in a tile ("b": adjacent single segments would be one run, so there are two streams); one
+# longer than two tiles, so that tiles 5 and 6 lie wholly inside it.
+EDGE_RUNS = {"a": ((1024, 2048), (3071, 3073), (4095, 4096), (5000, 7500)),
+             "b": ((1024, 2048), (3071, 3073), (4096, 4097), (5000, 7500))}
+EDGE_CUT_SEGS = (1023, 1025, 2049)
+
+
+def edge_on_segments(which):
+    on = np.zeros(LONG_N // LONG_LENGTH, bool)
+    for a, b in EDGE_RUNS[which]:
+        on[a:b] = True
+    return on
+
+
+def edge_case(kind, n_coeff, which):
+    def make():
+        x = gated_by_segment(kind, edge_on_segments(which))
+        th = 200.0  # as long_case: between noise alone and the tone
+        m = M.Model(kind, th, LONG_LENGTH, N_EST, 5000000, p_c=0.9, n_coeff=n_coeff)
+        y = m.run(x)
+        return x, th, m, y
+    return cached(("edge", kind, n_coeff, which), make)
+
+
+# A reset among the tiles: the gating of long_gated with n_segments_reset = 3000.  RESET_CUT_SEGS: run 2 starts with
+# n_segments = 2001 = n_reset − 1000 + 1 (walked), run 3 starts at segment 3001, where the reset falls, run 4 starts
+# with n_segments = 2000 = n_reset − 1000 (decided at once): the two sides of the scan's decision.
+RESET_N_RESET = 3000
+RESET_CUT_SEGS = (2001, 1000, 2000, 1000)
+
+
+def reset_on_segments():
+    return (np.arange(LONG_N // LONG_LENGTH) % 1000) >= 300
+
+
+def reset_case(kind, n_coeff=COV_N_COEFF):
+    def make():
+        x = gated_by_segment(kind, reset_on_segments())
+        th = 200.0
+        m = M.Model(kind, th, LONG_LENGTH, N_EST, RESET_N_RESET, p_c=0.9, n_coeff=n_coeff)
+        y = m.run(x)
+        return x, th, m, y
+    return cached(("reset", kind, n_coeff), make)
+
+
+ZERO_LENGTH = 32
+
+
+def leading_zeros_case(kind):
+    """3·n_est all-zero segments, then the content of the length-32 scenarios.  Pulse blanking's estimate is 0 and the
+    ratios after it are 0/0 and x/0; the notches' is the 1e-20 of the power spectrum."""
+    def make():
+        L = ZERO_LENGTH
+        if kind == M.PULSE_BLANKING:
+            tail, th = pulsed(L), thres_pfa(0.04, L)
+        else:
+            tail, th = cw_gated(L, NOTCH_SEEDS[(kind, L)]), notch_thres(L)
+        x = np.concatenate([np.zeros(3 * N_EST * L, np.complex64), tail])
+        m = M.Model(kind, th, L, N_EST, N_RESET, p_c=0.9, n_coeff=COV_N_COEFF)
+        y = m.run(x)
+        return x, th, m, y
+    return cached(("zeros", kind), make)
+
+
+def cov_notch_models():
+    """Every new notch scenario's model, for the estimate's tolerance (four times the worst est_err)."""
+    out = [cov_length_case(k, L)[2] for k in (M.NOTCH, M.NOTCH_LITE) for L in COV_LENGTHS]
+    out += [edge_case(k, COV_N_COEFF, w)[2] for k in (M.NOTCH, M.NOTCH_LITE) for w in EDGE_RUNS]
+    out += [reset_case(k)[2] for k in (M.NOTCH, M.NOTCH_LITE)]
+    out += [leading_zeros_case(k)[2] for k in (M.NOTCH, M.NOTCH_LITE)]
+    return out

@@ -155,3 +155,168 @@ def test_speculation_prediction_on_the_continuous_cw_stream():
     chunk, warm = S.chain_geometry(1.0)
     x, th, m, y = S.chain_case(1.0, chunk, warm)
     assert m.chunks_speculated > 0 and m.chunks_replayed > 0
+
+
+# ---- the coverage scenarios of tests/test_gpu_mit_coverage.py ----
+
+def runs_of(codes):
+    """Maximal runs [a, b) of filtered segments."""
+    c = np.concatenate([[0], (np.asarray(codes) != 0).astype(np.int8), [0]])
+    d = np.diff(c)
+    return list(zip(np.nonzero(d == 1)[0].tolist(), np.nonzero(d == -1)[0].tolist()))
+
+
+@pytest.mark.parametrize("kind", [M.NOTCH, M.NOTCH_LITE])
+@pytest.mark.parametrize("length", S.COV_LENGTHS)
+def test_coverage_lengths_keep_clear_of_the_threshold(kind, length):
+    """As test_notch_scenarios_keep_clear_of_the_threshold, for the lengths 2, 13, 255, 257; the cut of the two-run test
+    lies inside a filtered run; the thresholds at 255 and 257 lie between noise alone and the tone."""
+    M.require_glibc()
+    x, th, m, y = S.cov_length_case(kind, length)
+    r = np.array(m.ratios)
+    c = np.bincount(np.array(m.codes), minlength=3)
+    print(f"kind {kind} length {length} threshold {th:.1f} seed {S.COV_NOTCH_SEEDS[(kind, length)]}: codes {c.tolist()}, "
+          f"smallest |ratio - 1| {np.abs(r - 1.0).min():.3e}, est_err {m.est_err:.3e}")
+    assert np.all(np.abs(r - 1.0) > 1e-3), np.abs(r - 1.0).min()
+    assert c[0] > S.N_EST and c[1] > 0 and c[2] >= 3
+    assert m.est_err < 1e-4
+    cs = (S.run_cut_sample(length, len(x)) - m.off) // length   # the segment the cut falls in
+    assert m.codes[cs - 1] != 0 and m.codes[cs] != 0 and m.codes[cs + 1] != 0
+    if length >= 255:
+        assert S.thres_pfa(0.001, length) < 700 < th                      # the pfa threshold: below noise alone
+        assert np.median(r[r < 1.0]) * th > S.thres_pfa(0.001, length)        # noise alone sits above the pfa threshold
+        assert np.median(r[r < 1.0]) < 0.5 and r[r < 1.0].max() < 0.8 and r[r > 1.0].min() > 1.2   # the two decisions, well apart
+
+
+@pytest.mark.parametrize("length", S.COV_LENGTHS)
+def test_coverage_lengths_pulse_blanking_decides_both_ways(length):
+    x, th, m, y = S.cov_length_case(M.PULSE_BLANKING, length)
+    c = np.bincount(np.array(m.codes), minlength=2)
+    assert c[0] > S.N_EST and c[1] >= 3
+    assert max(m.n_trace) > S.N_RESET and m.n_trace.count(1) >= 2         # resets and new estimation windows
+
+
+@pytest.mark.parametrize("length", S.COV_CHAIN_LENGTHS)
+def test_coverage_chain_is_one_unbroken_run(length):
+    M.require_glibc()
+    chunk, warm = S.chain_geometry(0.9, length)
+    assert chunk % length == 0 and warm % length == 0 and chunk >= 2048
+    x, th, m, y = S.cov_chain_case(length, 0.9, chunk, warm)
+    c = np.array(m.codes)
+    assert np.all(c[S.N_EST + 1:] == 1) and c[S.N_EST] == 2
+    assert np.all(np.abs(np.array(m.ratios) - 1.0) > 1e-3)
+    assert m.chunks_speculated >= 10 and m.chunks_replayed == 0
+    chunk, warm = S.chain_geometry(1.0, length)
+    x, th, m, y = S.cov_chain_case(length, 1.0, chunk, warm)
+    assert m.chunks_speculated > 0 and m.chunks_replayed > 0
+
+
+@pytest.mark.parametrize("which", sorted(S.EDGE_RUNS))
+@pytest.mark.parametrize("kind,n_coeff", [(M.PULSE_BLANKING, 1), (M.NOTCH, 1), (M.NOTCH_LITE, 3), (M.NOTCH_LITE, 5000)])
+def test_tile_edge_runs_are_exactly_the_gating(kind, n_coeff, which):
+    """The model filters exactly the gated segments: a run that is one scan tile of 1024, one across a tile edge, a
+    single segment last (a) or first (b) in a tile, and one with two tiles wholly inside it; no reset, so every tile
+    past the first is decided at once."""
+    M.require_glibc()
+    x, th, m, y = S.edge_case(kind, n_coeff, which)
+    assert len(m.codes) == 8192 - (1 if kind == M.NOTCH else 0)
+    assert tuple(runs_of(m.codes)) == S.EDGE_RUNS[which]
+    runs = S.EDGE_RUNS[which]
+    assert (1024, 2048) in runs and (3071, 3073) in runs
+    assert ((4095, 4096) in runs) != ((4096, 4097) in runs)
+    a, b = runs[-1]
+    assert b - a > 2048 and sum(a <= t and t + 1024 <= b for t in range(0, 8192, 1024)) >= 2
+    assert np.all(np.abs(np.array(m.ratios) - 1.0) > 1e-3)
+    assert m.n_trace == list(range(len(m.codes)))                         # never reset
+    # the cut form: runs of 1023, 1025, 2049 segments and the rest, equal to the whole
+    mc = M.Model(kind, th, S.LONG_LENGTH, S.N_EST, 5000000, p_c=0.9, n_coeff=n_coeff)
+    emitted, outs, pos = [], [], 0
+    for n in S.segs_to_samples(kind, S.EDGE_CUT_SEGS) + [len(x)]:
+        outs.append(mc.run(x[pos:pos + n]))
+        emitted.append(len(outs[-1]) // S.LONG_LENGTH)
+        pos += n
+    assert tuple(emitted[:3]) == S.EDGE_CUT_SEGS and sum(emitted) == len(m.codes)
+    assert np.array_equal(np.concatenate(outs).view(np.uint32), y.view(np.uint32)) and mc.codes == m.codes
+
+
+def tile_kinds(n_trace, run_starts, n_est, n_reset, tile=1024):
+    """(base within the run, absolute first segment, decided at once?) for every scan tile of every run."""
+    out = []
+    bounds = list(run_starts) + [len(n_trace)]
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        for base in range(0, b - a, tile):
+            ln = min(tile, b - a - base)
+            n = n_trace[a + base]
+            out.append((base, a + base, ln, n, n >= n_est and n <= n_reset - ln))
+    return out
+
+
+@pytest.mark.parametrize("kind", [M.PULSE_BLANKING, M.NOTCH, M.NOTCH_LITE])
+def test_reset_falls_among_the_tiles(kind):
+    """From the model's n_segments trace: in one whole run tiles of both kinds occur past the first, and a reset with
+    its new estimation window falls in a walked tile with base >= 2048.  In the cut form one run starts with n_segments
+    == n_reset − nseg exactly (decided at once) and one with one more (walked)."""
+    M.require_glibc()
+    x, th, m, y = S.reset_case(kind)
+    tr = m.n_trace
+    tiles = tile_kinds(tr, [0], S.N_EST, S.RESET_N_RESET)
+    past_first = [t for t in tiles if t[0] > 0]
+    assert any(t[4] for t in past_first) and any(not t[4] for t in past_first)
+    resets = [s for s in range(1, len(tr)) if tr[s] == 1 and tr[s - 1] > S.RESET_N_RESET]   # first segment of a new window
+    assert len(resets) >= 2
+    hit = 0
+    for s in resets:
+        base = (s // 1024) * 1024
+        walked = not [t for t in tiles if t[0] == base][0][4]
+        window = tr[s: s + S.N_EST - 1] == list(range(1, S.N_EST))
+        if base >= 2048 and walked and window and base + 1024 >= s + S.N_EST:
+            hit += 1
+            assert all(c == 0 for c in m.codes[s - 1: s + S.N_EST - 1])          # the reset segment and the window are copied
+    assert hit >= 1
+    if kind != M.PULSE_BLANKING:
+        assert np.all(np.abs(np.array(m.ratios) - 1.0) > 1e-3)
+    c = np.bincount(np.array(m.codes), minlength=3)
+    assert c[0] > 2000 and c[1] + c[2] > 4000
+    # the cut form
+    mc = M.Model(kind, th, S.LONG_LENGTH, S.N_EST, S.RESET_N_RESET, p_c=0.9, n_coeff=S.COV_N_COEFF)
+    starts, outs, pos, sides = [], [], 0, []
+    for n in S.segs_to_samples(kind, S.RESET_CUT_SEGS) + [len(x)]:
+        n_before, seg0 = mc.n_segments, len(mc.codes)
+        outs.append(mc.run(x[pos:pos + n]))
+        nseg = len(mc.codes) - seg0
+        starts.append(seg0)
+        sides.append((n_before - (S.RESET_N_RESET - nseg), nseg))
+        pos += n
+    assert np.array_equal(np.concatenate(outs).view(np.uint32), y.view(np.uint32)) and mc.n_trace == tr
+    assert [s[1] for s in sides[:4]] == list(S.RESET_CUT_SEGS)
+    assert sides[1] == (1, 1000) and sides[3] == (0, 1000)                # one more, and exactly; both single tiles
+    assert starts[2] in resets or starts[2] + 1 in resets                  # run 3 starts where the reset falls
+    cut_tiles = tile_kinds(tr, starts, S.N_EST, S.RESET_N_RESET)
+    assert [t[4] for t in cut_tiles if t[1] == starts[1]] == [False] and [t[4] for t in cut_tiles if t[1] == starts[3]] == [True]
+
+
+@pytest.mark.parametrize("kind", [M.PULSE_BLANKING, M.NOTCH, M.NOTCH_LITE])
+def test_leading_zeros_give_a_zero_or_floor_estimate(kind):
+    M.require_glibc()
+    x, th, m, y = S.leading_zeros_case(kind)
+    L = S.ZERO_LENGTH
+    assert not np.any(x[:3 * S.N_EST * L]) and np.any(x[3 * S.N_EST * L:])
+    r = np.array(m.ratios)
+    c = np.bincount(np.array(m.codes), minlength=3)
+    if kind == M.PULSE_BLANKING:
+        assert m.noise == 0.0
+        assert np.isnan(r).sum() >= 2 * S.N_EST - 1 and np.isinf(r).sum() > 250   # 0/0 on the zeros, x/0 after them
+        assert c[0] >= 3 * S.N_EST and c[1] > 250
+        assert not np.any(y)                                                       # copies of zeros, then blanked
+    else:
+        assert 0.0 < float(m.noise) < 1e-20 and m.noise64 > 0.0
+        assert np.all((r == 0.0) | (r > 1e6))
+        assert c[0] >= 3 * S.N_EST - 1 and c[1] > 250 and c[2] == 1
+        assert m.est_err < 1e-4
+
+
+def test_coverage_estimate_tolerance_is_taken_over_the_new_streams():
+    M.require_glibc()
+    worst = max(m.est_err for m in S.cov_notch_models())
+    print(f"largest float32-against-float64 error of the noise estimate over the coverage streams {worst:.3e}")
+    assert 0.0 < worst < 1e-4
