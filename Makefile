@@ -127,6 +127,12 @@ $(DNAV_MIRROR_TEST): tests/cpp/dnav_mirror_test.cpp include/gnsship_cpp.hpp incl
 	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/dnav_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
 all: $(DNAV_MIRROR_TEST)
 
+# The GLONASS GNAV telemetry decoder mirror (tests/test_cpp_mirror_gnav.py)
+GNAV_MIRROR_TEST := tests/cpp/gnav_mirror_test
+$(GNAV_MIRROR_TEST): tests/cpp/gnav_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
+	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/gnav_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
+all: $(GNAV_MIRROR_TEST)
+
 # Profiling variant (workgroup phase timestamps in corr_batch_kernel; scripts/corr_wg_profile.py)
 PROF_LIB := scripts/libgnsship_prof.so
 PROF_OBJS := $(patsubst $(CSRC)/%.hip,$(PROF_OBJDIR)/%.o,$(HIP_SRCS)) $(patsubst $(CSRC)/%.cpp,$(PROF_OBJDIR)/%.cpp.o,$(CPP_SRCS))

@@ -323,6 +323,38 @@ DNAV_SUBFRAME_DTYPE = np.dtype([("symbol_counter", "<u8"), ("sample_counter", "<
                                 ("tow_at_current_symbol_ms", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
 assert DNAV_SUBFRAME_DTYPE.itemsize == 88
 
+# gnsship_gnav_conf.signal
+GNAV_L1CA, GNAV_L2CA = 0, 1
+# gnsship_gnav_string.flags
+GNAV_CRC_OK, GNAV_CORRECTED, GNAV_INVERTED, GNAV_NEW_TOW, GNAV_SLOT_UPDATED, GNAV_NEW_EPHEMERIS, GNAV_NEW_UTC_MODEL = 1, 2, 4, 8, 16, 32, 64
+# sflags of an entry (GNSSHIP_GNAV_S_*)
+GNAV_S_VALID_WORD, GNAV_S_STRING, GNAV_S_INVERTED = 1, 2, 4
+
+
+def gnav_strings_per_run(max_rounds: int) -> int:
+    """GNSSHIP_GNAV_STRINGS_PER_RUN."""
+    return max_rounds // 2000 + 1
+
+
+class GnavConf(ctypes.Structure):
+    """gnsship_gnav_conf — the most entries per channel one run may carry, and the signal (GNAV_L1CA / GNAV_L2CA)."""
+    _fields_ = [("max_rounds", ctypes.c_int32), ("signal", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+GNAV_STRING_DTYPE = np.dtype([("symbol_counter", "<u8"), ("sample_counter", "<u8"), ("tow", "<f8"), ("bits", "<u4", (3,)), ("channel", "<i4"),
+                              ("prn", "<i4"), ("string_id", "<i4"), ("flipped_bit", "<i4"), ("tow_at_current_symbol_ms", "<u4"),
+                              ("flags", "<u4"), ("reserved", "<u4")])
+assert GNAV_STRING_DTYPE.itemsize == 64
+# gnsship_gnav_state — the members of one channel's glonass_l1_ca / glonass_l2_ca_telemetry_decoder_gs object and of its
+# navigation object, the string in flight and the history's sign bits
+GNAV_STATE_DTYPE = np.dtype([("symbol_counter", "<u8"), ("preamble_index", "<u8"), ("tow_at_current_symbol", "<f8"), ("tow", "<f8"),
+                             ("tau_c", "<f8"), ("tau_gps", "<f8"), ("chip_acc", "<f8"), ("stat", "<i4"), ("crc_error_counter", "<i4"),
+                             ("history_size", "<i4"), ("prn", "<i4"), ("wn", "<i4"), ("t_k", "<u4"), ("t_b", "<u4"), ("previous_tb", "<u4"),
+                             ("n_t", "<u4"), ("n", "<u4"), ("n_4", "<u4"), ("frame_sync", "u1"), ("ephemeris_str", "u1", (4,)),
+                             ("utc_model_str_5", "u1"), ("tow_set", "u1"), ("tow_new", "u1"), ("reserved", "u1", (4,)),
+                             ("half_pos", "<u4", (6,)), ("half_neg", "<u4", (6,)), ("history", "<u4", (64,))])
+assert GNAV_STATE_DTYPE.itemsize == 416
+
 SYS_GPS_L1CA, SYS_GAL_E1, SYS_BDS_B1I, SYS_GPS_L5, SYS_BDS_B3I, SYS_GPS_L2C = 0, 1, 2, 3, 4, 5
 SYS_GAL_E5A, SYS_GAL_E5B = 6, 7
 SYS_GLO_L1CA, SYS_GLO_L2CA = 8, 9  # glonass_l1_ca / glonass_l2_ca_dll_pll_tracking_cc (include/gnsship.h)
@@ -590,6 +622,16 @@ _SIGNATURES = {
     "gnsship_dnav_new_channel": ([_vp, ctypes.c_int32, ctypes.c_int32], _i),
     "gnsship_dnav_state_get": ([_vp, ctypes.c_int32, ctypes.POINTER(DnavState)], _i),
     "gnsship_dnav_destroy": ([_vp], _i),
+    "gnsship_gnav_create": ([_vp, ctypes.POINTER(GnavConf), ctypes.c_int32, _vpp], _i),
+    "gnsship_gnav_run_symbols": ([_vp, _vp, _vp, _vp, _i, ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
+    "gnsship_gnav_run_records": ([_vp, _vp, _i, ctypes.c_int32, _vp, _vp, _vp, _vp], _i),
+    "gnsship_gnav_run_trk": ([_vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int32)], _i),
+    "gnsship_gnav_outputs_device": ([_vp, _vpp, _vpp, _vpp, _vpp, ctypes.POINTER(ctypes.c_int32)], _i),
+    "gnsship_gnav_set_satellite": ([_vp, ctypes.c_int32, ctypes.c_int32], _i),
+    "gnsship_gnav_new_channel": ([_vp, ctypes.c_int32, ctypes.c_int32], _i),
+    "gnsship_gnav_state_get": ([_vp, ctypes.c_int32, _vp], _i),
+    "gnsship_gnav_state_set": ([_vp, ctypes.c_int32, _vp], _i),
+    "gnsship_gnav_destroy": ([_vp], _i),
     "gnsship_trk_set_trace": ([_vp, _i], _i),
     "gnsship_trk_trace_records": ([_vp, _vp, _i], _i),
     "gnsship_trk_channel_state": ([_vp, _i, ctypes.POINTER(_i), ctypes.POINTER(ctypes.c_uint64)], _i),

@@ -1485,6 +1485,139 @@ def beidou_b3i_telemetry(ctx: Context, max_channels: int, max_rounds: int) -> Be
     return BeidouDnavTelemetryDecoder(ctx, max_channels, max_rounds, abi.DNAV_B3I)
 
 
+class GnavResult(NamedTuple):
+    """One gnsship_gnav run: strings [max_channels, strings_per_run] (abi.GNAV_STRING_DTYPE; slots k >= counts[c] are
+    unspecified), counts int32[max_channels], and the block's output stream per entry: tow_ms uint32[n_rounds, max_channels],
+    sflags uint8[n_rounds, max_channels] (abi.GNAV_S_*), both 0 where the entry is no symbol."""
+    strings: np.ndarray
+    counts: np.ndarray
+    tow_ms: np.ndarray
+    sflags: np.ndarray
+
+
+class GlonassGnavTelemetryDecoder:
+    """glonass_l1_ca_telemetry_decoder_gs (signal abi.GNAV_L1CA) or glonass_l2_ca_telemetry_decoder_gs (abi.GNAV_L2CA) up to the
+    time of week for up to ``channels`` channels on the device, one block object per channel: the 2000-symbol history, the
+    time-mark correlation over its 300 oldest entries, three-state frame sync, the double half-bit sums, the Hamming check
+    with its single-bit correction, what strings 1..5 give the time of week, glot_to_gpst and the double TOW stamp with
+    valid_word (include/gnsship.h, gnsship_gnav_*).  max_rounds: the most entries per channel one run may carry."""
+
+    def __init__(self, ctx: Context, channels: int, max_rounds: int, signal: int):
+        self.ctx = ctx
+        self.h = None
+        self.signal, self.max_channels, self.max_rounds = int(signal), int(channels), int(max_rounds)
+        self.conf = abi.GnavConf(max_rounds=self.max_rounds, signal=self.signal, reserved=0)
+        h = ctypes.c_void_p()
+        check(ctx.lib.gnsship_gnav_create(ctx.h, ctypes.byref(self.conf), self.max_channels, ctypes.byref(h)), "gnsship_gnav_create", ctx.h)
+        self.h = h
+        spr = ctypes.c_int32()
+        check(ctx.lib.gnsship_gnav_outputs_device(self.h, None, None, None, None, ctypes.byref(spr)), "gnsship_gnav_outputs_device", ctx.h)
+        self.strings_per_run = spr.value
+
+    def _outputs(self, host: bool, n_rounds: int):
+        if not host:
+            return None, (None, None, None, None)
+        res = GnavResult(np.zeros((self.max_channels, self.strings_per_run), abi.GNAV_STRING_DTYPE), np.zeros(self.max_channels, np.int32),
+                         np.zeros((n_rounds, self.max_channels), np.uint32), np.zeros((n_rounds, self.max_channels), np.uint8))
+        return res, tuple(ctypes.c_void_p(x.ctypes.data) for x in res)
+
+    def run_symbols(self, symbols, valid=None, out_valid=None, on_device: bool = False, n_rounds: int = None, host: bool = True):
+        """symbols float32[n_rounds, max_channels] (or a device pointer with on_device and n_rounds); valid and out_valid
+        uint8 of the same shape (and place) or None (out_valid is accepted and not read, as in the blocks).  Returns a GnavResult, or None when not host (asynchronous)."""
+        if on_device:
+            sp = ctypes.c_void_p(symbols)
+            vp, op = (ctypes.c_void_p(x) if x else None for x in (valid, out_valid))
+        else:
+            symbols = np.ascontiguousarray(symbols, np.float32).reshape(-1, self.max_channels)
+            n_rounds = symbols.shape[0] if n_rounds is None else int(n_rounds)
+            sp = ctypes.c_void_p(symbols.ctypes.data) if symbols.size else None
+            masks = []
+            for m, name in ((valid, "valid"), (out_valid, "out_valid")):
+                if m is not None:
+                    m = np.ascontiguousarray(m, np.uint8).reshape(-1, self.max_channels)
+                    if m.shape != symbols.shape:
+                        raise ValueError(f"{name} must have the symbols' shape")
+                masks.append(m)
+            valid, out_valid = masks
+            vp, op = (ctypes.c_void_p(m.ctypes.data) if m is not None and m.size else None for m in masks)
+        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
+        self._in_flight = (symbols, valid, out_valid)  # a run without a host copy returns before the stream has read them
+        check(self.ctx.lib.gnsship_gnav_run_symbols(self.h, sp, vp, op, int(on_device), int(n_rounds), *ptrs), "gnsship_gnav_run_symbols", self.ctx.h)
+        return res
+
+    def run_records(self, records, on_device: bool = False, n_rounds: int = None, host: bool = True):
+        """records: abi.TRK_EPOCH_DTYPE[n_rounds, max_channels] on the host, or a device pointer with on_device and n_rounds."""
+        if on_device:
+            rp = ctypes.c_void_p(records)
+        else:
+            records = np.ascontiguousarray(records, abi.TRK_EPOCH_DTYPE).reshape(-1, self.max_channels)
+            n_rounds = records.shape[0] if n_rounds is None else int(n_rounds)
+            rp = ctypes.c_void_p(records.ctypes.data) if records.size else None
+        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
+        self._in_flight = (records,)
+        check(self.ctx.lib.gnsship_gnav_run_records(self.h, rp, int(on_device), int(n_rounds), *ptrs), "gnsship_gnav_run_records", self.ctx.h)
+        return res
+
+    def run_trk(self, trk: "DllPllVemlTracking", host: bool = True):
+        """Consume, in place, the records the tracker's last run left on the device."""
+        res, ptrs = self._outputs(host, self.max_rounds)
+        rounds = ctypes.c_int32()
+        check(self.ctx.lib.gnsship_gnav_run_trk(self.h, trk.h, *ptrs, ctypes.byref(rounds)), "gnsship_gnav_run_trk", self.ctx.h)
+        if res is None:
+            return None
+        n = rounds.value  # the copies are dense over the run's rounds
+        flat = self.max_rounds * self.max_channels
+        return res._replace(tow_ms=res.tow_ms.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels),
+                            sflags=res.sflags.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels))
+
+    def outputs_device(self):
+        """Device pointers (strings, counts, tow_ms, sflags) of the handle's output buffers."""
+        p = [ctypes.c_void_p() for _ in range(4)]
+        check(self.ctx.lib.gnsship_gnav_outputs_device(self.h, *[ctypes.byref(x) for x in p], None), "gnsship_gnav_outputs_device", self.ctx.h)
+        return tuple(x.value for x in p)
+
+    def state(self, channel: int) -> np.ndarray:
+        """The channel's members (gnsship_gnav_state) as one abi.GNAV_STATE_DTYPE record."""
+        st = np.zeros(1, abi.GNAV_STATE_DTYPE)
+        check(self.ctx.lib.gnsship_gnav_state_get(self.h, channel, ctypes.c_void_p(st.ctypes.data)), "gnsship_gnav_state_get", self.ctx.h)
+        return st[0]
+
+    def set_state(self, channel: int, st):
+        """The channel's members become st (one abi.GNAV_STATE_DTYPE record)."""
+        st = np.ascontiguousarray(np.asarray(st, abi.GNAV_STATE_DTYPE).reshape(1))
+        check(self.ctx.lib.gnsship_gnav_state_set(self.h, channel, ctypes.c_void_p(st.ctypes.data)), "gnsship_gnav_state_set", self.ctx.h)
+
+    def set_satellite(self, channel: int, prn: int):
+        """The block's set_satellite(): the PRN only."""
+        check(self.ctx.lib.gnsship_gnav_set_satellite(self.h, channel, int(prn)), "gnsship_gnav_set_satellite", self.ctx.h)
+
+    def new_channel(self, channel: int, prn: int):
+        """A new block object on this channel, constructed on this PRN."""
+        check(self.ctx.lib.gnsship_gnav_new_channel(self.h, channel, int(prn)), "gnsship_gnav_new_channel", self.ctx.h)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.gnsship_gnav_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:
+                self.close()
+        except Exception:
+            pass
+
+
+def glonass_l1_ca_telemetry(ctx: Context, max_channels: int, max_rounds: int) -> GlonassGnavTelemetryDecoder:
+    """GLONASS L1 C/A GNAV (glonass_l1_ca_telemetry_decoder_gs)."""
+    return GlonassGnavTelemetryDecoder(ctx, max_channels, max_rounds, abi.GNAV_L1CA)
+
+
+def glonass_l2_ca_telemetry(ctx: Context, max_channels: int, max_rounds: int) -> GlonassGnavTelemetryDecoder:
+    """GLONASS L2 C/A GNAV (glonass_l2_ca_telemetry_decoder_gs): the same algorithm."""
+    return GlonassGnavTelemetryDecoder(ctx, max_channels, max_rounds, abi.GNAV_L2CA)
+
+
 class DllPllVemlTracking:
     """dll_pll_veml_tracking (dll_pll_veml_tracking.cc) for up to ``max_channels`` channels, the
     per-epoch loop resident on the device: ``start_tracking`` → :meth:`start`, ``general_work``

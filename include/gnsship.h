@@ -1378,6 +1378,174 @@ int gnsship_dnav_new_channel(gnsship_dnav* t, int32_t channel, int32_t prn);
 int gnsship_dnav_state_get(gnsship_dnav* t, int32_t channel, gnsship_dnav_state* st);
 int gnsship_dnav_destroy(gnsship_dnav* t);
 
+/* ---------------------------------------------------------------------------------------------
+ * GLONASS GNAV telemetry (L1 C/A and L2 C/A) on the device: glonass_l1_ca_telemetry_decoder_gs / glonass_l2_ca_telemetry_decoder_gs
+ * with what they use of Glonass_Gnav_Navigation_Message (CRC_test, string_decoder, have_new_ephemeris, have_new_utc_model)
+ * and Glonass_Gnav_Ephemeris::glot_to_gpst up to the time of week.  One block object per channel, one lane per channel.
+ * The two blocks are one algorithm (they differ in names and log text; the L2 block repeats its valid-word test), so the
+ * signal only names the handle.  Restated and not repaired — all of this is part of the contract:
+ *   history      a ring of capacity 2000; every symbol is pushed (its double Prompt_I) and d_sample_counter grows by one.
+ *   correlation  as soon as the history holds 300 entries, over its 300 OLDEST entries against the 30 time-mark bits
+ *                "111110001101110101000010010110" at 10 symbols each: -preamble where the entry is < 0.0, +preamble otherwise
+ *                (NaN, +0 and -0 count as +1).  While the ring is filling (fewer than 2000 entries) these are the first 300
+ *                symbols ever received, tested again on every symbol.  A hit is |corr| >= 300.
+ *   state 0      a hit sets preamble_index = counter and state 1.
+ *   state 1      on a hit only, with diff = (int32)(counter - preamble_index): diff == 2000 sets preamble_index = counter
+ *                and state 2 (nothing is decoded); diff > 2000 goes back to state 0 and the hit is thrown away; diff < 2000
+ *                does nothing.  Without a hit state 1 never times out.
+ *   state 2      hits are ignored.  When counter == preamble_index + 2000 the string is decoded whatever corr is; its
+ *                polarity is normal when corr > 0 and inverted when corr <= 0 (a time mark that did not match decodes
+ *                inverted when corr is 0 or negative).  The symbols decoded are history entries 300..1999.
+ *   decode       170 half-bits, each `sum > 0` of a double sum of 10 consecutive symbols added in order from 0.0; under
+ *                the inverted polarity every symbol is negated first, which is exact, so the half-bit is `sum < 0`: a NaN or
+ *                zero sum is '0' under both.  Half-bit pair "10" is relative bit 1, any other pair 0.  Data bit 0 is '0',
+ *                data bit i is relative bit i-1 XOR relative bit i.  Character i of the 85 enters the bitset as bit 84 - i.
+ *   CRC_test     eight parities C1..C7, C_Sigma (C_Sigma is the parity of all 85 bits).  In this order: (1) all eight zero:
+ *                accept.  (2) C_Sigma == 1 and exactly one of C1..C7 set: accept, nothing flipped.  (3) C_Sigma == 1 and the
+ *                parity of bits 8..84 odd: the syndrome C1 + 2 C2 + ... + 64 C7, when below 85, flips bits[locator[syndrome]]
+ *                and accepts; 85 or above rejects.  (4) reject.  In (3) the syndromes 1, 2, 4, ..., 64 cannot occur (branch 2
+ *                took them); syndrome 0 can, and flips bit 0.  A C_Sigma == 1 word with even parity over bits 8..84 is
+ *                rejected even where its syndrome names one bit.
+ *   nav object   a rejected string changes nothing.  String 1 sets t_k = 3600 h + 60 m + 30 s and flag 1.  Strings 2, 3, 4, 5
+ *                are read only if the flag of the string before is set: string 2 sets t_b (15-minute units, in seconds),
+ *                string 4 N_T, n and flag_update_slot_number, string 5 tau_c (sign-magnitude 32 bits, 2^-31), N_4, tau_gps
+ *                (sign-magnitude 22 bits, 2^-30), flag_utc_model_str_5 and, if flag 1 is set, d_WN / d_TOW with flag_TOW_set
+ *                and flag_TOW_new.  After every decode, accepted or not, have_new_ephemeris() and have_new_utc_model() run:
+ *                the first clears flags 1..4 when all four and the UTC flag are set and t_b differs from d_previous_tb (which
+ *                starts at 0, so a satellite with t_b == 0 never clears them); the second clears the UTC flag.  After string
+ *                4 the channel's PRN becomes n.  Almanac strings (6..15) touch nothing here.
+ *   glot_to_gpst integer dates: 1 January of 1996 + 4 (N_4 - 1), plus N_T - 1 days, plus t_k + 10 - 10800 seconds (which may
+ *                be negative, or more than a day).  The leap seconds are those of the first table entry (2017: 18, 2015: 17,
+ *                2012: 16, 2009: 15, 2006: 14, 1999: 13, 1 July 1997: 12, 1996: 11, 1 July 1994: 10, 1993: 9, 1992: 8,
+ *                1991: 7, ...) at or before that instant.  days is counted from 6 January 1980 to the UTC date, the
+ *                seconds of day are those of the GPS instant: a leap addition that crosses midnight is a day short.
+ *                d_WN = floor(total / 604800), d_TOW = total - 604800 floor(total / 604800), then d_TOW += (tau_c + tau_gps).
+ *   CRC counter  an accepted string zeroes it, raises d_flag_preamble for this symbol and sets frame sync; a rejected one
+ *                counts up and above 6 drops frame sync and returns to state 0.  Both set preamble_index = counter.
+ *   stamp        doubles throughout, IEEE divide, nothing contracted (the library is built with -ffp-contract=off): on an
+ *                accepted decode with flag_TOW_new, d_TOW_at_current_symbol = floor((d_TOW - 0.3) * 1000) / 1000; on every
+ *                other symbol it is + 0.001.  The output is round(x * 1000.0) (half away from zero) into a uint32: for a
+ *                negative value the block's conversion is undefined, and device and model take the low 32 bits of the int64
+ *                value, as an x86-64 build does.  Flag_valid_word is d_flag_frame_sync && flag_TOW_set.
+ *   faults       the blocks never publish on telemetry_to_trk: there is no fault output.  Flag_valid_symbol_output is not read.
+ * Not here: ephemeris, almanac and UTC fields and their messages (the record carries the 85 bits), the nav-data monitor,
+ * CRC statistics, dumps, the GLONASS-to-GPS offset the block leaves commented out. */
+#define GNSSHIP_GNAV_MAX_CHANNELS (1 << 20)
+#define GNSSHIP_GNAV_MAX_ROUNDS (1 << 20)
+#define GNSSHIP_GNAV_L1CA 0
+#define GNSSHIP_GNAV_L2CA 1
+/* The most records one run of max_rounds symbols can emit.  A record is a decode, and a decode happens only in state 2 at
+ * counter == preamble_index + 2000.  Every decode sets preamble_index = counter, and so does the entry into state 2: the
+ * next decode, whether state 2 was kept or left and entered again, is at least 2000 symbols later.  A run's first decode
+ * falls on its first symbol at the earliest, so n symbols hold at most (n - 1) / 2000 + 1 <= n / 2000 + 1 decodes, and
+ * n = 2000 k + 1 symbols starting on a due symbol of a channel that keeps state 2 hold exactly k + 1. */
+#define GNSSHIP_GNAV_STRINGS_PER_RUN(max_rounds) ((max_rounds) / 2000 + 1)
+typedef struct gnsship_gnav gnsship_gnav;
+typedef struct gnsship_gnav_conf {
+    int32_t max_rounds;      /* most entries per channel in one run, >= 1 */
+    int32_t signal;          /* GNSSHIP_GNAV_L1CA or GNSSHIP_GNAV_L2CA */
+    int32_t reserved;        /* 0 */
+} gnsship_gnav_conf;
+/* gnsship_gnav_string.flags */
+#define GNSSHIP_GNAV_CRC_OK 1        /* CRC_test accepted the string */
+#define GNSSHIP_GNAV_CORRECTED 2     /* ... after flipping bit flipped_bit */
+#define GNSSHIP_GNAV_INVERTED 4      /* decoded under the inverted polarity (corr <= 0) */
+#define GNSSHIP_GNAV_NEW_TOW 8       /* flag_TOW_new was set: the stamp was taken from d_TOW here */
+#define GNSSHIP_GNAV_SLOT_UPDATED 16 /* flag_update_slot_number: the PRN became n */
+#define GNSSHIP_GNAV_NEW_EPHEMERIS 32 /* have_new_ephemeris() returned true */
+#define GNSSHIP_GNAV_NEW_UTC_MODEL 64 /* have_new_utc_model() returned true */
+typedef struct gnsship_gnav_string { /* one decode, 64 bytes */
+    uint64_t symbol_counter;        /* d_sample_counter at the completing symbol */
+    uint64_t sample_counter;        /* the completing epoch's record.sample_counter; 0 for run_symbols */
+    double tow;                     /* the navigation object's d_TOW after the decode */
+    uint32_t bits[3];               /* the bitset after CRC_test: bit i in bits[i / 32] bit i % 32, i < 85 */
+    int32_t channel;
+    int32_t prn;                    /* the channel's PRN after the decode */
+    int32_t string_id;              /* bits 83..80, whatever CRC_test said */
+    int32_t flipped_bit;            /* the bit CRC_test flipped, or -1 */
+    uint32_t tow_at_current_symbol_ms; /* the block's output at this symbol */
+    uint32_t flags;                 /* GNSSHIP_GNAV_* above */
+    uint32_t reserved;
+} gnsship_gnav_string;
+typedef struct gnsship_gnav_state { /* every member of one block object and its navigation object that the above names, 416 bytes */
+    uint64_t symbol_counter;        /* d_sample_counter */
+    uint64_t preamble_index;
+    double tow_at_current_symbol;   /* d_TOW_at_current_symbol, seconds */
+    double tow;                     /* d_TOW */
+    double tau_c, tau_gps;
+    double chip_acc;                /* the half-bit sum in flight (state 2, between two half-bit boundaries) */
+    int32_t stat;
+    int32_t crc_error_counter;
+    int32_t history_size;           /* min(symbol_counter, 2000) */
+    int32_t prn;
+    int32_t wn;                     /* d_WN */
+    uint32_t t_k, t_b, previous_tb; /* seconds; doubles in the source, always integers */
+    uint32_t n_t, n, n_4;
+    uint8_t frame_sync;
+    uint8_t ephemeris_str[4];       /* flag_ephemeris_str_1..4 */
+    uint8_t utc_model_str_5;        /* always 0 between symbols: have_new_utc_model() clears it after every decode */
+    uint8_t tow_set, tow_new;       /* tow_new is always 0 between symbols: the block uses it at once */
+    uint8_t reserved[4];
+    /* Of state 2, where data symbol j (0..1699) is the one with counter preamble_index + 301 + j: half-bit h = j / 10 is
+     * complete once its tenth symbol has come; bit h % 32 of half_pos[h / 32] is `sum > 0`, of half_neg `sum < 0`.
+     * chip_acc is 0.0 after a complete half-bit.  Every decode clears all three, so outside state 2 they are zero. */
+    uint32_t half_pos[6], half_neg[6];
+    /* "Prompt_I < 0.0" of the last history_size symbols: the symbol pushed when the counter became k is bit (k % 2000) % 32
+     * of history[(k % 2000) / 32]. */
+    uint32_t history[64];
+} gnsship_gnav_state;
+#ifdef __cplusplus
+static_assert(sizeof(gnsship_gnav_string) == 64, "gnsship_gnav_string");
+static_assert(sizeof(gnsship_gnav_state) == 416, "gnsship_gnav_state");
+#else
+_Static_assert(sizeof(gnsship_gnav_string) == 64, "gnsship_gnav_string");
+_Static_assert(sizeof(gnsship_gnav_state) == 416, "gnsship_gnav_state");
+#endif
+/* sflags of an entry */
+#define GNSSHIP_GNAV_S_VALID_WORD 1 /* Flag_valid_word of this symbol */
+#define GNSSHIP_GNAV_S_STRING 2     /* a string was decoded at this symbol */
+#define GNSSHIP_GNAV_S_INVERTED 4   /* ... under the inverted polarity */
+/* Channels 0..max_channels-1 (1..GNSSHIP_GNAV_MAX_CHANNELS), each a new block object on PRN 0.  Device memory per channel:
+ * 416 bytes of members (the history is 2000 sign bits, the string in flight two 170-bit strings and one double),
+ * strings_per_run = GNSSHIP_GNAV_STRINGS_PER_RUN(max_rounds) slots of 64 bytes, and 5 bytes per entry of a run. */
+int gnsship_gnav_create(gnsship_ctx* ctx, const gnsship_gnav_conf* conf, int32_t max_channels, gnsship_gnav** out);
+/* symbols[r*max_channels + c], r < n_rounds (0..max_rounds), float on the host or (on_device) on the device, widened to
+ * double; valid and out_valid: uint8 of the same shape and place, or NULL.  Channel c consumes its valid entries in order
+ * of r.  out_valid is the entry's Flag_valid_symbol_output, which these blocks never read: it is accepted for the shape of
+ * the call and changes nothing.  Outputs, in the handle's own device buffers (gnsship_gnav_outputs_device) and copied to
+ * whichever host pointers are given:
+ *   strings[c][k], k < counts[c]     one record per decode, in order; slots beyond counts[c] are unspecified
+ *   counts int32[c]
+ *   tow_ms uint32[r*max_channels+c], sflags uint8[...]  r < n_rounds: TOW_at_current_symbol_ms of the symbol and
+ *                                    GNSSHIP_GNAV_S_*; both 0 for entries that are not symbols
+ * With no host pointer the call is asynchronous on the context stream (host inputs then stay the caller's until the
+ * stream has passed the run).  Any cut of a stream into runs gives the same outputs. */
+int gnsship_gnav_run_symbols(gnsship_gnav* t, const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int on_device,
+    int32_t n_rounds, gnsship_gnav_string* strings_host, int32_t* counts_host, uint32_t* tow_ms_host, uint8_t* sflags_host);
+/* The same over tracking records of that shape: an entry is a symbol when flags & 1, the symbol is the record's double
+ * prompt_i; the string's sample_counter is the completing record's. */
+int gnsship_gnav_run_records(gnsship_gnav* t, const gnsship_trk_epoch* records, int on_device, int32_t n_rounds,
+    gnsship_gnav_string* strings_host, int32_t* counts_host, uint32_t* tow_ms_host, uint8_t* sflags_host);
+/* The same over the records the tracker's last run left on the device (gnsship_trk_records_device), in place, ordered
+ * on the context stream.  n_rounds_out (may be NULL): the rounds of that run.  E_STATE if there are no records; E_INVAL if
+ * the handles are on different contexts, their max_channels differ or the run had more rounds than max_rounds. */
+int gnsship_gnav_run_trk(gnsship_gnav* t, gnsship_trk* trk, gnsship_gnav_string* strings_host, int32_t* counts_host,
+    uint32_t* tow_ms_host, uint8_t* sflags_host, int32_t* n_rounds_out);
+/* The handle's output buffers (any pointer may be NULL) and strings_per_run. */
+int gnsship_gnav_outputs_device(gnsship_gnav* t, gnsship_gnav_string** strings, int32_t** counts, uint32_t** tow_ms,
+    uint8_t** sflags, int32_t* strings_per_run);
+/* The block's set_satellite(): the PRN (0..63); nothing else moves. */
+int gnsship_gnav_set_satellite(gnsship_gnav* t, int32_t channel, int32_t prn);
+/* A new block object on this channel, constructed on this PRN. */
+int gnsship_gnav_new_channel(gnsship_gnav* t, int32_t channel, int32_t prn);
+/* The channel's members after everything run so far (waits for the context stream). */
+int gnsship_gnav_state_get(gnsship_gnav* t, int32_t channel, gnsship_gnav_state* st);
+/* The channel's members become *st (ordered on the context stream; *st is copied before the call returns): a channel
+ * moves between handles, or starts from a state the stream would take many seconds to reach.  E_INVAL unless stat is
+ * 0..2, history_size == min(symbol_counter, 2000), crc_error_counter >= 0 and the flags are 0 or 1. */
+int gnsship_gnav_state_set(gnsship_gnav* t, int32_t channel, const gnsship_gnav_state* st);
+int gnsship_gnav_destroy(gnsship_gnav* t);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Multi-GPU fan-out: one process per GPU, one RCCL communicator per context.  */
 /* The reference connects one conditioner output to every channel block (gnss_flowgraph.cc:    */

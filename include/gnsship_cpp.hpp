@@ -2035,6 +2035,136 @@ public:
     }
 };
 
+// glonass_l1_ca_telemetry_decoder_gs / glonass_l2_ca_telemetry_decoder_gs as gnsship_gnav_conf: max_rounds is the most entries
+// per channel one work_* call may carry.
+inline gnsship_gnav_conf glonass_l1_ca_tlm_conf(int32_t max_rounds)
+{
+    return gnsship_gnav_conf{max_rounds, GNSSHIP_GNAV_L1CA, 0};
+}
+inline gnsship_gnav_conf glonass_l2_ca_tlm_conf(int32_t max_rounds)
+{
+    return gnsship_gnav_conf{max_rounds, GNSSHIP_GNAV_L2CA, 0};
+}
+
+// The GLONASS GNAV telemetry decoders up to the time of week for many channels at once, one block object per channel
+// (include/gnsship.h, gnsship_gnav_*): symbols or tracking records in; decoded strings and the TOW stamp of every entry out.
+// After a work_* call, strings() / counts() / tow_ms() / sflags() hold that call's outputs.  The two blocks are one
+// algorithm; the configuration's signal only names the block.
+class Glonass_Gnav_Telemetry_Decoder_Hip {
+public:
+    Glonass_Gnav_Telemetry_Decoder_Hip(const gnsship_gnav_conf& c, int32_t max_channels, int device = 0)
+        : dev_(Device::get(device)), conf_(c), channels_(max_channels)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        if (gnsship_gnav_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
+            throw std::invalid_argument(std::string("gnsship_gnav_create: ") + gnsship_last_error(dev_->ctx()));
+        gnsship_gnav_outputs_device(h_, nullptr, nullptr, nullptr, nullptr, &strings_per_run_);
+        const size_t nc = static_cast<size_t>(max_channels);
+        strings_.resize(nc * strings_per_run_);
+        counts_.resize(nc);
+        tow_ms_.resize(nc * c.max_rounds);
+        sflags_.resize(nc * c.max_rounds);
+    }
+    ~Glonass_Gnav_Telemetry_Decoder_Hip()
+    {
+        if (h_) gnsship_gnav_destroy(h_);
+    }
+    Glonass_Gnav_Telemetry_Decoder_Hip(const Glonass_Gnav_Telemetry_Decoder_Hip&) = delete;
+    Glonass_Gnav_Telemetry_Decoder_Hip& operator=(const Glonass_Gnav_Telemetry_Decoder_Hip&) = delete;
+    const gnsship_gnav_conf& conf() const { return conf_; }
+    int32_t strings_per_run() const { return strings_per_run_; }
+    // the block's set_satellite() on one channel; new_channel: a new block object constructed on this PRN
+    bool set_satellite(int32_t channel, int32_t prn)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_gnav_set_satellite(h_, channel, prn) == GNSSHIP_OK;
+    }
+    bool new_channel(int32_t channel, int32_t prn)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_gnav_new_channel(h_, channel, prn) == GNSSHIP_OK;
+    }
+    // symbols[r · max_channels + c], r < n_rounds; valid: the same shape, or null for all valid; out_valid is not read
+    bool work_symbols(const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int32_t n_rounds, bool on_device = false)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = n_rounds;
+        return gnsship_gnav_run_symbols(h_, symbols, valid, out_valid, on_device ? 1 : 0, n_rounds, strings_.data(), counts_.data(), tow_ms_.data(),
+                   sflags_.data()) == GNSSHIP_OK;
+    }
+    // tracking records of that shape: a symbol when flags & 1; the symbol is the record's double prompt_i
+    bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = n_rounds;
+        return gnsship_gnav_run_records(h_, records, on_device ? 1 : 0, n_rounds, strings_.data(), counts_.data(), tow_ms_.data(), sflags_.data()) ==
+               GNSSHIP_OK;
+    }
+    // the records the tracker's last work() left on the device, in place
+    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        rounds_ = 0;
+        return gnsship_gnav_run_trk(h_, trk.handle(), strings_.data(), counts_.data(), tow_ms_.data(), sflags_.data(), &rounds_) == GNSSHIP_OK;
+    }
+    // the last work_* call's outputs: string k < counts()[c] of channel c is strings()[c · strings_per_run() + k];
+    // entry (r, c), r < rounds(), is tow_ms()[r · max_channels + c] and sflags()[r · max_channels + c]
+    const std::vector<gnsship_gnav_string>& strings() const { return strings_; }
+    const std::vector<int32_t>& counts() const { return counts_; }
+    const std::vector<uint32_t>& tow_ms() const { return tow_ms_; }
+    const std::vector<uint8_t>& sflags() const { return sflags_; }
+    int32_t rounds() const { return rounds_; }
+    gnsship_gnav_state state(int32_t channel) const
+    {
+        gnsship_gnav_state st{};
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        gnsship_gnav_state_get(h_, channel, &st);
+        return st;
+    }
+    bool set_state(int32_t channel, const gnsship_gnav_state& st)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        return gnsship_gnav_state_set(h_, channel, &st) == GNSSHIP_OK;
+    }
+    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
+
+protected:
+    // for the two block classes: the configuration must be their signal's
+    static const gnsship_gnav_conf& require(const gnsship_gnav_conf& c, int32_t signal)
+    {
+        if (c.signal != signal) throw std::invalid_argument("the configuration's signal is not this block's");
+        return c;
+    }
+
+private:
+    std::shared_ptr<Device> dev_;
+    gnsship_gnav_conf conf_;
+    gnsship_gnav* h_ = nullptr;
+    int32_t channels_ = 0, strings_per_run_ = 0, rounds_ = 0;
+    std::vector<gnsship_gnav_string> strings_;
+    std::vector<int32_t> counts_;
+    std::vector<uint32_t> tow_ms_;
+    std::vector<uint8_t> sflags_;
+};
+
+// glonass_l1_ca_telemetry_decoder_gs: construct with glonass_l1_ca_tlm_conf(max_rounds)
+class Glonass_L1_Ca_Telemetry_Decoder_Hip : public Glonass_Gnav_Telemetry_Decoder_Hip {
+public:
+    Glonass_L1_Ca_Telemetry_Decoder_Hip(const gnsship_gnav_conf& c, int32_t max_channels, int device = 0)
+        : Glonass_Gnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_GNAV_L1CA), max_channels, device)
+    {
+    }
+};
+
+// glonass_l2_ca_telemetry_decoder_gs: construct with glonass_l2_ca_tlm_conf(max_rounds)
+class Glonass_L2_Ca_Telemetry_Decoder_Hip : public Glonass_Gnav_Telemetry_Decoder_Hip {
+public:
+    Glonass_L2_Ca_Telemetry_Decoder_Hip(const gnsship_gnav_conf& c, int32_t max_channels, int device = 0)
+        : Glonass_Gnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_GNAV_L2CA), max_channels, device)
+    {
+    }
+};
+
 }  // namespace gnsship
 
 #endif  // GNSSHIP_CPP_HPP

@@ -151,6 +151,12 @@ struct Receiver_Conf {
     // new block object on that PRN.  The blocks publish nothing to tracking, so nothing goes back.  Off (the default):
     // exactly the receiver above, every output byte for byte.
     bool dnav{false};
+    // Decode the GLONASS GNAV telemetry of every channel on the device (gnsship_cpp.hpp Glonass_L1_Ca_Telemetry_Decoder_Hip /
+    // Glonass_L2_Ca_Telemetry_Decoder_Hip), system 'R' channels only.  Each tracking block's records go through the decoder
+    // where tracking left them on the device; a channel that is assigned a satellite gets a new block object on that PRN,
+    // and after string 4 the decoder's PRN is the slot number the satellite sent (the record's prn, gnav_prn()).  The blocks
+    // publish nothing to tracking, so nothing goes back.  Off (the default): exactly the receiver above, byte for byte.
+    bool gnav{false};
 };
 
 // One control event, in stream order.
@@ -192,6 +198,13 @@ struct Receiver_Cnav_Message {
 struct Receiver_Dnav_Subframe {
     uint32_t prn;
     gnsship_dnav_subframe subframe;
+};
+
+// One GLONASS GNAV string of a channel (every decode) with the satellite the channel was assigned; string.prn is the
+// decoder's own PRN after the decode, which follows the slot number of string 4.
+struct Receiver_Gnav_String {
+    uint32_t prn;
+    gnsship_gnav_string string;
 };
 
 class Gnss_Receiver_Hip {
@@ -248,6 +261,12 @@ public:
             if (!b3_) throw std::invalid_argument("Gnss_Receiver_Hip: dnav decodes BeiDou B3I channels (signal B3)");
             const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
             dnav_ = std::make_unique<Beidou_B3i_Telemetry_Decoder_Hip>(beidou_b3i_tlm_conf(max_ep), n_, conf_.device);
+        }
+        if (conf_.gnav) {
+            if (!glo_) throw std::invalid_argument("Gnss_Receiver_Hip: gnav decodes GLONASS channels (system R, signal 1G or 2G)");
+            const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
+            if (conf_.trk.signal[0] == '2') gnav_ = std::make_unique<Glonass_L2_Ca_Telemetry_Decoder_Hip>(glonass_l2_ca_tlm_conf(max_ep), n_, conf_.device);
+            else gnav_ = std::make_unique<Glonass_L1_Ca_Telemetry_Decoder_Hip>(glonass_l1_ca_tlm_conf(max_ep), n_, conf_.device);
         }
         if (conf_.use_conditioner) {
             const double fs_out = conf_.input_filter.sampling_frequency / std::max(1, conf_.input_filter.decimation_factor);
@@ -360,6 +379,10 @@ public:
     bool has_cnav() const { return cnav_ != nullptr; }
     // With conf.dnav: every subframe record in the order the blocks emitted them (channel by channel within a block).
     const std::vector<Receiver_Dnav_Subframe>& dnav_subframes() const { return dnav_subframes_; }
+    // With conf.gnav: every string record in the order the blocks emitted them (channel by channel within a block), and the
+    // PRN a channel's decoder is on (the assigned one until a string 4 has been decoded).
+    const std::vector<Receiver_Gnav_String>& gnav_strings() const { return gnav_strings_; }
+    uint32_t gnav_prn(int c) const { return gnav_ ? static_cast<uint32_t>(gnav_->state(c).prn) : 0U; }
     gnsship_cnav_state cnav_state(int c) const { return cnav_ ? cnav_->state(c) : gnsship_cnav_state{}; }
     uint64_t position() const { return pos_; }
     unsigned channel_fsm_state(int c) const { return fsm_[static_cast<size_t>(c)].state(); }
@@ -436,6 +459,7 @@ private:
         if (lnav_ && !lnav_->new_channel(c)) error_ = true;  // the channel starts on its satellite with a new block object
         if (cnav_ && !cnav_->new_channel(c)) error_ = true;  // likewise
         if (dnav_ && !dnav_->new_channel(c, static_cast<int32_t>(prn))) error_ = true;  // likewise, constructed on the PRN
+        if (gnav_ && !gnav_->new_channel(c, static_cast<int32_t>(prn))) error_ = true;  // likewise
         if (l5_) {  // GpsL5iPcpsAcquisition::set_local_code: the search runs on L5I
             const std::vector<std::complex<float>> code = gps_l5i_acquisition_code(prn, conf_.acq);
             if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
@@ -655,6 +679,13 @@ private:
                 for (int k = 0; k < dnav_->counts()[static_cast<size_t>(c)]; k++)
                     dnav_subframes_.push_back({prn_[static_cast<size_t>(c)], dnav_->subframes()[static_cast<size_t>(c) * spr + static_cast<size_t>(k)]});
         }
+        if (gnav_) {  // and for the GLONASS GNAV decoder, likewise
+            if (!gnav_->work_trk(*trk_)) return false;
+            const size_t spr = static_cast<size_t>(gnav_->strings_per_run());
+            for (int c = 0; c < n_; c++)
+                for (int k = 0; k < gnav_->counts()[static_cast<size_t>(c)]; k++)
+                    gnav_strings_.push_back({prn_[static_cast<size_t>(c)], gnav_->strings()[static_cast<size_t>(c) * spr + static_cast<size_t>(k)]});
+        }
         recs_.resize(static_cast<size_t>(n_));
         for (int c = 0; c < n_; c++) {
             bool lost = false;
@@ -709,6 +740,8 @@ private:
     std::vector<Receiver_Cnav_Message> cnav_messages_;
     std::unique_ptr<Beidou_B3i_Telemetry_Decoder_Hip> dnav_;  // the optional BeiDou D1/D2 telemetry (B3I)
     std::vector<Receiver_Dnav_Subframe> dnav_subframes_;
+    std::unique_ptr<Glonass_Gnav_Telemetry_Decoder_Hip> gnav_;  // the optional GLONASS GNAV telemetry (L1 or L2 C/A)
+    std::vector<Receiver_Gnav_String> gnav_strings_;
     std::unique_ptr<Freq_Xlating_Fir_Filter_Hip> cond_;  // the optional conditioner stage
     int64_t cond_block_ = 0;                             // its run size, in input samples
     std::vector<std::complex<float>> cond_host_;

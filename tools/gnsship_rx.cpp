@@ -14,7 +14,7 @@
 //              [--pll-bw 40] [--dll-bw 4] [--order 3] [--pull-in-time-s 10] [--rotator auto|generic|avx]
 //              [--max-carrier-lock-fail 5000] [--max-code-lock-fail 50] [--cn0-min 25]
 //              [--block-ms 100] [--acq-piece 8192] [--dump PREFIX] [--events CSV] [--records BIN]
-//              [--telemetry] [--telemetry-mode reference|full] [--lnav] [--cnav] [--dnav]
+//              [--telemetry] [--telemetry-mode reference|full] [--lnav] [--cnav] [--dnav] [--gnav]
 //              [--if-hz 0] [--decimation 1] [--filter-bw 0] [--filter-tw 0]
 //              [--input-filter pulse-blanking|notch|notch-lite] [--input-filter-pfa P] [--segment-length 32]
 //              [--segments-est 12500] [--segments-reset 5000000] [--p-c-factor 0.9] [--coeff-rate R]
@@ -37,6 +37,11 @@
 // --dnav (with --signal B3) sends each tracking block's records through the device BeiDou D1/D2 telemetry decoder and
 // prints, ahead of the summary, one line per decoded subframe: channel, PRN, symbol counter, FraID, Pnum, SOW, the TOW in
 // ms after the stamp, the corrected-rows mask and the flags in hex, the ten words in hex.
+//
+// --gnav (with --signal 1G or 2G) sends each tracking block's records through the device GLONASS GNAV telemetry decoder and
+// prints, ahead of the summary, one line per decoded string: channel, the PRN the channel was assigned, the decoder's PRN
+// after the decode (the slot number once string 4 has come), symbol and sample counter, string number, the flipped bit or
+// -1, the TOW in ms of that symbol, d_TOW, the flags in hex and the 85 bits as three words in hex.
 //
 // --input-filter puts the interference mitigation (InputFilter.implementation = Pulse_Blanking_Filter, Notch_Filter or
 // Notch_Filter_Lite; pfa, length, segments_est, segments_reset, p_c_factor, coeff_rate: 0 = the adapter's defaults)
@@ -167,6 +172,7 @@ int main(int argc, char** argv)
         else if (a == "--lnav") rc.lnav = true;
         else if (a == "--cnav") rc.cnav = true;
         else if (a == "--dnav") rc.dnav = true;
+        else if (a == "--gnav") rc.gnav = true;
         else if (a == "--telemetry-mode") {
             const std::string m = val();
             if (m != "reference" && m != "full") usage("--telemetry-mode must be reference or full");
@@ -209,6 +215,7 @@ int main(int argc, char** argv)
     if (rc.lnav && signal != "1C") usage("--lnav decodes GPS L1 C/A channels (--signal 1C)");
     if (rc.cnav && signal != "2S" && signal != "L5") usage("--cnav decodes GPS L2C or L5 channels (--signal 2S or L5)");
     if (rc.dnav && signal != "B3") usage("--dnav decodes BeiDou B3I channels (--signal B3)");
+    if (rc.gnav && signal != "1G" && signal != "2G") usage("--gnav decodes GLONASS channels (--signal 1G or 2G)");
     std::snprintf(rc.trk.signal, sizeof(rc.trk.signal), "%s", signal.c_str());
     if (signal == "B3") rc.trk.system = 'C';  // otherwise 'G'
     if (signal == "5X" || signal == "7X") rc.trk.system = 'E';
@@ -394,6 +401,13 @@ int main(int argc, char** argv)
                 static_cast<unsigned long long>(decisions), static_cast<unsigned long long>(symbols), static_cast<unsigned long long>(decoded));
         }
         std::printf("\n");
+    }
+    // --gnav: one line per decoded string
+    for (const auto& gs : rx.gnav_strings()) {
+        const gnsship_gnav_string& f = gs.string;
+        std::printf("gnav-string channel %d prn %u slot %d symbol %llu sample %llu string %d flipped %d tow_ms %u tow %.17g flags %02x bits %08x %08x %08x\n",
+            f.channel, gs.prn, f.prn, static_cast<unsigned long long>(f.symbol_counter), static_cast<unsigned long long>(f.sample_counter), f.string_id,
+            f.flipped_bit, f.tow_at_current_symbol_ms, f.tow, f.flags, f.bits[0], f.bits[1], f.bits[2]);
     }
     // --dnav: one line per decoded subframe
     for (const auto& ds : rx.dnav_subframes()) {
