@@ -245,7 +245,8 @@ bool derive_hd_job(const gnsship_corr_job& in, const float* code_dev, int code_l
     for (int t = 1; t < in.n_taps; t++) {
         const float q = (in.shifts_chips[t] - in.shifts_chips[t - 1]) / in.code_phase_step_chips;
         const double rq = std::round(static_cast<double>(q));
-        if (!std::isfinite(rq)) return false;
+        // outside int the reference's (int) cast is undefined (x86 yields INT_MIN, a sum beyond any N): refused
+        if (!std::isfinite(rq) || rq < -2147483648.0 || rq > 2147483647.0) return false;
         s += static_cast<uint32_t>(static_cast<int>(rq));
         if (s > static_cast<uint32_t>(in.n_samples)) return false;
         out.shift_samples[t] = s;

@@ -475,6 +475,7 @@ extern "C" int gnsship_batch_set_jobs(gnsship_batch* b, const gnsship_corr_job* 
     if ((!jobs && n_jobs) || n_jobs < 0 || n_jobs > b->max_jobs) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_batch_set_jobs: n_jobs out of range");
     if (int rc = set_device(ctx)) return rc;
     b->anchor_segs = 0;
+    b->n_jobs = 0;  // a refused job set leaves an empty batch: the host plans below no longer match the device copies
     if (int rc = sync_code_table(ctx)) return rc;
     b->jobs_host.resize(n_jobs);
     b->hd.jobs.clear();
