@@ -56,82 +56,12 @@ $(MIRROR_TEST): tests/cpp/mirror_test.cpp include/gnsship_cpp.hpp include/gnsshi
 	g++ -O2 -std=c++17 -Iinclude tests/cpp/mirror_test.cpp build/gnss_oracle_test.o build/avx_port_test.o -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
 all: $(MIRROR_TEST)
 
-# GPS L5 through the C++ mirror (tests/test_cpp_mirror_l5.py compares its records with the oracle)
-L5_MIRROR_TEST := tests/cpp/l5_mirror_test
-$(L5_MIRROR_TEST): tests/cpp/l5_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/l5_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(L5_MIRROR_TEST)
-
-# BeiDou B3I and GPS L2C through the C++ mirror (tests/test_cpp_mirror_b3i_l2c.py, tests/test_codes_b3i_l2c.py)
-B3I_L2C_MIRROR_TEST := tests/cpp/b3i_l2c_mirror_test
-$(B3I_L2C_MIRROR_TEST): tests/cpp/b3i_l2c_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/b3i_l2c_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(B3I_L2C_MIRROR_TEST)
-
-# Galileo E5a / E5b through the C++ mirror (tests/test_cpp_mirror_e5.py)
-E5_MIRROR_TEST := tests/cpp/e5_mirror_test
-$(E5_MIRROR_TEST): tests/cpp/e5_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/e5_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(E5_MIRROR_TEST)
-
-# The signal conditioner through the C++ mirror (tests/test_cpp_mirror_cond.py)
-COND_MIRROR_TEST := tests/cpp/cond_mirror_test
-$(COND_MIRROR_TEST): tests/cpp/cond_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/cond_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(COND_MIRROR_TEST)
-
-# The conditioner's real-sampled and bit-packed input items through the C++ mirror (tests/test_cpp_mirror_cond_ingest.py)
-COND_INGEST_MIRROR_TEST := tests/cpp/cond_ingest_mirror_test
-$(COND_INGEST_MIRROR_TEST): tests/cpp/cond_ingest_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/cond_ingest_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(COND_INGEST_MIRROR_TEST)
-
-# The interference-mitigation mirrors (tests/test_cpp_mirror_mit.py)
-MIT_MIRROR_TEST := tests/cpp/mit_mirror_test
-$(MIT_MIRROR_TEST): tests/cpp/mit_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/mit_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(MIT_MIRROR_TEST)
-
-# GLONASS L1 / L2 C/A acquisition through the C++ mirror (tests/test_cpp_mirror_glonass.py)
-GLONASS_MIRROR_TEST := tests/cpp/glonass_mirror_test
-$(GLONASS_MIRROR_TEST): tests/cpp/glonass_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/glonass_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(GLONASS_MIRROR_TEST)
-
-# The Viterbi decoder mirrors (tests/test_cpp_mirror_viterbi.py)
-VITERBI_MIRROR_TEST := tests/cpp/viterbi_mirror_test
-$(VITERBI_MIRROR_TEST): tests/cpp/viterbi_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/viterbi_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(VITERBI_MIRROR_TEST)
-
-# The telemetry decoder mirror (tests/test_cpp_mirror_tlm.py)
-TLM_MIRROR_TEST := tests/cpp/tlm_mirror_test
-$(TLM_MIRROR_TEST): tests/cpp/tlm_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/tlm_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(TLM_MIRROR_TEST)
-
-# The GPS L1 C/A telemetry decoder mirror (tests/test_cpp_mirror_lnav.py)
-LNAV_MIRROR_TEST := tests/cpp/lnav_mirror_test
-$(LNAV_MIRROR_TEST): tests/cpp/lnav_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/lnav_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-
-# The GPS CNAV telemetry decoder mirror (tests/test_cpp_mirror_cnav.py)
-CNAV_MIRROR_TEST := tests/cpp/cnav_mirror_test
-$(CNAV_MIRROR_TEST): tests/cpp/cnav_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/cnav_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(LNAV_MIRROR_TEST)
-
-# The BeiDou D1/D2 telemetry decoder mirror (tests/test_cpp_mirror_dnav.py)
-DNAV_MIRROR_TEST := tests/cpp/dnav_mirror_test
-$(DNAV_MIRROR_TEST): tests/cpp/dnav_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/dnav_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(DNAV_MIRROR_TEST)
-
-# The GLONASS GNAV telemetry decoder mirror (tests/test_cpp_mirror_gnav.py)
-GNAV_MIRROR_TEST := tests/cpp/gnav_mirror_test
-$(GNAV_MIRROR_TEST): tests/cpp/gnav_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
-	g++ -O2 -std=c++17 -Wall -Iinclude tests/cpp/gnav_mirror_test.cpp -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
-all: $(GNAV_MIRROR_TEST)
+# Every other tests/cpp/<name>_mirror_test: one feature through the C++ mirror, linked against the product library only
+# (tests/test_cpp_mirror_<name>.py runs it).  tests/cpp/mirror_test above has no stem and keeps its own rule.
+MIRROR_TESTS := $(patsubst %.cpp,%,$(wildcard tests/cpp/*_mirror_test.cpp))
+tests/cpp/%_mirror_test: tests/cpp/%_mirror_test.cpp include/gnsship_cpp.hpp include/gnsship.h $(LIB)
+	g++ -O2 -std=c++17 -Wall -Iinclude $< -o $@ -L$(PKG) -lgnsship -Wl,-rpath,'$$ORIGIN/../../$(PKG)' -lpthread -lm
+all: $(MIRROR_TESTS)
 
 # Profiling variant (workgroup phase timestamps in corr_batch_kernel; scripts/corr_wg_profile.py)
 PROF_LIB := scripts/libgnsship_prof.so

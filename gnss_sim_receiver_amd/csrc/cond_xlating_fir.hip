@@ -40,14 +40,11 @@
 #include <type_traits>
 #include <vector>
 
-#include "engine.h"
+#include "host_api.h"
 
 #pragma clang fp contract(off)
 
 namespace gnsship {
-int fail(gnsship_ctx* ctx, int code, const char* what);
-int hip_fail(gnsship_ctx* ctx, hipError_t e, const char* where);
-int set_device(gnsship_ctx* ctx);
 size_t fmt_bytes(int fmt);
 }  // namespace gnsship
 

@@ -42,17 +42,11 @@
 #include <cstring>
 #include <new>
 
-#include "engine.h"
+#include "host_api.h"
 #include "glibc_atanf.h"
 #include "glibc_sincosf.h"
 
 #pragma clang fp contract(off)
-
-namespace gnsship {
-int fail(gnsship_ctx* ctx, int code, const char* what);
-int hip_fail(gnsship_ctx* ctx, hipError_t e, const char* where);
-int set_device(gnsship_ctx* ctx);
-}  // namespace gnsship
 
 using namespace gnsship;
 

@@ -27,22 +27,17 @@
 //   CRC-24Q  linear: lane i XORs bit i's remainder x^(n−1−i+24) mod g from a table built at create, the checksum bits
 //            are XORed in at their own weights, a butterfly XOR joins the lanes: zero means the CRC holds.
 // Every LDS and HBM index comes from lane numbers, sizes and ballot bits, never from a symbol's value.
+// The host path around the kernel (staging, the run calls' checks, output copies) is tlm_host.h.
 #include <algorithm>
 #include <cstring>
 #include <new>
 #include <vector>
 
-#include "engine.h"
+#include "tlm_device.h"
+#include "tlm_host.h"
 #include "vit_wave.h"
 
 #pragma clang fp contract(off)
-
-namespace gnsship {
-int fail(gnsship_ctx* ctx, int code, const char* what);
-int hip_fail(gnsship_ctx* ctx, hipError_t e, const char* where);
-int set_device(gnsship_ctx* ctx);
-gnsship_ctx* trk_context(const gnsship_trk* t);
-}  // namespace gnsship
 
 using namespace gnsship;
 
@@ -93,14 +88,6 @@ __device__ __forceinline__ uint32_t tlm_wave_xor(uint32_t x)
 {
     for (int d = 32; d >= 1; d >>= 1) x ^= static_cast<uint32_t>(__shfl_xor(static_cast<int>(x), d));
     return x;
-}
-
-__device__ __forceinline__ int tlm_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t tlm_uniform64(uint64_t v)
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-    return (static_cast<uint64_t>(hi) << 32) | lo;
 }
 
 // kFull: GNSSHIP_VIT_MODE_FULL
@@ -348,10 +335,10 @@ __global__ void tlm_control_kernel(TlmChan* cs, int what)
 }  // namespace
 
 struct gnsship_tlm {
-    gnsship_ctx* ctx = nullptr;
+    TlmHost h;  // h.mask: unused
     gnsship_tlm_conf conf = {};
     TlmGeometry geo = {};
-    int32_t max_channels = 0, P = 0, cap = 0, pages_per_run = 0;
+    int32_t P = 0, cap = 0, pages_per_run = 0;
     uint32_t pre_zero_mask = 0;
     TlmChan* chans_dev = nullptr;
     float* ring_dev = nullptr;
@@ -361,31 +348,20 @@ struct gnsship_tlm {
     int32_t* counts_dev = nullptr;
     uint8_t* faults_dev = nullptr;
     uint32_t* crc_dev = nullptr;
-    void* stage_dev = nullptr;   // host symbols or records
-    uint8_t* valid_dev = nullptr;
-    size_t stage_cap = 0, valid_cap = 0;
 };
 
 extern "C" int gnsship_tlm_destroy(gnsship_tlm* t)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(t->ctx->device);
-    (void)hipStreamSynchronize(t->ctx->stream);
-    void* ptrs[] = {t->chans_dev, t->ring_dev, t->sections_dev, t->pages_dev, t->bits_dev, t->counts_dev, t->faults_dev, t->crc_dev, t->stage_dev,
-        t->valid_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    tlm_release(t->h, {t->chans_dev, t->ring_dev, t->sections_dev, t->pages_dev, t->bits_dev, t->counts_dev, t->faults_dev, t->crc_dev});
     delete t;
     return GNSSHIP_OK;
 }
 
 static int tlm_fill_sections(gnsship_tlm* t, int64_t first, int64_t n, const char* where)
 {
-    gnsship_ctx* ctx = t->ctx;
-    hipLaunchKernelGGL(tlm_fill_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, ctx->stream, t->sections_dev + first, n, -kVitMaxLog);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, where);
-    return GNSSHIP_OK;
+    hipLaunchKernelGGL(tlm_fill_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, t->h.ctx->stream, t->sections_dev + first, n, -kVitMaxLog);
+    return tlm_launched(t->h.ctx, where);
 }
 
 extern "C" int gnsship_tlm_create(gnsship_ctx* ctx, const gnsship_tlm_conf* conf, int32_t max_channels, gnsship_tlm** out)
@@ -403,10 +379,11 @@ extern "C" int gnsship_tlm_create(gnsship_ctx* ctx, const gnsship_tlm_conf* conf
     if (int rc = set_device(ctx)) return rc;
     gnsship_tlm* t = new (std::nothrow) gnsship_tlm();
     if (!t) return GNSSHIP_E_NOMEM;
-    t->ctx = ctx;
+    t->h.ctx = ctx;
+    t->h.max_channels = max_channels;
+    t->h.max_rounds = conf->max_rounds;
     t->conf = *conf;
     t->geo = kTlmGeometry[conf->frame_type];
-    t->max_channels = max_channels;
     t->P = static_cast<int32_t>(std::strlen(t->geo.preamble));
     t->cap = t->geo.required + 1;
     t->pages_per_run = conf->max_rounds / t->geo.period + 1;
@@ -424,20 +401,9 @@ extern "C" int gnsship_tlm_create(gnsship_ctx* ctx, const gnsship_tlm_conf* conf
     }
     for (int i = 0; i < n; i++) table[i] = rem[n - 1 - i + 24];
     const size_t nc = static_cast<size_t>(max_channels), slots = nc * t->pages_per_run;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&t->chans_dev), sizeof(TlmChan) * nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->ring_dev), sizeof(float) * nc * t->cap);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->sections_dev), sizeof(float) * 64 * nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->pages_dev), sizeof(gnsship_tlm_page) * slots);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->bits_dev), slots * t->geo.LL);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->counts_dev), sizeof(int32_t) * nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->faults_dev), nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->crc_dev), sizeof(uint32_t) * n);
-    if (e == hipSuccess) e = hipMemsetAsync(t->chans_dev, 0, sizeof(TlmChan) * nc, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->ring_dev, 0, sizeof(float) * nc * t->cap, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->pages_dev, 0, sizeof(gnsship_tlm_page) * slots, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->bits_dev, 0, slots * t->geo.LL, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->counts_dev, 0, sizeof(int32_t) * nc, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->faults_dev, 0, nc, ctx->stream);
+    hipError_t e = tlm_alloc(ctx, {tlm_buf(&t->chans_dev, nc, true), tlm_buf(&t->ring_dev, nc * t->cap, true), tlm_buf(&t->sections_dev, 64 * nc, false),
+                                      tlm_buf(&t->pages_dev, slots, true), tlm_buf(&t->bits_dev, slots * t->geo.LL, true), tlm_buf(&t->counts_dev, nc, true),
+                                      tlm_buf(&t->faults_dev, nc, true), tlm_buf(&t->crc_dev, static_cast<size_t>(n), false)});
     if (e == hipSuccess) e = hipMemcpyAsync(t->crc_dev, table.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // `table` is a local
     if (e != hipSuccess) {
@@ -456,7 +422,7 @@ extern "C" int gnsship_tlm_create(gnsship_ctx* ctx, const gnsship_tlm_conf* conf
 static int tlm_launch(gnsship_tlm* t, const float* sym, const uint8_t* valid, const gnsship_trk_epoch* rec, int32_t n_rounds, gnsship_tlm_page* pages_host,
     uint8_t* bits_host, int32_t* counts_host, uint8_t* faults_host, const char* who)
 {
-    gnsship_ctx* ctx = t->ctx;
+    gnsship_ctx* ctx = t->h.ctx;
     TlmArgs a = {};
     a.sym = sym;
     a.valid = valid;
@@ -469,7 +435,7 @@ static int tlm_launch(gnsship_tlm* t, const float* sym, const uint8_t* valid, co
     a.counts = t->counts_dev;
     a.faults = t->faults_dev;
     a.crc_table = t->crc_dev;
-    a.max_channels = t->max_channels;
+    a.max_channels = t->h.max_channels;
     a.n_rounds = n_rounds;
     a.pages_per_run = t->pages_per_run;
     a.frame_type = t->conf.frame_type;
@@ -484,101 +450,42 @@ static int tlm_launch(gnsship_tlm* t, const float* sym, const uint8_t* valid, co
     a.pre_zero_mask = t->pre_zero_mask;
     const size_t lds = 16 * static_cast<size_t>(vit_wave_lds_words(a.LL + kVitTail));  // 1.8 KiB I/NAV .. 11.6 KiB C/NAV
     if (t->conf.vit_mode == GNSSHIP_VIT_MODE_FULL)
-        hipLaunchKernelGGL(tlm_kernel<true>, dim3(static_cast<unsigned>(t->max_channels)), dim3(64), lds, ctx->stream, a);
+        hipLaunchKernelGGL(tlm_kernel<true>, dim3(static_cast<unsigned>(t->h.max_channels)), dim3(64), lds, ctx->stream, a);
     else
-        hipLaunchKernelGGL(tlm_kernel<false>, dim3(static_cast<unsigned>(t->max_channels)), dim3(64), lds, ctx->stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    if (!pages_host && !bits_host && !counts_host && !faults_host) return GNSSHIP_OK;
-    const size_t nc = static_cast<size_t>(t->max_channels), slots = nc * t->pages_per_run;
-    if (pages_host) e = hipMemcpyAsync(pages_host, t->pages_dev, sizeof(gnsship_tlm_page) * slots, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && bits_host) e = hipMemcpyAsync(bits_host, t->bits_dev, slots * t->geo.LL, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && counts_host) e = hipMemcpyAsync(counts_host, t->counts_dev, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && faults_host) e = hipMemcpyAsync(faults_host, t->faults_dev, nc, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
-}
-
-// Host data of `bytes` bytes to a staging buffer that grows as needed.
-static int tlm_stage(gnsship_tlm* t, void** buf, size_t* cap, const void* host, size_t bytes, const char* who)
-{
-    gnsship_ctx* ctx = t->ctx;
-    hipError_t e = hipSuccess;
-    if (*cap < bytes) {
-        e = hipStreamSynchronize(ctx->stream);  // earlier launches may still read the old buffer
-        if (*buf && e == hipSuccess) e = hipFree(*buf);
-        *buf = nullptr;
-        *cap = 0;
-        if (e == hipSuccess) e = hipMalloc(buf, bytes);
-        if (e != hipSuccess) return hip_fail(ctx, e, who);
-        *cap = bytes;
-    }
-    e = hipMemcpyAsync(*buf, host, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
+        hipLaunchKernelGGL(tlm_kernel<false>, dim3(static_cast<unsigned>(t->h.max_channels)), dim3(64), lds, ctx->stream, a);
+    if (int rc = tlm_launched(ctx, who)) return rc;
+    const size_t nc = static_cast<size_t>(t->h.max_channels), slots = nc * t->pages_per_run;
+    return tlm_copy_out(ctx, {{pages_host, t->pages_dev, sizeof(gnsship_tlm_page) * slots}, {bits_host, t->bits_dev, slots * t->geo.LL},
+                                 {counts_host, t->counts_dev, sizeof(int32_t) * nc}, {faults_host, t->faults_dev, nc}}, who);
 }
 
 extern "C" int gnsship_tlm_run_symbols(gnsship_tlm* t, const float* symbols, const uint8_t* valid, int on_device, int32_t n_rounds,
     gnsship_tlm_page* pages_host, uint8_t* bits_host, int32_t* counts_host, uint8_t* faults_host)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (n_rounds < 0 || n_rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_tlm_run_symbols: 0 <= n_rounds <= max_rounds");
-    if (n_rounds > 0 && !symbols) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_tlm_run_symbols: null symbols");
-    if (int rc = set_device(ctx)) return rc;
-    const size_t n = static_cast<size_t>(n_rounds) * t->max_channels;
-    const float* sym = symbols;
-    const uint8_t* val = valid;
-    if (!on_device && n > 0) {
-        if (int rc = tlm_stage(t, &t->stage_dev, &t->stage_cap, symbols, sizeof(float) * n, "gnsship_tlm_run_symbols(upload)")) return rc;
-        sym = static_cast<const float*>(t->stage_dev);
-        if (valid) {
-            void* vb = t->valid_dev;
-            const int rc = tlm_stage(t, &vb, &t->valid_cap, valid, n, "gnsship_tlm_run_symbols(upload)");
-            t->valid_dev = static_cast<uint8_t*>(vb);
-            if (rc) return rc;
-            val = t->valid_dev;
-        }
-    }
-    return tlm_launch(t, sym, val, nullptr, n_rounds, pages_host, bits_host, counts_host, faults_host, "gnsship_tlm_run_symbols");
+    const char* who = "gnsship_tlm_run_symbols";
+    if (int rc = tlm_symbols_in(t->h, who, on_device, n_rounds, &symbols, &valid, nullptr)) return rc;
+    return tlm_launch(t, symbols, valid, nullptr, n_rounds, pages_host, bits_host, counts_host, faults_host, who);
 }
 
 extern "C" int gnsship_tlm_run_records(gnsship_tlm* t, const gnsship_trk_epoch* records, int on_device, int32_t n_rounds, gnsship_tlm_page* pages_host,
     uint8_t* bits_host, int32_t* counts_host, uint8_t* faults_host)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (n_rounds < 0 || n_rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_tlm_run_records: 0 <= n_rounds <= max_rounds");
-    if (n_rounds > 0 && !records) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_tlm_run_records: null records");
-    if (int rc = set_device(ctx)) return rc;
-    const size_t n = static_cast<size_t>(n_rounds) * t->max_channels;
-    const gnsship_trk_epoch* rec = records;
-    if (!on_device && n > 0) {
-        if (int rc = tlm_stage(t, &t->stage_dev, &t->stage_cap, records, sizeof(gnsship_trk_epoch) * n, "gnsship_tlm_run_records(upload)")) return rc;
-        rec = static_cast<const gnsship_trk_epoch*>(t->stage_dev);
-    }
-    if (n_rounds == 0) return tlm_launch(t, nullptr, nullptr, nullptr, 0, pages_host, bits_host, counts_host, faults_host, "gnsship_tlm_run_records");
-    return tlm_launch(t, nullptr, nullptr, rec, n_rounds, pages_host, bits_host, counts_host, faults_host, "gnsship_tlm_run_records");
+    const char* who = "gnsship_tlm_run_records";
+    if (int rc = tlm_records_in(t->h, who, on_device, n_rounds, &records)) return rc;
+    return tlm_launch(t, nullptr, nullptr, records, n_rounds, pages_host, bits_host, counts_host, faults_host, who);
 }
 
 extern "C" int gnsship_tlm_run_trk(gnsship_tlm* t, gnsship_trk* trk, gnsship_tlm_page* pages_host, uint8_t* bits_host, int32_t* counts_host,
     uint8_t* faults_host)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (!trk) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_tlm_run_trk: null tracking handle");
-    if (trk_context(trk) != ctx) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_tlm_run_trk: the tracking handle is on another context");
+    const char* who = "gnsship_tlm_run_trk";
     const gnsship_trk_epoch* rec = nullptr;
-    int32_t rounds = 0, nc = 0;
-    if (int rc = gnsship_trk_records_device(trk, &rec, &rounds, &nc)) {
-        if (rc == GNSSHIP_E_STATE) return fail(ctx, GNSSHIP_E_STATE, "gnsship_tlm_run_trk: the tracker's last run kept no records on the device");
-        return rc;
-    }
-    if (nc != t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_tlm_run_trk: the handles' max_channels differ");
-    if (rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_tlm_run_trk: the tracker's run had more rounds than max_rounds");
-    if (int rc = set_device(ctx)) return rc;
-    return tlm_launch(t, nullptr, nullptr, rec, rounds, pages_host, bits_host, counts_host, faults_host, "gnsship_tlm_run_trk");
+    int32_t rounds = 0;
+    if (int rc = tlm_trk_in(t->h, who, trk, &rec, &rounds)) return rc;
+    return tlm_launch(t, nullptr, nullptr, rec, rounds, pages_host, bits_host, counts_host, faults_host, who);
 }
 
 extern "C" int gnsship_tlm_outputs_device(gnsship_tlm* t, gnsship_tlm_page** pages, uint8_t** bits, int32_t** counts, uint8_t** faults,
@@ -593,51 +500,40 @@ extern "C" int gnsship_tlm_outputs_device(gnsship_tlm* t, gnsship_tlm_page** pag
     return GNSSHIP_OK;
 }
 
-static int tlm_control(gnsship_tlm* t, int32_t channel, int what, const char* who, const char* range)
+static int tlm_control(gnsship_tlm* t, int32_t channel, int what, const char* who)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, range);
-    if (int rc = set_device(ctx)) return rc;
-    hipLaunchKernelGGL(tlm_control_kernel, dim3(1), dim3(1), 0, ctx->stream, t->chans_dev + channel, what);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
+    if (int rc = tlm_check_channel(t->h, who, channel)) return rc;
+    if (int rc = set_device(t->h.ctx)) return rc;
+    hipLaunchKernelGGL(tlm_control_kernel, dim3(1), dim3(1), 0, t->h.ctx->stream, t->chans_dev + channel, what);
+    return tlm_launched(t->h.ctx, who);
 }
 
-extern "C" int gnsship_tlm_reset_channel(gnsship_tlm* t, int32_t channel)
-{
-    return tlm_control(t, channel, 1, "gnsship_tlm_reset_channel", "gnsship_tlm_reset_channel: channel out of range");
-}
+extern "C" int gnsship_tlm_reset_channel(gnsship_tlm* t, int32_t channel) { return tlm_control(t, channel, 1, "gnsship_tlm_reset_channel"); }
 
-extern "C" int gnsship_tlm_set_satellite(gnsship_tlm* t, int32_t channel)
-{
-    return tlm_control(t, channel, 0, "gnsship_tlm_set_satellite", "gnsship_tlm_set_satellite: channel out of range");
-}
+extern "C" int gnsship_tlm_set_satellite(gnsship_tlm* t, int32_t channel) { return tlm_control(t, channel, 0, "gnsship_tlm_set_satellite"); }
 
 extern "C" int gnsship_tlm_new_channel(gnsship_tlm* t, int32_t channel)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_tlm_new_channel: channel out of range");
+    gnsship_ctx* ctx = t->h.ctx;
+    const char* who = "gnsship_tlm_new_channel";
+    if (int rc = tlm_check_channel(t->h, who, channel)) return rc;
     if (int rc = set_device(ctx)) return rc;
     hipError_t e = hipMemsetAsync(t->chans_dev + channel, 0, sizeof(TlmChan), ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(t->ring_dev + static_cast<size_t>(channel) * t->cap, 0, sizeof(float) * t->cap, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_tlm_new_channel");
-    return tlm_fill_sections(t, static_cast<int64_t>(channel) * 64, 64, "gnsship_tlm_new_channel");
+    if (e != hipSuccess) return hip_fail(ctx, e, who);
+    return tlm_fill_sections(t, static_cast<int64_t>(channel) * 64, 64, who);
 }
 
 extern "C" int gnsship_tlm_state_get(gnsship_tlm* t, int32_t channel, gnsship_tlm_state* st)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (!st) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_tlm_state_get: null state");
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_tlm_state_get: channel out of range");
-    if (int rc = set_device(ctx)) return rc;
+    const char* who = "gnsship_tlm_state_get";
+    if (int rc = tlm_check_state(t->h, who, channel, st)) return rc;
+    if (int rc = set_device(t->h.ctx)) return rc;
     TlmChan c;
-    hipError_t e = hipMemcpyAsync(&c, t->chans_dev + channel, sizeof(TlmChan), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_tlm_state_get");
+    if (int rc = tlm_copy_out(t->h.ctx, {{&c, t->chans_dev + channel, sizeof(TlmChan)}}, who)) return rc;
     std::memset(st, 0, sizeof(*st));
     st->symbol_counter = c.symbol_counter;
     st->preamble_index = c.preamble_index;

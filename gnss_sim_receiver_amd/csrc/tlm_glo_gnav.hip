@@ -24,16 +24,11 @@
 //   hits     popcount of (window XOR time mark): 0 or 300 is a hit, below 150 is corr > 0.
 // Every ring index is a counter reduced modulo 2000 and every record slot is below strings_per_run: no index comes from a
 // symbol's value.
+// The host path around the kernel (staging, the run calls' checks, output copies) is tlm_host.h, shared with the other
+// four decoders; the device helpers of their kernels (tlm_device.h) have no use here.
 #include <new>
 
-#include "engine.h"
-
-namespace gnsship {
-int fail(gnsship_ctx* ctx, int code, const char* what);
-int hip_fail(gnsship_ctx* ctx, hipError_t e, const char* where);
-int set_device(gnsship_ctx* ctx);
-gnsship_ctx* trk_context(const gnsship_trk* t);
-}  // namespace gnsship
+#include "tlm_host.h"
 
 using namespace gnsship;
 
@@ -461,38 +456,28 @@ __global__ void gnav_control_kernel(gnsship_gnav_state* chans, int first, int n,
 }  // namespace
 
 struct gnsship_gnav {
-    gnsship_ctx* ctx = nullptr;
+    TlmHost h;  // h.mask: unused, the blocks never read Flag_valid_symbol_output
     gnsship_gnav_conf conf = {};
-    int32_t max_channels = 0, strings_per_run = 0;
+    int32_t strings_per_run = 0;
     gnsship_gnav_state* chans_dev = nullptr;
     gnsship_gnav_string* strings_dev = nullptr;
     int32_t* counts_dev = nullptr;
     uint32_t* tow_dev = nullptr;
     uint8_t* sflags_dev = nullptr;
-    void* stage_dev = nullptr;   // host symbols or records
-    void* valid_dev = nullptr;
-    size_t stage_cap = 0, valid_cap = 0;
 };
 
 extern "C" int gnsship_gnav_destroy(gnsship_gnav* t)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(t->ctx->device);
-    (void)hipStreamSynchronize(t->ctx->stream);
-    void* ptrs[] = {t->chans_dev, t->strings_dev, t->counts_dev, t->tow_dev, t->sflags_dev, t->stage_dev, t->valid_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    tlm_release(t->h, {t->chans_dev, t->strings_dev, t->counts_dev, t->tow_dev, t->sflags_dev});
     delete t;
     return GNSSHIP_OK;
 }
 
 static int gnav_control(gnsship_gnav* t, int first, int n, int what, int prn, const char* who)
 {
-    gnsship_ctx* ctx = t->ctx;
-    hipLaunchKernelGGL(gnav_control_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, ctx->stream, t->chans_dev, first, n, what, prn);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
+    hipLaunchKernelGGL(gnav_control_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, t->h.ctx->stream, t->chans_dev, first, n, what, prn);
+    return tlm_launched(t->h.ctx, who);
 }
 
 extern "C" int gnsship_gnav_create(gnsship_ctx* ctx, const gnsship_gnav_conf* conf, int32_t max_channels, gnsship_gnav** out)
@@ -508,20 +493,14 @@ extern "C" int gnsship_gnav_create(gnsship_ctx* ctx, const gnsship_gnav_conf* co
     if (int rc = set_device(ctx)) return rc;
     gnsship_gnav* t = new (std::nothrow) gnsship_gnav();
     if (!t) return GNSSHIP_E_NOMEM;
-    t->ctx = ctx;
+    t->h.ctx = ctx;
+    t->h.max_channels = max_channels;
+    t->h.max_rounds = conf->max_rounds;
     t->conf = *conf;
-    t->max_channels = max_channels;
     t->strings_per_run = GNSSHIP_GNAV_STRINGS_PER_RUN(conf->max_rounds);
     const size_t nc = static_cast<size_t>(max_channels), slots = nc * t->strings_per_run, entries = nc * conf->max_rounds;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&t->chans_dev), sizeof(gnsship_gnav_state) * nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->strings_dev), sizeof(gnsship_gnav_string) * slots);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->counts_dev), sizeof(int32_t) * nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->tow_dev), sizeof(uint32_t) * entries);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->sflags_dev), entries);
-    if (e == hipSuccess) e = hipMemsetAsync(t->strings_dev, 0, sizeof(gnsship_gnav_string) * slots, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->counts_dev, 0, sizeof(int32_t) * nc, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->tow_dev, 0, sizeof(uint32_t) * entries, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->sflags_dev, 0, entries, ctx->stream);
+    const hipError_t e = tlm_alloc(ctx, {tlm_buf(&t->chans_dev, nc, false), tlm_buf(&t->strings_dev, slots, true), tlm_buf(&t->counts_dev, nc, true),
+                                            tlm_buf(&t->tow_dev, entries, true), tlm_buf(&t->sflags_dev, entries, true)});
     if (e != hipSuccess) {
         gnsship_gnav_destroy(t);
         return hip_fail(ctx, e, "gnsship_gnav_create");
@@ -538,7 +517,7 @@ extern "C" int gnsship_gnav_create(gnsship_ctx* ctx, const gnsship_gnav_conf* co
 static int gnav_launch(gnsship_gnav* t, const float* sym, const uint8_t* valid, const gnsship_trk_epoch* rec, int32_t n_rounds,
     gnsship_gnav_string* strings_host, int32_t* counts_host, uint32_t* tow_ms_host, uint8_t* sflags_host, const char* who)
 {
-    gnsship_ctx* ctx = t->ctx;
+    gnsship_ctx* ctx = t->h.ctx;
     GnavArgs a = {};
     a.sym = sym;
     a.valid = valid;
@@ -548,40 +527,14 @@ static int gnav_launch(gnsship_gnav* t, const float* sym, const uint8_t* valid, 
     a.counts = t->counts_dev;
     a.tow_ms = t->tow_dev;
     a.sflags = t->sflags_dev;
-    a.max_channels = t->max_channels;
+    a.max_channels = t->h.max_channels;
     a.n_rounds = n_rounds;
     a.strings_per_run = t->strings_per_run;
-    hipLaunchKernelGGL(gnav_kernel, dim3(static_cast<unsigned>((t->max_channels + 63) / 64)), dim3(64), 0, ctx->stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    if (!strings_host && !counts_host && !tow_ms_host && !sflags_host) return GNSSHIP_OK;
-    const size_t nc = static_cast<size_t>(t->max_channels), slots = nc * t->strings_per_run, entries = nc * n_rounds;
-    if (strings_host) e = hipMemcpyAsync(strings_host, t->strings_dev, sizeof(gnsship_gnav_string) * slots, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && counts_host) e = hipMemcpyAsync(counts_host, t->counts_dev, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && tow_ms_host && entries) e = hipMemcpyAsync(tow_ms_host, t->tow_dev, sizeof(uint32_t) * entries, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && sflags_host && entries) e = hipMemcpyAsync(sflags_host, t->sflags_dev, entries, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
-}
-
-// Host data of `bytes` bytes to a staging buffer that grows as needed.
-static int gnav_stage(gnsship_gnav* t, void** buf, size_t* cap, const void* host, size_t bytes, const char* who)
-{
-    gnsship_ctx* ctx = t->ctx;
-    hipError_t e = hipSuccess;
-    if (*cap < bytes) {
-        e = hipStreamSynchronize(ctx->stream);  // earlier launches may still read the old buffer
-        if (*buf && e == hipSuccess) e = hipFree(*buf);
-        *buf = nullptr;
-        *cap = 0;
-        if (e == hipSuccess) e = hipMalloc(buf, bytes);
-        if (e != hipSuccess) return hip_fail(ctx, e, who);
-        *cap = bytes;
-    }
-    e = hipMemcpyAsync(*buf, host, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
+    hipLaunchKernelGGL(gnav_kernel, dim3(static_cast<unsigned>((t->h.max_channels + 63) / 64)), dim3(64), 0, ctx->stream, a);  // a lane per channel
+    if (int rc = tlm_launched(ctx, who)) return rc;
+    const size_t nc = static_cast<size_t>(t->h.max_channels), slots = nc * t->strings_per_run, entries = nc * n_rounds;
+    return tlm_copy_out(ctx, {{strings_host, t->strings_dev, sizeof(gnsship_gnav_string) * slots}, {counts_host, t->counts_dev, sizeof(int32_t) * nc},
+                                 {tow_ms_host, t->tow_dev, sizeof(uint32_t) * entries}, {sflags_host, t->sflags_dev, entries}}, who);
 }
 
 extern "C" int gnsship_gnav_run_symbols(gnsship_gnav* t, const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int on_device,
@@ -589,63 +542,30 @@ extern "C" int gnsship_gnav_run_symbols(gnsship_gnav* t, const float* symbols, c
 {
     if (!t) return GNSSHIP_E_INVAL;
     (void)out_valid;  // Flag_valid_symbol_output: the blocks never read it
-    gnsship_ctx* ctx = t->ctx;
-    if (n_rounds < 0 || n_rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_run_symbols: 0 <= n_rounds <= max_rounds");
-    if (n_rounds > 0 && !symbols) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_run_symbols: null symbols");
-    if (int rc = set_device(ctx)) return rc;
-    const size_t n = static_cast<size_t>(n_rounds) * t->max_channels;
-    const float* sym = symbols;
-    const uint8_t* val = valid;
-    if (!on_device && n > 0) {
-        const char* who = "gnsship_gnav_run_symbols(upload)";
-        if (int rc = gnav_stage(t, &t->stage_dev, &t->stage_cap, symbols, sizeof(float) * n, who)) return rc;
-        sym = static_cast<const float*>(t->stage_dev);
-        if (valid) {
-            if (int rc = gnav_stage(t, &t->valid_dev, &t->valid_cap, valid, n, who)) return rc;
-            val = static_cast<const uint8_t*>(t->valid_dev);
-        }
-    }
-    return gnav_launch(t, sym, val, nullptr, n_rounds, strings_host, counts_host, tow_ms_host, sflags_host, "gnsship_gnav_run_symbols");
+    const char* who = "gnsship_gnav_run_symbols";
+    if (int rc = tlm_symbols_in(t->h, who, on_device, n_rounds, &symbols, &valid, nullptr)) return rc;
+    return gnav_launch(t, symbols, valid, nullptr, n_rounds, strings_host, counts_host, tow_ms_host, sflags_host, who);
 }
 
 extern "C" int gnsship_gnav_run_records(gnsship_gnav* t, const gnsship_trk_epoch* records, int on_device, int32_t n_rounds,
     gnsship_gnav_string* strings_host, int32_t* counts_host, uint32_t* tow_ms_host, uint8_t* sflags_host)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (n_rounds < 0 || n_rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_run_records: 0 <= n_rounds <= max_rounds");
-    if (n_rounds > 0 && !records) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_run_records: null records");
-    if (int rc = set_device(ctx)) return rc;
-    const size_t n = static_cast<size_t>(n_rounds) * t->max_channels;
-    const gnsship_trk_epoch* rec = records;
-    if (!on_device && n > 0) {
-        if (int rc = gnav_stage(t, &t->stage_dev, &t->stage_cap, records, sizeof(gnsship_trk_epoch) * n, "gnsship_gnav_run_records(upload)")) return rc;
-        rec = static_cast<const gnsship_trk_epoch*>(t->stage_dev);
-    }
-    // with no rounds the kernel reads no entry: any non-null pointer selects the record path
-    return gnav_launch(t, nullptr, nullptr, n_rounds > 0 ? rec : nullptr, n_rounds, strings_host, counts_host, tow_ms_host, sflags_host,
-        "gnsship_gnav_run_records");
+    const char* who = "gnsship_gnav_run_records";
+    if (int rc = tlm_records_in(t->h, who, on_device, n_rounds, &records)) return rc;
+    return gnav_launch(t, nullptr, nullptr, records, n_rounds, strings_host, counts_host, tow_ms_host, sflags_host, who);
 }
 
 extern "C" int gnsship_gnav_run_trk(gnsship_gnav* t, gnsship_trk* trk, gnsship_gnav_string* strings_host, int32_t* counts_host,
     uint32_t* tow_ms_host, uint8_t* sflags_host, int32_t* n_rounds_out)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (!trk) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_run_trk: null tracking handle");
-    if (trk_context(trk) != ctx) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_run_trk: the tracking handle is on another context");
+    const char* who = "gnsship_gnav_run_trk";
     const gnsship_trk_epoch* rec = nullptr;
-    int32_t rounds = 0, nc = 0;
-    if (int rc = gnsship_trk_records_device(trk, &rec, &rounds, &nc)) {
-        if (rc == GNSSHIP_E_STATE) return fail(ctx, GNSSHIP_E_STATE, "gnsship_gnav_run_trk: the tracker's last run kept no records on the device");
-        return rc;
-    }
-    if (nc != t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_run_trk: the handles' max_channels differ");
-    if (rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_run_trk: the tracker's run had more rounds than max_rounds");
-    if (int rc = set_device(ctx)) return rc;
+    int32_t rounds = 0;
+    if (int rc = tlm_trk_in(t->h, who, trk, &rec, &rounds)) return rc;
     if (n_rounds_out) *n_rounds_out = rounds;
-    return gnav_launch(t, nullptr, nullptr, rounds > 0 ? rec : nullptr, rounds, strings_host, counts_host, tow_ms_host, sflags_host,
-        "gnsship_gnav_run_trk");
+    return gnav_launch(t, nullptr, nullptr, rec, rounds, strings_host, counts_host, tow_ms_host, sflags_host, who);
 }
 
 extern "C" int gnsship_gnav_outputs_device(gnsship_gnav* t, gnsship_gnav_string** strings, int32_t** counts, uint32_t** tow_ms, uint8_t** sflags,
@@ -660,43 +580,40 @@ extern "C" int gnsship_gnav_outputs_device(gnsship_gnav* t, gnsship_gnav_string*
     return GNSSHIP_OK;
 }
 
-extern "C" int gnsship_gnav_set_satellite(gnsship_gnav* t, int32_t channel, int32_t prn)
+// set_satellite (what 1) and new_channel (2) on one channel
+static int gnav_channel_call(gnsship_gnav* t, int32_t channel, int what, int32_t prn, const char* who)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    if (channel < 0 || channel >= t->max_channels) return fail(t->ctx, GNSSHIP_E_INVAL, "gnsship_gnav_set_satellite: channel out of range");
-    if (prn < 0 || prn > 63) return fail(t->ctx, GNSSHIP_E_INVAL, "gnsship_gnav_set_satellite: 0 <= prn <= 63");
-    if (int rc = set_device(t->ctx)) return rc;
-    return gnav_control(t, channel, 1, 1, prn, "gnsship_gnav_set_satellite");
+    if (int rc = tlm_check_channel(t->h, who, channel)) return rc;
+    if (prn < 0 || prn > 63) return tlm_reject(t->h.ctx, GNSSHIP_E_INVAL, who, "0 <= prn <= 63");
+    if (int rc = set_device(t->h.ctx)) return rc;
+    return gnav_control(t, channel, 1, what, prn, who);
+}
+
+extern "C" int gnsship_gnav_set_satellite(gnsship_gnav* t, int32_t channel, int32_t prn)
+{
+    return gnav_channel_call(t, channel, 1, prn, "gnsship_gnav_set_satellite");
 }
 
 extern "C" int gnsship_gnav_new_channel(gnsship_gnav* t, int32_t channel, int32_t prn)
 {
-    if (!t) return GNSSHIP_E_INVAL;
-    if (channel < 0 || channel >= t->max_channels) return fail(t->ctx, GNSSHIP_E_INVAL, "gnsship_gnav_new_channel: channel out of range");
-    if (prn < 0 || prn > 63) return fail(t->ctx, GNSSHIP_E_INVAL, "gnsship_gnav_new_channel: 0 <= prn <= 63");
-    if (int rc = set_device(t->ctx)) return rc;
-    return gnav_control(t, channel, 1, 2, prn, "gnsship_gnav_new_channel");
+    return gnav_channel_call(t, channel, 2, prn, "gnsship_gnav_new_channel");
 }
 
 extern "C" int gnsship_gnav_state_get(gnsship_gnav* t, int32_t channel, gnsship_gnav_state* st)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (!st) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_state_get: null state");
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_state_get: channel out of range");
-    if (int rc = set_device(ctx)) return rc;
-    hipError_t e = hipMemcpyAsync(st, &t->chans_dev[channel], sizeof(*st), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_gnav_state_get");
-    return GNSSHIP_OK;
+    const char* who = "gnsship_gnav_state_get";
+    if (int rc = tlm_check_state(t->h, who, channel, st)) return rc;
+    if (int rc = set_device(t->h.ctx)) return rc;
+    return tlm_copy_out(t->h.ctx, {{st, &t->chans_dev[channel], sizeof(*st)}}, who);
 }
 
 extern "C" int gnsship_gnav_state_set(gnsship_gnav* t, int32_t channel, const gnsship_gnav_state* st)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (!st) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_state_set: null state");
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_state_set: channel out of range");
+    gnsship_ctx* ctx = t->h.ctx;
+    if (int rc = tlm_check_state(t->h, "gnsship_gnav_state_set", channel, st)) return rc;
     const uint64_t full = st->symbol_counter < 2000u ? st->symbol_counter : 2000u;
     const uint8_t flags[] = {st->frame_sync, st->ephemeris_str[0], st->ephemeris_str[1], st->ephemeris_str[2], st->ephemeris_str[3], st->utc_model_str_5,
         st->tow_set, st->tow_new};
@@ -705,7 +622,6 @@ extern "C" int gnsship_gnav_state_set(gnsship_gnav* t, int32_t channel, const gn
     if (!ok) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_gnav_state_set: stat 0..2, history_size == min(symbol_counter, 2000), crc_error_counter >= 0, flags 0 or 1");
     if (int rc = set_device(ctx)) return rc;
     // pageable host memory: the copy has left *st when the call returns, and is ordered on the stream
-    hipError_t e = hipMemcpyAsync(&t->chans_dev[channel], st, sizeof(*st), hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_gnav_state_set");
-    return GNSSHIP_OK;
+    const hipError_t e = hipMemcpyAsync(&t->chans_dev[channel], st, sizeof(*st), hipMemcpyHostToDevice, ctx->stream);
+    return e == hipSuccess ? GNSSHIP_OK : hip_fail(ctx, e, "gnsship_gnav_state_set");
 }

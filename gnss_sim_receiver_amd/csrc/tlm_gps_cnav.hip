@@ -25,16 +25,11 @@
 //             own additions — one `+= 0.02` per symbol, in order, each lane keeping the sum that is its own.
 //   both parts run in the same wave, one after the other; they share every symbol and either may flush the other.
 // Every LDS and HBM index comes from lane numbers, counters and ballot bits, never from a symbol's value.
+// The host path around the kernel (staging, the run calls' checks, output copies) is tlm_host.h.
 #include <new>
 
-#include "engine.h"
-
-namespace gnsship {
-int fail(gnsship_ctx* ctx, int code, const char* what);
-int hip_fail(gnsship_ctx* ctx, hipError_t e, const char* where);
-int set_device(gnsship_ctx* ctx);
-gnsship_ctx* trk_context(const gnsship_trk* t);
-}  // namespace gnsship
+#include "tlm_device.h"
+#include "tlm_host.h"
 
 using namespace gnsship;
 
@@ -69,17 +64,10 @@ struct CnavPart {  // one cnav_v27_part_t: four registers per lane, the rest wav
     bool old2, seen, invert, lock, crc_ok, init;
 };
 
-__device__ __forceinline__ int cnav_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint32_t cnav_uniform(uint32_t v) { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(v))); }
-__device__ __forceinline__ uint64_t cnav_uniform64(uint64_t v)
-{
-    const uint32_t lo = cnav_uniform(static_cast<uint32_t>(v)), hi = cnav_uniform(static_cast<uint32_t>(v >> 32));
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-}
 __device__ __forceinline__ uint32_t cnav_shfl(uint32_t v, int src) { return static_cast<uint32_t>(__shfl(static_cast<int>(v), src)); }
 __device__ __forceinline__ uint32_t cnav_lane(uint32_t v, int src)  // src is wave-uniform
 {
-    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), cnav_uniform(src)));
+    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), tlm_uniform(src)));
 }
 __device__ __forceinline__ uint32_t cnav_wave_min(uint32_t v)
 {
@@ -90,20 +78,20 @@ __device__ __forceinline__ unsigned long long cnav_below(int x) { return x >= 64
 
 __device__ __forceinline__ void cnav_load(CnavPart& p, const gnsship_cnav_part* s, uint8_t* sym, uint8_t* bit, int lane)
 {
-    p.old2 = cnav_uniform(static_cast<int>(s->old_is_metrics2)) != 0;
+    p.old2 = tlm_uniform(static_cast<int>(s->old_is_metrics2)) != 0;
     p.old = s->metrics[p.old2 ? 1 : 0][lane];
     p.stale = s->metrics[p.old2 ? 0 : 1][lane];
     p.dlo = s->decisions[lane][0];
     p.dhi = s->decisions[lane][1];
-    p.init = cnav_uniform(static_cast<int>(s->init)) != 0;
-    p.n_symbols = static_cast<int>(min(cnav_uniform(s->n_symbols), p.init ? 127u : 63u));
-    p.n_decoded = static_cast<int>(min(cnav_uniform(s->n_decoded), static_cast<uint32_t>(kCnavMaxHeld)));
-    p.n_crc_fail = static_cast<int>(cnav_uniform(s->n_crc_fail));
-    p.didx = static_cast<int>(cnav_uniform(s->decisions_index) & 63u);
-    p.seen = cnav_uniform(static_cast<int>(s->preamble_seen)) != 0;
-    p.invert = cnav_uniform(static_cast<int>(s->invert)) != 0;
-    p.lock = cnav_uniform(static_cast<int>(s->message_lock)) != 0;
-    p.crc_ok = cnav_uniform(static_cast<int>(s->crc_ok)) != 0;
+    p.init = tlm_uniform(static_cast<int>(s->init)) != 0;
+    p.n_symbols = static_cast<int>(min(tlm_uniform(s->n_symbols), p.init ? 127u : 63u));
+    p.n_decoded = static_cast<int>(min(tlm_uniform(s->n_decoded), static_cast<uint32_t>(kCnavMaxHeld)));
+    p.n_crc_fail = static_cast<int>(tlm_uniform(s->n_crc_fail));
+    p.didx = static_cast<int>(tlm_uniform(s->decisions_index) & 63u);
+    p.seen = tlm_uniform(static_cast<int>(s->preamble_seen)) != 0;
+    p.invert = tlm_uniform(static_cast<int>(s->invert)) != 0;
+    p.lock = tlm_uniform(static_cast<int>(s->message_lock)) != 0;
+    p.crc_ok = tlm_uniform(static_cast<int>(s->crc_ok)) != 0;
     sym[lane] = s->symbols[lane];
     sym[lane + 64] = s->symbols[lane + 64];
     const uint32_t byte = s->decoded[lane];  // bits 8·lane .. 8·lane + 7, MSB first
@@ -322,11 +310,11 @@ __global__ __launch_bounds__(64) void cnav_kernel(const CnavArgs a)
     CnavPart p1, p2;
     cnav_load(p1, &cs->part[0], s_sym[0], s_bit[0], lane);
     cnav_load(p2, &cs->part[1], s_sym[1], s_bit[1], lane);
-    uint64_t counter = cnav_uniform64(cs->symbol_counter), last_valid = cnav_uniform64(cs->last_valid_preamble);
-    double tow_s = __longlong_as_double(static_cast<long long>(cnav_uniform64(static_cast<uint64_t>(__double_as_longlong(cs->tow_s)))));
-    uint32_t tow_ms = cnav_uniform(cs->tow_ms), tow_pre = cnav_uniform(cs->tow_at_preamble);
-    bool pll180 = cnav_uniform(static_cast<int>(cs->pll_180)) != 0, vw = cnav_uniform(static_cast<int>(cs->valid_word)) != 0;
-    bool sent = cnav_uniform(static_cast<int>(cs->sent_tlm_failed)) != 0;
+    uint64_t counter = tlm_uniform64(cs->symbol_counter), last_valid = tlm_uniform64(cs->last_valid_preamble);
+    double tow_s = __longlong_as_double(static_cast<long long>(tlm_uniform64(static_cast<uint64_t>(__double_as_longlong(cs->tow_s)))));
+    uint32_t tow_ms = tlm_uniform(cs->tow_ms), tow_pre = tlm_uniform(cs->tow_at_preamble);
+    bool pll180 = tlm_uniform(static_cast<int>(cs->pll_180)) != 0, vw = tlm_uniform(static_cast<int>(cs->valid_word)) != 0;
+    bool sent = tlm_uniform(static_cast<int>(cs->sent_tlm_failed)) != 0;
     __syncthreads();
 
     int count = 0;
@@ -424,7 +412,7 @@ __global__ __launch_bounds__(64) void cnav_kernel(const CnavArgs a)
                 if (pos >= n) break;
 
                 // ---- symbol `pos`: cnav_msg_decoder_add_symbol in full ----
-                const uint8_t s = static_cast<uint8_t>(cnav_uniform(static_cast<int>(c_sym[pos])));
+                const uint8_t s = static_cast<uint8_t>(tlm_uniform(static_cast<int>(c_sym[pos])));
                 const bool ov_here = ((bad >> pos) & 1ull) == 0ull;
                 cnav_add(p1, s_sym[0], s_bit[0], s, lane);
                 cnav_add(p2, s_sym[1], s_bit[1], s, lane);
@@ -577,29 +565,21 @@ void cnav_new_state(gnsship_cnav_state* st)
 }  // namespace
 
 struct gnsship_cnav {
-    gnsship_ctx* ctx = nullptr;
+    TlmHost h;  // h.mask: the output-valid flags
     gnsship_cnav_conf conf = {};
-    int32_t max_channels = 0, messages_per_run = 0;
+    int32_t messages_per_run = 0;
     gnsship_cnav_state* chans_dev = nullptr;
     gnsship_cnav_message* messages_dev = nullptr;
     int32_t* counts_dev = nullptr;
     uint8_t* faults_dev = nullptr;
     uint32_t* tow_dev = nullptr;
     uint8_t* sflags_dev = nullptr;
-    void* stage_dev = nullptr;   // host symbols or records
-    void* valid_dev = nullptr;
-    void* ov_dev = nullptr;
-    size_t stage_cap = 0, valid_cap = 0, ov_cap = 0;
 };
 
 extern "C" int gnsship_cnav_destroy(gnsship_cnav* t)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(t->ctx->device);
-    (void)hipStreamSynchronize(t->ctx->stream);
-    void* ptrs[] = {t->chans_dev, t->messages_dev, t->counts_dev, t->faults_dev, t->tow_dev, t->sflags_dev, t->stage_dev, t->valid_dev, t->ov_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    tlm_release(t->h, {t->chans_dev, t->messages_dev, t->counts_dev, t->faults_dev, t->tow_dev, t->sflags_dev});
     delete t;
     return GNSSHIP_OK;
 }
@@ -616,22 +596,14 @@ extern "C" int gnsship_cnav_create(gnsship_ctx* ctx, const gnsship_cnav_conf* co
     if (int rc = set_device(ctx)) return rc;
     gnsship_cnav* t = new (std::nothrow) gnsship_cnav();
     if (!t) return GNSSHIP_E_NOMEM;
-    t->ctx = ctx;
+    t->h.ctx = ctx;
+    t->h.max_channels = max_channels;
+    t->h.max_rounds = conf->max_rounds;
     t->conf = *conf;
-    t->max_channels = max_channels;
     t->messages_per_run = GNSSHIP_CNAV_MESSAGES_PER_RUN(conf->max_rounds);
     const size_t nc = static_cast<size_t>(max_channels), slots = nc * t->messages_per_run, entries = nc * conf->max_rounds;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&t->chans_dev), sizeof(gnsship_cnav_state) * nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->messages_dev), sizeof(gnsship_cnav_message) * slots);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->counts_dev), sizeof(int32_t) * nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->faults_dev), nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->tow_dev), sizeof(uint32_t) * entries);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->sflags_dev), entries);
-    if (e == hipSuccess) e = hipMemsetAsync(t->messages_dev, 0, sizeof(gnsship_cnav_message) * slots, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->counts_dev, 0, sizeof(int32_t) * nc, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->faults_dev, 0, nc, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->tow_dev, 0, sizeof(uint32_t) * entries, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->sflags_dev, 0, entries, ctx->stream);
+    hipError_t e = tlm_alloc(ctx, {tlm_buf(&t->chans_dev, nc, false), tlm_buf(&t->messages_dev, slots, true), tlm_buf(&t->counts_dev, nc, true),
+                                      tlm_buf(&t->faults_dev, nc, true), tlm_buf(&t->tow_dev, entries, true), tlm_buf(&t->sflags_dev, entries, true)});
     if (e == hipSuccess) {  // every channel a new block object
         gnsship_cnav_state* fresh = new (std::nothrow) gnsship_cnav_state[nc];
         if (!fresh) {
@@ -655,7 +627,7 @@ extern "C" int gnsship_cnav_create(gnsship_ctx* ctx, const gnsship_cnav_conf* co
 static int cnav_launch(gnsship_cnav* t, const float* sym, const uint8_t* valid, const uint8_t* out_valid, const gnsship_trk_epoch* rec, int32_t n_rounds,
     gnsship_cnav_message* messages_host, int32_t* counts_host, uint8_t* faults_host, uint32_t* tow_ms_host, uint8_t* sflags_host, const char* who)
 {
-    gnsship_ctx* ctx = t->ctx;
+    gnsship_ctx* ctx = t->h.ctx;
     CnavArgs a = {};
     a.sym = sym;
     a.valid = valid;
@@ -667,109 +639,45 @@ static int cnav_launch(gnsship_cnav* t, const float* sym, const uint8_t* valid, 
     a.faults = t->faults_dev;
     a.tow_ms = t->tow_dev;
     a.sflags = t->sflags_dev;
-    a.max_channels = t->max_channels;
+    a.max_channels = t->h.max_channels;
     a.n_rounds = n_rounds;
     a.messages_per_run = t->messages_per_run;
     a.signal = t->conf.signal;
-    hipLaunchKernelGGL(cnav_kernel, dim3(static_cast<unsigned>(t->max_channels)), dim3(64), 0, ctx->stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    if (!messages_host && !counts_host && !faults_host && !tow_ms_host && !sflags_host) return GNSSHIP_OK;
-    const size_t nc = static_cast<size_t>(t->max_channels), slots = nc * t->messages_per_run, entries = nc * n_rounds;
-    if (messages_host) e = hipMemcpyAsync(messages_host, t->messages_dev, sizeof(gnsship_cnav_message) * slots, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && counts_host) e = hipMemcpyAsync(counts_host, t->counts_dev, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && faults_host) e = hipMemcpyAsync(faults_host, t->faults_dev, nc, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && tow_ms_host && entries) e = hipMemcpyAsync(tow_ms_host, t->tow_dev, sizeof(uint32_t) * entries, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && sflags_host && entries) e = hipMemcpyAsync(sflags_host, t->sflags_dev, entries, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
-}
-
-// Host data of `bytes` bytes to a staging buffer that grows as needed.
-static int cnav_stage(gnsship_cnav* t, void** buf, size_t* cap, const void* host, size_t bytes, const char* who)
-{
-    gnsship_ctx* ctx = t->ctx;
-    hipError_t e = hipSuccess;
-    if (*cap < bytes) {
-        e = hipStreamSynchronize(ctx->stream);  // earlier launches may still read the old buffer
-        if (*buf && e == hipSuccess) e = hipFree(*buf);
-        *buf = nullptr;
-        *cap = 0;
-        if (e == hipSuccess) e = hipMalloc(buf, bytes);
-        if (e != hipSuccess) return hip_fail(ctx, e, who);
-        *cap = bytes;
-    }
-    e = hipMemcpyAsync(*buf, host, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
+    hipLaunchKernelGGL(cnav_kernel, dim3(static_cast<unsigned>(t->h.max_channels)), dim3(64), 0, ctx->stream, a);
+    if (int rc = tlm_launched(ctx, who)) return rc;
+    const size_t nc = static_cast<size_t>(t->h.max_channels), slots = nc * t->messages_per_run, entries = nc * n_rounds;
+    return tlm_copy_out(ctx, {{messages_host, t->messages_dev, sizeof(gnsship_cnav_message) * slots}, {counts_host, t->counts_dev, sizeof(int32_t) * nc},
+                                 {faults_host, t->faults_dev, nc}, {tow_ms_host, t->tow_dev, sizeof(uint32_t) * entries}, {sflags_host, t->sflags_dev, entries}}, who);
 }
 
 extern "C" int gnsship_cnav_run_symbols(gnsship_cnav* t, const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int on_device,
     int32_t n_rounds, gnsship_cnav_message* messages_host, int32_t* counts_host, uint8_t* faults_host, uint32_t* tow_ms_host, uint8_t* sflags_host)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (n_rounds < 0 || n_rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_run_symbols: 0 <= n_rounds <= max_rounds");
-    if (n_rounds > 0 && !symbols) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_run_symbols: null symbols");
-    if (int rc = set_device(ctx)) return rc;
-    const size_t n = static_cast<size_t>(n_rounds) * t->max_channels;
-    const float* sym = symbols;
-    const uint8_t* val = valid;
-    const uint8_t* ov = out_valid;
-    if (!on_device && n > 0) {
-        const char* who = "gnsship_cnav_run_symbols(upload)";
-        if (int rc = cnav_stage(t, &t->stage_dev, &t->stage_cap, symbols, sizeof(float) * n, who)) return rc;
-        sym = static_cast<const float*>(t->stage_dev);
-        if (valid) {
-            if (int rc = cnav_stage(t, &t->valid_dev, &t->valid_cap, valid, n, who)) return rc;
-            val = static_cast<const uint8_t*>(t->valid_dev);
-        }
-        if (out_valid) {
-            if (int rc = cnav_stage(t, &t->ov_dev, &t->ov_cap, out_valid, n, who)) return rc;
-            ov = static_cast<const uint8_t*>(t->ov_dev);
-        }
-    }
-    return cnav_launch(t, sym, val, ov, nullptr, n_rounds, messages_host, counts_host, faults_host, tow_ms_host, sflags_host, "gnsship_cnav_run_symbols");
+    const char* who = "gnsship_cnav_run_symbols";
+    if (int rc = tlm_symbols_in(t->h, who, on_device, n_rounds, &symbols, &valid, &out_valid)) return rc;
+    return cnav_launch(t, symbols, valid, out_valid, nullptr, n_rounds, messages_host, counts_host, faults_host, tow_ms_host, sflags_host, who);
 }
 
 extern "C" int gnsship_cnav_run_records(gnsship_cnav* t, const gnsship_trk_epoch* records, int on_device, int32_t n_rounds,
     gnsship_cnav_message* messages_host, int32_t* counts_host, uint8_t* faults_host, uint32_t* tow_ms_host, uint8_t* sflags_host)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (n_rounds < 0 || n_rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_run_records: 0 <= n_rounds <= max_rounds");
-    if (n_rounds > 0 && !records) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_run_records: null records");
-    if (int rc = set_device(ctx)) return rc;
-    const size_t n = static_cast<size_t>(n_rounds) * t->max_channels;
-    const gnsship_trk_epoch* rec = records;
-    if (!on_device && n > 0) {
-        if (int rc = cnav_stage(t, &t->stage_dev, &t->stage_cap, records, sizeof(gnsship_trk_epoch) * n, "gnsship_cnav_run_records(upload)")) return rc;
-        rec = static_cast<const gnsship_trk_epoch*>(t->stage_dev);
-    }
-    return cnav_launch(t, nullptr, nullptr, nullptr, n_rounds > 0 ? rec : nullptr, n_rounds, messages_host, counts_host, faults_host, tow_ms_host,
-        sflags_host, "gnsship_cnav_run_records");
+    const char* who = "gnsship_cnav_run_records";
+    if (int rc = tlm_records_in(t->h, who, on_device, n_rounds, &records)) return rc;
+    return cnav_launch(t, nullptr, nullptr, nullptr, records, n_rounds, messages_host, counts_host, faults_host, tow_ms_host, sflags_host, who);
 }
 
 extern "C" int gnsship_cnav_run_trk(gnsship_cnav* t, gnsship_trk* trk, gnsship_cnav_message* messages_host, int32_t* counts_host, uint8_t* faults_host,
     uint32_t* tow_ms_host, uint8_t* sflags_host, int32_t* n_rounds_out)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (!trk) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_run_trk: null tracking handle");
-    if (trk_context(trk) != ctx) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_run_trk: the tracking handle is on another context");
+    const char* who = "gnsship_cnav_run_trk";
     const gnsship_trk_epoch* rec = nullptr;
-    int32_t rounds = 0, nc = 0;
-    if (int rc = gnsship_trk_records_device(trk, &rec, &rounds, &nc)) {
-        if (rc == GNSSHIP_E_STATE) return fail(ctx, GNSSHIP_E_STATE, "gnsship_cnav_run_trk: the tracker's last run kept no records on the device");
-        return rc;
-    }
-    if (nc != t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_run_trk: the handles' max_channels differ");
-    if (rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_run_trk: the tracker's run had more rounds than max_rounds");
-    if (int rc = set_device(ctx)) return rc;
+    int32_t rounds = 0;
+    if (int rc = tlm_trk_in(t->h, who, trk, &rec, &rounds)) return rc;
     if (n_rounds_out) *n_rounds_out = rounds;
-    return cnav_launch(t, nullptr, nullptr, nullptr, rounds > 0 ? rec : nullptr, rounds, messages_host, counts_host, faults_host, tow_ms_host, sflags_host,
-        "gnsship_cnav_run_trk");
+    return cnav_launch(t, nullptr, nullptr, nullptr, rec, rounds, messages_host, counts_host, faults_host, tow_ms_host, sflags_host, who);
 }
 
 extern "C" int gnsship_cnav_outputs_device(gnsship_cnav* t, gnsship_cnav_message** messages, int32_t** counts, uint8_t** faults, uint32_t** tow_ms,
@@ -788,55 +696,47 @@ extern "C" int gnsship_cnav_outputs_device(gnsship_cnav* t, gnsship_cnav_message
 extern "C" int gnsship_cnav_reset_channel(gnsship_cnav* t, int32_t channel)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_reset_channel: channel out of range");
-    if (int rc = set_device(ctx)) return rc;
-    hipLaunchKernelGGL(cnav_reset_kernel, dim3(1), dim3(1), 0, ctx->stream, t->chans_dev + channel, t->conf.signal == GNSSHIP_CNAV_L5 ? 1 : 0);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_cnav_reset_channel");
-    return GNSSHIP_OK;
+    const char* who = "gnsship_cnav_reset_channel";
+    if (int rc = tlm_check_channel(t->h, who, channel)) return rc;
+    if (int rc = set_device(t->h.ctx)) return rc;
+    hipLaunchKernelGGL(cnav_reset_kernel, dim3(1), dim3(1), 0, t->h.ctx->stream, t->chans_dev + channel, t->conf.signal == GNSSHIP_CNAV_L5 ? 1 : 0);
+    return tlm_launched(t->h.ctx, who);
 }
 
 // *st to the channel, through a staging copy so that the caller's memory is free when the call returns
 static int cnav_put_state(gnsship_cnav* t, int32_t channel, const gnsship_cnav_state* st, const char* who)
 {
-    gnsship_ctx* ctx = t->ctx;
+    gnsship_ctx* ctx = t->h.ctx;
     hipError_t e = hipMemcpyAsync(t->chans_dev + channel, st, sizeof(*st), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
+    return e == hipSuccess ? GNSSHIP_OK : hip_fail(ctx, e, who);
 }
 
 extern "C" int gnsship_cnav_new_channel(gnsship_cnav* t, int32_t channel)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_new_channel: channel out of range");
-    if (int rc = set_device(ctx)) return rc;
+    const char* who = "gnsship_cnav_new_channel";
+    if (int rc = tlm_check_channel(t->h, who, channel)) return rc;
+    if (int rc = set_device(t->h.ctx)) return rc;
     gnsship_cnav_state fresh;
     cnav_new_state(&fresh);
-    return cnav_put_state(t, channel, &fresh, "gnsship_cnav_new_channel");
+    return cnav_put_state(t, channel, &fresh, who);
 }
 
 extern "C" int gnsship_cnav_state_get(gnsship_cnav* t, int32_t channel, gnsship_cnav_state* st)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (!st) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_state_get: null state");
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_state_get: channel out of range");
-    if (int rc = set_device(ctx)) return rc;
-    hipError_t e = hipMemcpyAsync(st, t->chans_dev + channel, sizeof(*st), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_cnav_state_get");
-    return GNSSHIP_OK;
+    const char* who = "gnsship_cnav_state_get";
+    if (int rc = tlm_check_state(t->h, who, channel, st)) return rc;
+    if (int rc = set_device(t->h.ctx)) return rc;
+    return tlm_copy_out(t->h.ctx, {{st, t->chans_dev + channel, sizeof(*st)}}, who);
 }
 
 extern "C" int gnsship_cnav_state_set(gnsship_cnav* t, int32_t channel, const gnsship_cnav_state* st)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (!st) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_state_set: null state");
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_cnav_state_set: channel out of range");
+    gnsship_ctx* ctx = t->h.ctx;
+    if (int rc = tlm_check_state(t->h, "gnsship_cnav_state_set", channel, st)) return rc;
     for (int k = 0; k < 2; k++) {
         const gnsship_cnav_part& p = st->part[k];
         const uint8_t flags[] = {p.old_is_metrics2, p.preamble_seen, p.invert, p.message_lock, p.crc_ok, p.init};

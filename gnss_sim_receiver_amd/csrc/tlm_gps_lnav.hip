@@ -10,7 +10,8 @@
 // asks `x < 0` and `x > 0` of a symbol, so an entry is one of three codes — 0 (zero, −0, NaN: both tests false), 1 (> 0),
 // 2 (< 0) — and NaN and ±0 behave exactly as in the block.
 //   history  in HBM two 300-bit strings per channel (neg, pos; bit i is the i-th oldest entry), 80 bytes.  For the run
-//            they are unpacked into a linear LDS buffer of codes, oldest first, and packed again once at the end.
+//            they are unpacked into a linear LDS buffer of codes, oldest first, and packed again once at the end
+//            (tlm_device.h, shared with tlm_bds_dnav.hip).
 //   gather   64 entries at a time; a ballot of the valid entries and a prefix popcount give each symbol its ordinal, and
 //            the chunk's n symbols are appended at buf[size .. size + n).  The buffer is linear, not a ring: the history
 //            after the chunk's k-th symbol is the 300 entries ending at buf[size + k], whatever was appended behind it, so
@@ -29,16 +30,11 @@
 //   outputs  every lane keeps the tow_ms / sflags of its own entry: base + 20 · (distance from the last stamping symbol),
 //            written once per chunk.
 // Every LDS and HBM index comes from lane numbers, sizes and ballot bits, never from a symbol's value.
+// The host path around the kernel (staging, the run calls' checks, output copies) is tlm_host.h.
 #include <new>
 
-#include "engine.h"
-
-namespace gnsship {
-int fail(gnsship_ctx* ctx, int code, const char* what);
-int hip_fail(gnsship_ctx* ctx, hipError_t e, const char* where);
-int set_device(gnsship_ctx* ctx);
-gnsship_ctx* trk_context(const gnsship_trk* t);
-}  // namespace gnsship
+#include "tlm_device.h"
+#include "tlm_host.h"
 
 using namespace gnsship;
 
@@ -73,15 +69,6 @@ struct LnavArgs {
     int32_t max_channels, n_rounds, subframes_per_run;
 };
 
-__device__ __forceinline__ int lnav_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint32_t lnav_uniform(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ uint64_t lnav_uniform64(uint64_t v)
-{
-    const uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v));
-    const uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32));
-    return (static_cast<uint64_t>(hi) << 32) | lo;
-}
-
 __device__ __forceinline__ uint32_t lnav_rotl(uint32_t x, int n) { return (x << n) | (x >> (32 - n)); }
 
 // gps_word_parityCheck (:191-214)
@@ -100,24 +87,16 @@ __global__ __launch_bounds__(64) void lnav_kernel(const LnavArgs a)
     const int c = blockIdx.x;  // the grid is max_channels workgroups
 
     LnavChan* cs = a.chans + c;
-    uint64_t counter = lnav_uniform64(cs->st.symbol_counter), preamble_index = lnav_uniform64(cs->st.preamble_index);
-    uint64_t last_valid = lnav_uniform64(cs->st.last_valid_preamble), tried = lnav_uniform64(cs->st.subframes_tried);
-    uint32_t prev_word = lnav_uniform(cs->st.prev_word), tow_pre = lnav_uniform(cs->st.tow_at_preamble_ms);
-    uint32_t tow_cur = lnav_uniform(cs->st.tow_at_current_symbol_ms), nav_tow = lnav_uniform(cs->st.nav_tow_s);
-    int stat = lnav_uniform(cs->st.stat) != 0 ? 1 : 0, crc_err = lnav_uniform(cs->st.crc_error_counter);
-    int size = min(max(lnav_uniform(cs->st.history_size), 0), kLnavBits);
-    bool pll180 = lnav_uniform(static_cast<int>(cs->st.pll_180)) != 0, frame_sync = lnav_uniform(static_cast<int>(cs->st.frame_sync)) != 0;
-    bool tow_set = lnav_uniform(static_cast<int>(cs->st.tow_set)) != 0, sent = lnav_uniform(static_cast<int>(cs->st.sent_tlm_failed)) != 0;
+    uint64_t counter = tlm_uniform64(cs->st.symbol_counter), preamble_index = tlm_uniform64(cs->st.preamble_index);
+    uint64_t last_valid = tlm_uniform64(cs->st.last_valid_preamble), tried = tlm_uniform64(cs->st.subframes_tried);
+    uint32_t prev_word = tlm_uniform(cs->st.prev_word), tow_pre = tlm_uniform(cs->st.tow_at_preamble_ms);
+    uint32_t tow_cur = tlm_uniform(cs->st.tow_at_current_symbol_ms), nav_tow = tlm_uniform(cs->st.nav_tow_s);
+    int stat = tlm_uniform(cs->st.stat) != 0 ? 1 : 0, crc_err = tlm_uniform(cs->st.crc_error_counter);
+    int size = min(max(tlm_uniform(cs->st.history_size), 0), kLnavBits);
+    bool pll180 = tlm_uniform(static_cast<int>(cs->st.pll_180)) != 0, frame_sync = tlm_uniform(static_cast<int>(cs->st.frame_sync)) != 0;
+    bool tow_set = tlm_uniform(static_cast<int>(cs->st.tow_set)) != 0, sent = tlm_uniform(static_cast<int>(cs->st.sent_tlm_failed)) != 0;
 
-    // the bit strings → codes, oldest first
-    for (int i = lane; i < kLnavBuf; i += 64) {
-        uint8_t code = 0;
-        if (i < size) {
-            const uint32_t ng = (cs->neg[i >> 5] >> (i & 31)) & 1u, ps = (cs->pos[i >> 5] >> (i & 31)) & 1u;
-            code = ng ? 2 : (ps ? 1 : 0);
-        }
-        buf[i] = code;
-    }
+    tlm_codes_unpack(buf, kLnavBuf, cs->neg, cs->pos, size, lane);  // the bit strings → codes, oldest first
     __syncthreads();
 
     int count = 0;
@@ -312,18 +291,7 @@ __global__ __launch_bounds__(64) void lnav_kernel(const LnavArgs a)
         }
     }
 
-    // codes → the bit strings
-    for (int w = 0; w < kLnavHistWords / 2; w++) {
-        const int i = 64 * w + lane;
-        const uint8_t code = i < size ? buf[i] : 0;
-        const unsigned long long ng = __ballot(code == 2), ps = __ballot(code == 1);
-        if (lane == 0) {
-            cs->neg[2 * w] = static_cast<uint32_t>(ng);
-            cs->neg[2 * w + 1] = static_cast<uint32_t>(ng >> 32);
-            cs->pos[2 * w] = static_cast<uint32_t>(ps);
-            cs->pos[2 * w + 1] = static_cast<uint32_t>(ps >> 32);
-        }
-    }
+    tlm_codes_pack(buf, kLnavHistWords, cs->neg, cs->pos, size, lane);  // codes → the bit strings
     if (lane == 0) {
         gnsship_lnav_state o;
         o.symbol_counter = counter;
@@ -365,29 +333,21 @@ __global__ void lnav_control_kernel(LnavChan* cs, int what)
 }  // namespace
 
 struct gnsship_lnav {
-    gnsship_ctx* ctx = nullptr;
+    TlmHost h;  // h.mask: the 180° flags
     gnsship_lnav_conf conf = {};
-    int32_t max_channels = 0, subframes_per_run = 0;
+    int32_t subframes_per_run = 0;
     LnavChan* chans_dev = nullptr;
     gnsship_lnav_subframe* subframes_dev = nullptr;
     int32_t* counts_dev = nullptr;
     uint8_t* faults_dev = nullptr;
     uint32_t* tow_dev = nullptr;
     uint8_t* sflags_dev = nullptr;
-    void* stage_dev = nullptr;   // host symbols or records
-    void* valid_dev = nullptr;
-    void* f180_dev = nullptr;
-    size_t stage_cap = 0, valid_cap = 0, f180_cap = 0;
 };
 
 extern "C" int gnsship_lnav_destroy(gnsship_lnav* t)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(t->ctx->device);
-    (void)hipStreamSynchronize(t->ctx->stream);
-    void* ptrs[] = {t->chans_dev, t->subframes_dev, t->counts_dev, t->faults_dev, t->tow_dev, t->sflags_dev, t->stage_dev, t->valid_dev, t->f180_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    tlm_release(t->h, {t->chans_dev, t->subframes_dev, t->counts_dev, t->faults_dev, t->tow_dev, t->sflags_dev});
     delete t;
     return GNSSHIP_OK;
 }
@@ -403,23 +363,14 @@ extern "C" int gnsship_lnav_create(gnsship_ctx* ctx, const gnsship_lnav_conf* co
     if (int rc = set_device(ctx)) return rc;
     gnsship_lnav* t = new (std::nothrow) gnsship_lnav();
     if (!t) return GNSSHIP_E_NOMEM;
-    t->ctx = ctx;
+    t->h.ctx = ctx;
+    t->h.max_channels = max_channels;
+    t->h.max_rounds = conf->max_rounds;
     t->conf = *conf;
-    t->max_channels = max_channels;
     t->subframes_per_run = GNSSHIP_LNAV_SUBFRAMES_PER_RUN(conf->max_rounds);
     const size_t nc = static_cast<size_t>(max_channels), slots = nc * t->subframes_per_run, entries = nc * conf->max_rounds;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&t->chans_dev), sizeof(LnavChan) * nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->subframes_dev), sizeof(gnsship_lnav_subframe) * slots);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->counts_dev), sizeof(int32_t) * nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->faults_dev), nc);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->tow_dev), sizeof(uint32_t) * entries);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&t->sflags_dev), entries);
-    if (e == hipSuccess) e = hipMemsetAsync(t->chans_dev, 0, sizeof(LnavChan) * nc, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->subframes_dev, 0, sizeof(gnsship_lnav_subframe) * slots, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->counts_dev, 0, sizeof(int32_t) * nc, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->faults_dev, 0, nc, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->tow_dev, 0, sizeof(uint32_t) * entries, ctx->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(t->sflags_dev, 0, entries, ctx->stream);
+    const hipError_t e = tlm_alloc(ctx, {tlm_buf(&t->chans_dev, nc, true), tlm_buf(&t->subframes_dev, slots, true), tlm_buf(&t->counts_dev, nc, true),
+                                            tlm_buf(&t->faults_dev, nc, true), tlm_buf(&t->tow_dev, entries, true), tlm_buf(&t->sflags_dev, entries, true)});
     if (e != hipSuccess) {
         gnsship_lnav_destroy(t);
         return hip_fail(ctx, e, "gnsship_lnav_create");
@@ -432,7 +383,7 @@ extern "C" int gnsship_lnav_create(gnsship_ctx* ctx, const gnsship_lnav_conf* co
 static int lnav_launch(gnsship_lnav* t, const float* sym, const uint8_t* valid, const uint8_t* flags180, const gnsship_trk_epoch* rec, int32_t n_rounds,
     gnsship_lnav_subframe* subframes_host, int32_t* counts_host, uint8_t* faults_host, uint32_t* tow_ms_host, uint8_t* sflags_host, const char* who)
 {
-    gnsship_ctx* ctx = t->ctx;
+    gnsship_ctx* ctx = t->h.ctx;
     LnavArgs a = {};
     a.sym = sym;
     a.valid = valid;
@@ -444,108 +395,44 @@ static int lnav_launch(gnsship_lnav* t, const float* sym, const uint8_t* valid, 
     a.faults = t->faults_dev;
     a.tow_ms = t->tow_dev;
     a.sflags = t->sflags_dev;
-    a.max_channels = t->max_channels;
+    a.max_channels = t->h.max_channels;
     a.n_rounds = n_rounds;
     a.subframes_per_run = t->subframes_per_run;
-    hipLaunchKernelGGL(lnav_kernel, dim3(static_cast<unsigned>(t->max_channels)), dim3(64), 0, ctx->stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    if (!subframes_host && !counts_host && !faults_host && !tow_ms_host && !sflags_host) return GNSSHIP_OK;
-    const size_t nc = static_cast<size_t>(t->max_channels), slots = nc * t->subframes_per_run, entries = nc * n_rounds;
-    if (subframes_host) e = hipMemcpyAsync(subframes_host, t->subframes_dev, sizeof(gnsship_lnav_subframe) * slots, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && counts_host) e = hipMemcpyAsync(counts_host, t->counts_dev, sizeof(int32_t) * nc, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && faults_host) e = hipMemcpyAsync(faults_host, t->faults_dev, nc, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && tow_ms_host && entries) e = hipMemcpyAsync(tow_ms_host, t->tow_dev, sizeof(uint32_t) * entries, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess && sflags_host && entries) e = hipMemcpyAsync(sflags_host, t->sflags_dev, entries, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
-}
-
-// Host data of `bytes` bytes to a staging buffer that grows as needed.
-static int lnav_stage(gnsship_lnav* t, void** buf, size_t* cap, const void* host, size_t bytes, const char* who)
-{
-    gnsship_ctx* ctx = t->ctx;
-    hipError_t e = hipSuccess;
-    if (*cap < bytes) {
-        e = hipStreamSynchronize(ctx->stream);  // earlier launches may still read the old buffer
-        if (*buf && e == hipSuccess) e = hipFree(*buf);
-        *buf = nullptr;
-        *cap = 0;
-        if (e == hipSuccess) e = hipMalloc(buf, bytes);
-        if (e != hipSuccess) return hip_fail(ctx, e, who);
-        *cap = bytes;
-    }
-    e = hipMemcpyAsync(*buf, host, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
+    hipLaunchKernelGGL(lnav_kernel, dim3(static_cast<unsigned>(t->h.max_channels)), dim3(64), 0, ctx->stream, a);
+    if (int rc = tlm_launched(ctx, who)) return rc;
+    const size_t nc = static_cast<size_t>(t->h.max_channels), slots = nc * t->subframes_per_run, entries = nc * n_rounds;
+    return tlm_copy_out(ctx, {{subframes_host, t->subframes_dev, sizeof(gnsship_lnav_subframe) * slots}, {counts_host, t->counts_dev, sizeof(int32_t) * nc},
+                                 {faults_host, t->faults_dev, nc}, {tow_ms_host, t->tow_dev, sizeof(uint32_t) * entries}, {sflags_host, t->sflags_dev, entries}}, who);
 }
 
 extern "C" int gnsship_lnav_run_symbols(gnsship_lnav* t, const float* symbols, const uint8_t* valid, const uint8_t* flags180, int on_device,
     int32_t n_rounds, gnsship_lnav_subframe* subframes_host, int32_t* counts_host, uint8_t* faults_host, uint32_t* tow_ms_host, uint8_t* sflags_host)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (n_rounds < 0 || n_rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_lnav_run_symbols: 0 <= n_rounds <= max_rounds");
-    if (n_rounds > 0 && !symbols) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_lnav_run_symbols: null symbols");
-    if (int rc = set_device(ctx)) return rc;
-    const size_t n = static_cast<size_t>(n_rounds) * t->max_channels;
-    const float* sym = symbols;
-    const uint8_t* val = valid;
-    const uint8_t* f180 = flags180;
-    if (!on_device && n > 0) {
-        const char* who = "gnsship_lnav_run_symbols(upload)";
-        if (int rc = lnav_stage(t, &t->stage_dev, &t->stage_cap, symbols, sizeof(float) * n, who)) return rc;
-        sym = static_cast<const float*>(t->stage_dev);
-        if (valid) {
-            if (int rc = lnav_stage(t, &t->valid_dev, &t->valid_cap, valid, n, who)) return rc;
-            val = static_cast<const uint8_t*>(t->valid_dev);
-        }
-        if (flags180) {
-            if (int rc = lnav_stage(t, &t->f180_dev, &t->f180_cap, flags180, n, who)) return rc;
-            f180 = static_cast<const uint8_t*>(t->f180_dev);
-        }
-    }
-    return lnav_launch(t, sym, val, f180, nullptr, n_rounds, subframes_host, counts_host, faults_host, tow_ms_host, sflags_host, "gnsship_lnav_run_symbols");
+    const char* who = "gnsship_lnav_run_symbols";
+    if (int rc = tlm_symbols_in(t->h, who, on_device, n_rounds, &symbols, &valid, &flags180)) return rc;
+    return lnav_launch(t, symbols, valid, flags180, nullptr, n_rounds, subframes_host, counts_host, faults_host, tow_ms_host, sflags_host, who);
 }
 
 extern "C" int gnsship_lnav_run_records(gnsship_lnav* t, const gnsship_trk_epoch* records, int on_device, int32_t n_rounds,
     gnsship_lnav_subframe* subframes_host, int32_t* counts_host, uint8_t* faults_host, uint32_t* tow_ms_host, uint8_t* sflags_host)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (n_rounds < 0 || n_rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_lnav_run_records: 0 <= n_rounds <= max_rounds");
-    if (n_rounds > 0 && !records) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_lnav_run_records: null records");
-    if (int rc = set_device(ctx)) return rc;
-    const size_t n = static_cast<size_t>(n_rounds) * t->max_channels;
-    const gnsship_trk_epoch* rec = records;
-    if (!on_device && n > 0) {
-        if (int rc = lnav_stage(t, &t->stage_dev, &t->stage_cap, records, sizeof(gnsship_trk_epoch) * n, "gnsship_lnav_run_records(upload)")) return rc;
-        rec = static_cast<const gnsship_trk_epoch*>(t->stage_dev);
-    }
-    return lnav_launch(t, nullptr, nullptr, nullptr, n_rounds > 0 ? rec : nullptr, n_rounds, subframes_host, counts_host, faults_host, tow_ms_host,
-        sflags_host, "gnsship_lnav_run_records");
+    const char* who = "gnsship_lnav_run_records";
+    if (int rc = tlm_records_in(t->h, who, on_device, n_rounds, &records)) return rc;
+    return lnav_launch(t, nullptr, nullptr, nullptr, records, n_rounds, subframes_host, counts_host, faults_host, tow_ms_host, sflags_host, who);
 }
 
 extern "C" int gnsship_lnav_run_trk(gnsship_lnav* t, gnsship_trk* trk, gnsship_lnav_subframe* subframes_host, int32_t* counts_host, uint8_t* faults_host,
     uint32_t* tow_ms_host, uint8_t* sflags_host, int32_t* n_rounds_out)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (!trk) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_lnav_run_trk: null tracking handle");
-    if (trk_context(trk) != ctx) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_lnav_run_trk: the tracking handle is on another context");
+    const char* who = "gnsship_lnav_run_trk";
     const gnsship_trk_epoch* rec = nullptr;
-    int32_t rounds = 0, nc = 0;
-    if (int rc = gnsship_trk_records_device(trk, &rec, &rounds, &nc)) {
-        if (rc == GNSSHIP_E_STATE) return fail(ctx, GNSSHIP_E_STATE, "gnsship_lnav_run_trk: the tracker's last run kept no records on the device");
-        return rc;
-    }
-    if (nc != t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_lnav_run_trk: the handles' max_channels differ");
-    if (rounds > t->conf.max_rounds) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_lnav_run_trk: the tracker's run had more rounds than max_rounds");
-    if (int rc = set_device(ctx)) return rc;
+    int32_t rounds = 0;
+    if (int rc = tlm_trk_in(t->h, who, trk, &rec, &rounds)) return rc;
     if (n_rounds_out) *n_rounds_out = rounds;
-    return lnav_launch(t, nullptr, nullptr, nullptr, rounds > 0 ? rec : nullptr, rounds, subframes_host, counts_host, faults_host, tow_ms_host, sflags_host,
-        "gnsship_lnav_run_trk");
+    return lnav_launch(t, nullptr, nullptr, nullptr, rec, rounds, subframes_host, counts_host, faults_host, tow_ms_host, sflags_host, who);
 }
 
 extern "C" int gnsship_lnav_outputs_device(gnsship_lnav* t, gnsship_lnav_subframe** subframes, int32_t** counts, uint8_t** faults, uint32_t** tow_ms,
@@ -561,48 +448,34 @@ extern "C" int gnsship_lnav_outputs_device(gnsship_lnav* t, gnsship_lnav_subfram
     return GNSSHIP_OK;
 }
 
-static int lnav_control(gnsship_lnav* t, int32_t channel, int what, const char* who, const char* range)
+static int lnav_control(gnsship_lnav* t, int32_t channel, int what, const char* who)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, range);
-    if (int rc = set_device(ctx)) return rc;
-    hipLaunchKernelGGL(lnav_control_kernel, dim3(1), dim3(1), 0, ctx->stream, t->chans_dev + channel, what);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, who);
-    return GNSSHIP_OK;
+    if (int rc = tlm_check_channel(t->h, who, channel)) return rc;
+    if (int rc = set_device(t->h.ctx)) return rc;
+    hipLaunchKernelGGL(lnav_control_kernel, dim3(1), dim3(1), 0, t->h.ctx->stream, t->chans_dev + channel, what);
+    return tlm_launched(t->h.ctx, who);
 }
 
-extern "C" int gnsship_lnav_reset_channel(gnsship_lnav* t, int32_t channel)
-{
-    return lnav_control(t, channel, 1, "gnsship_lnav_reset_channel", "gnsship_lnav_reset_channel: channel out of range");
-}
+extern "C" int gnsship_lnav_reset_channel(gnsship_lnav* t, int32_t channel) { return lnav_control(t, channel, 1, "gnsship_lnav_reset_channel"); }
 
-extern "C" int gnsship_lnav_set_satellite(gnsship_lnav* t, int32_t channel)
-{
-    return lnav_control(t, channel, 0, "gnsship_lnav_set_satellite", "gnsship_lnav_set_satellite: channel out of range");
-}
+extern "C" int gnsship_lnav_set_satellite(gnsship_lnav* t, int32_t channel) { return lnav_control(t, channel, 0, "gnsship_lnav_set_satellite"); }
 
 extern "C" int gnsship_lnav_new_channel(gnsship_lnav* t, int32_t channel)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_lnav_new_channel: channel out of range");
-    if (int rc = set_device(ctx)) return rc;
-    const hipError_t e = hipMemsetAsync(t->chans_dev + channel, 0, sizeof(LnavChan), ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_lnav_new_channel");
-    return GNSSHIP_OK;
+    const char* who = "gnsship_lnav_new_channel";
+    if (int rc = tlm_check_channel(t->h, who, channel)) return rc;
+    if (int rc = set_device(t->h.ctx)) return rc;
+    const hipError_t e = hipMemsetAsync(t->chans_dev + channel, 0, sizeof(LnavChan), t->h.ctx->stream);
+    return e == hipSuccess ? GNSSHIP_OK : hip_fail(t->h.ctx, e, who);
 }
 
 extern "C" int gnsship_lnav_state_get(gnsship_lnav* t, int32_t channel, gnsship_lnav_state* st)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    gnsship_ctx* ctx = t->ctx;
-    if (!st) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_lnav_state_get: null state");
-    if (channel < 0 || channel >= t->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_lnav_state_get: channel out of range");
-    if (int rc = set_device(ctx)) return rc;
-    hipError_t e = hipMemcpyAsync(st, &t->chans_dev[channel].st, sizeof(*st), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_lnav_state_get");
-    return GNSSHIP_OK;
+    const char* who = "gnsship_lnav_state_get";
+    if (int rc = tlm_check_state(t->h, who, channel, st)) return rc;
+    if (int rc = set_device(t->h.ctx)) return rc;
+    return tlm_copy_out(t->h.ctx, {{st, &t->chans_dev[channel].st, sizeof(*st)}}, who);
 }

@@ -963,62 +963,57 @@ def galileo_cnav_page_decoder(ctx: Context, max_channels: int, mode="reference")
     return _galileo_page_decoder(ctx, max_channels, GALILEO_CNAV_PAGE, mode)
 
 
-class TlmResult(NamedTuple):
-    """One gnsship_tlm run: pages [max_channels, pages_per_run] (abi.TLM_PAGE_DTYPE), bits uint8[max_channels,
-    pages_per_run, LL], counts int32[max_channels], faults uint8[max_channels]; slots k >= counts[c] are unspecified."""
-    pages: np.ndarray
-    bits: np.ndarray
-    counts: np.ndarray
-    faults: np.ndarray
+class _TelemetryDecoder:
+    """What the five telemetry decoders share over the C ABI (gnsship_<family>_*, csrc/tlm_host.h): the handle's life
+    cycle, the three run calls and the device pointers.  A subclass states its C prefix, its result tuple and the name of
+    its per-run slot count, builds its configuration in __init__ and its host arrays in _new_result, and adds the calls
+    only its family has."""
+    _prefix = None   # "gnsship_lnav"
+    _result = None   # the run's NamedTuple; with tow_ms / sflags the family has a per-entry output stream
+    _per_run = None  # "subframes_per_run": the attribute holding the record slots per channel of one run
+    _state = None    # the ctypes state structure state() reads; a family whose state is a numpy record overrides state()
+    h = None
 
+    def _call(self, name: str, *args):
+        name = f"{self._prefix}_{name}"
+        check(getattr(self.ctx.lib, name)(self.h, *args), name, self.ctx.h)
 
-class GalileoTelemetryDecoder:
-    """The frame handling of galileo_telemetry_decoder_gs::general_work (:872-1094) for up to ``max_channels`` channels
-    on the device, one block object per channel: preamble synchronisation, page parts, Viterbi, CRC-24Q, the CRC-error
-    counter and check_tlm_separation (include/gnsship.h, gnsship_tlm_*).  frame_type abi.TLM_INAV / _FNAV / _CNAV;
-    mode "reference" | "full" as ViterbiDecoder; max_rounds: the most symbols per channel one run may carry."""
-
-    def __init__(self, ctx: Context, frame_type: int, max_channels: int, max_rounds: int, mode="reference"):
-        self.ctx = ctx
-        self.h = None
-        self.frame_type = int(frame_type)
-        self.mode = ViterbiDecoder.MODES[mode] if isinstance(mode, str) else int(mode)
+    def _open(self, ctx: Context, conf, max_channels: int, max_rounds: int):
+        self.ctx, self.conf = ctx, conf
         self.max_channels, self.max_rounds = int(max_channels), int(max_rounds)
-        self.conf = abi.TlmConf(frame_type=self.frame_type, vit_mode=self.mode, max_rounds=self.max_rounds, reserved=0)
         h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_tlm_create(ctx.h, ctypes.byref(self.conf), self.max_channels, ctypes.byref(h)), "gnsship_tlm_create", ctx.h)
+        name = f"{self._prefix}_create"
+        check(getattr(ctx.lib, name)(ctx.h, ctypes.byref(conf), self.max_channels, ctypes.byref(h)), name, ctx.h)
         self.h = h
-        self.preamble_symbols, self.period, self.required, self.data_length = abi.TLM_GEOMETRY[self.frame_type]
-        ppr = ctypes.c_int32()
-        check(ctx.lib.gnsship_tlm_outputs_device(self.h, None, None, None, None, ctypes.byref(ppr)), "gnsship_tlm_outputs_device", ctx.h)
-        self.pages_per_run = ppr.value
+        slots = ctypes.c_int32()
+        self._call("outputs_device", *[None] * len(self._result._fields), ctypes.byref(slots))
+        setattr(self, self._per_run, slots.value)
 
-    def _outputs(self, host: bool):
+    def _outputs(self, host: bool, n_rounds: int):
         if not host:
-            return None, (None, None, None, None)
-        res = TlmResult(np.zeros((self.max_channels, self.pages_per_run), abi.TLM_PAGE_DTYPE),
-                        np.zeros((self.max_channels, self.pages_per_run, self.data_length), np.uint8),
-                        np.zeros(self.max_channels, np.int32), np.zeros(self.max_channels, np.uint8))
+            return None, (None,) * len(self._result._fields)
+        res = self._new_result(n_rounds)
         return res, tuple(ctypes.c_void_p(x.ctypes.data) for x in res)
 
-    def run_symbols(self, symbols, valid=None, on_device: bool = False, n_rounds: int = None, host: bool = True):
-        """symbols float32[n_rounds, max_channels] (or a device pointer with on_device and n_rounds), valid uint8 of the
-        same shape (and place) or None.  Returns a TlmResult, or None when not host (asynchronous)."""
+    def _run_symbols(self, symbols, masks, on_device, n_rounds, host):
+        """masks: ((name, array or device pointer or None), ...) in the C call's order."""
+        names, masks = [n for n, _ in masks], [m for _, m in masks]
         if on_device:
-            sp, vp = ctypes.c_void_p(symbols), ctypes.c_void_p(valid) if valid else None
+            sp = ctypes.c_void_p(symbols)
+            ptrs_in = [ctypes.c_void_p(m) if m else None for m in masks]
         else:
             symbols = np.ascontiguousarray(symbols, np.float32).reshape(-1, self.max_channels)
             n_rounds = symbols.shape[0] if n_rounds is None else int(n_rounds)
             sp = ctypes.c_void_p(symbols.ctypes.data) if symbols.size else None
-            vp = None
-            if valid is not None:
-                valid = np.ascontiguousarray(valid, np.uint8).reshape(-1, self.max_channels)
-                if valid.shape != symbols.shape:
-                    raise ValueError("valid must have the symbols' shape")
-                vp = ctypes.c_void_p(valid.ctypes.data) if valid.size else None
-        res, ptrs = self._outputs(host)
-        self._in_flight = (symbols, valid)  # a run without a host copy returns before the stream has read them
-        check(self.ctx.lib.gnsship_tlm_run_symbols(self.h, sp, vp, int(on_device), int(n_rounds), *ptrs), "gnsship_tlm_run_symbols", self.ctx.h)
+            for i, m in enumerate(masks):
+                if m is not None:
+                    masks[i] = m = np.ascontiguousarray(m, np.uint8).reshape(-1, self.max_channels)
+                    if m.shape != symbols.shape:
+                        raise ValueError(f"{names[i]} must have the symbols' shape")
+            ptrs_in = [ctypes.c_void_p(m.ctypes.data) if m is not None and m.size else None for m in masks]
+        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
+        self._in_flight = (symbols, *masks)  # a run without a host copy returns before the stream has read them
+        self._call("run_symbols", sp, *ptrs_in, int(on_device), int(n_rounds), *ptrs)
         return res
 
     def run_records(self, records, on_device: bool = False, n_rounds: int = None, host: bool = True):
@@ -1029,44 +1024,41 @@ class GalileoTelemetryDecoder:
             records = np.ascontiguousarray(records, abi.TRK_EPOCH_DTYPE).reshape(-1, self.max_channels)
             n_rounds = records.shape[0] if n_rounds is None else int(n_rounds)
             rp = ctypes.c_void_p(records.ctypes.data) if records.size else None
-        res, ptrs = self._outputs(host)
+        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
         self._in_flight = (records,)
-        check(self.ctx.lib.gnsship_tlm_run_records(self.h, rp, int(on_device), int(n_rounds), *ptrs), "gnsship_tlm_run_records", self.ctx.h)
+        self._call("run_records", rp, int(on_device), int(n_rounds), *ptrs)
         return res
 
     def run_trk(self, trk: "DllPllVemlTracking", host: bool = True):
         """Consume, in place, the records the tracker's last run left on the device."""
-        res, ptrs = self._outputs(host)
-        check(self.ctx.lib.gnsship_tlm_run_trk(self.h, trk.h, *ptrs), "gnsship_tlm_run_trk", self.ctx.h)
-        return res
+        res, ptrs = self._outputs(host, self.max_rounds)
+        if "tow_ms" not in self._result._fields:
+            self._call("run_trk", trk.h, *ptrs)
+            return res
+        rounds = ctypes.c_int32()
+        self._call("run_trk", trk.h, *ptrs, ctypes.byref(rounds))
+        if res is None:
+            return None
+        n = rounds.value  # the copies are dense over the run's rounds
+        flat = self.max_rounds * self.max_channels
+        return res._replace(tow_ms=res.tow_ms.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels),
+                            sflags=res.sflags.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels))
 
     def outputs_device(self):
-        """Device pointers (pages, bits, counts, faults) of the handle's output buffers."""
-        p = [ctypes.c_void_p() for _ in range(4)]
-        check(self.ctx.lib.gnsship_tlm_outputs_device(self.h, *[ctypes.byref(x) for x in p], None), "gnsship_tlm_outputs_device", self.ctx.h)
+        """Device pointers of the handle's output buffers, one per field of the result tuple and in its order."""
+        p = [ctypes.c_void_p() for _ in self._result._fields]
+        self._call("outputs_device", *[ctypes.byref(x) for x in p], None)
         return tuple(x.value for x in p)
 
     def state(self, channel: int) -> dict:
-        """The channel's block members (gnsship_tlm_state) by name."""
-        st = abi.TlmState()
-        check(self.ctx.lib.gnsship_tlm_state_get(self.h, channel, ctypes.byref(st)), "gnsship_tlm_state_get", self.ctx.h)
+        """The channel's block members (gnsship_<family>_state) by name."""
+        st = self._state()
+        self._call("state_get", channel, ctypes.byref(st))
         return st.as_dict()
-
-    def reset_channel(self, channel: int):
-        """The block's reset()."""
-        check(self.ctx.lib.gnsship_tlm_reset_channel(self.h, channel), "gnsship_tlm_reset_channel", self.ctx.h)
-
-    def set_satellite(self, channel: int):
-        """The block's set_satellite()."""
-        check(self.ctx.lib.gnsship_tlm_set_satellite(self.h, channel), "gnsship_tlm_set_satellite", self.ctx.h)
-
-    def new_channel(self, channel: int):
-        """A new block object on this channel."""
-        check(self.ctx.lib.gnsship_tlm_new_channel(self.h, channel), "gnsship_tlm_new_channel", self.ctx.h)
 
     def close(self):
         if self.h:
-            self.ctx.lib.gnsship_tlm_destroy(self.h)
+            getattr(self.ctx.lib, f"{self._prefix}_destroy")(self.h)
             self.h = None
 
     def __del__(self):
@@ -1075,6 +1067,51 @@ class GalileoTelemetryDecoder:
                 self.close()
         except Exception:
             pass
+
+
+class TlmResult(NamedTuple):
+    """One gnsship_tlm run: pages [max_channels, pages_per_run] (abi.TLM_PAGE_DTYPE), bits uint8[max_channels,
+    pages_per_run, LL], counts int32[max_channels], faults uint8[max_channels]; slots k >= counts[c] are unspecified."""
+    pages: np.ndarray
+    bits: np.ndarray
+    counts: np.ndarray
+    faults: np.ndarray
+
+
+class GalileoTelemetryDecoder(_TelemetryDecoder):
+    """The frame handling of galileo_telemetry_decoder_gs::general_work (:872-1094) for up to ``max_channels`` channels
+    on the device, one block object per channel: preamble synchronisation, page parts, Viterbi, CRC-24Q, the CRC-error
+    counter and check_tlm_separation (include/gnsship.h, gnsship_tlm_*).  frame_type abi.TLM_INAV / _FNAV / _CNAV;
+    mode "reference" | "full" as ViterbiDecoder; max_rounds: the most symbols per channel one run may carry."""
+    _prefix, _result, _per_run, _state = "gnsship_tlm", TlmResult, "pages_per_run", abi.TlmState
+
+    def __init__(self, ctx: Context, frame_type: int, max_channels: int, max_rounds: int, mode="reference"):
+        self.frame_type = int(frame_type)
+        self.mode = ViterbiDecoder.MODES[mode] if isinstance(mode, str) else int(mode)
+        self._open(ctx, abi.TlmConf(frame_type=self.frame_type, vit_mode=self.mode, max_rounds=int(max_rounds), reserved=0), max_channels, max_rounds)
+        self.preamble_symbols, self.period, self.required, self.data_length = abi.TLM_GEOMETRY[self.frame_type]
+
+    def _new_result(self, n_rounds: int):
+        return TlmResult(np.zeros((self.max_channels, self.pages_per_run), abi.TLM_PAGE_DTYPE),
+                         np.zeros((self.max_channels, self.pages_per_run, self.data_length), np.uint8),
+                         np.zeros(self.max_channels, np.int32), np.zeros(self.max_channels, np.uint8))
+
+    def run_symbols(self, symbols, valid=None, on_device: bool = False, n_rounds: int = None, host: bool = True):
+        """symbols float32[n_rounds, max_channels] (or a device pointer with on_device and n_rounds), valid uint8 of the
+        same shape (and place) or None.  Returns a TlmResult, or None when not host (asynchronous)."""
+        return self._run_symbols(symbols, (("valid", valid),), on_device, n_rounds, host)
+
+    def reset_channel(self, channel: int):
+        """The block's reset()."""
+        self._call("reset_channel", channel)
+
+    def set_satellite(self, channel: int):
+        """The block's set_satellite()."""
+        self._call("set_satellite", channel)
+
+    def new_channel(self, channel: int):
+        """A new block object on this channel."""
+        self._call("new_channel", channel)
 
 
 def galileo_inav_telemetry(ctx: Context, max_channels: int, max_rounds: int, mode="reference") -> GalileoTelemetryDecoder:
@@ -1103,116 +1140,37 @@ class LnavResult(NamedTuple):
     sflags: np.ndarray
 
 
-class GpsL1CaTelemetryDecoder:
+class GpsL1CaTelemetryDecoder(_TelemetryDecoder):
     """gps_l1_ca_telemetry_decoder_gs up to the time of week for up to ``max_channels`` channels on the device, one block
     object per channel: preamble seeding, subframe synchronisation, the LNAV parity, subframe ID and TOW, the error
     counter, loss of sync, check_tlm_separation and the TOW stamp of every symbol (include/gnsship.h, gnsship_lnav_*).
     max_rounds: the most entries per channel one run may carry."""
+    _prefix, _result, _per_run, _state = "gnsship_lnav", LnavResult, "subframes_per_run", abi.LnavState
 
     def __init__(self, ctx: Context, max_channels: int, max_rounds: int):
-        self.ctx = ctx
-        self.h = None
-        self.max_channels, self.max_rounds = int(max_channels), int(max_rounds)
-        self.conf = abi.LnavConf(max_rounds=self.max_rounds, reserved=0)
-        h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_lnav_create(ctx.h, ctypes.byref(self.conf), self.max_channels, ctypes.byref(h)), "gnsship_lnav_create", ctx.h)
-        self.h = h
-        spr = ctypes.c_int32()
-        check(ctx.lib.gnsship_lnav_outputs_device(self.h, None, None, None, None, None, ctypes.byref(spr)), "gnsship_lnav_outputs_device", ctx.h)
-        self.subframes_per_run = spr.value
+        self._open(ctx, abi.LnavConf(max_rounds=int(max_rounds), reserved=0), max_channels, max_rounds)
 
-    def _outputs(self, host: bool, n_rounds: int):
-        if not host:
-            return None, (None, None, None, None, None)
-        res = LnavResult(np.zeros((self.max_channels, self.subframes_per_run), abi.LNAV_SUBFRAME_DTYPE),
-                         np.zeros(self.max_channels, np.int32), np.zeros(self.max_channels, np.uint8),
-                         np.zeros((n_rounds, self.max_channels), np.uint32), np.zeros((n_rounds, self.max_channels), np.uint8))
-        return res, tuple(ctypes.c_void_p(x.ctypes.data) for x in res)
+    def _new_result(self, n_rounds: int):
+        return LnavResult(np.zeros((self.max_channels, self.subframes_per_run), abi.LNAV_SUBFRAME_DTYPE),
+                          np.zeros(self.max_channels, np.int32), np.zeros(self.max_channels, np.uint8),
+                          np.zeros((n_rounds, self.max_channels), np.uint32), np.zeros((n_rounds, self.max_channels), np.uint8))
 
     def run_symbols(self, symbols, valid=None, flags180=None, on_device: bool = False, n_rounds: int = None, host: bool = True):
         """symbols float32[n_rounds, max_channels] (or a device pointer with on_device and n_rounds); valid and flags180
         uint8 of the same shape (and place) or None.  Returns an LnavResult, or None when not host (asynchronous)."""
-        if on_device:
-            sp = ctypes.c_void_p(symbols)
-            vp, fp = (ctypes.c_void_p(x) if x else None for x in (valid, flags180))
-        else:
-            symbols = np.ascontiguousarray(symbols, np.float32).reshape(-1, self.max_channels)
-            n_rounds = symbols.shape[0] if n_rounds is None else int(n_rounds)
-            sp = ctypes.c_void_p(symbols.ctypes.data) if symbols.size else None
-            masks = []
-            for m, name in ((valid, "valid"), (flags180, "flags180")):
-                if m is not None:
-                    m = np.ascontiguousarray(m, np.uint8).reshape(-1, self.max_channels)
-                    if m.shape != symbols.shape:
-                        raise ValueError(f"{name} must have the symbols' shape")
-                masks.append(m)
-            valid, flags180 = masks
-            vp, fp = (ctypes.c_void_p(m.ctypes.data) if m is not None and m.size else None for m in masks)
-        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
-        self._in_flight = (symbols, valid, flags180)  # a run without a host copy returns before the stream has read them
-        check(self.ctx.lib.gnsship_lnav_run_symbols(self.h, sp, vp, fp, int(on_device), int(n_rounds), *ptrs), "gnsship_lnav_run_symbols", self.ctx.h)
-        return res
-
-    def run_records(self, records, on_device: bool = False, n_rounds: int = None, host: bool = True):
-        """records: abi.TRK_EPOCH_DTYPE[n_rounds, max_channels] on the host, or a device pointer with on_device and n_rounds."""
-        if on_device:
-            rp = ctypes.c_void_p(records)
-        else:
-            records = np.ascontiguousarray(records, abi.TRK_EPOCH_DTYPE).reshape(-1, self.max_channels)
-            n_rounds = records.shape[0] if n_rounds is None else int(n_rounds)
-            rp = ctypes.c_void_p(records.ctypes.data) if records.size else None
-        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
-        self._in_flight = (records,)
-        check(self.ctx.lib.gnsship_lnav_run_records(self.h, rp, int(on_device), int(n_rounds), *ptrs), "gnsship_lnav_run_records", self.ctx.h)
-        return res
-
-    def run_trk(self, trk: "DllPllVemlTracking", host: bool = True):
-        """Consume, in place, the records the tracker's last run left on the device."""
-        res, ptrs = self._outputs(host, self.max_rounds)
-        rounds = ctypes.c_int32()
-        check(self.ctx.lib.gnsship_lnav_run_trk(self.h, trk.h, *ptrs, ctypes.byref(rounds)), "gnsship_lnav_run_trk", self.ctx.h)
-        if res is None:
-            return None
-        n = rounds.value  # the copies are dense over the run's rounds
-        flat = self.max_rounds * self.max_channels
-        return res._replace(tow_ms=res.tow_ms.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels),
-                            sflags=res.sflags.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels))
-
-    def outputs_device(self):
-        """Device pointers (subframes, counts, faults, tow_ms, sflags) of the handle's output buffers."""
-        p = [ctypes.c_void_p() for _ in range(5)]
-        check(self.ctx.lib.gnsship_lnav_outputs_device(self.h, *[ctypes.byref(x) for x in p], None), "gnsship_lnav_outputs_device", self.ctx.h)
-        return tuple(x.value for x in p)
-
-    def state(self, channel: int) -> dict:
-        """The channel's block members (gnsship_lnav_state) by name."""
-        st = abi.LnavState()
-        check(self.ctx.lib.gnsship_lnav_state_get(self.h, channel, ctypes.byref(st)), "gnsship_lnav_state_get", self.ctx.h)
-        return st.as_dict()
+        return self._run_symbols(symbols, (("valid", valid), ("flags180", flags180)), on_device, n_rounds, host)
 
     def reset_channel(self, channel: int):
         """The block's reset()."""
-        check(self.ctx.lib.gnsship_lnav_reset_channel(self.h, channel), "gnsship_lnav_reset_channel", self.ctx.h)
+        self._call("reset_channel", channel)
 
     def set_satellite(self, channel: int):
         """The block's set_satellite()."""
-        check(self.ctx.lib.gnsship_lnav_set_satellite(self.h, channel), "gnsship_lnav_set_satellite", self.ctx.h)
+        self._call("set_satellite", channel)
 
     def new_channel(self, channel: int):
         """A new block object on this channel."""
-        check(self.ctx.lib.gnsship_lnav_new_channel(self.h, channel), "gnsship_lnav_new_channel", self.ctx.h)
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.gnsship_lnav_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.close()
-        except Exception:
-            pass
+        self._call("new_channel", channel)
 
 
 def gps_l1_ca_telemetry(ctx: Context, max_channels: int, max_rounds: int) -> GpsL1CaTelemetryDecoder:
@@ -1231,117 +1189,45 @@ class CnavResult(NamedTuple):
     sflags: np.ndarray
 
 
-class GpsCnavTelemetryDecoder:
+class GpsCnavTelemetryDecoder(_TelemetryDecoder):
     """gps_l2c_telemetry_decoder_gs (signal abi.CNAV_L2C) or gps_l5_telemetry_decoder_gs (abi.CNAV_L5) up to the time of week
     for up to ``max_channels`` channels on the device, one block object per channel: libswiftcnav's two streaming Viterbi
     decoders, preamble rescan, CRC-24Q, the lock counter, and the block's watchdog, TOW stamp and valid_word
     (include/gnsship.h, gnsship_cnav_*).  max_rounds: the most entries per channel one run may carry."""
+    _prefix, _result, _per_run = "gnsship_cnav", CnavResult, "messages_per_run"
 
     def __init__(self, ctx: Context, signal: int, max_channels: int, max_rounds: int):
-        self.ctx = ctx
-        self.h = None
-        self.signal, self.max_channels, self.max_rounds = int(signal), int(max_channels), int(max_rounds)
-        self.conf = abi.CnavConf(max_rounds=self.max_rounds, signal=self.signal, reserved=0)
-        h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_cnav_create(ctx.h, ctypes.byref(self.conf), self.max_channels, ctypes.byref(h)), "gnsship_cnav_create", ctx.h)
-        self.h = h
-        mpr = ctypes.c_int32()
-        check(ctx.lib.gnsship_cnav_outputs_device(self.h, None, None, None, None, None, ctypes.byref(mpr)), "gnsship_cnav_outputs_device", ctx.h)
-        self.messages_per_run = mpr.value
+        self.signal = int(signal)
+        self._open(ctx, abi.CnavConf(max_rounds=int(max_rounds), signal=self.signal, reserved=0), max_channels, max_rounds)
 
-    def _outputs(self, host: bool, n_rounds: int):
-        if not host:
-            return None, (None, None, None, None, None)
-        res = CnavResult(np.zeros((self.max_channels, self.messages_per_run), abi.CNAV_MESSAGE_DTYPE),
-                         np.zeros(self.max_channels, np.int32), np.zeros(self.max_channels, np.uint8),
-                         np.zeros((n_rounds, self.max_channels), np.uint32), np.zeros((n_rounds, self.max_channels), np.uint8))
-        return res, tuple(ctypes.c_void_p(x.ctypes.data) for x in res)
+    def _new_result(self, n_rounds: int):
+        return CnavResult(np.zeros((self.max_channels, self.messages_per_run), abi.CNAV_MESSAGE_DTYPE),
+                          np.zeros(self.max_channels, np.int32), np.zeros(self.max_channels, np.uint8),
+                          np.zeros((n_rounds, self.max_channels), np.uint32), np.zeros((n_rounds, self.max_channels), np.uint8))
 
     def run_symbols(self, symbols, valid=None, out_valid=None, on_device: bool = False, n_rounds: int = None, host: bool = True):
         """symbols float32[n_rounds, max_channels] (or a device pointer with on_device and n_rounds); valid and out_valid
         uint8 of the same shape (and place) or None.  Returns a CnavResult, or None when not host (asynchronous)."""
-        if on_device:
-            sp = ctypes.c_void_p(symbols)
-            vp, op = (ctypes.c_void_p(x) if x else None for x in (valid, out_valid))
-        else:
-            symbols = np.ascontiguousarray(symbols, np.float32).reshape(-1, self.max_channels)
-            n_rounds = symbols.shape[0] if n_rounds is None else int(n_rounds)
-            sp = ctypes.c_void_p(symbols.ctypes.data) if symbols.size else None
-            masks = []
-            for m, name in ((valid, "valid"), (out_valid, "out_valid")):
-                if m is not None:
-                    m = np.ascontiguousarray(m, np.uint8).reshape(-1, self.max_channels)
-                    if m.shape != symbols.shape:
-                        raise ValueError(f"{name} must have the symbols' shape")
-                masks.append(m)
-            valid, out_valid = masks
-            vp, op = (ctypes.c_void_p(m.ctypes.data) if m is not None and m.size else None for m in masks)
-        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
-        self._in_flight = (symbols, valid, out_valid)  # a run without a host copy returns before the stream has read them
-        check(self.ctx.lib.gnsship_cnav_run_symbols(self.h, sp, vp, op, int(on_device), int(n_rounds), *ptrs), "gnsship_cnav_run_symbols", self.ctx.h)
-        return res
-
-    def run_records(self, records, on_device: bool = False, n_rounds: int = None, host: bool = True):
-        """records: abi.TRK_EPOCH_DTYPE[n_rounds, max_channels] on the host, or a device pointer with on_device and n_rounds."""
-        if on_device:
-            rp = ctypes.c_void_p(records)
-        else:
-            records = np.ascontiguousarray(records, abi.TRK_EPOCH_DTYPE).reshape(-1, self.max_channels)
-            n_rounds = records.shape[0] if n_rounds is None else int(n_rounds)
-            rp = ctypes.c_void_p(records.ctypes.data) if records.size else None
-        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
-        self._in_flight = (records,)
-        check(self.ctx.lib.gnsship_cnav_run_records(self.h, rp, int(on_device), int(n_rounds), *ptrs), "gnsship_cnav_run_records", self.ctx.h)
-        return res
-
-    def run_trk(self, trk: "DllPllVemlTracking", host: bool = True):
-        """Consume, in place, the records the tracker's last run left on the device."""
-        res, ptrs = self._outputs(host, self.max_rounds)
-        rounds = ctypes.c_int32()
-        check(self.ctx.lib.gnsship_cnav_run_trk(self.h, trk.h, *ptrs, ctypes.byref(rounds)), "gnsship_cnav_run_trk", self.ctx.h)
-        if res is None:
-            return None
-        n = rounds.value  # the copies are dense over the run's rounds
-        flat = self.max_rounds * self.max_channels
-        return res._replace(tow_ms=res.tow_ms.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels),
-                            sflags=res.sflags.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels))
-
-    def outputs_device(self):
-        """Device pointers (messages, counts, faults, tow_ms, sflags) of the handle's output buffers."""
-        p = [ctypes.c_void_p() for _ in range(5)]
-        check(self.ctx.lib.gnsship_cnav_outputs_device(self.h, *[ctypes.byref(x) for x in p], None), "gnsship_cnav_outputs_device", self.ctx.h)
-        return tuple(x.value for x in p)
+        return self._run_symbols(symbols, (("valid", valid), ("out_valid", out_valid)), on_device, n_rounds, host)
 
     def state(self, channel: int) -> np.ndarray:
         """Every member of the channel's block object: one abi.CNAV_STATE_DTYPE record (a 0-d array)."""
         st = np.zeros((), abi.CNAV_STATE_DTYPE)
-        check(self.ctx.lib.gnsship_cnav_state_get(self.h, channel, ctypes.c_void_p(st.ctypes.data)), "gnsship_cnav_state_get", self.ctx.h)
+        self._call("state_get", channel, ctypes.c_void_p(st.ctypes.data))
         return st
 
     def set_state(self, channel: int, state):
         """The channel's members become ``state`` (an abi.CNAV_STATE_DTYPE record, e.g. another handle's state())."""
         st = np.ascontiguousarray(state, abi.CNAV_STATE_DTYPE).reshape(())
-        check(self.ctx.lib.gnsship_cnav_state_set(self.h, channel, ctypes.c_void_p(st.ctypes.data)), "gnsship_cnav_state_set", self.ctx.h)
+        self._call("state_set", channel, ctypes.c_void_p(st.ctypes.data))
 
     def reset_channel(self, channel: int):
         """The block's reset()."""
-        check(self.ctx.lib.gnsship_cnav_reset_channel(self.h, channel), "gnsship_cnav_reset_channel", self.ctx.h)
+        self._call("reset_channel", channel)
 
     def new_channel(self, channel: int):
         """A new block object on this channel."""
-        check(self.ctx.lib.gnsship_cnav_new_channel(self.h, channel), "gnsship_cnav_new_channel", self.ctx.h)
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.gnsship_cnav_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.close()
-        except Exception:
-            pass
+        self._call("new_channel", channel)
 
 
 def gps_l2c_telemetry(ctx: Context, max_channels: int, max_rounds: int) -> GpsCnavTelemetryDecoder:
@@ -1364,115 +1250,37 @@ class DnavResult(NamedTuple):
     sflags: np.ndarray
 
 
-class BeidouDnavTelemetryDecoder:
+class BeidouDnavTelemetryDecoder(_TelemetryDecoder):
     """beidou_b1i_telemetry_decoder_gs (signal abi.DNAV_B1I) or beidou_b3i_telemetry_decoder_gs (abi.DNAV_B3I) up to the time
     of week for up to ``channels`` channels on the device, one block object per channel: the 311-symbol history, preamble
     correlation, three-state frame sync, BCH(15,11,1) with its de-interleaver, the D1 / D2 FraID, Pnum and SOW, and the TOW
     stamp with valid_word (include/gnsship.h, gnsship_dnav_*).  max_rounds: the most entries per channel one run may carry."""
+    _prefix, _result, _per_run, _state = "gnsship_dnav", DnavResult, "subframes_per_run", abi.DnavState
 
     def __init__(self, ctx: Context, channels: int, max_rounds: int, signal: int):
-        self.ctx = ctx
-        self.h = None
-        self.signal, self.max_channels, self.max_rounds = int(signal), int(channels), int(max_rounds)
-        self.conf = abi.DnavConf(max_rounds=self.max_rounds, signal=self.signal, reserved=0)
-        h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_dnav_create(ctx.h, ctypes.byref(self.conf), self.max_channels, ctypes.byref(h)), "gnsship_dnav_create", ctx.h)
-        self.h = h
-        spr = ctypes.c_int32()
-        check(ctx.lib.gnsship_dnav_outputs_device(self.h, None, None, None, None, ctypes.byref(spr)), "gnsship_dnav_outputs_device", ctx.h)
-        self.subframes_per_run = spr.value
+        self.signal = int(signal)
+        self._open(ctx, abi.DnavConf(max_rounds=int(max_rounds), signal=self.signal, reserved=0), channels, max_rounds)
 
-    def _outputs(self, host: bool, n_rounds: int):
-        if not host:
-            return None, (None, None, None, None)
-        res = DnavResult(np.zeros((self.max_channels, self.subframes_per_run), abi.DNAV_SUBFRAME_DTYPE), np.zeros(self.max_channels, np.int32),
-                         np.zeros((n_rounds, self.max_channels), np.uint32), np.zeros((n_rounds, self.max_channels), np.uint8))
-        return res, tuple(ctypes.c_void_p(x.ctypes.data) for x in res)
+    def _new_result(self, n_rounds: int):
+        return DnavResult(np.zeros((self.max_channels, self.subframes_per_run), abi.DNAV_SUBFRAME_DTYPE), np.zeros(self.max_channels, np.int32),
+                          np.zeros((n_rounds, self.max_channels), np.uint32), np.zeros((n_rounds, self.max_channels), np.uint8))
 
     def run_symbols(self, symbols, valid=None, out_valid=None, on_device: bool = False, n_rounds: int = None, host: bool = True):
         """symbols float32[n_rounds, max_channels] (or a device pointer with on_device and n_rounds); valid and out_valid
         uint8 of the same shape (and place) or None.  Returns a DnavResult, or None when not host (asynchronous)."""
-        if on_device:
-            sp = ctypes.c_void_p(symbols)
-            vp, op = (ctypes.c_void_p(x) if x else None for x in (valid, out_valid))
-        else:
-            symbols = np.ascontiguousarray(symbols, np.float32).reshape(-1, self.max_channels)
-            n_rounds = symbols.shape[0] if n_rounds is None else int(n_rounds)
-            sp = ctypes.c_void_p(symbols.ctypes.data) if symbols.size else None
-            masks = []
-            for m, name in ((valid, "valid"), (out_valid, "out_valid")):
-                if m is not None:
-                    m = np.ascontiguousarray(m, np.uint8).reshape(-1, self.max_channels)
-                    if m.shape != symbols.shape:
-                        raise ValueError(f"{name} must have the symbols' shape")
-                masks.append(m)
-            valid, out_valid = masks
-            vp, op = (ctypes.c_void_p(m.ctypes.data) if m is not None and m.size else None for m in masks)
-        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
-        self._in_flight = (symbols, valid, out_valid)  # a run without a host copy returns before the stream has read them
-        check(self.ctx.lib.gnsship_dnav_run_symbols(self.h, sp, vp, op, int(on_device), int(n_rounds), *ptrs), "gnsship_dnav_run_symbols", self.ctx.h)
-        return res
-
-    def run_records(self, records, on_device: bool = False, n_rounds: int = None, host: bool = True):
-        """records: abi.TRK_EPOCH_DTYPE[n_rounds, max_channels] on the host, or a device pointer with on_device and n_rounds."""
-        if on_device:
-            rp = ctypes.c_void_p(records)
-        else:
-            records = np.ascontiguousarray(records, abi.TRK_EPOCH_DTYPE).reshape(-1, self.max_channels)
-            n_rounds = records.shape[0] if n_rounds is None else int(n_rounds)
-            rp = ctypes.c_void_p(records.ctypes.data) if records.size else None
-        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
-        self._in_flight = (records,)
-        check(self.ctx.lib.gnsship_dnav_run_records(self.h, rp, int(on_device), int(n_rounds), *ptrs), "gnsship_dnav_run_records", self.ctx.h)
-        return res
-
-    def run_trk(self, trk: "DllPllVemlTracking", host: bool = True):
-        """Consume, in place, the records the tracker's last run left on the device."""
-        res, ptrs = self._outputs(host, self.max_rounds)
-        rounds = ctypes.c_int32()
-        check(self.ctx.lib.gnsship_dnav_run_trk(self.h, trk.h, *ptrs, ctypes.byref(rounds)), "gnsship_dnav_run_trk", self.ctx.h)
-        if res is None:
-            return None
-        n = rounds.value  # the copies are dense over the run's rounds
-        flat = self.max_rounds * self.max_channels
-        return res._replace(tow_ms=res.tow_ms.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels),
-                            sflags=res.sflags.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels))
-
-    def outputs_device(self):
-        """Device pointers (subframes, counts, tow_ms, sflags) of the handle's output buffers."""
-        p = [ctypes.c_void_p() for _ in range(4)]
-        check(self.ctx.lib.gnsship_dnav_outputs_device(self.h, *[ctypes.byref(x) for x in p], None), "gnsship_dnav_outputs_device", self.ctx.h)
-        return tuple(x.value for x in p)
-
-    def state(self, channel: int) -> dict:
-        """The channel's block members (gnsship_dnav_state) by name."""
-        st = abi.DnavState()
-        check(self.ctx.lib.gnsship_dnav_state_get(self.h, channel, ctypes.byref(st)), "gnsship_dnav_state_get", self.ctx.h)
-        return st.as_dict()
+        return self._run_symbols(symbols, (("valid", valid), ("out_valid", out_valid)), on_device, n_rounds, host)
 
     def reset_channel(self, channel: int):
         """The block's reset()."""
-        check(self.ctx.lib.gnsship_dnav_reset_channel(self.h, channel), "gnsship_dnav_reset_channel", self.ctx.h)
+        self._call("reset_channel", channel)
 
     def set_satellite(self, channel: int, prn: int):
         """The block's set_satellite(): timing and decoder choice only."""
-        check(self.ctx.lib.gnsship_dnav_set_satellite(self.h, channel, int(prn)), "gnsship_dnav_set_satellite", self.ctx.h)
+        self._call("set_satellite", channel, int(prn))
 
     def new_channel(self, channel: int, prn: int):
         """A new block object on this channel, constructed on this PRN."""
-        check(self.ctx.lib.gnsship_dnav_new_channel(self.h, channel, int(prn)), "gnsship_dnav_new_channel", self.ctx.h)
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.gnsship_dnav_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.close()
-        except Exception:
-            pass
+        self._call("new_channel", channel, int(prn))
 
 
 def beidou_b1i_telemetry(ctx: Context, max_channels: int, max_rounds: int) -> BeidouDnavTelemetryDecoder:
@@ -1495,117 +1303,45 @@ class GnavResult(NamedTuple):
     sflags: np.ndarray
 
 
-class GlonassGnavTelemetryDecoder:
+class GlonassGnavTelemetryDecoder(_TelemetryDecoder):
     """glonass_l1_ca_telemetry_decoder_gs (signal abi.GNAV_L1CA) or glonass_l2_ca_telemetry_decoder_gs (abi.GNAV_L2CA) up to the
     time of week for up to ``channels`` channels on the device, one block object per channel: the 2000-symbol history, the
     time-mark correlation over its 300 oldest entries, three-state frame sync, the double half-bit sums, the Hamming check
     with its single-bit correction, what strings 1..5 give the time of week, glot_to_gpst and the double TOW stamp with
     valid_word (include/gnsship.h, gnsship_gnav_*).  max_rounds: the most entries per channel one run may carry."""
+    _prefix, _result, _per_run = "gnsship_gnav", GnavResult, "strings_per_run"
 
     def __init__(self, ctx: Context, channels: int, max_rounds: int, signal: int):
-        self.ctx = ctx
-        self.h = None
-        self.signal, self.max_channels, self.max_rounds = int(signal), int(channels), int(max_rounds)
-        self.conf = abi.GnavConf(max_rounds=self.max_rounds, signal=self.signal, reserved=0)
-        h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_gnav_create(ctx.h, ctypes.byref(self.conf), self.max_channels, ctypes.byref(h)), "gnsship_gnav_create", ctx.h)
-        self.h = h
-        spr = ctypes.c_int32()
-        check(ctx.lib.gnsship_gnav_outputs_device(self.h, None, None, None, None, ctypes.byref(spr)), "gnsship_gnav_outputs_device", ctx.h)
-        self.strings_per_run = spr.value
+        self.signal = int(signal)
+        self._open(ctx, abi.GnavConf(max_rounds=int(max_rounds), signal=self.signal, reserved=0), channels, max_rounds)
 
-    def _outputs(self, host: bool, n_rounds: int):
-        if not host:
-            return None, (None, None, None, None)
-        res = GnavResult(np.zeros((self.max_channels, self.strings_per_run), abi.GNAV_STRING_DTYPE), np.zeros(self.max_channels, np.int32),
-                         np.zeros((n_rounds, self.max_channels), np.uint32), np.zeros((n_rounds, self.max_channels), np.uint8))
-        return res, tuple(ctypes.c_void_p(x.ctypes.data) for x in res)
+    def _new_result(self, n_rounds: int):
+        return GnavResult(np.zeros((self.max_channels, self.strings_per_run), abi.GNAV_STRING_DTYPE), np.zeros(self.max_channels, np.int32),
+                          np.zeros((n_rounds, self.max_channels), np.uint32), np.zeros((n_rounds, self.max_channels), np.uint8))
 
     def run_symbols(self, symbols, valid=None, out_valid=None, on_device: bool = False, n_rounds: int = None, host: bool = True):
         """symbols float32[n_rounds, max_channels] (or a device pointer with on_device and n_rounds); valid and out_valid
         uint8 of the same shape (and place) or None (out_valid is accepted and not read, as in the blocks).  Returns a GnavResult, or None when not host (asynchronous)."""
-        if on_device:
-            sp = ctypes.c_void_p(symbols)
-            vp, op = (ctypes.c_void_p(x) if x else None for x in (valid, out_valid))
-        else:
-            symbols = np.ascontiguousarray(symbols, np.float32).reshape(-1, self.max_channels)
-            n_rounds = symbols.shape[0] if n_rounds is None else int(n_rounds)
-            sp = ctypes.c_void_p(symbols.ctypes.data) if symbols.size else None
-            masks = []
-            for m, name in ((valid, "valid"), (out_valid, "out_valid")):
-                if m is not None:
-                    m = np.ascontiguousarray(m, np.uint8).reshape(-1, self.max_channels)
-                    if m.shape != symbols.shape:
-                        raise ValueError(f"{name} must have the symbols' shape")
-                masks.append(m)
-            valid, out_valid = masks
-            vp, op = (ctypes.c_void_p(m.ctypes.data) if m is not None and m.size else None for m in masks)
-        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
-        self._in_flight = (symbols, valid, out_valid)  # a run without a host copy returns before the stream has read them
-        check(self.ctx.lib.gnsship_gnav_run_symbols(self.h, sp, vp, op, int(on_device), int(n_rounds), *ptrs), "gnsship_gnav_run_symbols", self.ctx.h)
-        return res
-
-    def run_records(self, records, on_device: bool = False, n_rounds: int = None, host: bool = True):
-        """records: abi.TRK_EPOCH_DTYPE[n_rounds, max_channels] on the host, or a device pointer with on_device and n_rounds."""
-        if on_device:
-            rp = ctypes.c_void_p(records)
-        else:
-            records = np.ascontiguousarray(records, abi.TRK_EPOCH_DTYPE).reshape(-1, self.max_channels)
-            n_rounds = records.shape[0] if n_rounds is None else int(n_rounds)
-            rp = ctypes.c_void_p(records.ctypes.data) if records.size else None
-        res, ptrs = self._outputs(host, max(0, min(int(n_rounds), self.max_rounds)))
-        self._in_flight = (records,)
-        check(self.ctx.lib.gnsship_gnav_run_records(self.h, rp, int(on_device), int(n_rounds), *ptrs), "gnsship_gnav_run_records", self.ctx.h)
-        return res
-
-    def run_trk(self, trk: "DllPllVemlTracking", host: bool = True):
-        """Consume, in place, the records the tracker's last run left on the device."""
-        res, ptrs = self._outputs(host, self.max_rounds)
-        rounds = ctypes.c_int32()
-        check(self.ctx.lib.gnsship_gnav_run_trk(self.h, trk.h, *ptrs, ctypes.byref(rounds)), "gnsship_gnav_run_trk", self.ctx.h)
-        if res is None:
-            return None
-        n = rounds.value  # the copies are dense over the run's rounds
-        flat = self.max_rounds * self.max_channels
-        return res._replace(tow_ms=res.tow_ms.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels),
-                            sflags=res.sflags.reshape(flat)[:n * self.max_channels].reshape(n, self.max_channels))
-
-    def outputs_device(self):
-        """Device pointers (strings, counts, tow_ms, sflags) of the handle's output buffers."""
-        p = [ctypes.c_void_p() for _ in range(4)]
-        check(self.ctx.lib.gnsship_gnav_outputs_device(self.h, *[ctypes.byref(x) for x in p], None), "gnsship_gnav_outputs_device", self.ctx.h)
-        return tuple(x.value for x in p)
+        return self._run_symbols(symbols, (("valid", valid), ("out_valid", out_valid)), on_device, n_rounds, host)
 
     def state(self, channel: int) -> np.ndarray:
         """The channel's members (gnsship_gnav_state) as one abi.GNAV_STATE_DTYPE record."""
         st = np.zeros(1, abi.GNAV_STATE_DTYPE)
-        check(self.ctx.lib.gnsship_gnav_state_get(self.h, channel, ctypes.c_void_p(st.ctypes.data)), "gnsship_gnav_state_get", self.ctx.h)
+        self._call("state_get", channel, ctypes.c_void_p(st.ctypes.data))
         return st[0]
 
     def set_state(self, channel: int, st):
         """The channel's members become st (one abi.GNAV_STATE_DTYPE record)."""
         st = np.ascontiguousarray(np.asarray(st, abi.GNAV_STATE_DTYPE).reshape(1))
-        check(self.ctx.lib.gnsship_gnav_state_set(self.h, channel, ctypes.c_void_p(st.ctypes.data)), "gnsship_gnav_state_set", self.ctx.h)
+        self._call("state_set", channel, ctypes.c_void_p(st.ctypes.data))
 
     def set_satellite(self, channel: int, prn: int):
         """The block's set_satellite(): the PRN only."""
-        check(self.ctx.lib.gnsship_gnav_set_satellite(self.h, channel, int(prn)), "gnsship_gnav_set_satellite", self.ctx.h)
+        self._call("set_satellite", channel, int(prn))
 
     def new_channel(self, channel: int, prn: int):
         """A new block object on this channel, constructed on this PRN."""
-        check(self.ctx.lib.gnsship_gnav_new_channel(self.h, channel, int(prn)), "gnsship_gnav_new_channel", self.ctx.h)
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.gnsship_gnav_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.close()
-        except Exception:
-            pass
+        self._call("new_channel", channel, int(prn))
 
 
 def glonass_l1_ca_telemetry(ctx: Context, max_channels: int, max_rounds: int) -> GlonassGnavTelemetryDecoder:
