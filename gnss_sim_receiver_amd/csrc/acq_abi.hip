@@ -7,12 +7,9 @@
 #include <vector>
 
 #include "acq_engine.h"
-#include "engine.h"
+#include "host_api.h"
 
 namespace gnsship {
-int fail(gnsship_ctx* ctx, int code, const char* what);
-int hip_fail(gnsship_ctx* ctx, hipError_t e, const char* where);
-size_t fmt_bytes(int fmt);
 
 bool make_fft_plan(int n, FftPlan& plan)
 {
@@ -88,12 +85,6 @@ bool choose_acq_layout(int n, int force, FftPlan& plan, int& P, bool& huge)
 
 using namespace gnsship;
 
-#define HIP_TRY(ctx, expr)                                      \
-    do {                                                        \
-        hipError_t _e = (expr);                                 \
-        if (_e != hipSuccess) return hip_fail((ctx), _e, #expr); \
-    } while (0)
-
 struct gnsship_acq {
     gnsship_ctx* ctx = nullptr;
     gnsship_acq_conf conf{};
@@ -104,7 +95,6 @@ struct gnsship_acq {
     float2* twC = nullptr;       // huge: the column twiddles in column layout, twC[kq·M + m] = exp(-2πi m·kq/N)
     float2* T = nullptr;         // huge: forward column-stage scratch, n_bins × N
     float2* U = nullptr;         // huge: inverse row-stage scratch, prn_batch × n_bins × N
-    float* grid_scratch = nullptr; // unused: the huge search keeps no |y|² rows without a kept grid
     TileStat* tiles = nullptr;   // huge: lanes × prn_batch × n_bins × huge_tiles(M)
     int prn_batch = 0;
     int first_share = 50;        // huge, two lanes: percent of the PRNs in the first batch
@@ -125,8 +115,7 @@ struct gnsship_acq {
     gnsship_acq_result* res_host = nullptr;
     gnsship_acq_result* res_dev = nullptr;
     void* sig_dev = nullptr;     // staging for host input (N CF32)
-    float* grid_dev = nullptr;   // optional |Y|² grid (max_prns × n_bins × N)
-    size_t grid_bytes = 0;
+    DevBuf grid_dev;             // optional |Y|² grid (float, max_prns × n_bins × N)
     std::vector<char> code_set;
     int consumed = 0;            // d_consumed_samples: input samples used, the rest zero-padded
     Step2Spec step2{};           // make_2_steps: step-two grid active
@@ -161,23 +150,17 @@ static void acq_graph_reset(gnsship_acq* a)
 static void acq_free_grid_buffers(gnsship_acq* a)
 {
     acq_graph_reset(a);
-    void* hp[] = {a->T, a->U, a->grid_scratch, a->tiles};
-    for (void* p : hp)
+    void* ptrs[] = {a->T, a->U, a->tiles, a->wipe, a->X, a->rowstat};
+    for (void* p : ptrs)
         if (p) (void)hipFree(p);
     a->T = nullptr;
     a->U = nullptr;
-    a->grid_scratch = nullptr;
     a->tiles = nullptr;
     a->prn_batch = 0;
-    if (a->wipe) (void)hipFree(a->wipe);
-    if (a->X) (void)hipFree(a->X);
-    if (a->rowstat) (void)hipFree(a->rowstat);
-    if (a->grid_dev) (void)hipFree(a->grid_dev);
     a->wipe = nullptr;
     a->X = nullptr;
     a->rowstat = nullptr;
-    a->grid_dev = nullptr;
-    a->grid_bytes = 0;
+    release(a->grid_dev);
 }
 
 extern "C" int gnsship_acq_destroy(gnsship_acq* a)
@@ -495,12 +478,12 @@ static int acq_run_rows(gnsship_acq* a, const void* sig, int fmt, int sig_on_dev
     const bool keep_grid = (grid != nullptr) || a->conf.max_dwells > 1;
     const RowSpec rs = a->rows();
     const size_t gbytes = sizeof(float) * static_cast<size_t>(a->fdma_channels ? 1 : a->conf.max_prns) * a->n_bins * rs.row_len;
-    if (keep_grid && a->grid_bytes < gbytes) {
-        if (a->grid_dev) HIP_TRY(ctx, hipFree(a->grid_dev));
-        a->grid_dev = nullptr;
-        HIP_TRY(ctx, hipMalloc(&a->grid_dev, gbytes));
-        a->grid_bytes = gbytes;
+    if (keep_grid) {
+        bool grew = false;
+        if (int rc = reserve(ctx, a->grid_dev, gbytes, "gnsship_acq_run", "grid", &grew)) return rc;
+        if (grew) acq_graph_reset(a);  // a captured sweep holds the old grid's address
     }
+    float* const grid_dev = keep_grid ? a->grid_dev.as<float>() : nullptr;
     // non-coherent dwells (:657-665): restart the accumulation after max_dwells
     if (a->dwell_count >= a->conf.max_dwells) a->dwell_count = 0;
     const int accumulate = (a->conf.max_dwells > 1 && a->dwell_count > 0) ? 1 : 0;
@@ -520,7 +503,7 @@ static int acq_run_rows(gnsship_acq* a, const void* sig, int fmt, int sig_on_dev
                 if (two && i == 0) np = std::min(np, std::max(1, (n_prns * a->first_share + 99) / 100));
                 const int lane = two ? (i & 1) : 0;  // batches i and i + 2 share a lane's U and tiles, in stream order
                 // without a kept grid the |y|² rows never reach HBM (tile statistics + finalize's recomputation)
-                float* g = keep_grid ? a->grid_dev + static_cast<size_t>(p0) * a->n_bins * rs.row_len : nullptr;
+                float* g = keep_grid ? grid_dev + static_cast<size_t>(p0) * a->n_bins * rs.row_len : nullptr;
                 HIP_TRY(ctx, launch_acq_search_huge(a->X, codes, p0, np, a->n_bins, a->P, a->plan, a->twC, a->twM, a->U + lane * u_lane, g,
                                  keep_grid ? accumulate : 0, a->tiles + lane * t_lane, rs, a->rowstat, lane ? a->lane_stream : ctx->stream));
             }
@@ -530,12 +513,10 @@ static int acq_run_rows(gnsship_acq* a, const void* sig, int fmt, int sig_on_dev
             }
         } else if (a->P) {
             HIP_TRY(ctx, launch_acq_fft_big(src, fmt, a->wipe, a->n_bins, a->P, a->plan, a->tw, a->X, 0, a->consumed, ctx->stream));
-            HIP_TRY(ctx, launch_acq_search_big(a->X, codes, n_prns, a->n_bins, a->P, a->plan, a->tw, rs, accumulate,
-                             a->rowstat, keep_grid ? a->grid_dev : nullptr, ctx->stream));
+            HIP_TRY(ctx, launch_acq_search_big(a->X, codes, n_prns, a->n_bins, a->P, a->plan, a->tw, rs, accumulate, a->rowstat, grid_dev, ctx->stream));
         } else {
             HIP_TRY(ctx, launch_acq_fft_rows(src, fmt, a->wipe, a->n_bins, a->plan, a->tw, a->X, 0, a->consumed, ctx->stream));
-            HIP_TRY(ctx, launch_acq_search(a->X, codes, n_prns, a->n_bins, a->plan, a->tw, rs, accumulate,
-                             a->rowstat, keep_grid ? a->grid_dev : nullptr, ctx->stream));
+            HIP_TRY(ctx, launch_acq_search(a->X, codes, n_prns, a->n_bins, a->plan, a->tw, rs, accumulate, a->rowstat, grid_dev, ctx->stream));
         }
         HIP_TRY(ctx, launch_acq_decide(a->rowstat, n_decisions, dec_bins, rs.row_len, a->conf.doppler_max, a->conf.doppler_step, a->conf.doppler_center,
                          a->dwell_count, a->conf.use_cfar, a->conf.samples_per_code, a->conf.resampler_ratio > 0.0f ? a->conf.resampler_ratio : 1.0f,
@@ -548,8 +529,7 @@ static int acq_run_rows(gnsship_acq* a, const void* sig, int fmt, int sig_on_dev
     }();
     const bool graphs_on = graph_env < 0 ? a->huge : graph_env == 1;
     if (graphs_on && !a->graph_broken) {
-        const gnsship_acq::GraphKey key{src, fmt, n_prns, accumulate, keep_grid ? 1 : 0, a->dwell_count, slot0, n_decisions,
-            keep_grid ? a->grid_dev : nullptr, a->step2};
+        const gnsship_acq::GraphKey key{src, fmt, n_prns, accumulate, keep_grid ? 1 : 0, a->dwell_count, slot0, n_decisions, grid_dev, a->step2};
         const bool same = a->graph && std::memcmp(&key, &a->graph_key, sizeof(key)) == 0;
         if (!same) {
             acq_graph_reset(a);
@@ -575,7 +555,7 @@ static int acq_run_rows(gnsship_acq* a, const void* sig, int fmt, int sig_on_dev
         return rc;
     }
     if (grid)
-        HIP_TRY(ctx, hipMemcpyAsync(grid, a->grid_dev, sizeof(float) * static_cast<size_t>(n_prns) * a->n_bins * rs.row_len, hipMemcpyDeviceToHost,
+        HIP_TRY(ctx, hipMemcpyAsync(grid, grid_dev, sizeof(float) * static_cast<size_t>(n_prns) * a->n_bins * rs.row_len, hipMemcpyDeviceToHost,
                          ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     std::memcpy(results, a->res_host, sizeof(gnsship_acq_result) * n_decisions);

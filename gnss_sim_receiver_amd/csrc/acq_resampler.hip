@@ -125,8 +125,7 @@ struct gnsship_acq_resampler {
     float* taps_rev_dev = nullptr;
     float2* hist_dev[2] = {nullptr, nullptr};
     int hist_cur = 0;
-    void* stage_dev = nullptr;
-    size_t stage_cap = 0;
+    DevBuf stage_dev;  // host input
     float2* out_dev = nullptr;
 };
 
@@ -176,9 +175,10 @@ extern "C" int gnsship_acq_resampler_destroy(gnsship_acq_resampler* r)
     if (!r) return GNSSHIP_E_INVAL;
     (void)hipSetDevice(r->ctx->device);
     (void)hipStreamSynchronize(r->ctx->stream);
-    void* ptrs[] = {r->taps_rev_dev, r->hist_dev[0], r->hist_dev[1], r->stage_dev, r->out_dev};
+    void* ptrs[] = {r->taps_rev_dev, r->hist_dev[0], r->hist_dev[1], r->out_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    release(r->stage_dev);
     delete r;
     return GNSSHIP_OK;
 }
@@ -242,17 +242,10 @@ extern "C" int gnsship_acq_resampler_run(gnsship_acq_resampler* r, const void* i
     const void* src = in;
     if (!in_on_device) {
         const size_t bytes = fmt_bytes(fmt) * static_cast<size_t>(n_in);
-        if (r->stage_cap < bytes) {
-            if (r->stage_dev) (void)hipFree(r->stage_dev);
-            r->stage_dev = nullptr;
-            r->stage_cap = 0;
-            hipError_t e = hipMalloc(&r->stage_dev, bytes);
-            if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_acq_resampler_run(stage)");
-            r->stage_cap = bytes;
-        }
-        hipError_t e = hipMemcpyAsync(r->stage_dev, in, bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (int rc = reserve(ctx, r->stage_dev, bytes, "gnsship_acq_resampler_run", "stage")) return rc;
+        hipError_t e = hipMemcpyAsync(r->stage_dev.dev, in, bytes, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_acq_resampler_run(upload)");
-        src = r->stage_dev;
+        src = r->stage_dev.dev;
     }
     const int64_t nk = n_in / r->decim;
     const int64_t blocks = (nk + r->opb - 1) / r->opb;

@@ -12,7 +12,7 @@
 #include <cstring>
 #include <new>
 
-#include "engine.h"
+#include "host_api.h"
 
 struct gnsship_comm {
     gnsship_ctx* ctx = nullptr;

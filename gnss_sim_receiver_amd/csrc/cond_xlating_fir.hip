@@ -290,8 +290,7 @@ struct gnsship_cond {
     float2* hist_dev[2] = {nullptr, nullptr};
     int64_t* count_dev = nullptr;  // [2]
     int cur = 0;
-    void* stage_dev = nullptr;
-    size_t stage_cap = 0;
+    DevBuf stage_dev;  // host input
 };
 
 // The adapter's filter_type=lowpass taps (freq_xlating_fir_filter.cc:99-106):
@@ -313,9 +312,10 @@ extern "C" int gnsship_cond_destroy(gnsship_cond* c)
         if (c->taps_dev[b]) (void)hipFree(c->taps_dev[b]);
         if (c->out_dev[b]) (void)hipFree(c->out_dev[b]);
     }
-    void* ptrs[] = {c->hist_dev[0], c->hist_dev[1], c->count_dev, c->stage_dev};
+    void* ptrs[] = {c->hist_dev[0], c->hist_dev[1], c->count_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    release(c->stage_dev);
     delete c;
     return GNSSHIP_OK;
 }
@@ -420,20 +420,10 @@ extern "C" int gnsship_cond_run(gnsship_cond* c, const void* in, int fmt, int in
     const void* src = in;
     if (!in_on_device) {
         const size_t bytes = (static_cast<size_t>(n_in) * static_cast<size_t>(bps) + 7) / 8;
-        if (c->stage_cap < bytes) {
-            if (c->stage_dev) {
-                (void)hipStreamSynchronize(ctx->stream);  // an earlier run may still read it
-                (void)hipFree(c->stage_dev);
-            }
-            c->stage_dev = nullptr;
-            c->stage_cap = 0;
-            hipError_t e = hipMalloc(&c->stage_dev, bytes);
-            if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_cond_run(stage)");
-            c->stage_cap = bytes;
-        }
-        hipError_t e = hipMemcpyAsync(c->stage_dev, in, bytes, hipMemcpyHostToDevice, ctx->stream);
+        if (int rc = reserve(ctx, c->stage_dev, bytes, "gnsship_cond_run", "stage")) return rc;
+        hipError_t e = hipMemcpyAsync(c->stage_dev.dev, in, bytes, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_cond_run(upload)");
-        src = c->stage_dev;
+        src = c->stage_dev.dev;
     }
     CondArgs a;
     for (int b = 0; b < kCondMaxBands; b++) a.band[b] = c->band[b];

@@ -28,7 +28,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "engine.h"
+#include "host_api.h"
 #include "nco_math.h"
 
 #pragma clang fp contract(off)
@@ -186,23 +186,24 @@ hipError_t launch_corr_hd(const void* samples, int fmt, const HdPlan& plan, floa
     const int n_chunks = static_cast<int>(plan.chunks.size());
     if (n_jobs == 0) return hipSuccess;
     if (plan.max_code_len < 1 || plan.max_code_len > kMaxCodeLen) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(hd_anchor_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, stream, plan.jobs_dev, n_jobs, plan.anchors_dev);
+    const HdJob* jobs = plan.jobs_dev.as<HdJob>();
+    const HdChunk* chunks = plan.chunks_dev.as<HdChunk>();
+    HdAnchor* anchors = plan.anchors_dev.as<HdAnchor>();
+    float* partials = plan.partials_dev.as<float>();
+    hipLaunchKernelGGL(hd_anchor_kernel, dim3((n_jobs + 63) / 64), dim3(64), 0, stream, jobs, n_jobs, anchors);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (n_chunks > 0) {
         const size_t lds = sizeof(float) * static_cast<size_t>(plan.max_code_len);
         switch (fmt) {
         case GNSSHIP_FMT_CF32:
-            hipLaunchKernelGGL(hd_corr_kernel<GNSSHIP_FMT_CF32>, dim3(n_chunks), dim3(kHdThreads), lds, stream, samples, plan.jobs_dev, plan.chunks_dev,
-                plan.anchors_dev, plan.partials_dev);
+            hipLaunchKernelGGL(hd_corr_kernel<GNSSHIP_FMT_CF32>, dim3(n_chunks), dim3(kHdThreads), lds, stream, samples, jobs, chunks, anchors, partials);
             break;
         case GNSSHIP_FMT_CI16:
-            hipLaunchKernelGGL(hd_corr_kernel<GNSSHIP_FMT_CI16>, dim3(n_chunks), dim3(kHdThreads), lds, stream, samples, plan.jobs_dev, plan.chunks_dev,
-                plan.anchors_dev, plan.partials_dev);
+            hipLaunchKernelGGL(hd_corr_kernel<GNSSHIP_FMT_CI16>, dim3(n_chunks), dim3(kHdThreads), lds, stream, samples, jobs, chunks, anchors, partials);
             break;
         case GNSSHIP_FMT_CI8:
-            hipLaunchKernelGGL(hd_corr_kernel<GNSSHIP_FMT_CI8>, dim3(n_chunks), dim3(kHdThreads), lds, stream, samples, plan.jobs_dev, plan.chunks_dev,
-                plan.anchors_dev, plan.partials_dev);
+            hipLaunchKernelGGL(hd_corr_kernel<GNSSHIP_FMT_CI8>, dim3(n_chunks), dim3(kHdThreads), lds, stream, samples, jobs, chunks, anchors, partials);
             break;
         default: return hipErrorInvalidValue;
         }
@@ -210,7 +211,7 @@ hipError_t launch_corr_hd(const void* samples, int fmt, const HdPlan& plan, floa
         if (e != hipSuccess) return e;
     }
     const int total = n_jobs * 2 * kMaxTaps;
-    hipLaunchKernelGGL(hd_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, plan.jobs_dev, n_jobs, plan.partials_dev, out);
+    hipLaunchKernelGGL(hd_reduce_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, jobs, n_jobs, partials, out);
     return hipGetLastError();
 }
 
@@ -256,18 +257,10 @@ bool derive_hd_job(const gnsship_corr_job& in, const float* code_dev, int code_l
 
 void hd_plan_free(HdPlan& plan)
 {
-    void* ptrs[] = {plan.jobs_dev, plan.chunks_dev, plan.anchors_dev, plan.partials_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    plan.jobs_dev = nullptr;
-    plan.chunks_dev = nullptr;
-    plan.anchors_dev = nullptr;
-    plan.partials_dev = nullptr;
-    plan.job_cap = plan.chunk_cap = 0;
-    plan.anchor_cap = 0;
+    for (DevBuf* b : {&plan.jobs_dev, &plan.chunks_dev, &plan.anchors_dev, &plan.partials_dev}) release(*b);
 }
 
-hipError_t hd_plan_upload(HdPlan& plan, hipStream_t stream)
+int hd_plan_upload(gnsship_ctx* ctx, HdPlan& plan, const char* who)
 {
     plan.chunks.clear();
     int64_t anchors = 0;
@@ -286,32 +279,16 @@ hipError_t hd_plan_upload(HdPlan& plan, hipStream_t stream)
     }
     plan.n_anchors = anchors > 0 ? anchors : 1;
     plan.max_code_len = max_len;
-    const int nj = static_cast<int>(plan.jobs.size()), nc = static_cast<int>(plan.chunks.size());
+    const size_t nj = plan.jobs.size(), nc = plan.chunks.size();
+    if (int rc = reserve(ctx, plan.jobs_dev, sizeof(HdJob) * nj, who, "hd jobs")) return rc;
+    if (int rc = reserve(ctx, plan.chunks_dev, sizeof(HdChunk) * nc, who, "hd chunks")) return rc;
+    if (int rc = reserve(ctx, plan.partials_dev, sizeof(float) * 2 * kMaxTaps * nc, who, "hd partials")) return rc;
+    if (int rc = reserve(ctx, plan.anchors_dev, sizeof(HdAnchor) * plan.n_anchors, who, "hd anchors")) return rc;
     hipError_t e = hipSuccess;
-    if (nj > plan.job_cap) {
-        if (plan.jobs_dev) (void)hipFree(plan.jobs_dev);
-        plan.jobs_dev = nullptr;
-        if ((e = hipMalloc(&plan.jobs_dev, sizeof(HdJob) * nj)) != hipSuccess) return e;
-        plan.job_cap = nj;
-    }
-    if (nc > plan.chunk_cap) {
-        if (plan.chunks_dev) (void)hipFree(plan.chunks_dev);
-        if (plan.partials_dev) (void)hipFree(plan.partials_dev);
-        plan.chunks_dev = nullptr;
-        plan.partials_dev = nullptr;
-        if ((e = hipMalloc(&plan.chunks_dev, sizeof(HdChunk) * nc)) != hipSuccess) return e;
-        if ((e = hipMalloc(&plan.partials_dev, sizeof(float) * 2 * kMaxTaps * nc)) != hipSuccess) return e;
-        plan.chunk_cap = nc;
-    }
-    if (plan.n_anchors > plan.anchor_cap) {
-        if (plan.anchors_dev) (void)hipFree(plan.anchors_dev);
-        plan.anchors_dev = nullptr;
-        if ((e = hipMalloc(&plan.anchors_dev, sizeof(HdAnchor) * plan.n_anchors)) != hipSuccess) return e;
-        plan.anchor_cap = plan.n_anchors;
-    }
-    if (nj && (e = hipMemcpyAsync(plan.jobs_dev, plan.jobs.data(), sizeof(HdJob) * nj, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
-    if (nc && (e = hipMemcpyAsync(plan.chunks_dev, plan.chunks.data(), sizeof(HdChunk) * nc, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
-    return hipStreamSynchronize(stream);
+    if (nj) e = hipMemcpyAsync(plan.jobs_dev.dev, plan.jobs.data(), sizeof(HdJob) * nj, hipMemcpyHostToDevice, ctx->stream);
+    if (nc && e == hipSuccess) e = hipMemcpyAsync(plan.chunks_dev.dev, plan.chunks.data(), sizeof(HdChunk) * nc, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    return e == hipSuccess ? GNSSHIP_OK : hip_fail(ctx, e, who);
 }
 
 }  // namespace gnsship

@@ -195,39 +195,6 @@ struct HdAnchor {  // the Doppler chain at sample 256k (unnormalised)
 struct HdChunk {
     int32_t job, start, len, pad;
 };
-// Host-side plan of the high-dynamics jobs of a batch (or of one gnsship_corr_run).
-struct HdPlan {
-    std::vector<HdJob> jobs;
-    std::vector<HdChunk> chunks;
-    int64_t n_anchors = 0;
-    int max_code_len = 1;
-    HdJob* jobs_dev = nullptr;
-    HdChunk* chunks_dev = nullptr;
-    HdAnchor* anchors_dev = nullptr;
-    float* partials_dev = nullptr;
-    int job_cap = 0, chunk_cap = 0;
-    int64_t anchor_cap = 0;
-};
-// Derive one HdJob from a reference-style call; false when the arguments are outside what the
-// reference itself can run (taps, shifts that would make its memcpy lengths negative).
-bool derive_hd_job(const gnsship_corr_job& in, const float* code_dev, int code_len, int out_index, HdJob& out);
-// Chunks + anchor layout for plan.jobs; (re)allocates and uploads the device copies.
-hipError_t hd_plan_upload(HdPlan& plan, hipStream_t stream);
-void hd_plan_free(HdPlan& plan);
-// Doppler-chain anchors, per-chunk correlation, per-job reduction into out[out_index].
-hipError_t launch_corr_hd(const void* samples, int fmt, const HdPlan& plan, float* out, hipStream_t stream);
+// The host-side plan of a batch's high-dynamics jobs (HdPlan) and its launch function: host_api.h.
 
 }  // namespace gnsship
-
-struct gnsship_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t events[16] = {};
-    std::string last_error;
-    // code bank
-    std::vector<gnsship::CodeDesc> codes_host;  // ptr = device pointer
-    gnsship::CodeDesc* codes_dev = nullptr;
-    int codes_dev_cap = 0;
-    bool codes_dirty = false;
-    uint64_t codes_version = 0;  // bumped by every gnsship_code_set (holders of code pointers re-attach)
-};

@@ -9,7 +9,7 @@
 #include <map>
 #include <new>
 
-#include "engine.h"
+#include "host_api.h"
 
 using namespace gnsship;
 
@@ -31,12 +31,6 @@ int hip_fail(gnsship_ctx* ctx, hipError_t e, const char* where)
     return (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation) ? GNSSHIP_E_NOMEM : GNSSHIP_E_DEVICE;
 }
 
-#define HIP_TRY(ctx, expr)                                      \
-    do {                                                        \
-        hipError_t _e = (expr);                                 \
-        if (_e != hipSuccess) return hip_fail((ctx), _e, #expr); \
-    } while (0)
-
 int set_device(gnsship_ctx* ctx)
 {
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -47,15 +41,10 @@ int set_device(gnsship_ctx* ctx)
 int sync_code_table(gnsship_ctx* ctx)
 {
     if (!ctx->codes_dirty) return GNSSHIP_OK;
-    const int n = static_cast<int>(ctx->codes_host.size());
-    if (n > ctx->codes_dev_cap) {
-        if (ctx->codes_dev) HIP_TRY(ctx, hipFree(ctx->codes_dev));
-        ctx->codes_dev = nullptr;
-        const int cap = n < 64 ? 64 : 2 * n;
-        HIP_TRY(ctx, hipMalloc(&ctx->codes_dev, sizeof(CodeDesc) * cap));
-        ctx->codes_dev_cap = cap;
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->codes_dev, ctx->codes_host.data(), sizeof(CodeDesc) * n, hipMemcpyHostToDevice, ctx->stream));
+    const size_t n = ctx->codes_host.size();
+    if (sizeof(CodeDesc) * n > ctx->codes_dev.cap)  // room for the ids that follow: max(64, 2n) entries
+        if (int rc = reserve(ctx, ctx->codes_dev, sizeof(CodeDesc) * (n < 64 ? 64 : 2 * n), "sync_code_table", "codes")) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->codes_dev.dev, ctx->codes_host.data(), sizeof(CodeDesc) * n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->codes_dirty = false;
     return GNSSHIP_OK;
@@ -285,7 +274,7 @@ extern "C" int gnsship_ctx_destroy(gnsship_ctx* ctx)
     (void)hipStreamSynchronize(ctx->stream);
     for (auto& c : ctx->codes_host)
         if (c.ptr) (void)free_padded_code(c.ptr);
-    if (ctx->codes_dev) (void)hipFree(ctx->codes_dev);
+    release(ctx->codes_dev);
     for (auto& ev : ctx->events)
         if (ev) (void)hipEventDestroy(ev);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -399,16 +388,11 @@ struct gnsship_batch {
     int max_code_len = 1;
     bool any_multi = false;
     ChunkClass classes[kChunkClasses] = {};
-    int chunk_cap = 0;
     int n_items = 0;
-    int item_cap = 0;
-    DevJob* jobs_dev = nullptr;
-    ChunkDesc* chunks_dev = nullptr;
-    WorkItem* items_dev = nullptr;
-    float* partials_dev = nullptr;
+    DevJob* jobs_dev = nullptr;  // max_jobs
     float* out_dev = nullptr;
-    Anchor* anchors_dev = nullptr;
-    int64_t anchor_cap = 0;
+    // grown by set_jobs: ChunkDesc, WorkItem, float[chunk][2·kMaxTaps], Anchor (+ kAnchorPad), SerialJob
+    DevBuf chunks_dev, items_dev, partials_dev, anchors_dev, serial_dev;
     std::vector<DevJob> jobs_host;
     std::vector<ChunkDesc> chunks_host;
     std::vector<WorkItem> items_host;
@@ -429,16 +413,14 @@ struct gnsship_batch {
     // generic-rotator jobs in the reference's serial order (no AVX / TREE / HIGH_DYN flag):
     // corr_serial.hip after the main classes, likewise empty slots in the main plan
     std::vector<SerialJob> serial;
-    SerialJob* serial_dev = nullptr;
-    int serial_cap = 0;
 };
 
 static void batch_release(gnsship_batch* b)
 {
     hd_plan_free(b->hd);
-    void* ptrs[] = {b->jobs_dev, b->chunks_dev, b->items_dev, b->partials_dev, b->out_dev, b->anchors_dev, b->serial_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    for (DevBuf* d : {&b->chunks_dev, &b->items_dev, &b->partials_dev, &b->anchors_dev, &b->serial_dev}) release(*d);
+    if (b->jobs_dev) (void)hipFree(b->jobs_dev);
+    if (b->out_dev) (void)hipFree(b->out_dev);
     if (b->anchors_ready) (void)hipEventDestroy(b->anchors_ready);
     if (b->corr_done) (void)hipEventDestroy(b->corr_done);
     if (b->aux) (void)hipStreamDestroy(b->aux);
@@ -524,46 +506,33 @@ extern "C" int gnsship_batch_set_jobs(gnsship_batch* b, const gnsship_corr_job* 
     b->n_chunks = plan_chunks(b->jobs_host, b->chunks_host, b->items_host, b->any_multi, &n_anchors, b->classes, chunks_per_item_setting(), true);
     b->n_items = static_cast<int>(b->items_host.size());
     attach_codes(b->chunks_host, b->jobs_host, ctx->codes_host);
-    if (b->n_items > b->item_cap) {
-        if (b->items_dev) HIP_TRY(ctx, hipFree(b->items_dev));
-        b->items_dev = nullptr;
-        HIP_TRY(ctx, hipMalloc(&b->items_dev, sizeof(WorkItem) * b->n_items));
-        b->item_cap = b->n_items;
-    }
-    if (b->n_items) HIP_TRY(ctx, hipMemcpy(b->items_dev, b->items_host.data(), sizeof(WorkItem) * b->n_items, hipMemcpyHostToDevice));
-    if (n_anchors > b->anchor_cap) {
-        if (b->anchors_dev) HIP_TRY(ctx, hipFree(b->anchors_dev));
-        b->anchors_dev = nullptr;
-        HIP_TRY(ctx, hipMalloc(&b->anchors_dev, sizeof(Anchor) * (n_anchors + kAnchorPad)));
-        HIP_TRY(ctx, hipMemset(b->anchors_dev, 0, sizeof(Anchor) * (n_anchors + kAnchorPad)));
-        b->anchor_cap = n_anchors;
-    }
-    if (b->n_chunks > b->chunk_cap) {
-        if (b->chunks_dev) HIP_TRY(ctx, hipFree(b->chunks_dev));
-        if (b->partials_dev) HIP_TRY(ctx, hipFree(b->partials_dev));
-        b->chunks_dev = nullptr;
-        b->partials_dev = nullptr;
-        HIP_TRY(ctx, hipMalloc(&b->chunks_dev, sizeof(ChunkDesc) * b->n_chunks));
-        HIP_TRY(ctx, hipMalloc(&b->partials_dev, sizeof(float) * 2 * kMaxTaps * b->n_chunks));
-        b->chunk_cap = b->n_chunks;
-    }
-    b->n_jobs = n_jobs;
-    HIP_TRY(ctx, hd_plan_upload(b->hd, ctx->stream));
-    if (static_cast<int>(b->serial.size()) > b->serial_cap) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (b->serial_dev) HIP_TRY(ctx, hipFree(b->serial_dev));
-        b->serial_dev = nullptr;
-        HIP_TRY(ctx, hipMalloc(&b->serial_dev, sizeof(SerialJob) * b->serial.size()));
-        b->serial_cap = static_cast<int>(b->serial.size());
-    }
+    const char* who = "gnsship_batch_set_jobs";
+    bool grew = false;
+    if (int rc = reserve(ctx, b->items_dev, sizeof(WorkItem) * b->n_items, who, "items")) return rc;
+    if (b->n_items) HIP_TRY(ctx, hipMemcpy(b->items_dev.dev, b->items_host.data(), sizeof(WorkItem) * b->n_items, hipMemcpyHostToDevice));
+    if (int rc = reserve(ctx, b->anchors_dev, sizeof(Anchor) * (n_anchors + kAnchorPad), who, "anchors", &grew)) return rc;
+    if (grew) HIP_TRY(ctx, hipMemset(b->anchors_dev.dev, 0, b->anchors_dev.cap));
+    if (int rc = reserve(ctx, b->chunks_dev, sizeof(ChunkDesc) * b->n_chunks, who, "chunks")) return rc;
+    if (int rc = reserve(ctx, b->partials_dev, sizeof(float) * 2 * kMaxTaps * b->n_chunks, who, "partials")) return rc;
+    if (int rc = hd_plan_upload(ctx, b->hd, who)) return rc;
+    if (int rc = reserve(ctx, b->serial_dev, sizeof(SerialJob) * b->serial.size(), who, "serial jobs")) return rc;
     if (!b->serial.empty())
-        HIP_TRY(ctx, hipMemcpyAsync(b->serial_dev, b->serial.data(), sizeof(SerialJob) * b->serial.size(), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(b->serial_dev.dev, b->serial.data(), sizeof(SerialJob) * b->serial.size(), hipMemcpyHostToDevice, ctx->stream));
     if (n_jobs) {
         HIP_TRY(ctx, hipMemcpyAsync(b->jobs_dev, b->jobs_host.data(), sizeof(DevJob) * n_jobs, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(ctx, hipMemcpyAsync(b->chunks_dev, b->chunks_host.data(), sizeof(ChunkDesc) * b->n_chunks, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(b->chunks_dev.dev, b->chunks_host.data(), sizeof(ChunkDesc) * b->n_chunks, hipMemcpyHostToDevice, ctx->stream));
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
+    b->n_jobs = n_jobs;
     return GNSSHIP_OK;
+}
+
+// launch_corr_batch over the batch's plan: `n_items` work items, the stages and the stream of the caller's choice
+static hipError_t batch_correlate(const gnsship_batch* b, const void* dev_samples, int fmt, int n_items, hipStream_t stream, int stages,
+    const AnchorPrefetch* prefetch = nullptr, int replay_lanes = 1)
+{
+    return launch_corr_batch(dev_samples, fmt, b->jobs_dev, b->n_jobs, b->chunks_dev.as<ChunkDesc>(), b->items_dev.as<WorkItem>(), n_items, b->classes,
+        b->max_code_len, b->any_multi, b->anchors_dev.as<Anchor>(), b->partials_dev.as<float>(), b->out_dev, stream, stages, prefetch, replay_lanes);
 }
 
 extern "C" int gnsship_batch_launch(gnsship_batch* b, const void* dev_samples, int fmt)
@@ -582,19 +551,17 @@ extern "C" int gnsship_batch_launch_stages(gnsship_batch* b, const void* dev_sam
     if (stages & GNSSHIP_STAGE_ANCHORS) {
         // WAR: the previous correlation of this batch must have consumed the anchors
         HIP_TRY(ctx, hipStreamWaitEvent(b->aux, b->corr_done, 0));
-        hipError_t e = launch_corr_batch(dev_samples, fmt, b->jobs_dev, b->n_jobs, b->chunks_dev, b->items_dev, b->n_items, b->classes,
-            b->max_code_len, b->any_multi, b->anchors_dev, b->partials_dev, b->out_dev, b->aux, GNSSHIP_STAGE_ANCHORS, nullptr, b->replay_lanes);
+        hipError_t e = batch_correlate(b, dev_samples, fmt, b->n_items, b->aux, GNSSHIP_STAGE_ANCHORS, nullptr, b->replay_lanes);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_batch(anchors)");
         HIP_TRY(ctx, hipEventRecord(b->anchors_ready, b->aux));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, b->anchors_ready, 0));  // RAW: correlation (or caller) after replay
     }
     if (stages & GNSSHIP_STAGE_CORRELATE) {
-        hipError_t e = launch_corr_batch(dev_samples, fmt, b->jobs_dev, b->n_jobs, b->chunks_dev, b->items_dev, b->n_items, b->classes,
-            b->max_code_len, b->any_multi, b->anchors_dev, b->partials_dev, b->out_dev, ctx->stream, GNSSHIP_STAGE_CORRELATE);
+        hipError_t e = batch_correlate(b, dev_samples, fmt, b->n_items, ctx->stream, GNSSHIP_STAGE_CORRELATE);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_batch(correlate)");
         e = launch_corr_hd(dev_samples, fmt, b->hd, b->out_dev, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_hd");
-        e = launch_corr_serial(dev_samples, fmt, b->serial_dev, static_cast<int>(b->serial.size()), b->out_dev, ctx->stream);
+        e = launch_corr_serial(dev_samples, fmt, b->serial_dev.as<SerialJob>(), static_cast<int>(b->serial.size()), b->out_dev, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_serial");
         HIP_TRY(ctx, hipEventRecord(b->corr_done, ctx->stream));
     }
@@ -623,24 +590,21 @@ extern "C" int gnsship_batch_launch_pipelined2(gnsship_batch* b, const void* dev
     AnchorPrefetch pf{};
     const bool p1 = next && next->n_jobs > 0, p2 = next2 && next2->n_jobs > 0;
     if (p1)
-        pf.task[0] = ReplayTask{next->jobs_dev, next->anchors_dev, next->n_jobs, next->anchor_segs == 1 ? 1 : 0, kAnchorSegments, kAnchorSegments, 0,
+        pf.task[0] = ReplayTask{next->jobs_dev, next->anchors_dev.as<Anchor>(), next->n_jobs, next->anchor_segs == 1 ? 1 : 0, kAnchorSegments, kAnchorSegments, 0,
             next->replay_lanes};
-    if (p2) pf.task[1] = ReplayTask{next2->jobs_dev, next2->anchors_dev, next2->n_jobs, 0, 1, kAnchorSegments, 0, next2->replay_lanes};
+    if (p2) pf.task[1] = ReplayTask{next2->jobs_dev, next2->anchors_dev.as<Anchor>(), next2->n_jobs, 0, 1, kAnchorSegments, 0, next2->replay_lanes};
     if (b->n_jobs > 0 && b->anchor_segs < kAnchorSegments) {
-        hipError_t e = launch_corr_batch(dev_samples, fmt, b->jobs_dev, b->n_jobs, b->chunks_dev, b->items_dev, b->n_items, b->classes,
-            b->max_code_len, b->any_multi, b->anchors_dev, b->partials_dev, b->out_dev, ctx->stream, GNSSHIP_STAGE_ANCHORS, nullptr, b->replay_lanes);
+        hipError_t e = batch_correlate(b, dev_samples, fmt, b->n_items, ctx->stream, GNSSHIP_STAGE_ANCHORS, nullptr, b->replay_lanes);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_batch(anchors)");
     }
     if (b->n_jobs > 0 || p1 || p2) {
-        hipError_t e = launch_corr_batch(dev_samples, fmt, b->jobs_dev, b->n_jobs, b->chunks_dev, b->items_dev, b->n_jobs > 0 ? b->n_items : 0,
-            b->classes, b->max_code_len, b->any_multi, b->anchors_dev, b->partials_dev, b->out_dev, ctx->stream, GNSSHIP_STAGE_CORRELATE,
-            (p1 || p2) ? &pf : nullptr);
+        hipError_t e = batch_correlate(b, dev_samples, fmt, b->n_jobs > 0 ? b->n_items : 0, ctx->stream, GNSSHIP_STAGE_CORRELATE, (p1 || p2) ? &pf : nullptr);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_batch(pipelined)");
     }
     if (b->n_jobs > 0) {
         hipError_t e = launch_corr_hd(dev_samples, fmt, b->hd, b->out_dev, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_hd");
-        e = launch_corr_serial(dev_samples, fmt, b->serial_dev, static_cast<int>(b->serial.size()), b->out_dev, ctx->stream);
+        e = launch_corr_serial(dev_samples, fmt, b->serial_dev.as<SerialJob>(), static_cast<int>(b->serial.size()), b->out_dev, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_serial");
     }
     b->anchor_segs = b->n_jobs > 0 ? kAnchorSegments : 0;
@@ -809,7 +773,7 @@ extern "C" int gnsship_corr_run(gnsship_corr* c, const void* sig, int fmt, int s
         c->hd.jobs.resize(1);
         if (!derive_hd_job(in, c->code_dev, c->code_len, 0, c->hd.jobs[0]))
             return fail(ctx, GNSSHIP_E_INVAL, "gnsship_corr_run: invalid high-dynamics job (tap shifts beyond the signal length?)");
-        HIP_TRY(ctx, hd_plan_upload(c->hd, ctx->stream));
+        if (int rc = hd_plan_upload(ctx, c->hd, "gnsship_corr_run")) return rc;
         hipError_t e = launch_corr_hd(src, fmt, c->hd, c->out_dev, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_hd");
         float tmp[2 * kMaxTaps];

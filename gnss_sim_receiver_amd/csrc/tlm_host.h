@@ -8,7 +8,6 @@
 // (tests/test_gpu_tlm_rejections.py).  Order everywhere: argument checks, then set_device, then staging.
 // Everything here is `static inline`: the library exports nothing new.
 #pragma once
-#include <cstdio>
 #include <initializer_list>
 
 #include "host_api.h"
@@ -17,15 +16,10 @@ namespace gnsship {
 
 gnsship_ctx* trk_context(const gnsship_trk* t);  // trk_abi.hip
 
-struct TlmStage {  // a device copy of a host input, grown as needed
-    void* dev = nullptr;
-    size_t cap = 0;
-};
-
 struct TlmHost {  // what every telemetry handle holds for the calls below
     gnsship_ctx* ctx = nullptr;
     int32_t max_channels = 0, max_rounds = 0;
-    TlmStage stage, valid, mask;  // host symbols or records; the validity mask; the family's second mask, if any
+    DevBuf stage, valid, mask;  // device copies of host inputs: symbols or records; the validity mask; the family's second mask, if any
 };
 
 static inline int tlm_reject(gnsship_ctx* ctx, int code, const char* who, const char* what)
@@ -42,21 +36,15 @@ static inline int tlm_launched(gnsship_ctx* ctx, const char* who)
     return e == hipSuccess ? GNSSHIP_OK : hip_fail(ctx, e, who);
 }
 
-// Host data of `bytes` bytes to a staging buffer that grows only when it is too small.
-static inline int tlm_stage(gnsship_ctx* ctx, TlmStage* s, const void* host, size_t bytes, const char* who)
+// Host data of `bytes` bytes to a staging buffer that grows only when it is too small; either failure is "<who>(upload)".
+static inline int tlm_stage(gnsship_ctx* ctx, DevBuf& s, const void* host, size_t bytes, const char* who)
 {
-    hipError_t e = hipSuccess;
-    if (s->cap < bytes) {
-        e = hipStreamSynchronize(ctx->stream);  // earlier launches may still read the old buffer
-        if (s->dev && e == hipSuccess) e = hipFree(s->dev);
-        s->dev = nullptr;  // a failed grow leaves an empty buffer, not a dangling one
-        s->cap = 0;
-        if (e == hipSuccess) e = hipMalloc(&s->dev, bytes);
-        if (e != hipSuccess) return hip_fail(ctx, e, who);
-        s->cap = bytes;
-    }
-    e = hipMemcpyAsync(s->dev, host, bytes, hipMemcpyHostToDevice, ctx->stream);
-    return e == hipSuccess ? GNSSHIP_OK : hip_fail(ctx, e, who);
+    if (int rc = reserve(ctx, s, bytes, who, "upload")) return rc;
+    const hipError_t e = hipMemcpyAsync(s.dev, host, bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) return GNSSHIP_OK;
+    char up[128];
+    std::snprintf(up, sizeof(up), "%s(upload)", who);
+    return hip_fail(ctx, e, up);
 }
 
 // 0 <= n_rounds <= max_rounds, an input where there is a round (`null_input`: "null symbols" / "null records"), set_device
@@ -75,17 +63,15 @@ static inline int tlm_symbols_in(TlmHost& h, const char* who, int on_device, int
     if (int rc = tlm_check_run(h, who, n_rounds, *sym, "null symbols")) return rc;
     const size_t n = static_cast<size_t>(n_rounds) * h.max_channels;
     if (on_device || n == 0) return GNSSHIP_OK;
-    char up[96];
-    std::snprintf(up, sizeof(up), "%s(upload)", who);
-    if (int rc = tlm_stage(h.ctx, &h.stage, *sym, sizeof(float) * n, up)) return rc;
-    *sym = static_cast<const float*>(h.stage.dev);
+    if (int rc = tlm_stage(h.ctx, h.stage, *sym, sizeof(float) * n, who)) return rc;
+    *sym = h.stage.as<float>();
     if (*valid) {
-        if (int rc = tlm_stage(h.ctx, &h.valid, *valid, n, up)) return rc;
-        *valid = static_cast<const uint8_t*>(h.valid.dev);
+        if (int rc = tlm_stage(h.ctx, h.valid, *valid, n, who)) return rc;
+        *valid = h.valid.as<uint8_t>();
     }
     if (mask && *mask) {
-        if (int rc = tlm_stage(h.ctx, &h.mask, *mask, n, up)) return rc;
-        *mask = static_cast<const uint8_t*>(h.mask.dev);
+        if (int rc = tlm_stage(h.ctx, h.mask, *mask, n, who)) return rc;
+        *mask = h.mask.as<uint8_t>();
     }
     return GNSSHIP_OK;
 }
@@ -100,10 +86,8 @@ static inline int tlm_records_in(TlmHost& h, const char* who, int on_device, int
         return GNSSHIP_OK;
     }
     if (on_device) return GNSSHIP_OK;
-    char up[96];
-    std::snprintf(up, sizeof(up), "%s(upload)", who);
-    if (int rc = tlm_stage(h.ctx, &h.stage, *rec, sizeof(gnsship_trk_epoch) * n_rounds * h.max_channels, up)) return rc;
-    *rec = static_cast<const gnsship_trk_epoch*>(h.stage.dev);
+    if (int rc = tlm_stage(h.ctx, h.stage, *rec, sizeof(gnsship_trk_epoch) * n_rounds * h.max_channels, who)) return rc;
+    *rec = h.stage.as<gnsship_trk_epoch>();
     return GNSSHIP_OK;
 }
 
@@ -185,8 +169,7 @@ static inline void tlm_release(TlmHost& h, std::initializer_list<void*> owned)
     (void)hipStreamSynchronize(h.ctx->stream);
     for (void* p : owned)
         if (p) (void)hipFree(p);
-    for (TlmStage* s : {&h.stage, &h.valid, &h.mask})
-        if (s->dev) (void)hipFree(s->dev);
+    for (DevBuf* s : {&h.stage, &h.valid, &h.mask}) release(*s);
 }
 
 }  // namespace gnsship

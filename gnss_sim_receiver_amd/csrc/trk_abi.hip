@@ -13,18 +13,9 @@
 #include <new>
 #include <vector>
 
-#include "engine.h"
 #include "galileo_e5_tables.h"
+#include "host_api.h"
 #include "trk_engine.h"
-
-namespace gnsship {
-int fail(gnsship_ctx* ctx, int code, const char* what);
-int hip_fail(gnsship_ctx* ctx, hipError_t e, const char* where);
-int set_device(gnsship_ctx* ctx);
-int sync_code_table(gnsship_ctx* ctx);
-size_t fmt_bytes(int fmt);
-int chunks_per_item_setting();
-}  // namespace gnsship
 
 using namespace gnsship;
 static_assert(sizeof(gnsship_trk_epoch) == 96, "gnsship_trk_epoch layout");
@@ -32,12 +23,6 @@ static_assert(sizeof(gnsship_trk_corr_trace) == 104, "gnsship_trk_corr_trace lay
 static_assert(sizeof(gnsship_trk_dump_record) == 96 && offsetof(gnsship_trk_dump_record, PRN_start_sample_count) == 28 &&
                   offsetof(gnsship_trk_dump_record, aux2) == 84 && offsetof(gnsship_trk_dump_record, PRN) == 92,
     "gnsship_trk_dump_record = the log_data file record");
-
-#define HIP_TRY(ctx, expr)                                       \
-    do {                                                         \
-        hipError_t _e = (expr);                                  \
-        if (_e != hipSuccess) return hip_fail((ctx), _e, #expr); \
-    } while (0)
 
 struct gnsship_trk {
     gnsship_ctx* ctx = nullptr;
@@ -60,16 +45,9 @@ struct gnsship_trk {
     Anchor* anchors_dev = nullptr;
     float* partials_dev = nullptr;
     float* out_dev = nullptr;
-    gnsship_trk_epoch* rec_dev = nullptr;
-    size_t rec_cap = 0;
-    gnsship_trk_dump_record* dump_dev = nullptr;
-    size_t dump_cap = 0;
-    int* ran_dev = nullptr;
-    size_t ran_cap = 0;
-    void* stage_dev = nullptr;
-    size_t stage_cap = 0;
-    void* start_stage_dev = nullptr;  // gnsship_trk_start_many's staged channel states + indices
-    size_t start_stage_cap = 0;
+    // grown by the runs: gnsship_trk_epoch and gnsship_trk_dump_record [round][channel], int [round + 1], host input
+    DevBuf rec_dev, dump_dev, ran_dev, stage_dev;
+    DevBuf start_stage_dev;  // gnsship_trk_start_many's staged channel states + indices
     // high_dyn: the high-dynamics correlator's fixed plan (one HdJob per job, out_index = job) and
     // the channels' rate-smoother rings
     bool high_dyn = false;
@@ -90,8 +68,7 @@ struct gnsship_trk {
     bool trace_on = false;
     int last_engine = GNSSHIP_TRK_ENGINE_NONE;  // the engine the last run / launch used
     gnsship_trk_plan last_plan{};               // and the variant its launch function chose (gnsship_trk_last_plan)
-    gnsship_trk_corr_trace* trace_dev = nullptr;
-    size_t trace_cap = 0;
+    DevBuf trace_dev;    // gnsship_trk_corr_trace [round][channel]
     size_t trace_n = 0;  // records of the last run (max_rounds × max_channels)
 };
 
@@ -430,16 +407,17 @@ hipError_t upload_hd_code(gnsship_trk* t, int job, const CodeDesc& cd)
     HdJob& j = t->hd.jobs[job];
     j.code = cd.ptr;
     j.code_len = cd.ptr ? cd.len : 0;
-    return hipMemcpyAsync(reinterpret_cast<char*>(t->hd.jobs_dev + job) + offsetof(HdJob, code), &j.code, sizeof(const float*) + sizeof(int32_t),
+    return hipMemcpyAsync(reinterpret_cast<char*>(t->hd.jobs_dev.as<HdJob>() + job) + offsetof(HdJob, code), &j.code, sizeof(const float*) + sizeof(int32_t),
         hipMemcpyHostToDevice, t->ctx->stream);
 }
 
 void release(gnsship_trk* t)
 {
-    void* ptrs[] = {t->params_dev, t->chans_dev, t->jobs_dev, t->chunks_dev, t->items_dev, t->anchors_dev, t->partials_dev, t->out_dev, t->rec_dev,
-        t->ran_dev, t->stage_dev, t->hist_dev, t->dump_dev, t->trace_dev, t->start_stage_dev, t->serial_dev};
+    void* ptrs[] = {t->params_dev, t->chans_dev, t->jobs_dev, t->chunks_dev, t->items_dev, t->anchors_dev, t->partials_dev, t->out_dev, t->hist_dev,
+        t->serial_dev};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    for (DevBuf* b : {&t->rec_dev, &t->dump_dev, &t->ran_dev, &t->stage_dev, &t->trace_dev, &t->start_stage_dev}) release(*b);
     hd_plan_free(t->hd);
 }
 
@@ -572,6 +550,7 @@ extern "C" int gnsship_trk_create(gnsship_ctx* ctx, const gnsship_trk_conf* conf
     t->high_dyn = t->params.conf.high_dyn != 0;
     t->serial_rounds = !t->high_dyn && (conf->system == GNSSHIP_SYS_GAL_E5A || conf->system == GNSSHIP_SYS_GAL_E5B);
     if (e == hipSuccess && t->serial_rounds) e = hipMalloc(&t->serial_dev, sizeof(SerialJob) * static_cast<size_t>(t->n_jobs));
+    int hd_rc = GNSSHIP_OK;
     if (e == hipSuccess && t->high_dyn) {
         t->hd.jobs.assign(t->n_jobs, HdJob{});
         for (int i = 0; i < t->n_jobs; i++) {
@@ -580,19 +559,19 @@ extern "C" int gnsship_trk_create(gnsship_ctx* ctx, const gnsship_trk_conf* conf
             j.n_taps = (p.jobs_per_channel == 2 && (i % 2) == 1) ? 1 : p.n_taps;
             j.out_index = i;
         }
-        e = hd_plan_upload(t->hd, ctx->stream);  // chunk layout and anchor offsets for vector_length
-        if (e == hipSuccess) {  // idle until a channel starts (the step kernel rewrites both every round)
+        hd_rc = hd_plan_upload(ctx, t->hd, "gnsship_trk_create");  // chunk layout and anchor offsets for vector_length
+        if (hd_rc == GNSSHIP_OK) {  // idle until a channel starts (the step kernel rewrites both every round)
             for (auto& j : t->hd.jobs) j.n_samples = 0;
             for (auto& c : t->hd.chunks) c.len = 0;
-            e = hipMemcpy(t->hd.jobs_dev, t->hd.jobs.data(), sizeof(HdJob) * t->hd.jobs.size(), hipMemcpyHostToDevice);
+            e = hipMemcpy(t->hd.jobs_dev.dev, t->hd.jobs.data(), sizeof(HdJob) * t->hd.jobs.size(), hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMemcpy(t->hd.chunks_dev.dev, t->hd.chunks.data(), sizeof(HdChunk) * t->hd.chunks.size(), hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMalloc(&t->hist_dev, sizeof(TrkHist) * static_cast<size_t>(max_channels));
         }
-        if (e == hipSuccess) e = hipMemcpy(t->hd.chunks_dev, t->hd.chunks.data(), sizeof(HdChunk) * t->hd.chunks.size(), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMalloc(&t->hist_dev, sizeof(TrkHist) * static_cast<size_t>(max_channels));
     }
-    if (e != hipSuccess) {
+    if (e != hipSuccess || hd_rc) {
         release(t);
         delete t;
-        return hip_fail(ctx, e, "gnsship_trk_create");
+        return hd_rc ? hd_rc : hip_fail(ctx, e, "gnsship_trk_create");
     }
     *out = t;
     return GNSSHIP_OK;
@@ -835,14 +814,8 @@ extern "C" int gnsship_trk_start_many(gnsship_trk* t, int n, const int32_t* chan
     }
     std::memcpy(host.data() + idx_off, channels, sizeof(int32_t) * static_cast<size_t>(n));
     if (int rc = set_device(ctx)) return rc;
-    if (t->start_stage_cap < host.size()) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (t->start_stage_dev) HIP_TRY(ctx, hipFree(t->start_stage_dev));
-        t->start_stage_dev = nullptr;
-        HIP_TRY(ctx, hipMalloc(&t->start_stage_dev, host.size()));
-        t->start_stage_cap = host.size();
-    }
-    char* stage = static_cast<char*>(t->start_stage_dev);
+    if (int rc = reserve(ctx, t->start_stage_dev, host.size(), "gnsship_trk_start_many", "stage")) return rc;
+    char* stage = t->start_stage_dev.as<char>();
     HIP_TRY(ctx, hipMemcpyAsync(stage, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(trk_scatter_kernel, dim3(n), dim3(256), 0, ctx->stream, t->chans_dev, reinterpret_cast<const TrkChannel*>(stage),
         reinterpret_cast<const int32_t*>(stage + idx_off), n);
@@ -931,28 +904,16 @@ static int trk_enqueue(gnsship_trk* t, const void* src, int fmt, uint64_t buffer
         t->attached_version = ctx->codes_version;
     }
     const size_t nrec = static_cast<size_t>(max_rounds) * t->max_channels;
-    if (dump && t->dump_cap < nrec) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (t->dump_dev) HIP_TRY(ctx, hipFree(t->dump_dev));
-        t->dump_dev = nullptr;
-        HIP_TRY(ctx, hipMalloc(&t->dump_dev, sizeof(gnsship_trk_dump_record) * nrec));
-        t->dump_cap = nrec;
-    }
-    if (out && t->rec_cap < nrec) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (t->rec_dev) HIP_TRY(ctx, hipFree(t->rec_dev));
-        t->rec_dev = nullptr;
-        HIP_TRY(ctx, hipMalloc(&t->rec_dev, sizeof(gnsship_trk_epoch) * nrec));
-        t->rec_cap = nrec;
-    }
-    if (t->ran_cap < static_cast<size_t>(max_rounds) + 1) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (t->ran_dev) HIP_TRY(ctx, hipFree(t->ran_dev));
-        t->ran_dev = nullptr;
-        HIP_TRY(ctx, hipMalloc(&t->ran_dev, sizeof(int) * (max_rounds + 1)));
-        t->ran_cap = static_cast<size_t>(max_rounds) + 1;
-    }
-    HIP_TRY(ctx, hipMemsetAsync(t->ran_dev, 0, sizeof(int) * (max_rounds + 1), ctx->stream));
+    const char* who = "gnsship_trk_run";
+    if (dump)
+        if (int rc = reserve(ctx, t->dump_dev, sizeof(gnsship_trk_dump_record) * nrec, who, "dump")) return rc;
+    if (out)
+        if (int rc = reserve(ctx, t->rec_dev, sizeof(gnsship_trk_epoch) * nrec, who, "records")) return rc;
+    if (int rc = reserve(ctx, t->ran_dev, sizeof(int) * (static_cast<size_t>(max_rounds) + 1), who, "rounds run")) return rc;
+    gnsship_trk_epoch* const rec_dev = out ? t->rec_dev.as<gnsship_trk_epoch>() : nullptr;
+    gnsship_trk_dump_record* const dump_dev = dump ? t->dump_dev.as<gnsship_trk_dump_record>() : nullptr;
+    int* const ran_dev = t->ran_dev.as<int>();
+    HIP_TRY(ctx, hipMemsetAsync(ran_dev, 0, sizeof(int) * (max_rounds + 1), ctx->stream));
     const int nc = t->max_channels;
     const bool avx = t->params.conf.rotator == GNSSHIP_ROTATOR_AVX;
     const int code_cap = padded_code_quads(max_len) * 4;
@@ -964,21 +925,15 @@ static int trk_enqueue(gnsship_trk* t, const void* src, int fmt, uint64_t buffer
     gnsship_trk_corr_trace* trace = nullptr;
     t->trace_n = 0;
     if (t->trace_on && persist) {
-        if (t->trace_cap < nrec) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (t->trace_dev) HIP_TRY(ctx, hipFree(t->trace_dev));
-            t->trace_dev = nullptr;
-            HIP_TRY(ctx, hipMalloc(&t->trace_dev, sizeof(gnsship_trk_corr_trace) * nrec));
-            t->trace_cap = nrec;
-        }
-        HIP_TRY(ctx, hipMemsetAsync(t->trace_dev, 0, sizeof(gnsship_trk_corr_trace) * nrec, ctx->stream));
-        trace = t->trace_dev;
+        if (int rc = reserve(ctx, t->trace_dev, sizeof(gnsship_trk_corr_trace) * nrec, who, "trace")) return rc;
+        trace = t->trace_dev.as<gnsship_trk_corr_trace>();
+        HIP_TRY(ctx, hipMemsetAsync(trace, 0, sizeof(gnsship_trk_corr_trace) * nrec, ctx->stream));
         t->trace_n = nrec;
     }
     if (persist) {
         // records of epochs a channel did not run stay zero (flags 0), as in the round-based loop
-        if (out) HIP_TRY(ctx, hipMemsetAsync(t->rec_dev, 0, sizeof(gnsship_trk_epoch) * nrec, ctx->stream));
-        if (dump) HIP_TRY(ctx, hipMemsetAsync(t->dump_dev, 0, sizeof(gnsship_trk_dump_record) * nrec, ctx->stream));
+        if (out) HIP_TRY(ctx, hipMemsetAsync(rec_dev, 0, sizeof(gnsship_trk_epoch) * nrec, ctx->stream));
+        if (dump) HIP_TRY(ctx, hipMemsetAsync(dump_dev, 0, sizeof(gnsship_trk_dump_record) * nrec, ctx->stream));
         const int n_codes = static_cast<int>(ctx->codes_host.size());
         hipError_t e;
         // the sign-bit replicas need every chip ±1 — of the codes this tracker's channels use
@@ -993,15 +948,11 @@ static int trk_enqueue(gnsship_trk* t, const void* src, int fmt, uint64_t buffer
         t->last_engine = GNSSHIP_TRK_ENGINE_NONE;
         t->last_plan = gnsship_trk_plan{};
         gnsship_trk_plan plan{};
-        if (lanes)
-            e = launch_trk_lane(t->params_dev, t->params, t->chans_dev, nc, ctx->codes_dev, n_codes, code_cap, src, fmt, buffer_first_sample,
-                n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, ctx->stream, &plan);
-        else if (fast)
-            e = launch_trk_fast(t->params_dev, t->params, t->chans_dev, nc, ctx->codes_dev, n_codes, code_cap, src, fmt, buffer_first_sample,
-                n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, binary, ctx->stream, &plan);
-        else
-            e = launch_trk_persist(t->params_dev, t->params, t->chans_dev, nc, ctx->codes_dev, n_codes, code_cap, src, fmt, buffer_first_sample,
-                n_buffer_samples, max_rounds, out ? t->rec_dev : nullptr, dump ? t->dump_dev : nullptr, trace, t->ran_dev, avx, ctx->stream, &plan);
+        const TrkRun run{t->params_dev, t->params, t->chans_dev, nc, ctx->codes_dev.as<CodeDesc>(), n_codes, code_cap, src, fmt, buffer_first_sample,
+            n_buffer_samples, max_rounds, rec_dev, dump_dev, trace, ran_dev, ctx->stream};
+        if (lanes) e = launch_trk_lane(run, &plan);
+        else if (fast) e = launch_trk_fast(run, binary, &plan);
+        else e = launch_trk_persist(run, avx, &plan);
         if (e != hipSuccess) return hip_fail(ctx, e, lanes ? "launch_trk_lane" : fast ? "launch_trk_fast" : "launch_trk_persist");
         t->last_engine = lanes  ? GNSSHIP_TRK_ENGINE_LANES
                          : fast ? (trk_fast_thru(nc) ? GNSSHIP_TRK_ENGINE_FAST_THROUGHPUT : GNSSHIP_TRK_ENGINE_FAST_LATENCY)
@@ -1015,10 +966,11 @@ static int trk_enqueue(gnsship_trk* t, const void* src, int fmt, uint64_t buffer
     }
     for (int r = 0; r <= max_rounds && !persist; r++) {
         const int consume = r > 0 ? 1 : 0, emit = r < max_rounds ? 1 : 0;
-        gnsship_trk_epoch* rec = (out && r > 0) ? t->rec_dev + static_cast<size_t>(r - 1) * nc : nullptr;
-        gnsship_trk_dump_record* drec = (dump && r > 0) ? t->dump_dev + static_cast<size_t>(r - 1) * nc : nullptr;
+        gnsship_trk_epoch* rec = (out && r > 0) ? rec_dev + static_cast<size_t>(r - 1) * nc : nullptr;
+        gnsship_trk_dump_record* drec = (dump && r > 0) ? dump_dev + static_cast<size_t>(r - 1) * nc : nullptr;
         hipError_t e = launch_trk_step(t->params_dev, t->chans_dev, nc, t->jobs_dev, t->chunks_dev, t->out_dev, buffer_first_sample, n_buffer_samples,
-            consume, emit, rec, drec, t->ran_dev + r, t->hist_dev, t->high_dyn ? t->hd.jobs_dev : nullptr, t->high_dyn ? t->hd.chunks_dev : nullptr,
+            consume, emit, rec, drec, ran_dev + r, t->hist_dev, t->high_dyn ? t->hd.jobs_dev.as<HdJob>() : nullptr,
+            t->high_dyn ? t->hd.chunks_dev.as<HdChunk>() : nullptr,
             t->high_dyn ? nullptr : t->anchors_dev, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_trk_step");
         if (!emit) break;
@@ -1041,7 +993,7 @@ static int trk_enqueue(gnsship_trk* t, const void* src, int fmt, uint64_t buffer
         if (e != hipSuccess) return hip_fail(ctx, e, "launch_corr_batch(tracking)");
     }
     if (out && t->params.interchange_iq) {
-        hipLaunchKernelGGL(trk_exchange_kernel, dim3(static_cast<unsigned>((nrec + 255) / 256)), dim3(256), 0, ctx->stream, t->rec_dev, nrec);
+        hipLaunchKernelGGL(trk_exchange_kernel, dim3(static_cast<unsigned>((nrec + 255) / 256)), dim3(256), 0, ctx->stream, rec_dev, nrec);
         HIP_TRY(ctx, hipGetLastError());
     }
     t->pending_rounds = max_rounds;
@@ -1058,28 +1010,19 @@ static int trk_finish(gnsship_trk* t, gnsship_trk_epoch* out, gnsship_trk_dump_r
     const int max_rounds = t->pending_rounds;
     const size_t nrec = static_cast<size_t>(max_rounds) * t->max_channels;
     std::vector<int> ran(max_rounds + 1);
-    HIP_TRY(ctx, hipMemcpyAsync(ran.data(), t->ran_dev, sizeof(int) * (max_rounds + 1), hipMemcpyDeviceToHost, ctx->stream));
-    if ((out && !t->pending_out) || (dump && !t->pending_dump)) {  // the launch did not keep them: nothing to copy
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        t->pending_rounds = -1;
-        if (rounds_done) {  // the launch ran and advanced the channels: report the epochs it consumed
-            int n = 0;
-            for (int r = 0; r < max_rounds; r++)
-                if (ran[r] > 0) n = r + 1;
-            *rounds_done = n;
-        }
-        return fail(ctx, GNSSHIP_E_INVAL, "gnsship_trk_collect: records / dump requested that the launch did not keep (want_records / want_dump)");
-    }
-    if (out) HIP_TRY(ctx, hipMemcpyAsync(out, t->rec_dev, sizeof(gnsship_trk_epoch) * nrec, hipMemcpyDeviceToHost, ctx->stream));
-    if (dump) HIP_TRY(ctx, hipMemcpyAsync(dump, t->dump_dev, sizeof(gnsship_trk_dump_record) * nrec, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ran.data(), t->ran_dev.dev, sizeof(int) * (max_rounds + 1), hipMemcpyDeviceToHost, ctx->stream));
+    const bool kept = (!out || t->pending_out) && (!dump || t->pending_dump);  // false: the launch did not keep them, nothing to copy
+    if (kept && out) HIP_TRY(ctx, hipMemcpyAsync(out, t->rec_dev.dev, sizeof(gnsship_trk_epoch) * nrec, hipMemcpyDeviceToHost, ctx->stream));
+    if (kept && dump) HIP_TRY(ctx, hipMemcpyAsync(dump, t->dump_dev.dev, sizeof(gnsship_trk_dump_record) * nrec, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     t->pending_rounds = -1;
-    if (rounds_done) {
+    if (rounds_done) {  // the launch ran and advanced the channels, kept or not: the epochs it consumed
         int n = 0;
         for (int r = 0; r < max_rounds; r++)
             if (ran[r] > 0) n = r + 1;
         *rounds_done = n;
     }
+    if (!kept) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_trk_collect: records / dump requested that the launch did not keep (want_records / want_dump)");
     return GNSSHIP_OK;
 }
 
@@ -1097,15 +1040,9 @@ extern "C" int gnsship_trk_run_dump(gnsship_trk* t, const void* sig, int fmt, in
     const void* src = sig;
     if (!sig_on_device) {
         const size_t bytes = fmt_bytes(fmt) * static_cast<size_t>(n_buffer_samples);
-        if (t->stage_cap < bytes) {
-            HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-            if (t->stage_dev) HIP_TRY(ctx, hipFree(t->stage_dev));
-            t->stage_dev = nullptr;
-            HIP_TRY(ctx, hipMalloc(&t->stage_dev, bytes));
-            t->stage_cap = bytes;
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(t->stage_dev, sig, bytes, hipMemcpyHostToDevice, ctx->stream));
-        src = t->stage_dev;
+        if (int rc = reserve(ctx, t->stage_dev, bytes, "gnsship_trk_run", "stage")) return rc;
+        HIP_TRY(ctx, hipMemcpyAsync(t->stage_dev.dev, sig, bytes, hipMemcpyHostToDevice, ctx->stream));
+        src = t->stage_dev.dev;
     }
     if (int rc = trk_enqueue(t, src, fmt, buffer_first_sample, n_buffer_samples, max_rounds, out != nullptr, dump != nullptr)) {
         t->pending_rounds = -1;
@@ -1143,8 +1080,8 @@ extern "C" int gnsship_trk_records_device(gnsship_trk* t, const gnsship_trk_epoc
 {
     if (!t) return GNSSHIP_E_INVAL;
     if (!dev_ptr || !rounds || !max_channels) return fail(t->ctx, GNSSHIP_E_INVAL, "gnsship_trk_records_device: null argument");
-    if (t->rec_rounds < 1 || !t->rec_dev) return fail(t->ctx, GNSSHIP_E_STATE, "gnsship_trk_records_device: the last run kept no records on the device");
-    *dev_ptr = t->rec_dev;
+    if (t->rec_rounds < 1 || !t->rec_dev.dev) return fail(t->ctx, GNSSHIP_E_STATE, "gnsship_trk_records_device: the last run kept no records on the device");
+    *dev_ptr = t->rec_dev.as<gnsship_trk_epoch>();
     *rounds = t->rec_rounds;
     *max_channels = t->max_channels;
     return GNSSHIP_OK;
@@ -1170,7 +1107,7 @@ extern "C" int gnsship_trk_trace_records(gnsship_trk* t, gnsship_trk_corr_trace*
     if (t->trace_n == 0) return fail(ctx, GNSSHIP_E_STATE, "gnsship_trk_trace_records: no traced run (gnsship_trk_set_trace, persistent loop)");
     if (static_cast<size_t>(max_records) < t->trace_n) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_trk_trace_records: buffer smaller than the run");
     if (int rc = set_device(ctx)) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(out, t->trace_dev, sizeof(gnsship_trk_corr_trace) * t->trace_n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out, t->trace_dev.dev, sizeof(gnsship_trk_corr_trace) * t->trace_n, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return GNSSHIP_OK;
 }

@@ -149,10 +149,27 @@ inline bool trk_persist_supports(const TrkParams& p)
     return p.n_taps == 3 || p.n_taps == 5;  // each with and without the data prompt (jobs_per_channel 2)
 }
 constexpr size_t kTrkPersistMaxLds = 150 * 1024;  // of the 160 KiB per CU, beside the static state
-hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes,
-    int n_codes, int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool avx, hipStream_t stream, gnsship_trk_plan* plan = nullptr);
-// Every launch function fills `plan` (when given) with the variant it chose: gnsship_trk_last_plan.
+// What one run hands to whichever persistent engine takes it (trk_abi.hip fills it once).
+struct TrkRun {
+    const TrkParams* params_dev;
+    const TrkParams& params;
+    TrkChannel* chans;
+    int n_chans;
+    const CodeDesc* codes;
+    int n_codes, code_cap_floats;
+    const void* samples;
+    int fmt;
+    uint64_t buf_first;
+    int64_t buf_len;
+    int max_rounds;
+    gnsship_trk_epoch* rec;          // null: no epoch records
+    gnsship_trk_dump_record* dump;   // null: no dump records
+    gnsship_trk_corr_trace* trace;   // null: no correlation trace
+    int* ran_count;
+    hipStream_t stream;
+};
+hipError_t launch_trk_persist(const TrkRun& r, bool avx, gnsship_trk_plan* plan);
+// Every launch function fills `plan` with the variant it chose: gnsship_trk_last_plan.
 // The latency-optimised persistent loop for the AVX rotator (trk_fast.hip): register-resident loop
 // state, flagless phasor slots, lock detectors beside the loop update.
 // codes_binary: every chip of the channels' codes is ±1 (the GPS L5 tap layout holds its replicas as sign
@@ -164,12 +181,7 @@ int trk_device_cus();             // compute units of the current device
 // the buffer addressable with 32-bit byte offsets; used above one channel per CU (GNSSHIP_TRK_LANE=0/1
 // forces it off / on).
 bool trk_lane_supported(const TrkParams& p, int code_cap_floats, int n_chans, int fmt, int64_t buf_len, bool codes_binary);
-hipError_t launch_trk_lane(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes, int n_codes,
-    int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, hipStream_t stream, gnsship_trk_plan* plan = nullptr);
-hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes, int n_codes,
-    int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool codes_binary, hipStream_t stream,
-    gnsship_trk_plan* plan = nullptr);
+hipError_t launch_trk_lane(const TrkRun& r, gnsship_trk_plan* plan);
+hipError_t launch_trk_fast(const TrkRun& r, bool codes_binary, gnsship_trk_plan* plan);
 
 }  // namespace gnsship

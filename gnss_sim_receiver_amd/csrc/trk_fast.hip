@@ -1941,30 +1941,28 @@ static auto fast_kernel_of(int form) -> decltype(&trk_fast_kernel<F, NTV, DV, kF
     return form == 2 ? trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWavesLong, PK> : trk_fast_kernel<F, NTV, DV, kFastG, false, SR, kFWaves, PK>;
 }
 
-hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes, int n_codes,
-    int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool codes_binary, hipStream_t stream, gnsship_trk_plan* plan)
+hipError_t launch_trk_fast(const TrkRun& r, bool codes_binary, gnsship_trk_plan* plan)
 {
-    const FastPlan f = fast_plan(params, code_cap_floats, n_chans, codes_binary);
+    const FastPlan f = fast_plan(r.params, r.code_cap_floats, r.n_chans, codes_binary);
     if (f.bytes == 0) return hipErrorInvalidValue;
-    const int N = static_cast<int>(params.conf.vector_length);
+    const int N = static_cast<int>(r.params.conf.vector_length);
     const int S = std::max(1, (N / kAvxLanes + f.G - 1) / f.G);
     const bool sring = f.rs < S;
-    const bool data = params.jobs_per_channel > 1;
-    const bool thru = fast_thru(n_chans);
-    const int nt = params.n_taps;
+    const bool data = r.params.jobs_per_channel > 1;
+    const bool thru = fast_thru(r.n_chans);
+    const int nt = r.params.n_taps;
     // the form: throughput (more channels than CUs), long epochs (more producer waves), latency
     const int form = thru ? 1 : (N >= kLongEpoch ? 2 : 0);
     const int waves = form == 1 ? GNSSHIP_THRU_WAVES : form == 2 ? kFWavesLong : kFWaves;
-    dim3 grid(n_chans), block(waves * kWave);
+    dim3 grid(r.n_chans), block(waves * kWave);
 #define GNSSHIP_FAST(F, NTV, DV, SR, PK)                                                                                                         \
     do {                                                                                                                                         \
         auto kfn = fast_kernel_of<F, NTV, DV, SR, PK, (NTV) == 3>(form); /* five taps: no throughput form (fast_plan) */                          \
         if (!kfn) return hipErrorInvalidValue;                                                                                                   \
         hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(f.bytes)); \
         if (e0 != hipSuccess) return e0;                                                                                                         \
-        hipLaunchKernelGGL(kfn, grid, block, f.bytes, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans, \
-            code_cap_floats, f.rs, f.rg, rec, dump, trace, ran_count);                                                                           \
+        hipLaunchKernelGGL(kfn, grid, block, f.bytes, r.stream, r.params_dev, r.chans, r.codes, r.n_codes, r.samples, r.buf_first, r.buf_len,    \
+            r.max_rounds, r.n_chans, r.code_cap_floats, f.rs, f.rg, r.rec, r.dump, r.trace, r.ran_count);                                        \
     } while (0)
 #define GNSSHIP_FAST_R(F, NTV, DV, PK)                    \
     do {                                                  \
@@ -1980,7 +1978,7 @@ hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params,
         else if (nt == 5 && data) GNSSHIP_FAST_R(F, 5, true, false); \
         else return hipErrorInvalidValue;                    \
     } while (0)
-    switch (fmt) {
+    switch (r.fmt) {
     case GNSSHIP_FMT_CF32: GNSSHIP_FAST_F(GNSSHIP_FMT_CF32); break;
     case GNSSHIP_FMT_CI16: GNSSHIP_FAST_F(GNSSHIP_FMT_CI16); break;
     case GNSSHIP_FMT_CI8: GNSSHIP_FAST_F(GNSSHIP_FMT_CI8); break;
@@ -1989,20 +1987,18 @@ hipError_t launch_trk_fast(const TrkParams* params_dev, const TrkParams& params,
 #undef GNSSHIP_FAST_F
 #undef GNSSHIP_FAST_R
 #undef GNSSHIP_FAST
-    if (plan) {
-        *plan = gnsship_trk_plan{};
-        plan->engine = thru ? GNSSHIP_TRK_ENGINE_FAST_THROUGHPUT : GNSSHIP_TRK_ENGINE_FAST_LATENCY;
-        plan->format = fmt;
-        plan->n_taps = nt;
-        plan->data_prompt = data ? 1 : 0;
-        plan->packed = f.packed ? 1 : 0;
-        plan->sring = sring ? 1 : 0;
-        plan->rs = f.rs;
-        plan->rg = f.rg;
-        plan->lds_bytes = static_cast<int32_t>(f.bytes);
-        plan->thru = thru ? 1 : 0;
-        plan->long_plan = form == 2 ? 1 : 0;
-    }
+    *plan = gnsship_trk_plan{};
+    plan->engine = thru ? GNSSHIP_TRK_ENGINE_FAST_THROUGHPUT : GNSSHIP_TRK_ENGINE_FAST_LATENCY;
+    plan->format = r.fmt;
+    plan->n_taps = nt;
+    plan->data_prompt = data ? 1 : 0;
+    plan->packed = f.packed ? 1 : 0;
+    plan->sring = sring ? 1 : 0;
+    plan->rs = f.rs;
+    plan->rg = f.rg;
+    plan->lds_bytes = static_cast<int32_t>(f.bytes);
+    plan->thru = thru ? 1 : 0;
+    plan->long_plan = form == 2 ? 1 : 0;
     return hipGetLastError();
 }
 

@@ -355,25 +355,23 @@ bool trk_lane_supported(const TrkParams& p, int code_cap_floats, int n_chans, in
     return trk_fast_thru(n_chans);
 }
 
-hipError_t launch_trk_lane(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes, int n_codes,
-    int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, hipStream_t stream, gnsship_trk_plan* plan)
+hipError_t launch_trk_lane(const TrkRun& r, gnsship_trk_plan* plan)
 {
-    const bool data = params.jobs_per_channel > 1;
-    const int nt = params.n_taps;
+    const bool data = r.params.jobs_per_channel > 1;
+    const int nt = r.params.n_taps;
     // waves per workgroup: up to kLWaves, fewer while that leaves compute units idle
     const int cus = trk_device_cus();
-    const int nw = std::max(1, std::min(kLWaves, (n_chans + kLRows * cus - 1) / (kLRows * cus)));
+    const int nw = std::max(1, std::min(kLWaves, (r.n_chans + kLRows * cus - 1) / (kLRows * cus)));
     const int wg_chans = nw * kLRows;
-    const size_t lds = static_cast<size_t>(wg_chans) * (data ? 2 : 1) * lane_code_words(code_cap_floats) * sizeof(uint32_t);
-    dim3 grid((n_chans + wg_chans - 1) / wg_chans), block(nw * kWave);
+    const size_t lds = static_cast<size_t>(wg_chans) * (data ? 2 : 1) * lane_code_words(r.code_cap_floats) * sizeof(uint32_t);
+    dim3 grid((r.n_chans + wg_chans - 1) / wg_chans), block(nw * kWave);
 #define GNSSHIP_LANE(F, NTV, DV)                                                                                                                         \
     do {                                                                                                                                                 \
         auto kfn = trk_lane_kernel<F, NTV, DV>;                                                                                                          \
         hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));     \
         if (e0 != hipSuccess) return e0;                                                                                                                 \
-        hipLaunchKernelGGL(kfn, grid, block, lds, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans,          \
-            code_cap_floats, rec, dump, trace, ran_count);                                                                                               \
+        hipLaunchKernelGGL(kfn, grid, block, lds, r.stream, r.params_dev, r.chans, r.codes, r.n_codes, r.samples, r.buf_first, r.buf_len,                \
+            r.max_rounds, r.n_chans, r.code_cap_floats, r.rec, r.dump, r.trace, r.ran_count);                                                            \
     } while (0)
 #define GNSSHIP_LANE_F(F)                                   \
     do {                                                    \
@@ -383,7 +381,7 @@ hipError_t launch_trk_lane(const TrkParams* params_dev, const TrkParams& params,
         else if (nt == 5 && data) GNSSHIP_LANE(F, 5, true); \
         else return hipErrorInvalidValue;                   \
     } while (0)
-    switch (fmt) {
+    switch (r.fmt) {
     case GNSSHIP_FMT_CF32: GNSSHIP_LANE_F(GNSSHIP_FMT_CF32); break;
     case GNSSHIP_FMT_CI16: GNSSHIP_LANE_F(GNSSHIP_FMT_CI16); break;
     case GNSSHIP_FMT_CI8: GNSSHIP_LANE_F(GNSSHIP_FMT_CI8); break;
@@ -391,15 +389,13 @@ hipError_t launch_trk_lane(const TrkParams* params_dev, const TrkParams& params,
     }
 #undef GNSSHIP_LANE_F
 #undef GNSSHIP_LANE
-    if (plan) {
-        *plan = gnsship_trk_plan{};
-        plan->engine = GNSSHIP_TRK_ENGINE_LANES;
-        plan->format = fmt;
-        plan->n_taps = nt;
-        plan->data_prompt = data ? 1 : 0;
-        plan->lds_bytes = static_cast<int32_t>(lds);
-        plan->lane_waves = nw;
-    }
+    *plan = gnsship_trk_plan{};
+    plan->engine = GNSSHIP_TRK_ENGINE_LANES;
+    plan->format = r.fmt;
+    plan->n_taps = nt;
+    plan->data_prompt = data ? 1 : 0;
+    plan->lds_bytes = static_cast<int32_t>(lds);
+    plan->lane_waves = nw;
     return hipGetLastError();
 }
 

@@ -454,35 +454,33 @@ static size_t persist_lds(const TrkParams& p, int code_cap_floats, bool avx, int
 
 size_t trk_persist_lds_bytes(const TrkParams& p, int code_cap_floats, bool avx) { return persist_lds(p, code_cap_floats, avx, nullptr); }
 
-hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& params, TrkChannel* chans, int n_chans, const CodeDesc* codes,
-    int n_codes, int code_cap_floats, const void* samples, int fmt, uint64_t buf_first, int64_t buf_len, int max_rounds, gnsship_trk_epoch* rec,
-    gnsship_trk_dump_record* dump, gnsship_trk_corr_trace* trace, int* ran_count, bool avx, hipStream_t stream, gnsship_trk_plan* plan)
+hipError_t launch_trk_persist(const TrkRun& r, bool avx, gnsship_trk_plan* plan)
 {
     int ring_chunks = 0;  // the generic rotator's ring (0 for the AVX form)
-    const size_t lds = persist_lds(params, code_cap_floats, avx, &ring_chunks);
-    const bool data = params.jobs_per_channel > 1;
-    const bool glo = params.conf.system == GNSSHIP_SYS_GLO_L1CA || params.conf.system == GNSSHIP_SYS_GLO_L2CA;
-    if (glo && (avx || data || params.n_taps != 3)) return hipErrorInvalidValue;
+    const size_t lds = persist_lds(r.params, r.code_cap_floats, avx, &ring_chunks);
+    const bool data = r.params.jobs_per_channel > 1;
+    const bool glo = r.params.conf.system == GNSSHIP_SYS_GLO_L1CA || r.params.conf.system == GNSSHIP_SYS_GLO_L2CA;
+    if (glo && (avx || data || r.params.n_taps != 3)) return hipErrorInvalidValue;
     // more channels than CUs: the throughput variant (GNSSHIP_TRK_THRU=0/1 overrides, for A/B runs)
-    bool thru = n_chans > 256;
+    bool thru = r.n_chans > 256;
     if (const char* env = std::getenv("GNSSHIP_TRK_THRU")) thru = env[0] == '1';
-    const int nt = params.n_taps;
-    dim3 grid(n_chans), block(kPThreads);
+    const int nt = r.params.n_taps;
+    dim3 grid(r.n_chans), block(kPThreads);
 #define GNSSHIP_PERSIST(F, NTV, DV, AV)                                                                                                  \
     do {                                                                                                                                       \
         auto kfn = thru ? trk_persist_kernel<F, NTV, DV, AV, true> : trk_persist_kernel<F, NTV, DV, AV, false>;                             \
         hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)); \
         if (e0 != hipSuccess) return e0;                                                                                                       \
-        hipLaunchKernelGGL(kfn, grid, block, lds, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans,  \
-            code_cap_floats, ring_chunks, rec, dump, trace, ran_count);                                                                                     \
+        hipLaunchKernelGGL(kfn, grid, block, lds, r.stream, r.params_dev, r.chans, r.codes, r.n_codes, r.samples, r.buf_first, r.buf_len,      \
+            r.max_rounds, r.n_chans, r.code_cap_floats, ring_chunks, r.rec, r.dump, r.trace, r.ran_count);                                     \
     } while (0)
 #define GNSSHIP_PERSIST_GLO(F)                                                                                                                \
     do {                                                                                                                                      \
         auto kfn = thru ? trk_persist_kernel<F, 3, false, false, true, true> : trk_persist_kernel<F, 3, false, false, false, true>;               \
         hipError_t e0 = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds)); \
         if (e0 != hipSuccess) return e0;                                                                                                      \
-        hipLaunchKernelGGL(kfn, grid, block, lds, stream, params_dev, chans, codes, n_codes, samples, buf_first, buf_len, max_rounds, n_chans, \
-            code_cap_floats, ring_chunks, rec, dump, trace, ran_count);                                                                             \
+        hipLaunchKernelGGL(kfn, grid, block, lds, r.stream, r.params_dev, r.chans, r.codes, r.n_codes, r.samples, r.buf_first, r.buf_len,     \
+            r.max_rounds, r.n_chans, r.code_cap_floats, ring_chunks, r.rec, r.dump, r.trace, r.ran_count);                                    \
     } while (0)
 #define GNSSHIP_PERSIST_F(F)                                                      \
     do {                                                                          \
@@ -504,7 +502,7 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
             return hipErrorInvalidValue;                                          \
         }                                                                         \
     } while (0)
-    switch (fmt) {
+    switch (r.fmt) {
     case GNSSHIP_FMT_CF32: GNSSHIP_PERSIST_F(GNSSHIP_FMT_CF32); break;
     case GNSSHIP_FMT_CI16: GNSSHIP_PERSIST_F(GNSSHIP_FMT_CI16); break;
     case GNSSHIP_FMT_CI8: GNSSHIP_PERSIST_F(GNSSHIP_FMT_CI8); break;
@@ -513,16 +511,14 @@ hipError_t launch_trk_persist(const TrkParams* params_dev, const TrkParams& para
 #undef GNSSHIP_PERSIST_F
 #undef GNSSHIP_PERSIST_GLO
 #undef GNSSHIP_PERSIST
-    if (plan) {
-        *plan = gnsship_trk_plan{};
-        plan->engine = GNSSHIP_TRK_ENGINE_PERSIST;
-        plan->format = fmt;
-        plan->n_taps = nt;
-        plan->data_prompt = data ? 1 : 0;
-        plan->lds_bytes = static_cast<int32_t>(lds);
-        plan->thru = thru ? 1 : 0;
-        plan->avx = avx ? 1 : 0;
-    }
+    *plan = gnsship_trk_plan{};
+    plan->engine = GNSSHIP_TRK_ENGINE_PERSIST;
+    plan->format = r.fmt;
+    plan->n_taps = nt;
+    plan->data_prompt = data ? 1 : 0;
+    plan->lds_bytes = static_cast<int32_t>(lds);
+    plan->thru = thru ? 1 : 0;
+    plan->avx = avx ? 1 : 0;
     return hipGetLastError();
 }
 

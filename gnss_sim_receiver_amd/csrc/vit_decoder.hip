@@ -109,11 +109,8 @@ struct gnsship_vit {
     int32_t max_channels = 0;
     int32_t frame = 0;  // symbols per frame
     float* sections_dev = nullptr;
-    int32_t* channels_dev = nullptr;
-    uint8_t* negate_dev = nullptr;
-    float* sym_dev = nullptr;
-    uint8_t* bits_dev = nullptr;
-    int64_t frame_cap = 0, sym_cap = 0;
+    DevBuf channels_dev, negate_dev, bits_dev;  // per frame: int32_t, uint8_t, data_length × uint8_t
+    DevBuf sym_dev;                             // host symbols (float)
     std::vector<uint32_t> seen;  // per channel: the run that last named it
     uint32_t run_id = 0;
 };
@@ -123,9 +120,8 @@ extern "C" int gnsship_vit_destroy(gnsship_vit* v)
     if (!v) return GNSSHIP_E_INVAL;
     (void)hipSetDevice(v->ctx->device);
     (void)hipStreamSynchronize(v->ctx->stream);
-    void* ptrs[] = {v->sections_dev, v->channels_dev, v->negate_dev, v->sym_dev, v->bits_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    if (v->sections_dev) (void)hipFree(v->sections_dev);
+    for (DevBuf* b : {&v->channels_dev, &v->negate_dev, &v->bits_dev, &v->sym_dev}) release(*b);
     delete v;
     return GNSSHIP_OK;
 }
@@ -222,48 +218,28 @@ extern "C" int gnsship_vit_run(gnsship_vit* v, const float* symbols, int on_devi
     }
     if (int rc = set_device(ctx)) return rc;
     const int LL = v->conf.data_length;
+    const size_t nf = static_cast<size_t>(n_frames);
+    if (int rc = reserve(ctx, v->channels_dev, sizeof(int32_t) * nf, "gnsship_vit_run", "buffers")) return rc;
+    if (int rc = reserve(ctx, v->negate_dev, nf, "gnsship_vit_run", "buffers")) return rc;
+    if (int rc = reserve(ctx, v->bits_dev, nf * LL, "gnsship_vit_run", "buffers")) return rc;
     hipError_t e = hipSuccess;
-    if (n_frames > v->frame_cap) {
-        // the stream's earlier launches may still read the old buffers
-        e = hipStreamSynchronize(ctx->stream);
-        void* old[] = {v->channels_dev, v->negate_dev, v->bits_dev};
-        for (void* p : old)
-            if (p && e == hipSuccess) e = hipFree(p);
-        v->channels_dev = nullptr;
-        v->negate_dev = nullptr;
-        v->bits_dev = nullptr;
-        v->frame_cap = 0;
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&v->channels_dev), sizeof(int32_t) * static_cast<size_t>(n_frames));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&v->negate_dev), static_cast<size_t>(n_frames));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&v->bits_dev), static_cast<size_t>(n_frames) * LL);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_vit_run(buffers)");
-        v->frame_cap = n_frames;
-    }
     const float* src = symbols;
     if (!on_device) {
-        const int64_t n_sym = static_cast<int64_t>(n_frames) * v->frame;
-        if (n_sym > v->sym_cap) {
-            e = hipStreamSynchronize(ctx->stream);
-            if (v->sym_dev && e == hipSuccess) e = hipFree(v->sym_dev);
-            v->sym_dev = nullptr;
-            v->sym_cap = 0;
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&v->sym_dev), sizeof(float) * static_cast<size_t>(n_sym));
-            if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_vit_run(stage)");
-            v->sym_cap = n_sym;
-        }
-        e = hipMemcpyAsync(v->sym_dev, symbols, sizeof(float) * static_cast<size_t>(n_sym), hipMemcpyHostToDevice, ctx->stream);
+        const size_t bytes = sizeof(float) * nf * v->frame;
+        if (int rc = reserve(ctx, v->sym_dev, bytes, "gnsship_vit_run", "stage")) return rc;
+        e = hipMemcpyAsync(v->sym_dev.dev, symbols, bytes, hipMemcpyHostToDevice, ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_vit_run(upload)");
-        src = v->sym_dev;
+        src = v->sym_dev.as<float>();
     }
-    e = hipMemcpyAsync(v->channels_dev, channels, sizeof(int32_t) * static_cast<size_t>(n_frames), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && negate) e = hipMemcpyAsync(v->negate_dev, negate, static_cast<size_t>(n_frames), hipMemcpyHostToDevice, ctx->stream);
+    e = hipMemcpyAsync(v->channels_dev.dev, channels, sizeof(int32_t) * nf, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && negate) e = hipMemcpyAsync(v->negate_dev.dev, negate, nf, hipMemcpyHostToDevice, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_vit_run(upload)");
     VitArgs a = {};
     a.sym = src;
-    a.channels = v->channels_dev;
-    a.negate = negate ? v->negate_dev : nullptr;
+    a.channels = v->channels_dev.as<int32_t>();
+    a.negate = negate ? v->negate_dev.as<uint8_t>() : nullptr;
     a.sections = v->sections_dev;
-    a.bits = bits_dev ? static_cast<uint8_t*>(bits_dev) : v->bits_dev;
+    a.bits = bits_dev ? static_cast<uint8_t*>(bits_dev) : v->bits_dev.as<uint8_t>();
     a.n_frames = n_frames;
     a.steps = LL + kVitTail;
     a.data_length = LL;
