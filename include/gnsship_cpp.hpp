@@ -23,6 +23,7 @@
 #include <thread>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gnsship.h"
@@ -50,6 +51,14 @@ public:
     }
     gnsship_ctx* ctx() const { return ctx_; }
     std::mutex& mutex() { return mu_; }  // serialises calls that share the context stream
+    // One C call under the mutex: true when it returns GNSSHIP_OK.  Whoever must hold the lock over more than one call
+    // (a create and the error text of its failure, a sequence that must not be interleaved) keeps a guard of its own.
+    template <class Fn, class... A>
+    bool call(Fn fn, A&&... a)
+    {
+        std::lock_guard<std::mutex> lk(mu_);
+        return fn(std::forward<A>(a)...) == GNSSHIP_OK;
+    }
 
 private:
     explicit Device(int device)
@@ -100,9 +109,7 @@ public:
     // The reference borrows the pointers (:53-63); the device engine copies the code at this call.
     bool set_local_code_and_taps(int code_length_chips, const float* local_code_in, float* shifts_chips)
     {
-        if (!h_) return false;
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_corr_set_local_code_and_taps(h_, code_length_chips, local_code_in, shifts_chips) == GNSSHIP_OK;
+        return h_ && dev_->call(gnsship_corr_set_local_code_and_taps, h_, code_length_chips, local_code_in, shifts_chips);
     }
     bool set_input_output_vectors(std::complex<float>* corr_out, const std::complex<float>* sig_in)
     {
@@ -115,13 +122,9 @@ public:
     {
         if (!h_ || !out_ || !in_) return false;
         std::vector<float> tmp(2 * static_cast<size_t>(n_));
-        int rc;
-        {
-            std::lock_guard<std::mutex> lk(dev_->mutex());
-            rc = gnsship_corr_run(h_, in_, GNSSHIP_FMT_CF32, 0, rem_carrier_phase_in_rad, phase_step_rad, phase_rate_step_rad, rem_code_phase_chips,
-                code_phase_step_chips, code_phase_rate_step_chips, signal_length_samples, tmp.data());
-        }
-        if (rc != GNSSHIP_OK) return false;
+        if (!dev_->call(gnsship_corr_run, h_, in_, GNSSHIP_FMT_CF32, 0, rem_carrier_phase_in_rad, phase_step_rad, phase_rate_step_rad,
+                rem_code_phase_chips, code_phase_step_chips, code_phase_rate_step_chips, signal_length_samples, tmp.data()))
+            return false;
         for (int t = 0; t < n_; t++) out_[t] = std::complex<float>(tmp[2 * t], tmp[2 * t + 1]);
         return true;
     }
@@ -133,8 +136,8 @@ public:
     }
     bool free()
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        free_locked();
+        if (h_) dev_->call(gnsship_corr_destroy, h_);
+        h_ = nullptr;
         return true;
     }
     const char* last_error() const { return gnsship_last_error(dev_->ctx()); }
@@ -236,9 +239,7 @@ public:
     // n_in gr_complex samples (a multiple of decimation()) -> n_in / decimation() into out
     bool work(const std::complex<float>* in, int64_t n_in, std::complex<float>* out)
     {
-        if (!h_) return false;
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_acq_resampler_run(h_, in, GNSSHIP_FMT_CF32, 0, n_in, reinterpret_cast<float*>(out), nullptr, nullptr) == GNSSHIP_OK;
+        return h_ && dev_->call(gnsship_acq_resampler_run, h_, in, GNSSHIP_FMT_CF32, 0, n_in, reinterpret_cast<float*>(out), nullptr, nullptr);
     }
 
 private:
@@ -371,9 +372,7 @@ public:
         std::vector<float*> ho(conf_.size(), nullptr);
         if (host_out)
             for (size_t b = 0; b < conf_.size(); b++) ho[b] = reinterpret_cast<float*>(host_out[b]);
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_cond_run(h_, in, fmt, in_on_device ? 1 : 0, n_in, dev_dst, host_out ? ho.data() : nullptr, dev_out_.data(), n_out_.data()) ==
-               GNSSHIP_OK;
+        return dev_->call(gnsship_cond_run, h_, in, fmt, in_on_device ? 1 : 0, n_in, dev_dst, host_out ? ho.data() : nullptr, dev_out_.data(), n_out_.data());
     }
     // the same with the items of the configuration's input_item_type (gr_complex / float / short / byte)
     bool work_items(const void* in, bool in_on_device, int64_t n_in, void* const* dev_dst = nullptr, std::complex<float>* const* host_out = nullptr)
@@ -392,8 +391,7 @@ public:
     int64_t n_out(int band = 0) const { return n_out_[static_cast<size_t>(band)]; }
     bool reset(uint64_t first_sample = 0)
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_cond_reset(h_, first_sample) == GNSSHIP_OK;
+        return dev_->call(gnsship_cond_reset, h_, first_sample);
     }
     uint64_t samples_in() const
     {
@@ -469,21 +467,18 @@ public:
     // own, valid until the next work()); without host_out the call is asynchronous on the context stream.
     virtual bool work(const std::complex<float>* in, bool in_on_device, int64_t n_in, void* dev_dst = nullptr, std::complex<float>* host_out = nullptr)
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_mit_run(h_, in, in_on_device ? 1 : 0, n_in, dev_dst, reinterpret_cast<float*>(host_out), &dev_out_, &n_out_) == GNSSHIP_OK;
+        return dev_->call(gnsship_mit_run, h_, in, in_on_device ? 1 : 0, n_in, dev_dst, reinterpret_cast<float*>(host_out), &dev_out_, &n_out_);
     }
     void* dev_out() const { return dev_out_; }
     int64_t n_out() const { return n_out_; }
     virtual bool reset()
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_mit_reset(h_) == GNSSHIP_OK;
+        return dev_->call(gnsship_mit_reset, h_);
     }
     gnsship_mit_state state() const
     {
         gnsship_mit_state st{};
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        gnsship_mit_state_get(h_, &st);
+        dev_->call(gnsship_mit_state_get, h_, &st);
         return st;
     }
     std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
@@ -596,8 +591,7 @@ public:
     std::array<float, 64> section() const
     {
         std::array<float, 64> s{};
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        gnsship_vit_state_get(h_, 0, s.data());
+        dev_->call(gnsship_vit_state_get, h_, 0, s.data());
         return s;
     }
 
@@ -646,20 +640,17 @@ public:
         const size_t n = channels.size();
         if (symbols.size() != n * static_cast<size_t>(frame_symbols()) || (!negate.empty() && negate.size() != n)) return false;
         bits.resize(n * static_cast<size_t>(conf_.data_length));
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_vit_run(h_, symbols.data(), 0, static_cast<int32_t>(n), channels.data(), negate.empty() ? nullptr : negate.data(), bits.data(),
-                   nullptr) == GNSSHIP_OK;
+        return dev_->call(gnsship_vit_run, h_, symbols.data(), 0, static_cast<int32_t>(n), channels.data(), negate.empty() ? nullptr : negate.data(),
+            bits.data(), nullptr);
     }
     bool reset_channel(int32_t channel)
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_vit_reset_channel(h_, channel) == GNSSHIP_OK;
+        return dev_->call(gnsship_vit_reset_channel, h_, channel);
     }
     std::array<float, 64> section(int32_t channel) const
     {
         std::array<float, 64> s{};
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        gnsship_vit_state_get(h_, channel, s.data());
+        dev_->call(gnsship_vit_state_get, h_, channel, s.data());
         return s;
     }
     std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
@@ -800,10 +791,7 @@ public:
     {
         if (fdma_channels_ < 1) return false;
         std::vector<gnsship_acq_result> r(static_cast<size_t>(fdma_channels_));
-        {
-            std::lock_guard<std::mutex> lk(dev_->mutex());
-            if (gnsship_acq_run_fdma(h_, in, GNSSHIP_FMT_CF32, 0, 0, r.data(), nullptr) != GNSSHIP_OK) return false;
-        }
+        if (!dev_->call(gnsship_acq_run_fdma, h_, in, GNSSHIP_FMT_CF32, 0, 0, r.data(), nullptr)) return false;
         out.assign(r.size(), Acq_Outcome{});
         for (size_t g = 0; g < r.size(); g++) {
             out[g].Acq_delay_samples = r[g].acq_delay_samples - static_cast<double>(resampler_latency_);
@@ -819,8 +807,7 @@ public:
     // set_local_code (:175-208): FFT of the zero-padded sampled code + conjugate, on the device
     bool set_local_code(const std::complex<float>* code)
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_acq_set_local_code(h_, 0, reinterpret_cast<const float*>(code)) == GNSSHIP_OK;
+        return dev_->call(gnsship_acq_set_local_code, h_, 0, reinterpret_cast<const float*>(code));
     }
     // init (:248-292): rebuild the Doppler wipeoff grid for the current max/step/center
     bool init()
@@ -853,10 +840,7 @@ public:
     bool acquisition_core(const std::complex<float>* in, uint64_t samp_count, Acq_Outcome& out)
     {
         gnsship_acq_result r{};
-        {
-            std::lock_guard<std::mutex> lk(dev_->mutex());
-            if (gnsship_acq_run(h_, in, GNSSHIP_FMT_CF32, 0, 1, &r, nullptr) != GNSSHIP_OK) return false;
-        }
+        if (!dev_->call(gnsship_acq_run, h_, in, GNSSHIP_FMT_CF32, 0, 1, &r, nullptr)) return false;
         r.doppler_hz -= doppler_bias_;  // the grid's centre carried the FDMA bias; Acq_doppler_hz does not
         out.Acq_delay_samples = r.acq_delay_samples - static_cast<double>(resampler_latency_);  // :686-687
         out.Acq_doppler_hz = static_cast<double>(r.doppler_hz);
@@ -869,15 +853,14 @@ public:
         const bool hit = r.test_statistic > threshold_;
         out.positive = hit && (!conf_.make_2_steps || step_two_);
         if (conf_.make_2_steps) {
-            std::lock_guard<std::mutex> lk(dev_->mutex());
             if (hit && !step_two_) {
-                if (gnsship_acq_set_grid_step2(h_, static_cast<float>(r.doppler_hz), conf_.doppler_step2,
-                        static_cast<int>(conf_.num_doppler_bins_step2), r.input_power) != GNSSHIP_OK)
+                if (!dev_->call(gnsship_acq_set_grid_step2, h_, static_cast<float>(r.doppler_hz), conf_.doppler_step2,
+                        static_cast<int>(conf_.num_doppler_bins_step2), r.input_power))
                     return false;
                 step_two_ = true;
             } else if (step_two_) {
                 const int step = doppler_step_ ? static_cast<int>(doppler_step_) : static_cast<int>(conf_.doppler_step);
-                if (gnsship_acq_set_grid(h_, conf_.doppler_max, step, doppler_center_ + doppler_bias_) != GNSSHIP_OK) return false;
+                if (!dev_->call(gnsship_acq_set_grid, h_, conf_.doppler_max, step, doppler_center_ + doppler_bias_)) return false;
                 step_two_ = false;
             }
         }
@@ -975,10 +958,7 @@ private:
     {
         counter_++;
         gnsship_acq_result r{};
-        {
-            std::lock_guard<std::mutex> lk(dev_->mutex());
-            if (gnsship_acq_run(h_, in, GNSSHIP_FMT_CF32, 0, 1, &r, nullptr) != GNSSHIP_OK) return;
-        }
+        if (!dev_->call(gnsship_acq_run, h_, in, GNSSHIP_FMT_CF32, 0, 1, &r, nullptr)) return;
         r.doppler_hz -= doppler_bias_;  // the grid's centre carried the FDMA bias; Acq_doppler_hz does not
         synchro_.Acq_delay_samples = r.acq_delay_samples - static_cast<double>(resampler_latency_);
         synchro_.Acq_doppler_hz = static_cast<double>(r.doppler_hz);
@@ -992,8 +972,7 @@ private:
         const bool hit = r.test_statistic > threshold_;
         auto to_step_one = [&]() {
             const int step = doppler_step_ ? static_cast<int>(doppler_step_) : static_cast<int>(conf_.doppler_step);
-            std::lock_guard<std::mutex> lk(dev_->mutex());
-            gnsship_acq_set_grid(h_, conf_.doppler_max, step, doppler_center_ + doppler_bias_);
+            dev_->call(gnsship_acq_set_grid, h_, conf_.doppler_max, step, doppler_center_ + doppler_bias_);
             step_two_ = false;
         };
         auto on_hit = [&]() {
@@ -1004,9 +983,8 @@ private:
                     to_step_one();
                     fsm_state_ = 0;
                 } else {
-                    std::lock_guard<std::mutex> lk(dev_->mutex());
-                    gnsship_acq_set_grid_step2(h_, static_cast<float>(r.doppler_hz), conf_.doppler_step2, static_cast<int>(conf_.num_doppler_bins_step2),
-                        r.input_power);
+                    dev_->call(gnsship_acq_set_grid_step2, h_, static_cast<float>(r.doppler_hz), conf_.doppler_step2,
+                        static_cast<int>(conf_.num_doppler_bins_step2), r.input_power);
                     step_two_ = true;
                     counter_ = 0;
                     fsm_state_ = 0;
@@ -1048,10 +1026,7 @@ private:
             }
         }
         if (counter_ == conf_.max_dwells || positive_acq || conf_.bit_transition_flag) counter_ = 0;
-        if (counter_ == 0) {
-            std::lock_guard<std::mutex> lk(dev_->mutex());
-            gnsship_acq_reset_dwells(h_);
-        }
+        if (counter_ == 0) dev_->call(gnsship_acq_reset_dwells, h_);
     }
 
     std::mutex set_lock_;
@@ -1079,6 +1054,22 @@ private:
     int fdma_channels_ = 0;      // > 0: the FDMA sweep's grid is set (init_fdma)
     uint32_t resampler_latency_ = 0;
 };
+
+// set_local_code of the PCPS acquisition adapters: one sampled code of code_length = floor(fs / codes_per_second) samples
+// from gen(dest, fs) (negative: no such code, the result is empty), copied num_codes times into vector_length =
+// floor(sampled_ms · samples_per_ms) samples, doubled with bit_transition_flag: the rest stays zero.  fs is the rate the
+// acquisition runs at, resampled_fs when set.  The *_acquisition_code functions below are this with their signal's constants.
+template <class Gen>
+std::vector<std::complex<float>> pcps_acquisition_code(const Acq_Conf& conf, double codes_per_second, uint32_t num_codes, Gen gen)
+{
+    const int64_t fs = conf.resampled_fs ? conf.resampled_fs : conf.fs_in;
+    const auto code_length = static_cast<size_t>(std::floor(static_cast<double>(fs) / codes_per_second));
+    const auto vector_length = static_cast<size_t>(std::floor(conf.sampled_ms * (static_cast<float>(fs) * 0.001F)) * (conf.bit_transition_flag ? 2.0 : 1.0));
+    std::vector<std::complex<float>> one(code_length), out(std::max(vector_length, code_length * num_codes));
+    if (gen(one.data(), static_cast<int32_t>(fs)) < 0) return {};
+    for (uint32_t i = 0; i < num_codes; i++) std::copy(one.begin(), one.end(), out.begin() + static_cast<size_t>(i) * code_length);
+    return out;
+}
 
 // ---- GPS L5 (gps_l5_signal_replica.h, GPS_L5.h:32-46, gps_l5i_pcps_acquisition.cc:49-69, :151-170) ----
 constexpr double GPS_L5_FREQ_HZ = 1176.45e6;
@@ -1114,13 +1105,8 @@ inline Acq_Conf gps_l5i_acq_conf(Acq_Conf conf)
 // bit_transition_flag: the rest stays zero).  Empty: PRN outside 1..32.
 inline std::vector<std::complex<float>> gps_l5i_acquisition_code(uint32_t prn, const Acq_Conf& conf)
 {
-    const int64_t fs = conf.resampled_fs ? conf.resampled_fs : conf.fs_in;
-    const auto code_length = static_cast<size_t>(std::floor(static_cast<double>(fs) / (GPS_L5I_CODE_RATE_CPS / GPS_L5I_CODE_LENGTH_CHIPS)));
-    const auto vector_length = static_cast<size_t>(std::floor(conf.sampled_ms * (static_cast<float>(fs) * 0.001F)) * (conf.bit_transition_flag ? 2.0 : 1.0));
-    std::vector<std::complex<float>> one(code_length), out(std::max(vector_length, code_length * conf.sampled_ms));
-    if (gps_l5i_code_gen_complex_sampled(one.data(), prn, static_cast<int32_t>(fs)) < 0) return {};
-    for (uint32_t i = 0; i < conf.sampled_ms; i++) std::copy(one.begin(), one.end(), out.begin() + static_cast<size_t>(i) * code_length);
-    return out;
+    return pcps_acquisition_code(conf, GPS_L5I_CODE_RATE_CPS / GPS_L5I_CODE_LENGTH_CHIPS, conf.sampled_ms,
+        [prn](std::complex<float>* dest, int32_t fs) { return gps_l5i_code_gen_complex_sampled(dest, prn, fs); });
 }
 
 // ---- BeiDou B3I (beidou_b3i_signal_replica.h, Beidou_B3I.h, beidou_b3i_pcps_acquisition.cc:46-63) and GPS L2C,
@@ -1174,17 +1160,10 @@ inline Acq_Conf gps_l2_m_acq_conf(Acq_Conf conf)
 // samples (doubled with bit_transition_flag: the rest stays zero).  Empty: PRN out of range.
 inline std::vector<std::complex<float>> acquisition_code_10230(uint32_t prn, const Acq_Conf& conf, bool l2c)
 {
-    const int64_t fs = conf.resampled_fs ? conf.resampled_fs : conf.fs_in;
     const double rate = l2c ? GPS_L2_M_CODE_RATE_CPS : BEIDOU_B3I_CODE_RATE_CPS;
-    const auto code_length = static_cast<size_t>(std::floor(static_cast<double>(fs) / (rate / 10230.0)));
-    const auto vector_length = static_cast<size_t>(std::floor(conf.sampled_ms * (static_cast<float>(fs) * 0.001F)) * (conf.bit_transition_flag ? 2.0 : 1.0));
-    const uint32_t num_codes = conf.sampled_ms / (l2c ? 20U : 1U);
-    std::vector<std::complex<float>> one(code_length), out(std::max(vector_length, code_length * num_codes));
-    const int rc = l2c ? gps_l2c_m_code_gen_complex_sampled(one.data(), prn, static_cast<int32_t>(fs))
-                       : beidou_b3i_code_gen_complex_sampled(one.data(), prn, static_cast<int32_t>(fs), 0);
-    if (rc < 0) return {};
-    for (uint32_t i = 0; i < num_codes; i++) std::copy(one.begin(), one.end(), out.begin() + static_cast<size_t>(i) * code_length);
-    return out;
+    return pcps_acquisition_code(conf, rate / 10230.0, conf.sampled_ms / (l2c ? 20U : 1U), [prn, l2c](std::complex<float>* dest, int32_t fs) {
+        return l2c ? gps_l2c_m_code_gen_complex_sampled(dest, prn, fs) : beidou_b3i_code_gen_complex_sampled(dest, prn, fs, 0);
+    });
 }
 inline std::vector<std::complex<float>> beidou_b3i_acquisition_code(uint32_t prn, const Acq_Conf& conf) { return acquisition_code_10230(prn, conf, false); }
 inline std::vector<std::complex<float>> gps_l2c_m_acquisition_code(uint32_t prn, const Acq_Conf& conf) { return acquisition_code_10230(prn, conf, true); }
@@ -1233,13 +1212,8 @@ inline Acq_Conf glonass_l2_ca_acq_conf(Acq_Conf conf) { return glonass_l1_ca_acq
 // times into vector_length = floor(sampled_ms · samples_per_ms) samples (doubled with bit_transition_flag: the rest zero).
 inline std::vector<std::complex<float>> glonass_l1_ca_acquisition_code(const Acq_Conf& conf)
 {
-    const int64_t fs = conf.resampled_fs ? conf.resampled_fs : conf.fs_in;
-    const auto code_length = static_cast<size_t>(std::floor(static_cast<double>(fs) / (GLONASS_L1_CA_CODE_RATE_CPS / GLONASS_L1_CA_CODE_LENGTH_CHIPS)));
-    const auto vector_length = static_cast<size_t>(std::floor(conf.sampled_ms * (static_cast<float>(fs) * 0.001F)) * (conf.bit_transition_flag ? 2.0 : 1.0));
-    std::vector<std::complex<float>> one(code_length), out(std::max(vector_length, code_length * conf.sampled_ms));
-    if (glonass_l1_ca_code_gen_complex_sampled(one.data(), static_cast<int32_t>(fs), 0) < 0) return {};
-    for (uint32_t i = 0; i < conf.sampled_ms; i++) std::copy(one.begin(), one.end(), out.begin() + static_cast<size_t>(i) * code_length);
-    return out;
+    return pcps_acquisition_code(conf, GLONASS_L1_CA_CODE_RATE_CPS / GLONASS_L1_CA_CODE_LENGTH_CHIPS, conf.sampled_ms,
+        [](std::complex<float>* dest, int32_t fs) { return glonass_l1_ca_code_gen_complex_sampled(dest, fs, 0); });
 }
 inline std::vector<std::complex<float>> glonass_l2_ca_acquisition_code(const Acq_Conf& conf) { return glonass_l1_ca_acquisition_code(conf); }
 
@@ -1304,16 +1278,11 @@ inline Acq_Conf galileo_e5_acq_conf(Acq_Conf conf)
 inline std::vector<std::complex<float>> galileo_e5_acquisition_code(uint32_t prn, const Acq_Conf& conf, bool band_b, bool acquire_pilot = false,
     bool acquire_iq = false)
 {
-    const int64_t fs = conf.resampled_fs ? conf.resampled_fs : conf.fs_in;
-    const auto code_length = static_cast<size_t>(std::floor(static_cast<double>(fs) / (GALILEO_E5A_CODE_CHIP_RATE_CPS / GALILEO_E5A_CODE_LENGTH_CHIPS)));
-    const auto vector_length = static_cast<size_t>(std::floor(conf.sampled_ms * (static_cast<float>(fs) * 0.001F)) * (conf.bit_transition_flag ? 2.0 : 1.0));
     const std::array<char, 3> id = {{band_b ? '7' : '5', acquire_iq ? 'X' : acquire_pilot ? 'Q' : 'I', '\0'}};
-    std::vector<std::complex<float>> one(code_length), out(std::max(vector_length, code_length * conf.sampled_ms));
-    const int rc = band_b ? galileo_e5_b_code_gen_complex_sampled(one.data(), prn, id, static_cast<int32_t>(fs), 0)
-                          : galileo_e5_a_code_gen_complex_sampled(one.data(), prn, id, static_cast<int32_t>(fs), 0);
-    if (rc < 0) return {};
-    for (uint32_t i = 0; i < conf.sampled_ms; i++) std::copy(one.begin(), one.end(), out.begin() + static_cast<size_t>(i) * code_length);
-    return out;
+    return pcps_acquisition_code(conf, GALILEO_E5A_CODE_CHIP_RATE_CPS / GALILEO_E5A_CODE_LENGTH_CHIPS, conf.sampled_ms,
+        [prn, band_b, &id](std::complex<float>* dest, int32_t fs) {
+            return band_b ? galileo_e5_b_code_gen_complex_sampled(dest, prn, id, fs, 0) : galileo_e5_a_code_gen_complex_sampled(dest, prn, id, fs, 0);
+        });
 }
 
 // Mirror of Dll_Pll_Conf (src/algorithms/tracking/libs/dll_pll_conf.h:33-80): same field names and
@@ -1480,15 +1449,13 @@ public:
     }
     bool stop_tracking(int channel)
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_trk_stop(h_, channel) == GNSSHIP_OK;
+        return dev_->call(gnsship_trk_stop, h_, channel);
     }
     // msg_handler_telemetry_to_trk (dll_pll_veml_tracking.cc:617-640): the telemetry decoder's
     // fault message (event 1) forces loss of lock at the channel's next lock check
     bool msg_handler_telemetry_to_trk(int channel, int tlm_event)
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_trk_telemetry_event(h_, channel, tlm_event) == GNSSHIP_OK;
+        return dev_->call(gnsship_trk_telemetry_event, h_, channel, tlm_event);
     }
     // general_work for every channel over gr_complex samples [first_sample, first_sample + n): up to
     // max_epochs epochs per channel; records (max_epochs × max_channels, optional) as gnsship_trk_epoch.
@@ -1496,9 +1463,7 @@ public:
         bool in_on_device = false)
     {
         int done = 0;
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        if (gnsship_trk_run(h_, in, GNSSHIP_FMT_CF32, in_on_device ? 1 : 0, first_sample, n, max_epochs, records, &done) != GNSSHIP_OK) return -1;
-        return done;
+        return dev_->call(gnsship_trk_run, h_, in, GNSSHIP_FMT_CF32, in_on_device ? 1 : 0, first_sample, n, max_epochs, records, &done) ? done : -1;
     }
     // work() with Dll_Pll_Conf::dump on: dumps (max_epochs × max_channels) receives the log_data
     // records (:1376-1466) of the epochs whose record has flags & 16.
@@ -1506,11 +1471,7 @@ public:
         gnsship_trk_dump_record* dumps, bool in_on_device = false)
     {
         int done = 0;
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        if (gnsship_trk_run_dump(h_, in, GNSSHIP_FMT_CF32, in_on_device ? 1 : 0, first_sample, n, max_epochs, records, dumps, &done) !=
-            GNSSHIP_OK)
-            return -1;
-        return done;
+        return dev_->call(gnsship_trk_run_dump, h_, in, GNSSHIP_FMT_CF32, in_on_device ? 1 : 0, first_sample, n, max_epochs, records, dumps, &done) ? done : -1;
     }
     // Append channel `channel`'s records to its dump file (<dump_filename><channel>.dat, as the
     // block's d_dump_file): the binary layout tracking_dump_reader reads.
@@ -1540,8 +1501,7 @@ public:
     int state(int channel, uint64_t* next_sample = nullptr)
     {
         int st = -1;
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        gnsship_trk_channel_state(h_, channel, &st, next_sample);
+        dev_->call(gnsship_trk_channel_state, h_, channel, &st, next_sample);
         return st;
     }
     const char* last_error() const { return gnsship_last_error(dev_->ctx()); }
@@ -1561,608 +1521,377 @@ private:
     bool glonass_ = false;  // the GLONASS block: its dump file has the 88-byte record
 };
 
-// The frame types of galileo_telemetry_decoder_gs (:167-213) as gnsship_tlm_conf: max_rounds is the most symbols per
-// channel one work_* call may carry.
-inline gnsship_tlm_conf galileo_tlm_conf(int32_t frame_type, int32_t max_rounds, int mode)
-{
-    return gnsship_tlm_conf{frame_type, mode, max_rounds, 0};
-}
-inline gnsship_tlm_conf galileo_inav_tlm_conf(int32_t max_rounds, int mode = GNSSHIP_VIT_MODE_REFERENCE)
-{
-    return galileo_tlm_conf(GNSSHIP_TLM_INAV, max_rounds, mode);
-}
-inline gnsship_tlm_conf galileo_fnav_tlm_conf(int32_t max_rounds, int mode = GNSSHIP_VIT_MODE_REFERENCE)
-{
-    return galileo_tlm_conf(GNSSHIP_TLM_FNAV, max_rounds, mode);
-}
-inline gnsship_tlm_conf galileo_cnav_tlm_conf(int32_t max_rounds, int mode = GNSSHIP_VIT_MODE_REFERENCE)
-{
-    return galileo_tlm_conf(GNSSHIP_TLM_CNAV, max_rounds, mode);
-}
+// ---- The telemetry decoders: five families of blocks (gnsship_tlm_*, _lnav_*, _cnav_*, _dnav_*, _gnav_* of include/gnsship.h),
+// each for many channels at once, one block object per channel: symbols or tracking records in, the family's records out. ----
 
-// The frame handling of galileo_telemetry_decoder_gs::general_work (:872-1094) for many channels at once, one block
-// object per channel (include/gnsship.h, gnsship_tlm_*): symbols or tracking records in, CRC-checked page parts and
-// check_tlm_separation faults out.  After a work_* call, pages() / bits() / counts() / faults() hold that call's outputs.
-class Galileo_Telemetry_Decoder_Hip {
+// What the families share, over a family's types and the C functions every family has (the *_Tlm_Api structs below): the
+// handle (created and destroyed here, not copyable; deleting a signal-named block through its family class is fine), the
+// host vectors a work_* call's outputs land in, sized for the most the C contract lets one run write, state() and
+// last_error().  For the family classes: call() and, for the families with a TOW stream, run() / run_trk().
+template <class Api>
+class Telemetry_Decoder_Hip {
 public:
-    Galileo_Telemetry_Decoder_Hip(const gnsship_tlm_conf& c, int32_t max_channels, int device = 0)
-        : dev_(Device::get(device)), conf_(c), channels_(max_channels)
+    virtual ~Telemetry_Decoder_Hip()
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        if (gnsship_tlm_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
-            throw std::invalid_argument(std::string("gnsship_tlm_create: ") + gnsship_last_error(dev_->ctx()));
-        gnsship_tlm_outputs_device(h_, nullptr, nullptr, nullptr, nullptr, &pages_per_run_);
-        data_length_ = c.frame_type == GNSSHIP_TLM_INAV ? 114 : c.frame_type == GNSSHIP_TLM_FNAV ? 238 : 486;
-        const size_t slots = static_cast<size_t>(max_channels) * pages_per_run_;
-        pages_.resize(slots);
-        bits_.resize(slots * data_length_);
-        counts_.resize(static_cast<size_t>(max_channels));
-        faults_.resize(static_cast<size_t>(max_channels));
+        if (h_) Api::destroy(h_);
     }
-    ~Galileo_Telemetry_Decoder_Hip()
-    {
-        if (h_) gnsship_tlm_destroy(h_);
-    }
-    Galileo_Telemetry_Decoder_Hip(const Galileo_Telemetry_Decoder_Hip&) = delete;
-    Galileo_Telemetry_Decoder_Hip& operator=(const Galileo_Telemetry_Decoder_Hip&) = delete;
-    int32_t data_length() const { return data_length_; }
-    int32_t pages_per_run() const { return pages_per_run_; }
-    // the block's set_satellite() (:771-789) and reset() (:792-820) on one channel; new_channel: a new block object
-    bool set_satellite(int32_t channel)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_tlm_set_satellite(h_, channel) == GNSSHIP_OK;
-    }
-    bool reset(int32_t channel)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_tlm_reset_channel(h_, channel) == GNSSHIP_OK;
-    }
-    bool new_channel(int32_t channel)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_tlm_new_channel(h_, channel) == GNSSHIP_OK;
-    }
-    // symbols[r · max_channels + c], r < n_rounds; valid: the same shape, or null for all valid
-    bool work_symbols(const float* symbols, const uint8_t* valid, int32_t n_rounds, bool on_device = false)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_tlm_run_symbols(h_, symbols, valid, on_device ? 1 : 0, n_rounds, pages_.data(), bits_.data(), counts_.data(), faults_.data()) ==
-               GNSSHIP_OK;
-    }
-    // tracking records of that shape: an entry is a symbol when flags & 1, the symbol is (float)prompt_i
-    bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_tlm_run_records(h_, records, on_device ? 1 : 0, n_rounds, pages_.data(), bits_.data(), counts_.data(), faults_.data()) ==
-               GNSSHIP_OK;
-    }
-    // the records the tracker's last work() left on the device, in place
-    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_tlm_run_trk(h_, trk.handle(), pages_.data(), bits_.data(), counts_.data(), faults_.data()) == GNSSHIP_OK;
-    }
-    // the last work_* call's outputs: part k < counts()[c] of channel c is pages()[c · pages_per_run() + k], its bits
-    // (bytes of 0 / 1) start at bits()[(c · pages_per_run() + k) · data_length()]
-    const std::vector<gnsship_tlm_page>& pages() const { return pages_; }
-    const std::vector<uint8_t>& bits() const { return bits_; }
+    Telemetry_Decoder_Hip(const Telemetry_Decoder_Hip&) = delete;
+    Telemetry_Decoder_Hip& operator=(const Telemetry_Decoder_Hip&) = delete;
+    static constexpr bool has_faults = Api::has_faults;  // the family raises faults: it has a public faults()
+    const typename Api::Conf& conf() const { return conf_; }
+    // the last work_* call's outputs: record k < counts()[c] of channel c is records()[c · per_run() + k] (each family has
+    // its own names for the two); entry (r, c), r < rounds(), of a TOW stream is tow_ms()[r · max_channels + c] and
+    // sflags()[r · max_channels + c] (Galileo has no stream: empty).  rounds(): n_rounds of work_symbols / work_records;
+    // for work_trk 0, then the rounds of the tracker's run as the library reports them
+    const std::vector<typename Api::Record>& records() const { return records_; }
+    int32_t per_run() const { return per_run_; }
     const std::vector<int32_t>& counts() const { return counts_; }
-    const std::vector<uint8_t>& faults() const { return faults_; }
-    gnsship_tlm_state state(int32_t channel) const
-    {
-        gnsship_tlm_state st{};
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        gnsship_tlm_state_get(h_, channel, &st);
-        return st;
-    }
-    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
-
-private:
-    std::shared_ptr<Device> dev_;
-    gnsship_tlm_conf conf_;
-    gnsship_tlm* h_ = nullptr;
-    int32_t channels_ = 0, pages_per_run_ = 0, data_length_ = 0;
-    std::vector<gnsship_tlm_page> pages_;
-    std::vector<uint8_t> bits_;
-    std::vector<int32_t> counts_;
-    std::vector<uint8_t> faults_;
-};
-
-// gps_l1_ca_telemetry_decoder_gs as gnsship_lnav_conf: max_rounds is the most entries per channel one work_* call may carry.
-inline gnsship_lnav_conf gps_l1_ca_tlm_conf(int32_t max_rounds)
-{
-    return gnsship_lnav_conf{max_rounds, 0};
-}
-
-// gps_l1_ca_telemetry_decoder_gs up to the time of week for many channels at once, one block object per channel
-// (include/gnsship.h, gnsship_lnav_*): symbols or tracking records in; subframes, the TOW stamp of every entry and
-// check_tlm_separation faults out.  After a work_* call, subframes() / counts() / faults() / tow_ms() / sflags() hold that
-// call's outputs.
-class Gps_L1_Ca_Telemetry_Decoder_Hip {
-public:
-    Gps_L1_Ca_Telemetry_Decoder_Hip(const gnsship_lnav_conf& c, int32_t max_channels, int device = 0)
-        : dev_(Device::get(device)), conf_(c), channels_(max_channels)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        if (gnsship_lnav_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
-            throw std::invalid_argument(std::string("gnsship_lnav_create: ") + gnsship_last_error(dev_->ctx()));
-        gnsship_lnav_outputs_device(h_, nullptr, nullptr, nullptr, nullptr, nullptr, &subframes_per_run_);
-        const size_t nc = static_cast<size_t>(max_channels);
-        subframes_.resize(nc * subframes_per_run_);
-        counts_.resize(nc);
-        faults_.resize(nc);
-        tow_ms_.resize(nc * c.max_rounds);
-        sflags_.resize(nc * c.max_rounds);
-    }
-    ~Gps_L1_Ca_Telemetry_Decoder_Hip()
-    {
-        if (h_) gnsship_lnav_destroy(h_);
-    }
-    Gps_L1_Ca_Telemetry_Decoder_Hip(const Gps_L1_Ca_Telemetry_Decoder_Hip&) = delete;
-    Gps_L1_Ca_Telemetry_Decoder_Hip& operator=(const Gps_L1_Ca_Telemetry_Decoder_Hip&) = delete;
-    int32_t subframes_per_run() const { return subframes_per_run_; }
-    // the block's set_satellite() (:217-224) and reset() (:436-445) on one channel; new_channel: a new block object
-    bool set_satellite(int32_t channel)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_lnav_set_satellite(h_, channel) == GNSSHIP_OK;
-    }
-    bool reset(int32_t channel)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_lnav_reset_channel(h_, channel) == GNSSHIP_OK;
-    }
-    bool new_channel(int32_t channel)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_lnav_new_channel(h_, channel) == GNSSHIP_OK;
-    }
-    // symbols[r · max_channels + c], r < n_rounds; valid, flags180: the same shape, or null for all valid / all false
-    bool work_symbols(const float* symbols, const uint8_t* valid, const uint8_t* flags180, int32_t n_rounds, bool on_device = false)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = n_rounds;
-        return gnsship_lnav_run_symbols(h_, symbols, valid, flags180, on_device ? 1 : 0, n_rounds, subframes_.data(), counts_.data(), faults_.data(),
-                   tow_ms_.data(), sflags_.data()) == GNSSHIP_OK;
-    }
-    // tracking records of that shape: a symbol when flags & 1, the symbol is (float)prompt_i, the 180° input flags & 4
-    bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = n_rounds;
-        return gnsship_lnav_run_records(h_, records, on_device ? 1 : 0, n_rounds, subframes_.data(), counts_.data(), faults_.data(), tow_ms_.data(),
-                   sflags_.data()) == GNSSHIP_OK;
-    }
-    // the records the tracker's last work() left on the device, in place
-    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = 0;
-        return gnsship_lnav_run_trk(h_, trk.handle(), subframes_.data(), counts_.data(), faults_.data(), tow_ms_.data(), sflags_.data(), &rounds_) ==
-               GNSSHIP_OK;
-    }
-    // the last work_* call's outputs: subframe k < counts()[c] of channel c is subframes()[c · subframes_per_run() + k];
-    // entry (r, c), r < rounds(), is tow_ms()[r · max_channels + c] and sflags()[r · max_channels + c]
-    const std::vector<gnsship_lnav_subframe>& subframes() const { return subframes_; }
-    const std::vector<int32_t>& counts() const { return counts_; }
-    const std::vector<uint8_t>& faults() const { return faults_; }
     const std::vector<uint32_t>& tow_ms() const { return tow_ms_; }
     const std::vector<uint8_t>& sflags() const { return sflags_; }
     int32_t rounds() const { return rounds_; }
-    gnsship_lnav_state state(int32_t channel) const
+    typename Api::State state(int32_t channel) const
     {
-        gnsship_lnav_state st{};
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        gnsship_lnav_state_get(h_, channel, &st);
+        typename Api::State st{};
+        call(Api::state_get, channel, &st);
         return st;
-    }
-    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
-
-private:
-    std::shared_ptr<Device> dev_;
-    gnsship_lnav_conf conf_;
-    gnsship_lnav* h_ = nullptr;
-    int32_t channels_ = 0, subframes_per_run_ = 0, rounds_ = 0;
-    std::vector<gnsship_lnav_subframe> subframes_;
-    std::vector<int32_t> counts_;
-    std::vector<uint8_t> faults_;
-    std::vector<uint32_t> tow_ms_;
-    std::vector<uint8_t> sflags_;
-};
-
-// gps_l2c_telemetry_decoder_gs / gps_l5_telemetry_decoder_gs as gnsship_cnav_conf: max_rounds is the most entries per
-// channel one work_* call may carry.
-inline gnsship_cnav_conf gps_l2c_tlm_conf(int32_t max_rounds)
-{
-    return gnsship_cnav_conf{max_rounds, GNSSHIP_CNAV_L2C, 0};
-}
-inline gnsship_cnav_conf gps_l5_tlm_conf(int32_t max_rounds)
-{
-    return gnsship_cnav_conf{max_rounds, GNSSHIP_CNAV_L5, 0};
-}
-
-// The GPS CNAV telemetry decoders up to the time of week for many channels at once, one block object per channel
-// (include/gnsship.h, gnsship_cnav_*): symbols or tracking records in; messages, the TOW stamp of every entry and
-// watchdog faults out.  After a work_* call, messages() / counts() / faults() / tow_ms() / sflags() hold that call's
-// outputs.  The two blocks differ in the configuration's signal only.
-class Gps_Cnav_Telemetry_Decoder_Hip {
-public:
-    Gps_Cnav_Telemetry_Decoder_Hip(const gnsship_cnav_conf& c, int32_t max_channels, int device = 0)
-        : dev_(Device::get(device)), conf_(c), channels_(max_channels)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        if (gnsship_cnav_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
-            throw std::invalid_argument(std::string("gnsship_cnav_create: ") + gnsship_last_error(dev_->ctx()));
-        gnsship_cnav_outputs_device(h_, nullptr, nullptr, nullptr, nullptr, nullptr, &messages_per_run_);
-        const size_t nc = static_cast<size_t>(max_channels);
-        messages_.resize(nc * messages_per_run_);
-        counts_.resize(nc);
-        faults_.resize(nc);
-        tow_ms_.resize(nc * c.max_rounds);
-        sflags_.resize(nc * c.max_rounds);
-    }
-    ~Gps_Cnav_Telemetry_Decoder_Hip()
-    {
-        if (h_) gnsship_cnav_destroy(h_);
-    }
-    Gps_Cnav_Telemetry_Decoder_Hip(const Gps_Cnav_Telemetry_Decoder_Hip&) = delete;
-    Gps_Cnav_Telemetry_Decoder_Hip& operator=(const Gps_Cnav_Telemetry_Decoder_Hip&) = delete;
-    const gnsship_cnav_conf& conf() const { return conf_; }
-    int32_t messages_per_run() const { return messages_per_run_; }
-    // the block's reset() on one channel; new_channel: a new block object
-    bool reset(int32_t channel)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_cnav_reset_channel(h_, channel) == GNSSHIP_OK;
-    }
-    bool new_channel(int32_t channel)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_cnav_new_channel(h_, channel) == GNSSHIP_OK;
-    }
-    // symbols[r · max_channels + c], r < n_rounds; valid, out_valid: the same shape, or null for all valid / all true
-    bool work_symbols(const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int32_t n_rounds, bool on_device = false)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = n_rounds;
-        return gnsship_cnav_run_symbols(h_, symbols, valid, out_valid, on_device ? 1 : 0, n_rounds, messages_.data(), counts_.data(), faults_.data(),
-                   tow_ms_.data(), sflags_.data()) == GNSSHIP_OK;
-    }
-    // tracking records of that shape: a symbol when flags & 1; the symbol is prompt_i > 0 (L2C) or prompt_q > 0 (L5)
-    bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = n_rounds;
-        return gnsship_cnav_run_records(h_, records, on_device ? 1 : 0, n_rounds, messages_.data(), counts_.data(), faults_.data(), tow_ms_.data(),
-                   sflags_.data()) == GNSSHIP_OK;
-    }
-    // the records the tracker's last work() left on the device, in place
-    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = 0;
-        return gnsship_cnav_run_trk(h_, trk.handle(), messages_.data(), counts_.data(), faults_.data(), tow_ms_.data(), sflags_.data(), &rounds_) ==
-               GNSSHIP_OK;
-    }
-    // the last work_* call's outputs: message k < counts()[c] of channel c is messages()[c · messages_per_run() + k];
-    // entry (r, c), r < rounds(), is tow_ms()[r · max_channels + c] and sflags()[r · max_channels + c]
-    const std::vector<gnsship_cnav_message>& messages() const { return messages_; }
-    const std::vector<int32_t>& counts() const { return counts_; }
-    const std::vector<uint8_t>& faults() const { return faults_; }
-    const std::vector<uint32_t>& tow_ms() const { return tow_ms_; }
-    const std::vector<uint8_t>& sflags() const { return sflags_; }
-    int32_t rounds() const { return rounds_; }
-    gnsship_cnav_state state(int32_t channel) const
-    {
-        gnsship_cnav_state st{};
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        gnsship_cnav_state_get(h_, channel, &st);
-        return st;
-    }
-    bool set_state(int32_t channel, const gnsship_cnav_state& st)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_cnav_state_set(h_, channel, &st) == GNSSHIP_OK;
     }
     std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
 
 protected:
-    // for the two block classes: the configuration must be their signal's
-    static const gnsship_cnav_conf& require(const gnsship_cnav_conf& c, int32_t signal)
+    Telemetry_Decoder_Hip(const typename Api::Conf& c, int32_t max_channels, int device) : dev_(Device::get(device)), conf_(c)
+    {
+        std::lock_guard<std::mutex> lk(dev_->mutex());
+        if (Api::create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
+            throw std::invalid_argument(std::string(Api::create_name) + ": " + gnsship_last_error(dev_->ctx()));
+        Api::per_run(h_, &per_run_);
+        const size_t nc = static_cast<size_t>(max_channels);
+        records_.resize(nc * per_run_);
+        counts_.resize(nc);
+        if (Api::has_faults) faults_.resize(nc);
+        if (Api::has_tow) tow_ms_.resize(nc * c.max_rounds);
+        if (Api::has_tow) sflags_.resize(nc * c.max_rounds);
+    }
+    // for the signal-named block classes: the configuration must be their signal's
+    static const typename Api::Conf& require(const typename Api::Conf& c, int32_t signal)
     {
         if (c.signal != signal) throw std::invalid_argument("the configuration's signal is not this block's");
         return c;
     }
+    // one C call on the handle, under the device mutex
+    template <class Fn, class... A>
+    bool call(Fn fn, A... a) const
+    {
+        return dev_->call(fn, h_, a...);
+    }
+    // A run of a family with a TOW stream: fn(handle, in..., the host outputs in the C functions' order)
+    template <class Fn, class... In>
+    bool run(int32_t n_rounds, Fn fn, In... in)
+    {
+        rounds_ = n_rounds;
+        return with_outputs([&](auto... out) { return call(fn, in..., out...); });
+    }
+    // ... over the records the tracker's last work() left on the device, in place
+    template <class Fn>
+    bool run_trk(Fn fn, const Dll_Pll_Veml_Tracking_Hip& trk)
+    {
+        rounds_ = 0;
+        return with_outputs([&](auto... out) { return call(fn, trk.handle(), out..., &rounds_); });
+    }
+    const std::vector<uint8_t>& faults() const { return faults_; }  // public in the families that raise faults
 
-private:
-    std::shared_ptr<Device> dev_;
-    gnsship_cnav_conf conf_;
-    gnsship_cnav* h_ = nullptr;
-    int32_t channels_ = 0, messages_per_run_ = 0, rounds_ = 0;
-    std::vector<gnsship_cnav_message> messages_;
+    std::vector<typename Api::Record> records_;
     std::vector<int32_t> counts_;
     std::vector<uint8_t> faults_;
+
+private:
+    template <class Use>
+    bool with_outputs(Use use)
+    {
+        if constexpr (Api::has_faults) return use(records_.data(), counts_.data(), faults_.data(), tow_ms_.data(), sflags_.data());
+        else return use(records_.data(), counts_.data(), tow_ms_.data(), sflags_.data());
+    }
+    std::shared_ptr<Device> dev_;
+    typename Api::Conf conf_;
+    typename Api::Handle* h_ = nullptr;
+    int32_t per_run_ = 0, rounds_ = 0;
     std::vector<uint32_t> tow_ms_;
     std::vector<uint8_t> sflags_;
+};
+
+// The frame types of galileo_telemetry_decoder_gs (:167-213) as gnsship_tlm_conf: max_rounds is the most symbols per
+// channel one work_* call may carry.
+inline gnsship_tlm_conf galileo_tlm_conf(int32_t frame_type, int32_t max_rounds, int mode) { return gnsship_tlm_conf{frame_type, mode, max_rounds, 0}; }
+inline gnsship_tlm_conf galileo_inav_tlm_conf(int32_t max_rounds, int mode = GNSSHIP_VIT_MODE_REFERENCE) { return galileo_tlm_conf(GNSSHIP_TLM_INAV, max_rounds, mode); }
+inline gnsship_tlm_conf galileo_fnav_tlm_conf(int32_t max_rounds, int mode = GNSSHIP_VIT_MODE_REFERENCE) { return galileo_tlm_conf(GNSSHIP_TLM_FNAV, max_rounds, mode); }
+inline gnsship_tlm_conf galileo_cnav_tlm_conf(int32_t max_rounds, int mode = GNSSHIP_VIT_MODE_REFERENCE) { return galileo_tlm_conf(GNSSHIP_TLM_CNAV, max_rounds, mode); }
+
+struct Galileo_Tlm_Api {
+    using Handle = gnsship_tlm;
+    using Conf = gnsship_tlm_conf;
+    using Record = gnsship_tlm_page;
+    using State = gnsship_tlm_state;
+    static constexpr const char* create_name = "gnsship_tlm_create";
+    static constexpr auto create = gnsship_tlm_create;
+    static constexpr auto destroy = gnsship_tlm_destroy;
+    static constexpr auto state_get = gnsship_tlm_state_get;
+    static constexpr bool has_faults = true, has_tow = false;
+    static void per_run(Handle* h, int32_t* n) { gnsship_tlm_outputs_device(h, nullptr, nullptr, nullptr, nullptr, n); }
+};
+
+// The frame handling of galileo_telemetry_decoder_gs::general_work (:872-1094): CRC-checked page parts and
+// check_tlm_separation faults out.  After a work_* call, pages() / bits() / counts() / faults() hold that call's outputs.
+// The one family without a TOW stream, and the one with a second per-record output, the page's data bits.
+class Galileo_Telemetry_Decoder_Hip : public Telemetry_Decoder_Hip<Galileo_Tlm_Api> {
+public:
+    Galileo_Telemetry_Decoder_Hip(const gnsship_tlm_conf& c, int32_t max_channels, int device = 0)
+        : Telemetry_Decoder_Hip(c, max_channels, device),
+          data_length_(c.frame_type == GNSSHIP_TLM_INAV ? 114 : c.frame_type == GNSSHIP_TLM_FNAV ? 238 : 486)
+    {
+        bits_.resize(records_.size() * data_length_);
+    }
+    int32_t data_length() const { return data_length_; }
+    int32_t pages_per_run() const { return per_run(); }
+    // the block's set_satellite() (:771-789) and reset() (:792-820) on one channel; new_channel: a new block object
+    bool set_satellite(int32_t channel) { return call(gnsship_tlm_set_satellite, channel); }
+    bool reset(int32_t channel) { return call(gnsship_tlm_reset_channel, channel); }
+    bool new_channel(int32_t channel) { return call(gnsship_tlm_new_channel, channel); }
+    // symbols[r · max_channels + c], r < n_rounds; valid: the same shape, or null for all valid
+    bool work_symbols(const float* symbols, const uint8_t* valid, int32_t n_rounds, bool on_device = false)
+    {
+        return call(gnsship_tlm_run_symbols, symbols, valid, on_device ? 1 : 0, n_rounds, records_.data(), bits_.data(), counts_.data(), faults_.data());
+    }
+    // tracking records of that shape: an entry is a symbol when flags & 1, the symbol is (float)prompt_i
+    bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
+    {
+        return call(gnsship_tlm_run_records, records, on_device ? 1 : 0, n_rounds, records_.data(), bits_.data(), counts_.data(), faults_.data());
+    }
+    // the records the tracker's last work() left on the device, in place
+    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk)
+    {
+        return call(gnsship_tlm_run_trk, trk.handle(), records_.data(), bits_.data(), counts_.data(), faults_.data());
+    }
+    // part k < counts()[c] of channel c is pages()[c · pages_per_run() + k], its bits (bytes of 0 / 1) start at
+    // bits()[(c · pages_per_run() + k) · data_length()]
+    const std::vector<gnsship_tlm_page>& pages() const { return records_; }
+    const std::vector<uint8_t>& bits() const { return bits_; }
+    using Telemetry_Decoder_Hip::faults;
+
+private:
+    int32_t data_length_ = 0;
+    std::vector<uint8_t> bits_;
+};
+
+// gps_l1_ca_telemetry_decoder_gs as gnsship_lnav_conf: max_rounds is the most entries per channel one work_* call may carry.
+inline gnsship_lnav_conf gps_l1_ca_tlm_conf(int32_t max_rounds) { return gnsship_lnav_conf{max_rounds, 0}; }
+
+struct Lnav_Tlm_Api {
+    using Handle = gnsship_lnav;
+    using Conf = gnsship_lnav_conf;
+    using Record = gnsship_lnav_subframe;
+    using State = gnsship_lnav_state;
+    static constexpr const char* create_name = "gnsship_lnav_create";
+    static constexpr auto create = gnsship_lnav_create;
+    static constexpr auto destroy = gnsship_lnav_destroy;
+    static constexpr auto state_get = gnsship_lnav_state_get;
+    static constexpr bool has_faults = true, has_tow = true;
+    static void per_run(Handle* h, int32_t* n) { gnsship_lnav_outputs_device(h, nullptr, nullptr, nullptr, nullptr, nullptr, n); }
+};
+
+// gps_l1_ca_telemetry_decoder_gs up to the time of week: subframes, the TOW stamp of every entry and check_tlm_separation
+// faults out.  After a work_* call, subframes() / counts() / faults() / tow_ms() / sflags() hold that call's outputs.
+class Gps_L1_Ca_Telemetry_Decoder_Hip : public Telemetry_Decoder_Hip<Lnav_Tlm_Api> {
+public:
+    Gps_L1_Ca_Telemetry_Decoder_Hip(const gnsship_lnav_conf& c, int32_t max_channels, int device = 0) : Telemetry_Decoder_Hip(c, max_channels, device) {}
+    int32_t subframes_per_run() const { return per_run(); }
+    // the block's set_satellite() (:217-224) and reset() (:436-445) on one channel; new_channel: a new block object
+    bool set_satellite(int32_t channel) { return call(gnsship_lnav_set_satellite, channel); }
+    bool reset(int32_t channel) { return call(gnsship_lnav_reset_channel, channel); }
+    bool new_channel(int32_t channel) { return call(gnsship_lnav_new_channel, channel); }
+    // symbols[r · max_channels + c], r < n_rounds; valid, flags180: the same shape, or null for all valid / all false
+    bool work_symbols(const float* symbols, const uint8_t* valid, const uint8_t* flags180, int32_t n_rounds, bool on_device = false)
+    {
+        return run(n_rounds, gnsship_lnav_run_symbols, symbols, valid, flags180, on_device ? 1 : 0, n_rounds);
+    }
+    // tracking records of that shape: a symbol when flags & 1, the symbol is (float)prompt_i, the 180° input flags & 4
+    bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
+    {
+        return run(n_rounds, gnsship_lnav_run_records, records, on_device ? 1 : 0, n_rounds);
+    }
+    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk) { return run_trk(gnsship_lnav_run_trk, trk); }
+    const std::vector<gnsship_lnav_subframe>& subframes() const { return records_; }
+    using Telemetry_Decoder_Hip::faults;
+};
+
+// gps_l2c_telemetry_decoder_gs / gps_l5_telemetry_decoder_gs as gnsship_cnav_conf: max_rounds is the most entries per
+// channel one work_* call may carry.
+inline gnsship_cnav_conf gps_l2c_tlm_conf(int32_t max_rounds) { return gnsship_cnav_conf{max_rounds, GNSSHIP_CNAV_L2C, 0}; }
+inline gnsship_cnav_conf gps_l5_tlm_conf(int32_t max_rounds) { return gnsship_cnav_conf{max_rounds, GNSSHIP_CNAV_L5, 0}; }
+
+struct Cnav_Tlm_Api {
+    using Handle = gnsship_cnav;
+    using Conf = gnsship_cnav_conf;
+    using Record = gnsship_cnav_message;
+    using State = gnsship_cnav_state;
+    static constexpr const char* create_name = "gnsship_cnav_create";
+    static constexpr auto create = gnsship_cnav_create;
+    static constexpr auto destroy = gnsship_cnav_destroy;
+    static constexpr auto state_get = gnsship_cnav_state_get;
+    static constexpr bool has_faults = true, has_tow = true;
+    static void per_run(Handle* h, int32_t* n) { gnsship_cnav_outputs_device(h, nullptr, nullptr, nullptr, nullptr, nullptr, n); }
+};
+
+// The GPS CNAV telemetry decoders up to the time of week: messages, the TOW stamp of every entry and watchdog faults out.
+// After a work_* call, messages() / counts() / faults() / tow_ms() / sflags() hold that call's outputs.  The two blocks
+// differ in the configuration's signal only.
+class Gps_Cnav_Telemetry_Decoder_Hip : public Telemetry_Decoder_Hip<Cnav_Tlm_Api> {
+public:
+    Gps_Cnav_Telemetry_Decoder_Hip(const gnsship_cnav_conf& c, int32_t max_channels, int device = 0) : Telemetry_Decoder_Hip(c, max_channels, device) {}
+    int32_t messages_per_run() const { return per_run(); }
+    // the block's reset() on one channel; new_channel: a new block object
+    bool reset(int32_t channel) { return call(gnsship_cnav_reset_channel, channel); }
+    bool new_channel(int32_t channel) { return call(gnsship_cnav_new_channel, channel); }
+    // symbols[r · max_channels + c], r < n_rounds; valid, out_valid: the same shape, or null for all valid / all true
+    bool work_symbols(const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int32_t n_rounds, bool on_device = false)
+    {
+        return run(n_rounds, gnsship_cnav_run_symbols, symbols, valid, out_valid, on_device ? 1 : 0, n_rounds);
+    }
+    // tracking records of that shape: a symbol when flags & 1; the symbol is prompt_i > 0 (L2C) or prompt_q > 0 (L5)
+    bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
+    {
+        return run(n_rounds, gnsship_cnav_run_records, records, on_device ? 1 : 0, n_rounds);
+    }
+    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk) { return run_trk(gnsship_cnav_run_trk, trk); }
+    const std::vector<gnsship_cnav_message>& messages() const { return records_; }
+    using Telemetry_Decoder_Hip::faults;
+    bool set_state(int32_t channel, const gnsship_cnav_state& st) { return call(gnsship_cnav_state_set, channel, &st); }
 };
 
 // gps_l2c_telemetry_decoder_gs: construct with gps_l2c_tlm_conf(max_rounds)
 class Gps_L2c_Telemetry_Decoder_Hip : public Gps_Cnav_Telemetry_Decoder_Hip {
 public:
     Gps_L2c_Telemetry_Decoder_Hip(const gnsship_cnav_conf& c, int32_t max_channels, int device = 0)
-        : Gps_Cnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_CNAV_L2C), max_channels, device)
-    {
-    }
+        : Gps_Cnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_CNAV_L2C), max_channels, device) {}
 };
 
 // gps_l5_telemetry_decoder_gs: construct with gps_l5_tlm_conf(max_rounds)
 class Gps_L5_Telemetry_Decoder_Hip : public Gps_Cnav_Telemetry_Decoder_Hip {
 public:
     Gps_L5_Telemetry_Decoder_Hip(const gnsship_cnav_conf& c, int32_t max_channels, int device = 0)
-        : Gps_Cnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_CNAV_L5), max_channels, device)
-    {
-    }
+        : Gps_Cnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_CNAV_L5), max_channels, device) {}
 };
 
 // beidou_b1i_telemetry_decoder_gs / beidou_b3i_telemetry_decoder_gs as gnsship_dnav_conf: max_rounds is the most entries
 // per channel one work_* call may carry.
-inline gnsship_dnav_conf beidou_b1i_tlm_conf(int32_t max_rounds)
-{
-    return gnsship_dnav_conf{max_rounds, GNSSHIP_DNAV_B1I, 0};
-}
-inline gnsship_dnav_conf beidou_b3i_tlm_conf(int32_t max_rounds)
-{
-    return gnsship_dnav_conf{max_rounds, GNSSHIP_DNAV_B3I, 0};
-}
+inline gnsship_dnav_conf beidou_b1i_tlm_conf(int32_t max_rounds) { return gnsship_dnav_conf{max_rounds, GNSSHIP_DNAV_B1I, 0}; }
+inline gnsship_dnav_conf beidou_b3i_tlm_conf(int32_t max_rounds) { return gnsship_dnav_conf{max_rounds, GNSSHIP_DNAV_B3I, 0}; }
 
-// The BeiDou D1/D2 telemetry decoders up to the time of week for many channels at once, one block object per channel
-// (include/gnsship.h, gnsship_dnav_*): symbols or tracking records in; subframes and the TOW stamp of every entry out.
-// After a work_* call, subframes() / counts() / tow_ms() / sflags() hold that call's outputs.  The two blocks differ in
-// the configuration's signal only: which PRNs take the D2 decoder.
-class Beidou_Dnav_Telemetry_Decoder_Hip {
+struct Dnav_Tlm_Api {
+    using Handle = gnsship_dnav;
+    using Conf = gnsship_dnav_conf;
+    using Record = gnsship_dnav_subframe;
+    using State = gnsship_dnav_state;
+    static constexpr const char* create_name = "gnsship_dnav_create";
+    static constexpr auto create = gnsship_dnav_create;
+    static constexpr auto destroy = gnsship_dnav_destroy;
+    static constexpr auto state_get = gnsship_dnav_state_get;
+    static constexpr bool has_faults = false, has_tow = true;
+    static void per_run(Handle* h, int32_t* n) { gnsship_dnav_outputs_device(h, nullptr, nullptr, nullptr, nullptr, n); }
+};
+
+// The BeiDou D1/D2 telemetry decoders up to the time of week: subframes and the TOW stamp of every entry out; the blocks
+// raise no fault.  After a work_* call, subframes() / counts() / tow_ms() / sflags() hold that call's outputs.  The two
+// blocks differ in the configuration's signal only: which PRNs take the D2 decoder.
+class Beidou_Dnav_Telemetry_Decoder_Hip : public Telemetry_Decoder_Hip<Dnav_Tlm_Api> {
 public:
-    Beidou_Dnav_Telemetry_Decoder_Hip(const gnsship_dnav_conf& c, int32_t max_channels, int device = 0)
-        : dev_(Device::get(device)), conf_(c), channels_(max_channels)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        if (gnsship_dnav_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
-            throw std::invalid_argument(std::string("gnsship_dnav_create: ") + gnsship_last_error(dev_->ctx()));
-        gnsship_dnav_outputs_device(h_, nullptr, nullptr, nullptr, nullptr, &subframes_per_run_);
-        const size_t nc = static_cast<size_t>(max_channels);
-        subframes_.resize(nc * subframes_per_run_);
-        counts_.resize(nc);
-        tow_ms_.resize(nc * c.max_rounds);
-        sflags_.resize(nc * c.max_rounds);
-    }
-    ~Beidou_Dnav_Telemetry_Decoder_Hip()
-    {
-        if (h_) gnsship_dnav_destroy(h_);
-    }
-    Beidou_Dnav_Telemetry_Decoder_Hip(const Beidou_Dnav_Telemetry_Decoder_Hip&) = delete;
-    Beidou_Dnav_Telemetry_Decoder_Hip& operator=(const Beidou_Dnav_Telemetry_Decoder_Hip&) = delete;
-    const gnsship_dnav_conf& conf() const { return conf_; }
-    int32_t subframes_per_run() const { return subframes_per_run_; }
+    Beidou_Dnav_Telemetry_Decoder_Hip(const gnsship_dnav_conf& c, int32_t max_channels, int device = 0) : Telemetry_Decoder_Hip(c, max_channels, device) {}
+    int32_t subframes_per_run() const { return per_run(); }
     // the block's reset() and set_satellite() on one channel; new_channel: a new block object constructed on this PRN
-    bool reset(int32_t channel)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_dnav_reset_channel(h_, channel) == GNSSHIP_OK;
-    }
-    bool set_satellite(int32_t channel, int32_t prn)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_dnav_set_satellite(h_, channel, prn) == GNSSHIP_OK;
-    }
-    bool new_channel(int32_t channel, int32_t prn)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_dnav_new_channel(h_, channel, prn) == GNSSHIP_OK;
-    }
+    bool reset(int32_t channel) { return call(gnsship_dnav_reset_channel, channel); }
+    bool set_satellite(int32_t channel, int32_t prn) { return call(gnsship_dnav_set_satellite, channel, prn); }
+    bool new_channel(int32_t channel, int32_t prn) { return call(gnsship_dnav_new_channel, channel, prn); }
     // symbols[r · max_channels + c], r < n_rounds; valid, out_valid: the same shape, or null for all valid / all true
     bool work_symbols(const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int32_t n_rounds, bool on_device = false)
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = n_rounds;
-        return gnsship_dnav_run_symbols(h_, symbols, valid, out_valid, on_device ? 1 : 0, n_rounds, subframes_.data(), counts_.data(), tow_ms_.data(),
-                   sflags_.data()) == GNSSHIP_OK;
+        return run(n_rounds, gnsship_dnav_run_symbols, symbols, valid, out_valid, on_device ? 1 : 0, n_rounds);
     }
     // tracking records of that shape: a symbol when flags & 1; the symbol is (float)prompt_i
     bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = n_rounds;
-        return gnsship_dnav_run_records(h_, records, on_device ? 1 : 0, n_rounds, subframes_.data(), counts_.data(), tow_ms_.data(), sflags_.data()) ==
-               GNSSHIP_OK;
+        return run(n_rounds, gnsship_dnav_run_records, records, on_device ? 1 : 0, n_rounds);
     }
-    // the records the tracker's last work() left on the device, in place
-    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = 0;
-        return gnsship_dnav_run_trk(h_, trk.handle(), subframes_.data(), counts_.data(), tow_ms_.data(), sflags_.data(), &rounds_) == GNSSHIP_OK;
-    }
-    // the last work_* call's outputs: subframe k < counts()[c] of channel c is subframes()[c · subframes_per_run() + k];
-    // entry (r, c), r < rounds(), is tow_ms()[r · max_channels + c] and sflags()[r · max_channels + c]
-    const std::vector<gnsship_dnav_subframe>& subframes() const { return subframes_; }
-    const std::vector<int32_t>& counts() const { return counts_; }
-    const std::vector<uint32_t>& tow_ms() const { return tow_ms_; }
-    const std::vector<uint8_t>& sflags() const { return sflags_; }
-    int32_t rounds() const { return rounds_; }
-    gnsship_dnav_state state(int32_t channel) const
-    {
-        gnsship_dnav_state st{};
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        gnsship_dnav_state_get(h_, channel, &st);
-        return st;
-    }
-    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
-
-protected:
-    // for the two block classes: the configuration must be their signal's
-    static const gnsship_dnav_conf& require(const gnsship_dnav_conf& c, int32_t signal)
-    {
-        if (c.signal != signal) throw std::invalid_argument("the configuration's signal is not this block's");
-        return c;
-    }
-
-private:
-    std::shared_ptr<Device> dev_;
-    gnsship_dnav_conf conf_;
-    gnsship_dnav* h_ = nullptr;
-    int32_t channels_ = 0, subframes_per_run_ = 0, rounds_ = 0;
-    std::vector<gnsship_dnav_subframe> subframes_;
-    std::vector<int32_t> counts_;
-    std::vector<uint32_t> tow_ms_;
-    std::vector<uint8_t> sflags_;
+    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk) { return run_trk(gnsship_dnav_run_trk, trk); }
+    const std::vector<gnsship_dnav_subframe>& subframes() const { return records_; }
 };
 
 // beidou_b1i_telemetry_decoder_gs: construct with beidou_b1i_tlm_conf(max_rounds)
 class Beidou_B1i_Telemetry_Decoder_Hip : public Beidou_Dnav_Telemetry_Decoder_Hip {
 public:
     Beidou_B1i_Telemetry_Decoder_Hip(const gnsship_dnav_conf& c, int32_t max_channels, int device = 0)
-        : Beidou_Dnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_DNAV_B1I), max_channels, device)
-    {
-    }
+        : Beidou_Dnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_DNAV_B1I), max_channels, device) {}
 };
 
 // beidou_b3i_telemetry_decoder_gs: construct with beidou_b3i_tlm_conf(max_rounds)
 class Beidou_B3i_Telemetry_Decoder_Hip : public Beidou_Dnav_Telemetry_Decoder_Hip {
 public:
     Beidou_B3i_Telemetry_Decoder_Hip(const gnsship_dnav_conf& c, int32_t max_channels, int device = 0)
-        : Beidou_Dnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_DNAV_B3I), max_channels, device)
-    {
-    }
+        : Beidou_Dnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_DNAV_B3I), max_channels, device) {}
 };
 
 // glonass_l1_ca_telemetry_decoder_gs / glonass_l2_ca_telemetry_decoder_gs as gnsship_gnav_conf: max_rounds is the most entries
 // per channel one work_* call may carry.
-inline gnsship_gnav_conf glonass_l1_ca_tlm_conf(int32_t max_rounds)
-{
-    return gnsship_gnav_conf{max_rounds, GNSSHIP_GNAV_L1CA, 0};
-}
-inline gnsship_gnav_conf glonass_l2_ca_tlm_conf(int32_t max_rounds)
-{
-    return gnsship_gnav_conf{max_rounds, GNSSHIP_GNAV_L2CA, 0};
-}
+inline gnsship_gnav_conf glonass_l1_ca_tlm_conf(int32_t max_rounds) { return gnsship_gnav_conf{max_rounds, GNSSHIP_GNAV_L1CA, 0}; }
+inline gnsship_gnav_conf glonass_l2_ca_tlm_conf(int32_t max_rounds) { return gnsship_gnav_conf{max_rounds, GNSSHIP_GNAV_L2CA, 0}; }
 
-// The GLONASS GNAV telemetry decoders up to the time of week for many channels at once, one block object per channel
-// (include/gnsship.h, gnsship_gnav_*): symbols or tracking records in; decoded strings and the TOW stamp of every entry out.
-// After a work_* call, strings() / counts() / tow_ms() / sflags() hold that call's outputs.  The two blocks are one
-// algorithm; the configuration's signal only names the block.
-class Glonass_Gnav_Telemetry_Decoder_Hip {
+struct Gnav_Tlm_Api {
+    using Handle = gnsship_gnav;
+    using Conf = gnsship_gnav_conf;
+    using Record = gnsship_gnav_string;
+    using State = gnsship_gnav_state;
+    static constexpr const char* create_name = "gnsship_gnav_create";
+    static constexpr auto create = gnsship_gnav_create;
+    static constexpr auto destroy = gnsship_gnav_destroy;
+    static constexpr auto state_get = gnsship_gnav_state_get;
+    static constexpr bool has_faults = false, has_tow = true;
+    static void per_run(Handle* h, int32_t* n) { gnsship_gnav_outputs_device(h, nullptr, nullptr, nullptr, nullptr, n); }
+};
+
+// The GLONASS GNAV telemetry decoders up to the time of week: decoded strings and the TOW stamp of every entry out; the
+// blocks raise no fault and have no reset().  After a work_* call, strings() / counts() / tow_ms() / sflags() hold that
+// call's outputs.  The two blocks are one algorithm; the configuration's signal only names the block.
+class Glonass_Gnav_Telemetry_Decoder_Hip : public Telemetry_Decoder_Hip<Gnav_Tlm_Api> {
 public:
-    Glonass_Gnav_Telemetry_Decoder_Hip(const gnsship_gnav_conf& c, int32_t max_channels, int device = 0)
-        : dev_(Device::get(device)), conf_(c), channels_(max_channels)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        if (gnsship_gnav_create(dev_->ctx(), &c, max_channels, &h_) != GNSSHIP_OK)
-            throw std::invalid_argument(std::string("gnsship_gnav_create: ") + gnsship_last_error(dev_->ctx()));
-        gnsship_gnav_outputs_device(h_, nullptr, nullptr, nullptr, nullptr, &strings_per_run_);
-        const size_t nc = static_cast<size_t>(max_channels);
-        strings_.resize(nc * strings_per_run_);
-        counts_.resize(nc);
-        tow_ms_.resize(nc * c.max_rounds);
-        sflags_.resize(nc * c.max_rounds);
-    }
-    ~Glonass_Gnav_Telemetry_Decoder_Hip()
-    {
-        if (h_) gnsship_gnav_destroy(h_);
-    }
-    Glonass_Gnav_Telemetry_Decoder_Hip(const Glonass_Gnav_Telemetry_Decoder_Hip&) = delete;
-    Glonass_Gnav_Telemetry_Decoder_Hip& operator=(const Glonass_Gnav_Telemetry_Decoder_Hip&) = delete;
-    const gnsship_gnav_conf& conf() const { return conf_; }
-    int32_t strings_per_run() const { return strings_per_run_; }
+    Glonass_Gnav_Telemetry_Decoder_Hip(const gnsship_gnav_conf& c, int32_t max_channels, int device = 0) : Telemetry_Decoder_Hip(c, max_channels, device) {}
+    int32_t strings_per_run() const { return per_run(); }
     // the block's set_satellite() on one channel; new_channel: a new block object constructed on this PRN
-    bool set_satellite(int32_t channel, int32_t prn)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_gnav_set_satellite(h_, channel, prn) == GNSSHIP_OK;
-    }
-    bool new_channel(int32_t channel, int32_t prn)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_gnav_new_channel(h_, channel, prn) == GNSSHIP_OK;
-    }
+    bool set_satellite(int32_t channel, int32_t prn) { return call(gnsship_gnav_set_satellite, channel, prn); }
+    bool new_channel(int32_t channel, int32_t prn) { return call(gnsship_gnav_new_channel, channel, prn); }
     // symbols[r · max_channels + c], r < n_rounds; valid: the same shape, or null for all valid; out_valid is not read
     bool work_symbols(const float* symbols, const uint8_t* valid, const uint8_t* out_valid, int32_t n_rounds, bool on_device = false)
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = n_rounds;
-        return gnsship_gnav_run_symbols(h_, symbols, valid, out_valid, on_device ? 1 : 0, n_rounds, strings_.data(), counts_.data(), tow_ms_.data(),
-                   sflags_.data()) == GNSSHIP_OK;
+        return run(n_rounds, gnsship_gnav_run_symbols, symbols, valid, out_valid, on_device ? 1 : 0, n_rounds);
     }
     // tracking records of that shape: a symbol when flags & 1; the symbol is the record's double prompt_i
     bool work_records(const gnsship_trk_epoch* records, int32_t n_rounds, bool on_device = false)
     {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = n_rounds;
-        return gnsship_gnav_run_records(h_, records, on_device ? 1 : 0, n_rounds, strings_.data(), counts_.data(), tow_ms_.data(), sflags_.data()) ==
-               GNSSHIP_OK;
+        return run(n_rounds, gnsship_gnav_run_records, records, on_device ? 1 : 0, n_rounds);
     }
-    // the records the tracker's last work() left on the device, in place
-    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        rounds_ = 0;
-        return gnsship_gnav_run_trk(h_, trk.handle(), strings_.data(), counts_.data(), tow_ms_.data(), sflags_.data(), &rounds_) == GNSSHIP_OK;
-    }
-    // the last work_* call's outputs: string k < counts()[c] of channel c is strings()[c · strings_per_run() + k];
-    // entry (r, c), r < rounds(), is tow_ms()[r · max_channels + c] and sflags()[r · max_channels + c]
-    const std::vector<gnsship_gnav_string>& strings() const { return strings_; }
-    const std::vector<int32_t>& counts() const { return counts_; }
-    const std::vector<uint32_t>& tow_ms() const { return tow_ms_; }
-    const std::vector<uint8_t>& sflags() const { return sflags_; }
-    int32_t rounds() const { return rounds_; }
-    gnsship_gnav_state state(int32_t channel) const
-    {
-        gnsship_gnav_state st{};
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        gnsship_gnav_state_get(h_, channel, &st);
-        return st;
-    }
-    bool set_state(int32_t channel, const gnsship_gnav_state& st)
-    {
-        std::lock_guard<std::mutex> lk(dev_->mutex());
-        return gnsship_gnav_state_set(h_, channel, &st) == GNSSHIP_OK;
-    }
-    std::string last_error() const { return gnsship_last_error(dev_->ctx()); }
-
-protected:
-    // for the two block classes: the configuration must be their signal's
-    static const gnsship_gnav_conf& require(const gnsship_gnav_conf& c, int32_t signal)
-    {
-        if (c.signal != signal) throw std::invalid_argument("the configuration's signal is not this block's");
-        return c;
-    }
-
-private:
-    std::shared_ptr<Device> dev_;
-    gnsship_gnav_conf conf_;
-    gnsship_gnav* h_ = nullptr;
-    int32_t channels_ = 0, strings_per_run_ = 0, rounds_ = 0;
-    std::vector<gnsship_gnav_string> strings_;
-    std::vector<int32_t> counts_;
-    std::vector<uint32_t> tow_ms_;
-    std::vector<uint8_t> sflags_;
+    bool work_trk(const Dll_Pll_Veml_Tracking_Hip& trk) { return run_trk(gnsship_gnav_run_trk, trk); }
+    const std::vector<gnsship_gnav_string>& strings() const { return records_; }
+    bool set_state(int32_t channel, const gnsship_gnav_state& st) { return call(gnsship_gnav_state_set, channel, &st); }
 };
 
 // glonass_l1_ca_telemetry_decoder_gs: construct with glonass_l1_ca_tlm_conf(max_rounds)
 class Glonass_L1_Ca_Telemetry_Decoder_Hip : public Glonass_Gnav_Telemetry_Decoder_Hip {
 public:
     Glonass_L1_Ca_Telemetry_Decoder_Hip(const gnsship_gnav_conf& c, int32_t max_channels, int device = 0)
-        : Glonass_Gnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_GNAV_L1CA), max_channels, device)
-    {
-    }
+        : Glonass_Gnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_GNAV_L1CA), max_channels, device) {}
 };
 
 // glonass_l2_ca_telemetry_decoder_gs: construct with glonass_l2_ca_tlm_conf(max_rounds)
 class Glonass_L2_Ca_Telemetry_Decoder_Hip : public Glonass_Gnav_Telemetry_Decoder_Hip {
 public:
     Glonass_L2_Ca_Telemetry_Decoder_Hip(const gnsship_gnav_conf& c, int32_t max_channels, int device = 0)
-        : Glonass_Gnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_GNAV_L2CA), max_channels, device)
-    {
-    }
+        : Glonass_Gnav_Telemetry_Decoder_Hip(require(c, GNSSHIP_GNAV_L2CA), max_channels, device) {}
 };
 
 }  // namespace gnsship

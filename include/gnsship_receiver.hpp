@@ -207,67 +207,145 @@ struct Receiver_Gnav_String {
     gnsship_gnav_string string;
 };
 
+// What the signal of the channels decides, chosen once from trk.system / trk.signal (of()).  A new signal is one more row
+// of the table and the functions the row names.
+struct Signal_Profile {
+    enum Telemetry { NONE, GALILEO, LNAV, CNAV, DNAV, GNAV };
+    using Code = std::vector<std::complex<float>>;
+    char system;                      // trk.system (0: any)
+    const char* signal;               // the first two characters of trk.signal (nullptr: any)
+    Acq_Conf (*acq_conf)(Acq_Conf);   // the acquisition adapter's Acq_Conf (nullptr: the caller's as it stands)
+    uint32_t prns;                    // set_signals_list: PRN 1..prns
+    double codes_per_second;          // trk.vector_length 0 means round(fs / codes_per_second) ...
+    bool own_vector_length;           // ... and L2C takes no other: one 20 ms code per epoch
+    Code (*acquisition_code)(const Pcps_Acquisition_Hip& a, uint32_t prn, const Acq_Conf& acq);  // the adapter's set_local_code (empty: no such PRN)
+    const char* fdma_signal;          // GLONASS: set_gnss_synchro(fdma_signal, prn) ahead of it, is_fdma()'s bias and grid
+    // start_tracking's replicas: the tracked code and, where the block has a data prompt, the data code of the same length
+    bool (*replicas)(uint32_t prn, bool track_pilot, std::vector<float>& tracked, std::vector<float>& data);
+    Telemetry telemetry;              // the telemetry option the signal accepts ...
+    int32_t telemetry_signal;         // ... and the frame type or signal of that decoder's configuration
+
+    static const Signal_Profile& of(const Dll_Pll_Conf& trk)
+    {
+        static const Signal_Profile table[] = {
+            // Channels_L5: acquisition on L5I, tracking on the L5Q pilot with L5I on the data prompt (start_tracking :670-678)
+            {'G', "L5", gps_l5i_acq_conf, 32U, 1000.0, false,
+                [](const Pcps_Acquisition_Hip&, uint32_t prn, const Acq_Conf& acq) { return gps_l5i_acquisition_code(prn, acq); }, nullptr,
+                [](uint32_t prn, bool, std::vector<float>& tracked, std::vector<float>& data) {
+                    tracked.resize(GPS_L5Q_CODE_LENGTH_CHIPS);
+                    data.resize(GPS_L5I_CODE_LENGTH_CHIPS);
+                    return gps_l5q_code_gen_float(tracked.data(), prn) && gps_l5i_code_gen_float(data.data(), prn);
+                },
+                CNAV, GNSSHIP_CNAV_L5},
+            // Channels_2S and Channels_B3: acquisition and tracking on one code, no data prompt (start_tracking :666-668,
+            // :799-801); a B3I GEO satellite is recognised by the PRN start_tracking passes on
+            {'G', "2S", gps_l2_m_acq_conf, 32U, 50.0, true,
+                [](const Pcps_Acquisition_Hip&, uint32_t prn, const Acq_Conf& acq) { return gps_l2c_m_acquisition_code(prn, acq); }, nullptr,
+                [](uint32_t prn, bool, std::vector<float>& tracked, std::vector<float>&) {
+                    tracked.resize(GPS_L2_M_CODE_LENGTH_CHIPS);
+                    return gps_l2c_m_code_gen_float(tracked.data(), prn);
+                },
+                CNAV, GNSSHIP_CNAV_L2C},
+            {'C', "B3", beidou_b3i_acq_conf, 63U, 1000.0, false,
+                [](const Pcps_Acquisition_Hip&, uint32_t prn, const Acq_Conf& acq) { return beidou_b3i_acquisition_code(prn, acq); }, nullptr,
+                [](uint32_t prn, bool, std::vector<float>& tracked, std::vector<float>&) {
+                    tracked.resize(BEIDOU_B3I_CODE_LENGTH_CHIPS);
+                    return beidou_b3i_code_gen_float(tracked.data(), static_cast<int32_t>(prn), 0);
+                },
+                DNAV, GNSSHIP_DNAV_B3I},
+            // Channels_5X / Channels_7X: acquisition on the I component (acquire_pilot and acquire_iq at their defaults),
+            // tracking on the Q pilot with the I component on the data prompt, or — trk.track_pilot false — on the I component alone
+            {'E', "5X", galileo_e5_acq_conf, 36U, 1000.0, false,
+                [](const Pcps_Acquisition_Hip&, uint32_t prn, const Acq_Conf& acq) { return galileo_e5_acquisition_code(prn, acq, false); }, nullptr,
+                [](uint32_t prn, bool pilot, std::vector<float>& tracked, std::vector<float>& data) { return e5_replicas(false, prn, pilot, tracked, data); },
+                GALILEO, GNSSHIP_TLM_FNAV},
+            {'E', "7X", galileo_e5_acq_conf, 36U, 1000.0, false,
+                [](const Pcps_Acquisition_Hip&, uint32_t prn, const Acq_Conf& acq) { return galileo_e5_acquisition_code(prn, acq, true); }, nullptr,
+                [](uint32_t prn, bool pilot, std::vector<float>& tracked, std::vector<float>& data) { return e5_replicas(true, prn, pilot, tracked, data); },
+                GALILEO, GNSSHIP_TLM_INAV},
+            // Channels_1G / Channels_2G: one code for every satellite; each channel's acquisition searches under its satellite's
+            // FDMA bias (pcps_acquisition::is_fdma), as the reference's channels do, and the tracker takes the frequency
+            // channel from the PRN
+            {'R', "1G", glonass_l1_ca_acq_conf, 24U, 1000.0, false, glonass_code, "1G", glonass_replicas, GNAV, GNSSHIP_GNAV_L1CA},
+            {'R', "2G", glonass_l1_ca_acq_conf, 24U, 1000.0, false, glonass_code, "2G", glonass_replicas, GNAV, GNSSHIP_GNAV_L2CA},
+            // Channels_1C, and what every other signal is run as; only system 'G' takes the LNAV decoder
+            {'G', nullptr, nullptr, 32U, 1000.0, false, l1_ca_code, nullptr, l1_ca_replicas, LNAV, 0},
+            {0, nullptr, nullptr, 32U, 1000.0, false, l1_ca_code, nullptr, l1_ca_replicas, NONE, 0},
+        };
+        const Signal_Profile* p = table;
+        while ((p->system && p->system != trk.system) || (p->signal && (p->signal[0] != trk.signal[0] || p->signal[1] != trk.signal[1]))) p++;
+        return *p;
+    }
+
+private:
+    // start_tracking :699-746: the X primary's imaginary part tracked, its real part the data code
+    static bool e5_replicas(bool band_b, uint32_t prn, bool pilot, std::vector<float>& tracked, std::vector<float>& data)
+    {
+        std::vector<std::complex<float>> x(GALILEO_E5A_CODE_LENGTH_CHIPS);
+        const std::array<char, 3> id = {{band_b ? '7' : '5', 'X', '\0'}};
+        if (!(band_b ? galileo_e5_b_code_gen_complex_primary(x.data(), static_cast<int32_t>(prn), id)
+                     : galileo_e5_a_code_gen_complex_primary(x.data(), static_cast<int32_t>(prn), id)))
+            return false;
+        std::vector<float>& i_code = pilot ? data : tracked;
+        i_code.resize(x.size());
+        for (size_t i = 0; i < x.size(); i++) i_code[i] = x[i].real();
+        if (pilot) tracked.resize(x.size());
+        for (size_t i = 0; pilot && i < x.size(); i++) tracked[i] = x[i].imag();
+        return true;
+    }
+    static Code glonass_code(const Pcps_Acquisition_Hip&, uint32_t, const Acq_Conf& acq) { return glonass_l1_ca_acquisition_code(acq); }
+    // glonass_l1_ca_dll_pll_tracking_cc::start_tracking :198-200: the one code from chip 1
+    static bool glonass_replicas(uint32_t, bool, std::vector<float>& tracked, std::vector<float>&)
+    {
+        std::vector<std::complex<float>> z(511);
+        glonass_l1_ca_code_gen_complex(z.data(), 0);
+        tracked.resize(z.size());
+        for (size_t i = 0; i < z.size(); i++) tracked[i] = z[i].real();
+        return true;
+    }
+    static Code l1_ca_code(const Pcps_Acquisition_Hip& a, uint32_t prn, const Acq_Conf& acq)
+    {
+        Code code(static_cast<size_t>(a.consumed_samples()));
+        gnsship_gps_l1_ca_code_gen_complex_sampled(reinterpret_cast<float*>(code.data()), prn, static_cast<int32_t>(acq.fs_in), 0);
+        return code;
+    }
+    static bool l1_ca_replicas(uint32_t prn, bool, std::vector<float>& tracked, std::vector<float>&)
+    {
+        tracked.resize(1023);
+        gnsship_gps_l1_ca_code_gen_float(tracked.data(), static_cast<int32_t>(prn), 0);
+        return true;
+    }
+};
+
 class Gnss_Receiver_Hip {
 public:
-    explicit Gnss_Receiver_Hip(const Receiver_Conf& conf) : conf_(conf), dev_(Device::get(conf.device))
+    explicit Gnss_Receiver_Hip(const Receiver_Conf& conf) : conf_(conf), dev_(Device::get(conf.device)), sig_(Signal_Profile::of(conf.trk))
     {
-        // Channels_L5 (trk.system 'G', trk.signal "L5"): acquisition on L5I, tracking on the L5Q pilot
-        l5_ = conf_.trk.system == 'G' && conf_.trk.signal[0] == 'L' && conf_.trk.signal[1] == '5';
-        if (l5_) conf_.acq = gps_l5i_acq_conf(conf_.acq);
-        // Channels_B3 (system 'C', signal "B3") and Channels_2S (system 'G', signal "2S"): acquisition and tracking on
-        // the same code; a B3I GEO satellite is recognised by the PRN start_tracking passes on
-        b3_ = conf_.trk.system == 'C' && conf_.trk.signal[0] == 'B' && conf_.trk.signal[1] == '3';
-        l2c_ = conf_.trk.system == 'G' && conf_.trk.signal[0] == '2' && conf_.trk.signal[1] == 'S';
-        if (b3_) conf_.acq = beidou_b3i_acq_conf(conf_.acq);
-        if (l2c_) conf_.acq = gps_l2_m_acq_conf(conf_.acq);
-        // Channels_5X / Channels_7X (system 'E', signal "5X" / "7X"): acquisition on the I component (acquire_pilot and
-        // acquire_iq at their defaults), tracking on the Q pilot with the I component on the data prompt, or — trk.track_pilot
-        // false — on the I component alone
-        e5a_ = conf_.trk.system == 'E' && conf_.trk.signal[0] == '5' && conf_.trk.signal[1] == 'X';
-        e5b_ = conf_.trk.system == 'E' && conf_.trk.signal[0] == '7' && conf_.trk.signal[1] == 'X';
-        if (e5a_ || e5b_) conf_.acq = galileo_e5_acq_conf(conf_.acq);
-        // Channels_1G / Channels_2G (system 'R', signal "1G" / "2G"): one code for every satellite; each channel's
-        // acquisition searches under its satellite's FDMA bias (pcps_acquisition::is_fdma), as the reference's channels do,
-        // and the tracker takes the frequency channel from the PRN
-        glo_ = conf_.trk.system == 'R' && conf_.trk.signal[1] == 'G' && (conf_.trk.signal[0] == '1' || conf_.trk.signal[0] == '2');
-        if (glo_) conf_.acq = glonass_l1_ca_acq_conf(conf_.acq);
+        if (sig_.acq_conf) conf_.acq = sig_.acq_conf(conf_.acq);
         n_ = std::max(1, conf_.channels);
         max_acq_ = std::min(std::max(0, conf_.in_acquisition), n_);
         conf_.satellite.resize(static_cast<size_t>(n_), 0U);
-        if (conf_.trk.vector_length == 0 || l2c_) conf_.trk.vector_length = static_cast<uint32_t>(std::lround(conf_.trk.fs_in / (l2c_ ? 50.0 : 1000.0)));
+        if (conf_.trk.vector_length == 0 || sig_.own_vector_length)
+            conf_.trk.vector_length = static_cast<uint32_t>(std::lround(conf_.trk.fs_in / sig_.codes_per_second));
         vl_ = static_cast<int64_t>(conf_.trk.vector_length);
         block_ = conf_.block_samples > 0 ? conf_.block_samples : static_cast<int64_t>(conf_.trk.fs_in / 10.0);
         tail_ = 2 * vl_;
         trk_ = std::make_unique<Dll_Pll_Veml_Tracking_Hip>(conf_.trk, n_, conf_.device);
-        if (conf_.telemetry) {
-            if (!e5a_ && !e5b_) throw std::invalid_argument("Gnss_Receiver_Hip: telemetry decodes Galileo channels (signal 5X or 7X)");
-            const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
-            tlm_ = std::make_unique<Galileo_Telemetry_Decoder_Hip>(
-                e5a_ ? galileo_fnav_tlm_conf(max_ep, conf_.telemetry_mode) : galileo_inav_tlm_conf(max_ep, conf_.telemetry_mode), n_, conf_.device);
-        }
-        if (conf_.lnav) {
-            if (l5_ || b3_ || l2c_ || e5a_ || e5b_ || glo_ || conf_.trk.system != 'G')
-                throw std::invalid_argument("Gnss_Receiver_Hip: lnav decodes GPS L1 C/A channels (signal 1C)");
-            const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
+        const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
+        const auto asked = [this](bool option, Signal_Profile::Telemetry kind, const char* refusal) {
+            if (option && sig_.telemetry != kind) throw std::invalid_argument(refusal);
+            return option;
+        };
+        if (asked(conf_.telemetry, Signal_Profile::GALILEO, "Gnss_Receiver_Hip: telemetry decodes Galileo channels (signal 5X or 7X)"))
+            tlm_ = std::make_unique<Galileo_Telemetry_Decoder_Hip>(galileo_tlm_conf(sig_.telemetry_signal, max_ep, conf_.telemetry_mode), n_, conf_.device);
+        if (asked(conf_.lnav, Signal_Profile::LNAV, "Gnss_Receiver_Hip: lnav decodes GPS L1 C/A channels (signal 1C)"))
             lnav_ = std::make_unique<Gps_L1_Ca_Telemetry_Decoder_Hip>(gps_l1_ca_tlm_conf(max_ep), n_, conf_.device);
-        }
-        if (conf_.cnav) {
-            if (!l2c_ && !l5_) throw std::invalid_argument("Gnss_Receiver_Hip: cnav decodes GPS L2C or L5 channels (signal 2S or L5)");
-            const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
-            if (l5_) cnav_ = std::make_unique<Gps_L5_Telemetry_Decoder_Hip>(gps_l5_tlm_conf(max_ep), n_, conf_.device);
-            else cnav_ = std::make_unique<Gps_L2c_Telemetry_Decoder_Hip>(gps_l2c_tlm_conf(max_ep), n_, conf_.device);
-        }
-        if (conf_.dnav) {
-            if (!b3_) throw std::invalid_argument("Gnss_Receiver_Hip: dnav decodes BeiDou B3I channels (signal B3)");
-            const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
-            dnav_ = std::make_unique<Beidou_B3i_Telemetry_Decoder_Hip>(beidou_b3i_tlm_conf(max_ep), n_, conf_.device);
-        }
-        if (conf_.gnav) {
-            if (!glo_) throw std::invalid_argument("Gnss_Receiver_Hip: gnav decodes GLONASS channels (system R, signal 1G or 2G)");
-            const int32_t max_ep = static_cast<int32_t>((block_ + tail_) / std::max<int64_t>(1, vl_ - 1)) + 2;  // process_block's bound
-            if (conf_.trk.signal[0] == '2') gnav_ = std::make_unique<Glonass_L2_Ca_Telemetry_Decoder_Hip>(glonass_l2_ca_tlm_conf(max_ep), n_, conf_.device);
-            else gnav_ = std::make_unique<Glonass_L1_Ca_Telemetry_Decoder_Hip>(glonass_l1_ca_tlm_conf(max_ep), n_, conf_.device);
-        }
+        if (asked(conf_.cnav, Signal_Profile::CNAV, "Gnss_Receiver_Hip: cnav decodes GPS L2C or L5 channels (signal 2S or L5)"))
+            cnav_ = std::make_unique<Gps_Cnav_Telemetry_Decoder_Hip>(gnsship_cnav_conf{max_ep, sig_.telemetry_signal, 0}, n_, conf_.device);
+        if (asked(conf_.dnav, Signal_Profile::DNAV, "Gnss_Receiver_Hip: dnav decodes BeiDou B3I channels (signal B3)"))
+            dnav_ = std::make_unique<Beidou_Dnav_Telemetry_Decoder_Hip>(gnsship_dnav_conf{max_ep, sig_.telemetry_signal, 0}, n_, conf_.device);
+        if (asked(conf_.gnav, Signal_Profile::GNAV, "Gnss_Receiver_Hip: gnav decodes GLONASS channels (system R, signal 1G or 2G)"))
+            gnav_ = std::make_unique<Glonass_Gnav_Telemetry_Decoder_Hip>(gnsship_gnav_conf{max_ep, sig_.telemetry_signal, 0}, n_, conf_.device);
         if (conf_.use_conditioner) {
             const double fs_out = conf_.input_filter.sampling_frequency / std::max(1, conf_.input_filter.decimation_factor);
             if (fs_out != conf_.trk.fs_in || static_cast<int64_t>(fs_out) != conf_.acq.fs_in)
@@ -284,7 +362,7 @@ public:
         else if (!conf_.mitigation.empty())
             throw std::invalid_argument("Gnss_Receiver_Hip: mitigation must be Pulse_Blanking_Filter, Notch_Filter or Notch_Filter_Lite");
         // set_signals_list (GPS: 1-32, BeiDou: 1-63, Galileo: 1-36)
-        for (uint32_t p = 1; p <= (glo_ ? 24U : b3_ ? 63U : (e5a_ || e5b_) ? 36U : 32U); p++) available_.push_back(p);
+        for (uint32_t p = 1; p <= sig_.prns; p++) available_.push_back(p);
         prn_.assign(static_cast<size_t>(n_), 0U);
         apos_.assign(static_cast<size_t>(n_), 0U);
         fsm_.resize(static_cast<size_t>(n_));
@@ -403,47 +481,11 @@ private:
         f.start_tracking = [this, c]() {  // trk_->start_tracking(); queue (channel, 1)
             const Acq_Outcome& s = acq_[static_cast<size_t>(c)]->gnss_synchro();
             const uint32_t prn = prn_[static_cast<size_t>(c)];
-            if (l5_) {  // start_tracking :670-678: the L5Q pilot tracked, L5I on the data prompt
-                std::vector<float> pilot(GPS_L5Q_CODE_LENGTH_CHIPS), data(GPS_L5I_CODE_LENGTH_CHIPS);
-                if (!gps_l5q_code_gen_float(pilot.data(), prn) || !gps_l5i_code_gen_float(data.data(), prn) ||
-                    !trk_->start_tracking(c, pilot.data(), data.data(), GPS_L5Q_CODE_LENGTH_CHIPS, s.Acq_delay_samples, s.Acq_doppler_hz,
-                        s.Acq_samplestamp_samples, now_, static_cast<int>(prn)))
-                    error_ = true;
-            } else if (e5a_ || e5b_) {  // start_tracking :699-746: the X primary's imaginary part tracked, its real part the data code
-                std::vector<std::complex<float>> x(10230);
-                std::vector<float> i_code(10230), q_code(10230);
-                const std::array<char, 3> id = {{e5a_ ? '5' : '7', 'X', '\0'}};
-                bool ok = e5a_ ? galileo_e5_a_code_gen_complex_primary(x.data(), static_cast<int32_t>(prn), id)
-                               : galileo_e5_b_code_gen_complex_primary(x.data(), static_cast<int32_t>(prn), id);
-                for (size_t i = 0; i < x.size(); i++) {
-                    i_code[i] = x[i].real();
-                    q_code[i] = x[i].imag();
-                }
-                const bool pilot = conf_.trk.track_pilot;
-                if (!ok || !trk_->start_tracking(c, pilot ? q_code.data() : i_code.data(), pilot ? i_code.data() : nullptr, 10230, s.Acq_delay_samples,
-                               s.Acq_doppler_hz, s.Acq_samplestamp_samples, now_, static_cast<int>(prn)))
-                    error_ = true;
-            } else if (glo_) {  // glonass_l1_ca_dll_pll_tracking_cc::start_tracking :198-200: the one code from chip 1
-                std::vector<std::complex<float>> z(511);
-                std::vector<float> code(511);
-                glonass_l1_ca_code_gen_complex(z.data(), 0);
-                for (size_t i = 0; i < z.size(); i++) code[i] = z[i].real();
-                if (!trk_->start_tracking(c, code.data(), nullptr, 511, s.Acq_delay_samples, s.Acq_doppler_hz, s.Acq_samplestamp_samples, now_,
-                        static_cast<int>(prn)))
-                    error_ = true;
-            } else if (b3_ || l2c_) {  // start_tracking :666-668, :799-801: one replica, no data prompt
-                std::vector<float> code(10230);
-                if (!(b3_ ? beidou_b3i_code_gen_float(code.data(), static_cast<int32_t>(prn), 0) : gps_l2c_m_code_gen_float(code.data(), prn)) ||
-                    !trk_->start_tracking(c, code.data(), nullptr, 10230, s.Acq_delay_samples, s.Acq_doppler_hz, s.Acq_samplestamp_samples, now_,
-                        static_cast<int>(prn)))
-                    error_ = true;
-            } else {
-                float code[1023];
-                gnsship_gps_l1_ca_code_gen_float(code, static_cast<int32_t>(prn), 0);
-                if (!trk_->start_tracking(c, code, nullptr, 1023, s.Acq_delay_samples, s.Acq_doppler_hz, s.Acq_samplestamp_samples, now_,
-                        static_cast<int>(prn)))
-                    error_ = true;
-            }
+            std::vector<float> tracked, data;  // the local codes as the block generates them (d_tracking_code, d_data_code)
+            if (!sig_.replicas(prn, conf_.trk.track_pilot, tracked, data) ||
+                !trk_->start_tracking(c, tracked.data(), data.empty() ? nullptr : data.data(), static_cast<int>(tracked.size()), s.Acq_delay_samples,
+                    s.Acq_doppler_hz, s.Acq_samplestamp_samples, now_, static_cast<int>(prn)))
+                error_ = true;
             queue_.push_back({c, 1});
         };
         f.stop_tracking = [this, c]() { trk_->stop_tracking(c); };
@@ -460,31 +502,9 @@ private:
         if (cnav_ && !cnav_->new_channel(c)) error_ = true;  // likewise
         if (dnav_ && !dnav_->new_channel(c, static_cast<int32_t>(prn))) error_ = true;  // likewise, constructed on the PRN
         if (gnav_ && !gnav_->new_channel(c, static_cast<int32_t>(prn))) error_ = true;  // likewise
-        if (l5_) {  // GpsL5iPcpsAcquisition::set_local_code: the search runs on L5I
-            const std::vector<std::complex<float>> code = gps_l5i_acquisition_code(prn, conf_.acq);
-            if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
-            return;
-        }
-        if (e5a_ || e5b_) {  // GalileoE5aPcpsAcquisition / GalileoE5bPcpsAcquisition::set_local_code: the search runs on the I component
-            const std::vector<std::complex<float>> code = galileo_e5_acquisition_code(prn, conf_.acq, e5b_);
-            if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
-            return;
-        }
-        if (glo_) {  // GlonassL1CaPcpsAcquisition::set_local_code, and set_gnss_synchro's PRN → is_fdma()'s bias and grid
-            const std::vector<std::complex<float>> code = glonass_l1_ca_acquisition_code(conf_.acq);
-            const char sig[3] = {conf_.trk.signal[0], 'G', '\0'};
-            if (code.empty() || !acq_[static_cast<size_t>(c)]->set_gnss_synchro(sig, prn) || !acq_[static_cast<size_t>(c)]->set_local_code(code.data()))
-                error_ = true;
-            return;
-        }
-        if (b3_ || l2c_) {  // BeidouB3iPcpsAcquisition / GpsL2MPcpsAcquisition::set_local_code
-            const std::vector<std::complex<float>> code = b3_ ? beidou_b3i_acquisition_code(prn, conf_.acq) : gps_l2c_m_acquisition_code(prn, conf_.acq);
-            if (code.empty() || !acq_[static_cast<size_t>(c)]->set_local_code(code.data())) error_ = true;
-            return;
-        }
-        std::vector<float> code(2 * static_cast<size_t>(acq_[static_cast<size_t>(c)]->consumed_samples()));
-        gnsship_gps_l1_ca_code_gen_complex_sampled(code.data(), prn, static_cast<int32_t>(conf_.acq.fs_in), 0);
-        if (!acq_[static_cast<size_t>(c)]->set_local_code(reinterpret_cast<const std::complex<float>*>(code.data()))) error_ = true;
+        Pcps_Acquisition_Hip& a = *acq_[static_cast<size_t>(c)];
+        const Signal_Profile::Code code = sig_.acquisition_code(a, prn, conf_.acq);
+        if (code.empty() || (sig_.fdma_signal && !a.set_gnss_synchro(sig_.fdma_signal, prn)) || !a.set_local_code(code.data())) error_ = true;
     }
     void start_acquisition(int c) { fsm_[static_cast<size_t>(c)].Event_start_acquisition(); }  // Channel::start_acquisition
 
@@ -567,6 +587,41 @@ private:
         }
     }
 
+    // An acquisition decision of channel c at now_: the event, then channel_msg_receiver_cc::msg_handler_channel_events (:64-100)
+    void acquisition_event(int c, Pcps_Acquisition_Hip::Acq_Event ev)
+    {
+        const Acq_Outcome& s = acq_[static_cast<size_t>(c)]->gnss_synchro();
+        events_.push_back({now_, c, ev == Pcps_Acquisition_Hip::ACQ_SUCCESS ? 1 : 0, prn_[static_cast<size_t>(c)], s.Acq_doppler_hz, s.Acq_delay_samples,
+            s.test_statistics});
+        ChannelFsm& f = fsm_[static_cast<size_t>(c)];
+        if (ev == Pcps_Acquisition_Hip::ACQ_SUCCESS)
+            f.Event_valid_acquisition();
+        else if (conf_.repeat_satellite)
+            f.Event_failed_acquisition_repeat();
+        else
+            f.Event_failed_acquisition_no_repeat();
+        drain();
+    }
+
+    // One telemetry decoder (when configured) over the records tracking left on the device: every record it emitted goes to
+    // `out` with the channel's PRN (and extra(slot)...), channel by channel; a channel's fault, in the families that raise
+    // them, goes back to its tracking (msg_handler_telemetry_to_trk).
+    template <class Decoder, class Out, class... Extra>
+    bool decode(const std::unique_ptr<Decoder>& d, std::vector<Out>& out, Extra... extra)
+    {
+        if (!d) return true;
+        if (!d->work_trk(*trk_)) return false;
+        for (int c = 0; c < n_; c++) {
+            for (int k = 0; k < d->counts()[static_cast<size_t>(c)]; k++) {
+                const size_t slot = static_cast<size_t>(c) * static_cast<size_t>(d->per_run()) + static_cast<size_t>(k);
+                out.push_back({prn_[static_cast<size_t>(c)], d->records()[slot], extra(slot)...});
+            }
+            if constexpr (Decoder::has_faults)
+                if (d->faults()[static_cast<size_t>(c)] && !trk_->msg_handler_telemetry_to_trk(c, 1)) return false;
+        }
+        return true;
+    }
+
     bool process_block(const std::complex<float>* x, int64_t n)
     {
         const uint64_t b0 = pos_, b1 = pos_ + static_cast<uint64_t>(n);
@@ -586,40 +641,16 @@ private:
             apos_[static_cast<size_t>(c)] = p + static_cast<uint64_t>(used);
             now_ = apos_[static_cast<size_t>(c)];
             if (ev != Pcps_Acquisition_Hip::ACQ_NONE) {
-                const Acq_Outcome& s = a.gnss_synchro();
-                events_.push_back({now_, c, ev == Pcps_Acquisition_Hip::ACQ_SUCCESS ? 1 : 0, prn_[static_cast<size_t>(c)], s.Acq_doppler_hz,
-                    s.Acq_delay_samples, s.test_statistics});
-                // channel_msg_receiver_cc::msg_handler_channel_events (:64-100)
-                ChannelFsm& f = fsm_[static_cast<size_t>(c)];
-                if (ev == Pcps_Acquisition_Hip::ACQ_SUCCESS)
-                    f.Event_valid_acquisition();
-                else if (conf_.repeat_satellite)
-                    f.Event_failed_acquisition_repeat();
-                else
-                    f.Event_failed_acquisition_no_repeat();
-                drain();
+                acquisition_event(c, ev);
             } else if (used == 0 && !a.worker_active()) {
                 // a decision is pending in state 2 (blocking: the next call makes it); a block that can
                 // consume nothing more in this piece ends the channel's turn
                 Pcps_Acquisition_Hip::Acq_Event ev2 = Pcps_Acquisition_Hip::ACQ_NONE;
                 const int used2 = a.general_work(x + (p - b0), m, &ev2);
-                if (used2 == 0 && ev2 == Pcps_Acquisition_Hip::ACQ_NONE) apos_[static_cast<size_t>(c)] = b1;
-                else if (ev2 != Pcps_Acquisition_Hip::ACQ_NONE) {
-                    apos_[static_cast<size_t>(c)] = p + static_cast<uint64_t>(used2);
+                apos_[static_cast<size_t>(c)] = used2 == 0 && ev2 == Pcps_Acquisition_Hip::ACQ_NONE ? b1 : p + static_cast<uint64_t>(used2);
+                if (ev2 != Pcps_Acquisition_Hip::ACQ_NONE) {
                     now_ = apos_[static_cast<size_t>(c)];
-                    const Acq_Outcome& s = a.gnss_synchro();
-                    events_.push_back({now_, c, ev2 == Pcps_Acquisition_Hip::ACQ_SUCCESS ? 1 : 0, prn_[static_cast<size_t>(c)], s.Acq_doppler_hz,
-                        s.Acq_delay_samples, s.test_statistics});
-                    ChannelFsm& f = fsm_[static_cast<size_t>(c)];
-                    if (ev2 == Pcps_Acquisition_Hip::ACQ_SUCCESS)
-                        f.Event_valid_acquisition();
-                    else if (conf_.repeat_satellite)
-                        f.Event_failed_acquisition_repeat();
-                    else
-                        f.Event_failed_acquisition_no_repeat();
-                    drain();
-                } else {
-                    apos_[static_cast<size_t>(c)] = p + static_cast<uint64_t>(used2);
+                    acquisition_event(c, ev2);
                 }
             }
             if (error_) return false;
@@ -631,10 +662,7 @@ private:
         win_.insert(win_.end(), x, x + n);
         const int64_t wn = static_cast<int64_t>(win_.size());
         if (!ensure_dev(static_cast<size_t>(wn) * sizeof(std::complex<float>))) return false;
-        {
-            std::lock_guard<std::mutex> lk(dev_->mutex());
-            if (gnsship_dev_upload(dev_->ctx(), dev_buf_, win_.data(), static_cast<size_t>(wn) * sizeof(std::complex<float>)) != GNSSHIP_OK) return false;
-        }
+        if (!dev_->call(gnsship_dev_upload, dev_->ctx(), dev_buf_, win_.data(), static_cast<size_t>(wn) * sizeof(std::complex<float>))) return false;
         const int max_ep = static_cast<int>(wn / std::max<int64_t>(1, vl_ - 1)) + 2;
         rec_buf_.assign(static_cast<size_t>(max_ep) * n_, gnsship_trk_epoch{});
         const bool dump = !conf_.dump_filename.empty();
@@ -642,50 +670,13 @@ private:
         const int rounds = trk_->work_dump(reinterpret_cast<const std::complex<float>*>(dev_buf_), win_first_, wn, max_ep, rec_buf_.data(),
             dump ? dump_buf_.data() : nullptr, true);
         if (rounds < 0) return false;
-        if (tlm_) {  // the records where tracking left them; a fault goes back to the channel's tracking (telemetry_to_trk)
-            if (!tlm_->work_trk(*trk_)) return false;
-            const size_t LL = static_cast<size_t>(tlm_->data_length()), ppr = static_cast<size_t>(tlm_->pages_per_run());
-            for (int c = 0; c < n_; c++) {
-                for (int k = 0; k < tlm_->counts()[static_cast<size_t>(c)]; k++) {
-                    const size_t slot = static_cast<size_t>(c) * ppr + static_cast<size_t>(k);
-                    const uint8_t* b = tlm_->bits().data() + slot * LL;
-                    pages_.push_back({prn_[static_cast<size_t>(c)], tlm_->pages()[slot], std::vector<uint8_t>(b, b + LL)});
-                }
-                if (tlm_->faults()[static_cast<size_t>(c)] && !trk_->msg_handler_telemetry_to_trk(c, 1)) return false;
-            }
-        }
-        if (lnav_) {  // likewise for the GPS L1 C/A decoder
-            if (!lnav_->work_trk(*trk_)) return false;
-            const size_t spr = static_cast<size_t>(lnav_->subframes_per_run());
-            for (int c = 0; c < n_; c++) {
-                for (int k = 0; k < lnav_->counts()[static_cast<size_t>(c)]; k++)
-                    subframes_.push_back({prn_[static_cast<size_t>(c)], lnav_->subframes()[static_cast<size_t>(c) * spr + static_cast<size_t>(k)]});
-                if (lnav_->faults()[static_cast<size_t>(c)] && !trk_->msg_handler_telemetry_to_trk(c, 1)) return false;
-            }
-        }
-        if (cnav_) {  // and for the GPS CNAV decoder
-            if (!cnav_->work_trk(*trk_)) return false;
-            const size_t mpr = static_cast<size_t>(cnav_->messages_per_run());
-            for (int c = 0; c < n_; c++) {
-                for (int k = 0; k < cnav_->counts()[static_cast<size_t>(c)]; k++)
-                    cnav_messages_.push_back({prn_[static_cast<size_t>(c)], cnav_->messages()[static_cast<size_t>(c) * mpr + static_cast<size_t>(k)]});
-                if (cnav_->faults()[static_cast<size_t>(c)] && !trk_->msg_handler_telemetry_to_trk(c, 1)) return false;
-            }
-        }
-        if (dnav_) {  // and for the BeiDou D1/D2 decoder, which has no fault to hand back
-            if (!dnav_->work_trk(*trk_)) return false;
-            const size_t spr = static_cast<size_t>(dnav_->subframes_per_run());
-            for (int c = 0; c < n_; c++)
-                for (int k = 0; k < dnav_->counts()[static_cast<size_t>(c)]; k++)
-                    dnav_subframes_.push_back({prn_[static_cast<size_t>(c)], dnav_->subframes()[static_cast<size_t>(c) * spr + static_cast<size_t>(k)]});
-        }
-        if (gnav_) {  // and for the GLONASS GNAV decoder, likewise
-            if (!gnav_->work_trk(*trk_)) return false;
-            const size_t spr = static_cast<size_t>(gnav_->strings_per_run());
-            for (int c = 0; c < n_; c++)
-                for (int k = 0; k < gnav_->counts()[static_cast<size_t>(c)]; k++)
-                    gnav_strings_.push_back({prn_[static_cast<size_t>(c)], gnav_->strings()[static_cast<size_t>(c) * spr + static_cast<size_t>(k)]});
-        }
+        const auto page_bits = [this](size_t slot) {  // Galileo's one extra: the page part's data bits
+            const uint8_t* b = tlm_->bits().data() + slot * static_cast<size_t>(tlm_->data_length());
+            return std::vector<uint8_t>(b, b + tlm_->data_length());
+        };
+        if (!decode(tlm_, pages_, page_bits) || !decode(lnav_, subframes_) || !decode(cnav_, cnav_messages_) || !decode(dnav_, dnav_subframes_) ||
+            !decode(gnav_, gnav_strings_))
+            return false;
         recs_.resize(static_cast<size_t>(n_));
         for (int c = 0; c < n_; c++) {
             bool lost = false;
@@ -729,6 +720,7 @@ public:
 private:
     Receiver_Conf conf_;
     std::shared_ptr<Device> dev_;
+    const Signal_Profile& sig_;  // what the channels' signal decides
     int n_ = 1, max_acq_ = 1, acq_count_ = 0;
     int64_t vl_ = 0, block_ = 0, tail_ = 0;
     std::unique_ptr<Dll_Pll_Veml_Tracking_Hip> trk_;
@@ -738,7 +730,7 @@ private:
     std::vector<Receiver_Subframe> subframes_;
     std::unique_ptr<Gps_Cnav_Telemetry_Decoder_Hip> cnav_;  // the optional GPS CNAV telemetry (L2C or L5)
     std::vector<Receiver_Cnav_Message> cnav_messages_;
-    std::unique_ptr<Beidou_B3i_Telemetry_Decoder_Hip> dnav_;  // the optional BeiDou D1/D2 telemetry (B3I)
+    std::unique_ptr<Beidou_Dnav_Telemetry_Decoder_Hip> dnav_;  // the optional BeiDou D1/D2 telemetry (B3I)
     std::vector<Receiver_Dnav_Subframe> dnav_subframes_;
     std::unique_ptr<Glonass_Gnav_Telemetry_Decoder_Hip> gnav_;  // the optional GLONASS GNAV telemetry (L1 or L2 C/A)
     std::vector<Receiver_Gnav_String> gnav_strings_;
@@ -769,10 +761,6 @@ private:
     std::vector<gnsship_trk_epoch> rec_buf_;
     std::vector<gnsship_trk_dump_record> dump_buf_;
     bool error_ = false;
-    bool l5_ = false;  // GPS L5 channels (acquisition L5I, tracking L5Q pilot + L5I prompt)
-    bool b3_ = false, l2c_ = false;  // BeiDou B3I / GPS L2C channels (acquisition and tracking on one code)
-    bool e5a_ = false, e5b_ = false;  // Galileo E5a / E5b channels (acquisition on the I component, tracking on the Q pilot)
-    bool glo_ = false;  // GLONASS L1 / L2 C/A channels (one code, each satellite under its FDMA bias)
 };
 
 }  // namespace gnsship
