@@ -150,9 +150,7 @@ static void acq_graph_reset(gnsship_acq* a)
 static void acq_free_grid_buffers(gnsship_acq* a)
 {
     acq_graph_reset(a);
-    void* ptrs[] = {a->T, a->U, a->tiles, a->wipe, a->X, a->rowstat};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    free_all({a->T, a->U, a->tiles, a->wipe, a->X, a->rowstat});
     a->T = nullptr;
     a->U = nullptr;
     a->tiles = nullptr;
@@ -166,13 +164,10 @@ static void acq_free_grid_buffers(gnsship_acq* a)
 extern "C" int gnsship_acq_destroy(gnsship_acq* a)
 {
     if (!a) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(a->ctx->device);
-    (void)hipStreamSynchronize(a->ctx->stream);
+    quiesce(a->ctx);
     acq_free_grid_buffers(a);
     acq_graph_reset(a);
-    void* ptrs[] = {a->tw, a->twM, a->twC, a->codes_fft, a->sig_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    free_all({a->tw, a->twM, a->twC, a->codes_fft, a->sig_dev});
     if (a->res_host) (void)hipHostFree(a->res_host);
     if (a->lane_stream) (void)hipStreamDestroy(a->lane_stream);
     if (a->ev_fwd) (void)hipEventDestroy(a->ev_fwd);

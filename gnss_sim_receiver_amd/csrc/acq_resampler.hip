@@ -173,11 +173,8 @@ extern "C" int gnsship_acq_resampler_design(int64_t fs_in, double opt_acq_fs, in
 extern "C" int gnsship_acq_resampler_destroy(gnsship_acq_resampler* r)
 {
     if (!r) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(r->ctx->device);
-    (void)hipStreamSynchronize(r->ctx->stream);
-    void* ptrs[] = {r->taps_rev_dev, r->hist_dev[0], r->hist_dev[1], r->out_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    quiesce(r->ctx);
+    free_all({r->taps_rev_dev, r->hist_dev[0], r->hist_dev[1], r->out_dev});
     release(r->stage_dev);
     delete r;
     return GNSSHIP_OK;
@@ -202,14 +199,12 @@ extern "C" int gnsship_acq_resampler_create(gnsship_ctx* ctx, const float* taps,
     r->max_in = max_in_samples;
     std::vector<float> rev(n_taps);
     for (int t = 0; t < n_taps; t++) rev[t] = taps[n_taps - 1 - t];  // fir_filter's d_taps (reversed)
-    const size_t hist_bytes = sizeof(float2) * static_cast<size_t>(n_taps > 1 ? n_taps - 1 : 1);
+    const size_t n_hist = static_cast<size_t>(n_taps > 1 ? n_taps - 1 : 1);
     hipError_t e = hipMalloc(&r->taps_rev_dev, sizeof(float) * n_taps);
     if (e == hipSuccess) e = hipMemcpy(r->taps_rev_dev, rev.data(), sizeof(float) * n_taps, hipMemcpyHostToDevice);
-    for (int b = 0; b < 2 && e == hipSuccess; b++) {
-        e = hipMalloc(&r->hist_dev[b], hist_bytes);
-        if (e == hipSuccess) e = hipMemset(r->hist_dev[b], 0, hist_bytes);
-    }
-    if (e == hipSuccess) e = hipMalloc(&r->out_dev, sizeof(float2) * static_cast<size_t>(max_in_samples / decimation));
+    if (e == hipSuccess)  // the histories are zeroed on the stream: ordered before the runs
+        e = alloc_all(ctx, {dev_alloc(&r->hist_dev[0], n_hist, true), dev_alloc(&r->hist_dev[1], n_hist, true),
+                               dev_alloc(&r->out_dev, static_cast<size_t>(max_in_samples / decimation))});
     if (e != hipSuccess) {
         gnsship_acq_resampler_destroy(r);
         return hip_fail(ctx, e, "gnsship_acq_resampler_create");
@@ -241,10 +236,7 @@ extern "C" int gnsship_acq_resampler_run(gnsship_acq_resampler* r, const void* i
     if (int rc = set_device(ctx)) return rc;
     const void* src = in;
     if (!in_on_device) {
-        const size_t bytes = fmt_bytes(fmt) * static_cast<size_t>(n_in);
-        if (int rc = reserve(ctx, r->stage_dev, bytes, "gnsship_acq_resampler_run", "stage")) return rc;
-        hipError_t e = hipMemcpyAsync(r->stage_dev.dev, in, bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_acq_resampler_run(upload)");
+        if (int rc = stage(ctx, r->stage_dev, in, fmt_bytes(fmt) * static_cast<size_t>(n_in), "gnsship_acq_resampler_run", "stage")) return rc;
         src = r->stage_dev.dev;
     }
     const int64_t nk = n_in / r->decim;
@@ -255,34 +247,25 @@ extern "C" int gnsship_acq_resampler_run(gnsship_acq_resampler* r, const void* i
     float2* hist_next = r->hist_dev[r->hist_cur ^ 1];
     const int n_hist = r->ntaps - 1;
     const int hb = (n_hist + 255) / 256;
+#define GNSSHIP_FIR_LAUNCH(FMT)                                                                                                        \
+    hipLaunchKernelGGL(fir_decim_kernel<FMT>, dim3(static_cast<unsigned>(blocks)), dim3(kFirThreads), lds, ctx->stream, src, hist,      \
+        r->taps_rev_dev, r->ntaps, r->decim, r->opb, nk, r->out_dev);                                                                   \
+    if (n_hist > 0) hipLaunchKernelGGL(fir_history_kernel<FMT>, dim3(hb), dim3(256), 0, ctx->stream, src, n_in, hist, n_hist, hist_next)
     switch (fmt) {
     case GNSSHIP_FMT_CF32:
-        hipLaunchKernelGGL(fir_decim_kernel<GNSSHIP_FMT_CF32>, dim3(static_cast<unsigned>(blocks)), dim3(kFirThreads), lds, ctx->stream, src, hist,
-            r->taps_rev_dev, r->ntaps, r->decim, r->opb, nk, r->out_dev);
-        if (n_hist > 0)
-            hipLaunchKernelGGL(fir_history_kernel<GNSSHIP_FMT_CF32>, dim3(hb), dim3(256), 0, ctx->stream, src, n_in, hist, n_hist, hist_next);
+        GNSSHIP_FIR_LAUNCH(GNSSHIP_FMT_CF32);
         break;
     case GNSSHIP_FMT_CI16:
-        hipLaunchKernelGGL(fir_decim_kernel<GNSSHIP_FMT_CI16>, dim3(static_cast<unsigned>(blocks)), dim3(kFirThreads), lds, ctx->stream, src, hist,
-            r->taps_rev_dev, r->ntaps, r->decim, r->opb, nk, r->out_dev);
-        if (n_hist > 0)
-            hipLaunchKernelGGL(fir_history_kernel<GNSSHIP_FMT_CI16>, dim3(hb), dim3(256), 0, ctx->stream, src, n_in, hist, n_hist, hist_next);
+        GNSSHIP_FIR_LAUNCH(GNSSHIP_FMT_CI16);
         break;
     default:
-        hipLaunchKernelGGL(fir_decim_kernel<GNSSHIP_FMT_CI8>, dim3(static_cast<unsigned>(blocks)), dim3(kFirThreads), lds, ctx->stream, src, hist,
-            r->taps_rev_dev, r->ntaps, r->decim, r->opb, nk, r->out_dev);
-        if (n_hist > 0)
-            hipLaunchKernelGGL(fir_history_kernel<GNSSHIP_FMT_CI8>, dim3(hb), dim3(256), 0, ctx->stream, src, n_in, hist, n_hist, hist_next);
+        GNSSHIP_FIR_LAUNCH(GNSSHIP_FMT_CI8);
         break;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_acq_resampler_run(launch)");
+#undef GNSSHIP_FIR_LAUNCH
+    if (int rc = launched(ctx, "gnsship_acq_resampler_run(launch)")) return rc;
     if (n_hist > 0) r->hist_cur ^= 1;
-    if (host_out) {
-        e = hipMemcpyAsync(host_out, r->out_dev, sizeof(float2) * static_cast<size_t>(nk), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_acq_resampler_run(download)");
-    }
+    if (int rc = copy_out(ctx, {{host_out, r->out_dev, sizeof(float2) * static_cast<size_t>(nk)}}, "gnsship_acq_resampler_run(download)")) return rc;
     if (dev_out) *dev_out = r->out_dev;
     if (n_out) *n_out = nk;
     return GNSSHIP_OK;

@@ -306,15 +306,9 @@ extern "C" int gnsship_cond_lowpass_taps(double fs, int decimation, double bw, d
 extern "C" int gnsship_cond_destroy(gnsship_cond* c)
 {
     if (!c) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(c->ctx->device);
-    (void)hipStreamSynchronize(c->ctx->stream);
-    for (int b = 0; b < kCondMaxBands; b++) {
-        if (c->taps_dev[b]) (void)hipFree(c->taps_dev[b]);
-        if (c->out_dev[b]) (void)hipFree(c->out_dev[b]);
-    }
-    void* ptrs[] = {c->hist_dev[0], c->hist_dev[1], c->count_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    quiesce(c->ctx);
+    for (int b = 0; b < kCondMaxBands; b++) free_all({c->taps_dev[b], c->out_dev[b]});
+    free_all({c->hist_dev[0], c->hist_dev[1], c->count_dev});
     release(c->stage_dev);
     delete c;
     return GNSSHIP_OK;
@@ -351,7 +345,7 @@ extern "C" int gnsship_cond_create(gnsship_ctx* ctx, double fs_in, const gnsship
     c->max_in = max_in_samples;
     c->n_hist = t_max - 1;
     c->tile = (c->n_hist <= kCondSpanSmall / 2 ? kCondSpanSmall : kCondSpanLarge) - c->n_hist;  // >= half the span
-    const size_t hist_bytes = sizeof(float2) * static_cast<size_t>(c->n_hist > 0 ? c->n_hist : 1);
+    const size_t n_hist_alloc = static_cast<size_t>(c->n_hist > 0 ? c->n_hist : 1);
     hipError_t e = hipSuccess;
     for (int b = 0; b < n_bands && e == hipSuccess; b++) {
         const gnsship_cond_band& bd = bands[b];
@@ -367,12 +361,8 @@ extern "C" int gnsship_cond_create(gnsship_ctx* ctx, double fs_in, const gnsship
         c->band[b].fc_mod = static_cast<uint32_t>(fc);
         c->band[b].step_mod = static_cast<uint32_t>((static_cast<uint64_t>(fc) * kCondThreads) % static_cast<uint64_t>(fs));
     }
-    for (int h = 0; h < 2 && e == hipSuccess; h++) {
-        e = hipMalloc(&c->hist_dev[h], hist_bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(c->hist_dev[h], 0, hist_bytes, ctx->stream);  // ordered before the runs
-    }
-    if (e == hipSuccess) e = hipMalloc(&c->count_dev, 2 * sizeof(int64_t));
-    if (e == hipSuccess) e = hipMemsetAsync(c->count_dev, 0, 2 * sizeof(int64_t), ctx->stream);
+    if (e == hipSuccess)  // zeroed on the stream: ordered before the runs
+        e = alloc_all(ctx, {dev_alloc(&c->hist_dev[0], n_hist_alloc, true), dev_alloc(&c->hist_dev[1], n_hist_alloc, true), dev_alloc(&c->count_dev, 2, true)});
     if (e != hipSuccess) {
         gnsship_cond_destroy(c);
         return hip_fail(ctx, e, "gnsship_cond_create");
@@ -420,9 +410,7 @@ extern "C" int gnsship_cond_run(gnsship_cond* c, const void* in, int fmt, int in
     const void* src = in;
     if (!in_on_device) {
         const size_t bytes = (static_cast<size_t>(n_in) * static_cast<size_t>(bps) + 7) / 8;
-        if (int rc = reserve(ctx, c->stage_dev, bytes, "gnsship_cond_run", "stage")) return rc;
-        hipError_t e = hipMemcpyAsync(c->stage_dev.dev, in, bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_cond_run(upload)");
+        if (int rc = stage(ctx, c->stage_dev, in, bytes, "gnsship_cond_run", "stage")) return rc;
         src = c->stage_dev.dev;
     }
     CondArgs a;
@@ -476,24 +464,15 @@ extern "C" int gnsship_cond_run(gnsship_cond* c, const void* in, int fmt, int in
         break;
     }
 #undef GNSSHIP_COND_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_cond_run(launch)");
+    if (int rc = launched(ctx, "gnsship_cond_run(launch)")) return rc;
     c->cur ^= 1;
     c->count_host += n_in;
-    bool waited = false;
+    DevCopy copies[kCondMaxBands] = {};
     for (int b = 0; b < c->n_bands; b++) {
         const int64_t nk = n_in / c->band[b].decim;
-        if (host_out && host_out[b]) {
-            e = hipMemcpyAsync(host_out[b], a.band[b].out, sizeof(float2) * static_cast<size_t>(nk), hipMemcpyDeviceToHost, ctx->stream);
-            if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_cond_run(download)");
-            waited = true;
-        }
+        if (host_out) copies[b] = {host_out[b], a.band[b].out, sizeof(float2) * static_cast<size_t>(nk)};
         if (dev_out) dev_out[b] = a.band[b].out;
         if (n_out) n_out[b] = nk;
     }
-    if (waited) {
-        e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_cond_run(download)");
-    }
-    return GNSSHIP_OK;
+    return copy_out(ctx, copies, static_cast<size_t>(c->n_bands), "gnsship_cond_run(download)");
 }

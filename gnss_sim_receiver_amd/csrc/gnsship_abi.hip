@@ -270,8 +270,7 @@ extern "C" int gnsship_ctx_create(int device, gnsship_ctx** out)
 extern "C" int gnsship_ctx_destroy(gnsship_ctx* ctx)
 {
     if (!ctx) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    quiesce(ctx);
     for (auto& c : ctx->codes_host)
         if (c.ptr) (void)free_padded_code(c.ptr);
     release(ctx->codes_dev);
@@ -639,8 +638,7 @@ extern "C" int gnsship_batch_destroy(gnsship_batch* b)
 {
     if (!b) return GNSSHIP_E_INVAL;
     gnsship_ctx* ctx = b->ctx;
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
+    quiesce(ctx);
     if (b->aux) (void)hipStreamSynchronize(b->aux);
     batch_release(b);
     return GNSSHIP_OK;
@@ -819,13 +817,10 @@ extern "C" int gnsship_corr_run(gnsship_corr* c, const void* sig, int fmt, int s
 extern "C" int gnsship_corr_destroy(gnsship_corr* c)
 {
     if (!c) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(c->ctx->device);
-    (void)hipStreamSynchronize(c->ctx->stream);
+    quiesce(c->ctx);
     (void)free_padded_code(c->code_dev);
     hd_plan_free(c->hd);
-    void* ptrs[] = {c->code_table_dev, c->sig_dev, c->job_dev, c->chunks_dev, c->items_dev, c->partials_dev, c->out_dev, c->anchors_dev, c->serial_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    free_all({c->code_table_dev, c->sig_dev, c->job_dev, c->chunks_dev, c->items_dev, c->partials_dev, c->out_dev, c->anchors_dev, c->serial_dev});
     delete c;
     return GNSSHIP_OK;
 }

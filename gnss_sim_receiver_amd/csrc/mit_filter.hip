@@ -502,7 +502,7 @@ struct gnsship_mit {
     uint8_t* spec_dev = nullptr;
     MitDevState* st_dev = nullptr;
     float2* twiddle_dev = nullptr;
-    void* stage_dev = nullptr;
+    DevBuf stage_dev;  // host input: sized once, to max_in samples, at the first host run
 };
 
 extern "C" int gnsship_mit_threshold(double pfa, int length, float* thres)
@@ -518,12 +518,10 @@ extern "C" int gnsship_mit_threshold(double pfa, int length, float* thres)
 extern "C" int gnsship_mit_destroy(gnsship_mit* m)
 {
     if (!m) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(m->ctx->device);
-    (void)hipStreamSynchronize(m->ctx->stream);
-    void* ptrs[] = {m->carry_dev[0], m->carry_dev[1], m->out_dev, m->a_dev, m->b_dev, m->energy_dev, m->zseg_dev, m->code_dev,
-        m->y_pred_dev, m->y_end_dev, m->spec_dev, m->st_dev, m->twiddle_dev, m->stage_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    quiesce(m->ctx);
+    free_all({m->carry_dev[0], m->carry_dev[1], m->out_dev, m->a_dev, m->b_dev, m->energy_dev, m->zseg_dev, m->code_dev, m->y_pred_dev,
+        m->y_end_dev, m->spec_dev, m->st_dev, m->twiddle_dev});
+    release(m->stage_dev);
     delete m;
     return GNSSHIP_OK;
 }
@@ -589,23 +587,13 @@ extern "C" int gnsship_mit_create(gnsship_ctx* ctx, const gnsship_mit_conf* conf
     const int64_t seg_cap = m->out_cap / L + 1;
     const int64_t chunk_cap = seg_cap / m->chunk_segs + 1;
     const bool notch = conf->kind != GNSSHIP_MIT_PULSE_BLANKING;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](auto** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(p), bytes);
-    };
-    for (int h = 0; h < 2; h++) alloc(&m->carry_dev[h], sizeof(float2) * (L + 2));
-    alloc(&m->out_dev, sizeof(float2) * m->out_cap);
-    alloc(&m->energy_dev, sizeof(float) * seg_cap);
-    alloc(&m->code_dev, seg_cap);
-    alloc(&m->st_dev, sizeof(MitDevState));
+    hipError_t e = alloc_all(ctx, {dev_alloc(&m->carry_dev[0], L + 2), dev_alloc(&m->carry_dev[1], L + 2), dev_alloc(&m->out_dev, m->out_cap),
+                                      dev_alloc(&m->energy_dev, seg_cap), dev_alloc(&m->code_dev, seg_cap), dev_alloc(&m->st_dev, 1)});
     if (notch) {
-        alloc(&m->a_dev, sizeof(float2) * m->out_cap);
-        alloc(&m->b_dev, sizeof(float2) * m->out_cap);
-        alloc(&m->zseg_dev, sizeof(float2) * seg_cap);
-        alloc(&m->y_pred_dev, sizeof(float2) * chunk_cap);
-        alloc(&m->y_end_dev, sizeof(float2) * chunk_cap);
-        alloc(&m->spec_dev, chunk_cap);
-        alloc(&m->twiddle_dev, sizeof(float2) * L);
+        if (e == hipSuccess)
+            e = alloc_all(ctx, {dev_alloc(&m->a_dev, m->out_cap), dev_alloc(&m->b_dev, m->out_cap), dev_alloc(&m->zseg_dev, seg_cap),
+                                   dev_alloc(&m->y_pred_dev, chunk_cap), dev_alloc(&m->y_end_dev, chunk_cap), dev_alloc(&m->spec_dev, chunk_cap)});
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&m->twiddle_dev), sizeof(float2) * L);
         if (e == hipSuccess) {
             float2 tw[kMitMaxLen];
             const double pi = 3.14159265358979323846;
@@ -634,9 +622,7 @@ extern "C" int gnsship_mit_state_get(gnsship_mit* m, gnsship_mit_state* st)
     gnsship_ctx* ctx = m->ctx;
     if (int rc = set_device(ctx)) return rc;
     MitDevState d;
-    hipError_t e = hipMemcpyAsync(&d, m->st_dev, sizeof(d), hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_mit_state_get");
+    if (int rc = copy_out(ctx, {{&d, m->st_dev, sizeof(d)}}, "gnsship_mit_state_get")) return rc;
     st->noise_power = d.noise;
     st->threshold = m->thres;
     st->n_segments = d.n_segments;
@@ -663,13 +649,11 @@ extern "C" int gnsship_mit_run(gnsship_mit* m, const void* in, int in_on_device,
     if (int rc = set_device(ctx)) return rc;
     const void* src = in;
     if (!in_on_device && n_in > 0) {
-        if (!m->stage_dev) {
-            hipError_t e = hipMalloc(&m->stage_dev, sizeof(float2) * static_cast<size_t>(m->max_in));
-            if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_mit_run(stage)");
-        }
-        hipError_t e = hipMemcpyAsync(m->stage_dev, in, sizeof(float2) * static_cast<size_t>(n_in), hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_mit_run(upload)");
-        src = m->stage_dev;
+        // sized once, at the first host run, to the largest run there can be
+        if (int rc = stage(ctx, m->stage_dev, in, sizeof(float2) * static_cast<size_t>(n_in), "gnsship_mit_run", "stage",
+                sizeof(float2) * static_cast<size_t>(m->max_in)))
+            return rc;
+        src = m->stage_dev.dev;
     }
     const int L = m->conf.length;
     const int64_t avail = m->n_pending + n_in;  // <= max_in + L
@@ -721,8 +705,7 @@ extern "C" int gnsship_mit_run(gnsship_mit* m, const void* in, int in_on_device,
             }
         }
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_mit_run(launch)");
+    if (int rc = launched(ctx, "gnsship_mit_run(launch)")) return rc;
     m->carry_cur ^= 1;
     m->cur ^= 1;
     m->n_pending = avail - nk;
@@ -730,10 +713,9 @@ extern "C" int gnsship_mit_run(gnsship_mit* m, const void* in, int in_on_device,
     m->samples_out += static_cast<uint64_t>(nk);
     if (dev_out) *dev_out = a.out;
     if (n_out) *n_out = nk;
-    if (host_out) {
-        if (nk > 0) e = hipMemcpyAsync(host_out, a.out, sizeof(float2) * static_cast<size_t>(nk), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (host_out && nk == 0) {  // a host run returns finished even when it emits nothing: copy_out would not wait
+        const hipError_t e = hipStreamSynchronize(ctx->stream);
         if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_mit_run(download)");
     }
-    return GNSSHIP_OK;
+    return copy_out(ctx, {{host_out, a.out, sizeof(float2) * static_cast<size_t>(nk)}}, "gnsship_mit_run(download)");
 }

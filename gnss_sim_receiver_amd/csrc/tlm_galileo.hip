@@ -353,7 +353,7 @@ struct gnsship_tlm {
 extern "C" int gnsship_tlm_destroy(gnsship_tlm* t)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    tlm_release(t->h, {t->chans_dev, t->ring_dev, t->sections_dev, t->pages_dev, t->bits_dev, t->counts_dev, t->faults_dev, t->crc_dev});
+    t->h.release_all({t->chans_dev, t->ring_dev, t->sections_dev, t->pages_dev, t->bits_dev, t->counts_dev, t->faults_dev, t->crc_dev});
     delete t;
     return GNSSHIP_OK;
 }
@@ -361,7 +361,7 @@ extern "C" int gnsship_tlm_destroy(gnsship_tlm* t)
 static int tlm_fill_sections(gnsship_tlm* t, int64_t first, int64_t n, const char* where)
 {
     hipLaunchKernelGGL(tlm_fill_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, t->h.ctx->stream, t->sections_dev + first, n, -kVitMaxLog);
-    return tlm_launched(t->h.ctx, where);
+    return launched(t->h.ctx, where);
 }
 
 extern "C" int gnsship_tlm_create(gnsship_ctx* ctx, const gnsship_tlm_conf* conf, int32_t max_channels, gnsship_tlm** out)
@@ -401,9 +401,9 @@ extern "C" int gnsship_tlm_create(gnsship_ctx* ctx, const gnsship_tlm_conf* conf
     }
     for (int i = 0; i < n; i++) table[i] = rem[n - 1 - i + 24];
     const size_t nc = static_cast<size_t>(max_channels), slots = nc * t->pages_per_run;
-    hipError_t e = tlm_alloc(ctx, {tlm_buf(&t->chans_dev, nc, true), tlm_buf(&t->ring_dev, nc * t->cap, true), tlm_buf(&t->sections_dev, 64 * nc, false),
-                                      tlm_buf(&t->pages_dev, slots, true), tlm_buf(&t->bits_dev, slots * t->geo.LL, true), tlm_buf(&t->counts_dev, nc, true),
-                                      tlm_buf(&t->faults_dev, nc, true), tlm_buf(&t->crc_dev, static_cast<size_t>(n), false)});
+    hipError_t e = alloc_all(ctx, {dev_alloc(&t->chans_dev, nc, true), dev_alloc(&t->ring_dev, nc * t->cap, true), dev_alloc(&t->sections_dev, 64 * nc, false),
+                                      dev_alloc(&t->pages_dev, slots, true), dev_alloc(&t->bits_dev, slots * t->geo.LL, true), dev_alloc(&t->counts_dev, nc, true),
+                                      dev_alloc(&t->faults_dev, nc, true), dev_alloc(&t->crc_dev, static_cast<size_t>(n), false)});
     if (e == hipSuccess) e = hipMemcpyAsync(t->crc_dev, table.data(), sizeof(uint32_t) * n, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // `table` is a local
     if (e != hipSuccess) {
@@ -453,9 +453,9 @@ static int tlm_launch(gnsship_tlm* t, const float* sym, const uint8_t* valid, co
         hipLaunchKernelGGL(tlm_kernel<true>, dim3(static_cast<unsigned>(t->h.max_channels)), dim3(64), lds, ctx->stream, a);
     else
         hipLaunchKernelGGL(tlm_kernel<false>, dim3(static_cast<unsigned>(t->h.max_channels)), dim3(64), lds, ctx->stream, a);
-    if (int rc = tlm_launched(ctx, who)) return rc;
+    if (int rc = launched(ctx, who)) return rc;
     const size_t nc = static_cast<size_t>(t->h.max_channels), slots = nc * t->pages_per_run;
-    return tlm_copy_out(ctx, {{pages_host, t->pages_dev, sizeof(gnsship_tlm_page) * slots}, {bits_host, t->bits_dev, slots * t->geo.LL},
+    return copy_out(ctx, {{pages_host, t->pages_dev, sizeof(gnsship_tlm_page) * slots}, {bits_host, t->bits_dev, slots * t->geo.LL},
                                  {counts_host, t->counts_dev, sizeof(int32_t) * nc}, {faults_host, t->faults_dev, nc}}, who);
 }
 
@@ -506,7 +506,7 @@ static int tlm_control(gnsship_tlm* t, int32_t channel, int what, const char* wh
     if (int rc = tlm_check_channel(t->h, who, channel)) return rc;
     if (int rc = set_device(t->h.ctx)) return rc;
     hipLaunchKernelGGL(tlm_control_kernel, dim3(1), dim3(1), 0, t->h.ctx->stream, t->chans_dev + channel, what);
-    return tlm_launched(t->h.ctx, who);
+    return launched(t->h.ctx, who);
 }
 
 extern "C" int gnsship_tlm_reset_channel(gnsship_tlm* t, int32_t channel) { return tlm_control(t, channel, 1, "gnsship_tlm_reset_channel"); }
@@ -533,7 +533,7 @@ extern "C" int gnsship_tlm_state_get(gnsship_tlm* t, int32_t channel, gnsship_tl
     if (int rc = tlm_check_state(t->h, who, channel, st)) return rc;
     if (int rc = set_device(t->h.ctx)) return rc;
     TlmChan c;
-    if (int rc = tlm_copy_out(t->h.ctx, {{&c, t->chans_dev + channel, sizeof(TlmChan)}}, who)) return rc;
+    if (int rc = copy_out(t->h.ctx, {{&c, t->chans_dev + channel, sizeof(TlmChan)}}, who)) return rc;
     std::memset(st, 0, sizeof(*st));
     st->symbol_counter = c.symbol_counter;
     st->preamble_index = c.preamble_index;

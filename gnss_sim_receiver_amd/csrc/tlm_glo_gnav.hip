@@ -469,7 +469,7 @@ struct gnsship_gnav {
 extern "C" int gnsship_gnav_destroy(gnsship_gnav* t)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    tlm_release(t->h, {t->chans_dev, t->strings_dev, t->counts_dev, t->tow_dev, t->sflags_dev});
+    t->h.release_all({t->chans_dev, t->strings_dev, t->counts_dev, t->tow_dev, t->sflags_dev});
     delete t;
     return GNSSHIP_OK;
 }
@@ -477,7 +477,7 @@ extern "C" int gnsship_gnav_destroy(gnsship_gnav* t)
 static int gnav_control(gnsship_gnav* t, int first, int n, int what, int prn, const char* who)
 {
     hipLaunchKernelGGL(gnav_control_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, t->h.ctx->stream, t->chans_dev, first, n, what, prn);
-    return tlm_launched(t->h.ctx, who);
+    return launched(t->h.ctx, who);
 }
 
 extern "C" int gnsship_gnav_create(gnsship_ctx* ctx, const gnsship_gnav_conf* conf, int32_t max_channels, gnsship_gnav** out)
@@ -499,8 +499,8 @@ extern "C" int gnsship_gnav_create(gnsship_ctx* ctx, const gnsship_gnav_conf* co
     t->conf = *conf;
     t->strings_per_run = GNSSHIP_GNAV_STRINGS_PER_RUN(conf->max_rounds);
     const size_t nc = static_cast<size_t>(max_channels), slots = nc * t->strings_per_run, entries = nc * conf->max_rounds;
-    const hipError_t e = tlm_alloc(ctx, {tlm_buf(&t->chans_dev, nc, false), tlm_buf(&t->strings_dev, slots, true), tlm_buf(&t->counts_dev, nc, true),
-                                            tlm_buf(&t->tow_dev, entries, true), tlm_buf(&t->sflags_dev, entries, true)});
+    const hipError_t e = alloc_all(ctx, {dev_alloc(&t->chans_dev, nc, false), dev_alloc(&t->strings_dev, slots, true), dev_alloc(&t->counts_dev, nc, true),
+                                            dev_alloc(&t->tow_dev, entries, true), dev_alloc(&t->sflags_dev, entries, true)});
     if (e != hipSuccess) {
         gnsship_gnav_destroy(t);
         return hip_fail(ctx, e, "gnsship_gnav_create");
@@ -531,9 +531,9 @@ static int gnav_launch(gnsship_gnav* t, const float* sym, const uint8_t* valid, 
     a.n_rounds = n_rounds;
     a.strings_per_run = t->strings_per_run;
     hipLaunchKernelGGL(gnav_kernel, dim3(static_cast<unsigned>((t->h.max_channels + 63) / 64)), dim3(64), 0, ctx->stream, a);  // a lane per channel
-    if (int rc = tlm_launched(ctx, who)) return rc;
+    if (int rc = launched(ctx, who)) return rc;
     const size_t nc = static_cast<size_t>(t->h.max_channels), slots = nc * t->strings_per_run, entries = nc * n_rounds;
-    return tlm_copy_out(ctx, {{strings_host, t->strings_dev, sizeof(gnsship_gnav_string) * slots}, {counts_host, t->counts_dev, sizeof(int32_t) * nc},
+    return copy_out(ctx, {{strings_host, t->strings_dev, sizeof(gnsship_gnav_string) * slots}, {counts_host, t->counts_dev, sizeof(int32_t) * nc},
                                  {tow_ms_host, t->tow_dev, sizeof(uint32_t) * entries}, {sflags_host, t->sflags_dev, entries}}, who);
 }
 
@@ -585,7 +585,7 @@ static int gnav_channel_call(gnsship_gnav* t, int32_t channel, int what, int32_t
 {
     if (!t) return GNSSHIP_E_INVAL;
     if (int rc = tlm_check_channel(t->h, who, channel)) return rc;
-    if (prn < 0 || prn > 63) return tlm_reject(t->h.ctx, GNSSHIP_E_INVAL, who, "0 <= prn <= 63");
+    if (prn < 0 || prn > 63) return reject(t->h.ctx, GNSSHIP_E_INVAL, who, "0 <= prn <= 63");
     if (int rc = set_device(t->h.ctx)) return rc;
     return gnav_control(t, channel, 1, what, prn, who);
 }
@@ -606,7 +606,7 @@ extern "C" int gnsship_gnav_state_get(gnsship_gnav* t, int32_t channel, gnsship_
     const char* who = "gnsship_gnav_state_get";
     if (int rc = tlm_check_state(t->h, who, channel, st)) return rc;
     if (int rc = set_device(t->h.ctx)) return rc;
-    return tlm_copy_out(t->h.ctx, {{st, &t->chans_dev[channel], sizeof(*st)}}, who);
+    return copy_out(t->h.ctx, {{st, &t->chans_dev[channel], sizeof(*st)}}, who);
 }
 
 extern "C" int gnsship_gnav_state_set(gnsship_gnav* t, int32_t channel, const gnsship_gnav_state* st)

@@ -579,7 +579,7 @@ struct gnsship_cnav {
 extern "C" int gnsship_cnav_destroy(gnsship_cnav* t)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    tlm_release(t->h, {t->chans_dev, t->messages_dev, t->counts_dev, t->faults_dev, t->tow_dev, t->sflags_dev});
+    t->h.release_all({t->chans_dev, t->messages_dev, t->counts_dev, t->faults_dev, t->tow_dev, t->sflags_dev});
     delete t;
     return GNSSHIP_OK;
 }
@@ -602,8 +602,8 @@ extern "C" int gnsship_cnav_create(gnsship_ctx* ctx, const gnsship_cnav_conf* co
     t->conf = *conf;
     t->messages_per_run = GNSSHIP_CNAV_MESSAGES_PER_RUN(conf->max_rounds);
     const size_t nc = static_cast<size_t>(max_channels), slots = nc * t->messages_per_run, entries = nc * conf->max_rounds;
-    hipError_t e = tlm_alloc(ctx, {tlm_buf(&t->chans_dev, nc, false), tlm_buf(&t->messages_dev, slots, true), tlm_buf(&t->counts_dev, nc, true),
-                                      tlm_buf(&t->faults_dev, nc, true), tlm_buf(&t->tow_dev, entries, true), tlm_buf(&t->sflags_dev, entries, true)});
+    hipError_t e = alloc_all(ctx, {dev_alloc(&t->chans_dev, nc, false), dev_alloc(&t->messages_dev, slots, true), dev_alloc(&t->counts_dev, nc, true),
+                                      dev_alloc(&t->faults_dev, nc, true), dev_alloc(&t->tow_dev, entries, true), dev_alloc(&t->sflags_dev, entries, true)});
     if (e == hipSuccess) {  // every channel a new block object
         gnsship_cnav_state* fresh = new (std::nothrow) gnsship_cnav_state[nc];
         if (!fresh) {
@@ -644,9 +644,9 @@ static int cnav_launch(gnsship_cnav* t, const float* sym, const uint8_t* valid, 
     a.messages_per_run = t->messages_per_run;
     a.signal = t->conf.signal;
     hipLaunchKernelGGL(cnav_kernel, dim3(static_cast<unsigned>(t->h.max_channels)), dim3(64), 0, ctx->stream, a);
-    if (int rc = tlm_launched(ctx, who)) return rc;
+    if (int rc = launched(ctx, who)) return rc;
     const size_t nc = static_cast<size_t>(t->h.max_channels), slots = nc * t->messages_per_run, entries = nc * n_rounds;
-    return tlm_copy_out(ctx, {{messages_host, t->messages_dev, sizeof(gnsship_cnav_message) * slots}, {counts_host, t->counts_dev, sizeof(int32_t) * nc},
+    return copy_out(ctx, {{messages_host, t->messages_dev, sizeof(gnsship_cnav_message) * slots}, {counts_host, t->counts_dev, sizeof(int32_t) * nc},
                                  {faults_host, t->faults_dev, nc}, {tow_ms_host, t->tow_dev, sizeof(uint32_t) * entries}, {sflags_host, t->sflags_dev, entries}}, who);
 }
 
@@ -700,7 +700,7 @@ extern "C" int gnsship_cnav_reset_channel(gnsship_cnav* t, int32_t channel)
     if (int rc = tlm_check_channel(t->h, who, channel)) return rc;
     if (int rc = set_device(t->h.ctx)) return rc;
     hipLaunchKernelGGL(cnav_reset_kernel, dim3(1), dim3(1), 0, t->h.ctx->stream, t->chans_dev + channel, t->conf.signal == GNSSHIP_CNAV_L5 ? 1 : 0);
-    return tlm_launched(t->h.ctx, who);
+    return launched(t->h.ctx, who);
 }
 
 // *st to the channel, through a staging copy so that the caller's memory is free when the call returns
@@ -729,7 +729,7 @@ extern "C" int gnsship_cnav_state_get(gnsship_cnav* t, int32_t channel, gnsship_
     const char* who = "gnsship_cnav_state_get";
     if (int rc = tlm_check_state(t->h, who, channel, st)) return rc;
     if (int rc = set_device(t->h.ctx)) return rc;
-    return tlm_copy_out(t->h.ctx, {{st, t->chans_dev + channel, sizeof(*st)}}, who);
+    return copy_out(t->h.ctx, {{st, t->chans_dev + channel, sizeof(*st)}}, who);
 }
 
 extern "C" int gnsship_cnav_state_set(gnsship_cnav* t, int32_t channel, const gnsship_cnav_state* st)

@@ -347,7 +347,7 @@ struct gnsship_lnav {
 extern "C" int gnsship_lnav_destroy(gnsship_lnav* t)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    tlm_release(t->h, {t->chans_dev, t->subframes_dev, t->counts_dev, t->faults_dev, t->tow_dev, t->sflags_dev});
+    t->h.release_all({t->chans_dev, t->subframes_dev, t->counts_dev, t->faults_dev, t->tow_dev, t->sflags_dev});
     delete t;
     return GNSSHIP_OK;
 }
@@ -369,8 +369,8 @@ extern "C" int gnsship_lnav_create(gnsship_ctx* ctx, const gnsship_lnav_conf* co
     t->conf = *conf;
     t->subframes_per_run = GNSSHIP_LNAV_SUBFRAMES_PER_RUN(conf->max_rounds);
     const size_t nc = static_cast<size_t>(max_channels), slots = nc * t->subframes_per_run, entries = nc * conf->max_rounds;
-    const hipError_t e = tlm_alloc(ctx, {tlm_buf(&t->chans_dev, nc, true), tlm_buf(&t->subframes_dev, slots, true), tlm_buf(&t->counts_dev, nc, true),
-                                            tlm_buf(&t->faults_dev, nc, true), tlm_buf(&t->tow_dev, entries, true), tlm_buf(&t->sflags_dev, entries, true)});
+    const hipError_t e = alloc_all(ctx, {dev_alloc(&t->chans_dev, nc, true), dev_alloc(&t->subframes_dev, slots, true), dev_alloc(&t->counts_dev, nc, true),
+                                            dev_alloc(&t->faults_dev, nc, true), dev_alloc(&t->tow_dev, entries, true), dev_alloc(&t->sflags_dev, entries, true)});
     if (e != hipSuccess) {
         gnsship_lnav_destroy(t);
         return hip_fail(ctx, e, "gnsship_lnav_create");
@@ -399,9 +399,9 @@ static int lnav_launch(gnsship_lnav* t, const float* sym, const uint8_t* valid, 
     a.n_rounds = n_rounds;
     a.subframes_per_run = t->subframes_per_run;
     hipLaunchKernelGGL(lnav_kernel, dim3(static_cast<unsigned>(t->h.max_channels)), dim3(64), 0, ctx->stream, a);
-    if (int rc = tlm_launched(ctx, who)) return rc;
+    if (int rc = launched(ctx, who)) return rc;
     const size_t nc = static_cast<size_t>(t->h.max_channels), slots = nc * t->subframes_per_run, entries = nc * n_rounds;
-    return tlm_copy_out(ctx, {{subframes_host, t->subframes_dev, sizeof(gnsship_lnav_subframe) * slots}, {counts_host, t->counts_dev, sizeof(int32_t) * nc},
+    return copy_out(ctx, {{subframes_host, t->subframes_dev, sizeof(gnsship_lnav_subframe) * slots}, {counts_host, t->counts_dev, sizeof(int32_t) * nc},
                                  {faults_host, t->faults_dev, nc}, {tow_ms_host, t->tow_dev, sizeof(uint32_t) * entries}, {sflags_host, t->sflags_dev, entries}}, who);
 }
 
@@ -454,7 +454,7 @@ static int lnav_control(gnsship_lnav* t, int32_t channel, int what, const char* 
     if (int rc = tlm_check_channel(t->h, who, channel)) return rc;
     if (int rc = set_device(t->h.ctx)) return rc;
     hipLaunchKernelGGL(lnav_control_kernel, dim3(1), dim3(1), 0, t->h.ctx->stream, t->chans_dev + channel, what);
-    return tlm_launched(t->h.ctx, who);
+    return launched(t->h.ctx, who);
 }
 
 extern "C" int gnsship_lnav_reset_channel(gnsship_lnav* t, int32_t channel) { return lnav_control(t, channel, 1, "gnsship_lnav_reset_channel"); }
@@ -477,5 +477,5 @@ extern "C" int gnsship_lnav_state_get(gnsship_lnav* t, int32_t channel, gnsship_
     const char* who = "gnsship_lnav_state_get";
     if (int rc = tlm_check_state(t->h, who, channel, st)) return rc;
     if (int rc = set_device(t->h.ctx)) return rc;
-    return tlm_copy_out(t->h.ctx, {{st, &t->chans_dev[channel].st, sizeof(*st)}}, who);
+    return copy_out(t->h.ctx, {{st, &t->chans_dev[channel].st, sizeof(*st)}}, who);
 }

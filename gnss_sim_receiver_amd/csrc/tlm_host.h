@@ -1,15 +1,13 @@
 // tlm_host.h — the host half the five telemetry decoders share (tlm_galileo.hip, tlm_gps_lnav.hip, tlm_gps_cnav.hip,
-// tlm_bds_dnav.hip, tlm_glo_gnav.hip): the staging buffers of host inputs, the argument checks of the run calls, the copy
-// of the outputs a caller asked for, and allocation and release of a handle's device buffers.  A decoder's file keeps its
-// kernels, its Args struct, its launch geometry and what only its family checks.
+// tlm_bds_dnav.hip, tlm_glo_gnav.hip) beyond what every handle shares (host_api.h: reject, launched, stage, copy_out,
+// alloc_all, free_all): the staging buffers of host inputs and the argument checks of the run, channel and state calls.
+// A decoder's file keeps its kernels, its Args struct, its launch geometry and what only its family checks.
 //
 // Every function takes `who`, the entry point's name ("gnsship_dnav_run_symbols"): a rejection's text is "<who>: <what>",
 // a HIP error's is "<who>: <HIP's text>", an upload's "<who>(upload): <HIP's text>".  These texts are part of the C ABI
 // (tests/test_gpu_tlm_rejections.py).  Order everywhere: argument checks, then set_device, then staging.
 // Everything here is `static inline`: the library exports nothing new.
 #pragma once
-#include <initializer_list>
-
 #include "host_api.h"
 
 namespace gnsship {
@@ -20,38 +18,20 @@ struct TlmHost {  // what every telemetry handle holds for the calls below
     gnsship_ctx* ctx = nullptr;
     int32_t max_channels = 0, max_rounds = 0;
     DevBuf stage, valid, mask;  // device copies of host inputs: symbols or records; the validity mask; the family's second mask, if any
+    // what gnsship_<f>_destroy does ahead of `delete`: wait for the stream, free `owned` and the staging buffers
+    void release_all(std::initializer_list<void*> owned)
+    {
+        quiesce(ctx);
+        free_all(owned);
+        for (DevBuf* s : {&stage, &valid, &mask}) release(*s);
+    }
 };
-
-static inline int tlm_reject(gnsship_ctx* ctx, int code, const char* who, const char* what)
-{
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), "%s: %s", who, what);
-    return fail(ctx, code, buf);
-}
-
-// after a kernel launch
-static inline int tlm_launched(gnsship_ctx* ctx, const char* who)
-{
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GNSSHIP_OK : hip_fail(ctx, e, who);
-}
-
-// Host data of `bytes` bytes to a staging buffer that grows only when it is too small; either failure is "<who>(upload)".
-static inline int tlm_stage(gnsship_ctx* ctx, DevBuf& s, const void* host, size_t bytes, const char* who)
-{
-    if (int rc = reserve(ctx, s, bytes, who, "upload")) return rc;
-    const hipError_t e = hipMemcpyAsync(s.dev, host, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) return GNSSHIP_OK;
-    char up[128];
-    std::snprintf(up, sizeof(up), "%s(upload)", who);
-    return hip_fail(ctx, e, up);
-}
 
 // 0 <= n_rounds <= max_rounds, an input where there is a round (`null_input`: "null symbols" / "null records"), set_device
 static inline int tlm_check_run(const TlmHost& h, const char* who, int32_t n_rounds, const void* input, const char* null_input)
 {
-    if (n_rounds < 0 || n_rounds > h.max_rounds) return tlm_reject(h.ctx, GNSSHIP_E_INVAL, who, "0 <= n_rounds <= max_rounds");
-    if (n_rounds > 0 && !input) return tlm_reject(h.ctx, GNSSHIP_E_INVAL, who, null_input);
+    if (n_rounds < 0 || n_rounds > h.max_rounds) return reject(h.ctx, GNSSHIP_E_INVAL, who, "0 <= n_rounds <= max_rounds");
+    if (n_rounds > 0 && !input) return reject(h.ctx, GNSSHIP_E_INVAL, who, null_input);
     return set_device(h.ctx);
 }
 
@@ -63,14 +43,14 @@ static inline int tlm_symbols_in(TlmHost& h, const char* who, int on_device, int
     if (int rc = tlm_check_run(h, who, n_rounds, *sym, "null symbols")) return rc;
     const size_t n = static_cast<size_t>(n_rounds) * h.max_channels;
     if (on_device || n == 0) return GNSSHIP_OK;
-    if (int rc = tlm_stage(h.ctx, h.stage, *sym, sizeof(float) * n, who)) return rc;
+    if (int rc = stage(h.ctx, h.stage, *sym, sizeof(float) * n, who, "upload")) return rc;
     *sym = h.stage.as<float>();
     if (*valid) {
-        if (int rc = tlm_stage(h.ctx, h.valid, *valid, n, who)) return rc;
+        if (int rc = stage(h.ctx, h.valid, *valid, n, who, "upload")) return rc;
         *valid = h.valid.as<uint8_t>();
     }
     if (mask && *mask) {
-        if (int rc = tlm_stage(h.ctx, h.mask, *mask, n, who)) return rc;
+        if (int rc = stage(h.ctx, h.mask, *mask, n, who, "upload")) return rc;
         *mask = h.mask.as<uint8_t>();
     }
     return GNSSHIP_OK;
@@ -86,7 +66,7 @@ static inline int tlm_records_in(TlmHost& h, const char* who, int on_device, int
         return GNSSHIP_OK;
     }
     if (on_device) return GNSSHIP_OK;
-    if (int rc = tlm_stage(h.ctx, h.stage, *rec, sizeof(gnsship_trk_epoch) * n_rounds * h.max_channels, who)) return rc;
+    if (int rc = stage(h.ctx, h.stage, *rec, sizeof(gnsship_trk_epoch) * n_rounds * h.max_channels, who, "upload")) return rc;
     *rec = h.stage.as<gnsship_trk_epoch>();
     return GNSSHIP_OK;
 }
@@ -95,81 +75,29 @@ static inline int tlm_records_in(TlmHost& h, const char* who, int on_device, int
 static inline int tlm_trk_in(const TlmHost& h, const char* who, gnsship_trk* trk, const gnsship_trk_epoch** rec, int32_t* rounds)
 {
     gnsship_ctx* ctx = h.ctx;
-    if (!trk) return tlm_reject(ctx, GNSSHIP_E_INVAL, who, "null tracking handle");
-    if (trk_context(trk) != ctx) return tlm_reject(ctx, GNSSHIP_E_INVAL, who, "the tracking handle is on another context");
+    if (!trk) return reject(ctx, GNSSHIP_E_INVAL, who, "null tracking handle");
+    if (trk_context(trk) != ctx) return reject(ctx, GNSSHIP_E_INVAL, who, "the tracking handle is on another context");
     int32_t nc = 0;
     if (int rc = gnsship_trk_records_device(trk, rec, rounds, &nc)) {
-        if (rc == GNSSHIP_E_STATE) return tlm_reject(ctx, GNSSHIP_E_STATE, who, "the tracker's last run kept no records on the device");
+        if (rc == GNSSHIP_E_STATE) return reject(ctx, GNSSHIP_E_STATE, who, "the tracker's last run kept no records on the device");
         return rc;
     }
-    if (nc != h.max_channels) return tlm_reject(ctx, GNSSHIP_E_INVAL, who, "the handles' max_channels differ");
-    if (*rounds > h.max_rounds) return tlm_reject(ctx, GNSSHIP_E_INVAL, who, "the tracker's run had more rounds than max_rounds");
+    if (nc != h.max_channels) return reject(ctx, GNSSHIP_E_INVAL, who, "the handles' max_channels differ");
+    if (*rounds > h.max_rounds) return reject(ctx, GNSSHIP_E_INVAL, who, "the tracker's run had more rounds than max_rounds");
     return set_device(ctx);
 }
 
 static inline int tlm_check_channel(const TlmHost& h, const char* who, int32_t channel)
 {
-    if (channel < 0 || channel >= h.max_channels) return tlm_reject(h.ctx, GNSSHIP_E_INVAL, who, "channel out of range");
+    if (channel < 0 || channel >= h.max_channels) return reject(h.ctx, GNSSHIP_E_INVAL, who, "channel out of range");
     return GNSSHIP_OK;
 }
 
 // the arguments of gnsship_<f>_state_get and _state_set
 static inline int tlm_check_state(const TlmHost& h, const char* who, int32_t channel, const void* st)
 {
-    if (!st) return tlm_reject(h.ctx, GNSSHIP_E_INVAL, who, "null state");
+    if (!st) return reject(h.ctx, GNSSHIP_E_INVAL, who, "null state");
     return tlm_check_channel(h, who, channel);
-}
-
-// Copy what the caller asked for: the entries with a host pointer and a size, in order, then one stream synchronise —
-// none when nothing was copied (a run without a host copy stays asynchronous).
-struct TlmCopy {
-    void* host;
-    const void* dev;
-    size_t bytes;
-};
-static inline int tlm_copy_out(gnsship_ctx* ctx, std::initializer_list<TlmCopy> list, const char* who)
-{
-    bool any = false;
-    for (const TlmCopy& c : list) {
-        if (!c.host || c.bytes == 0) continue;
-        const hipError_t e = hipMemcpyAsync(c.host, c.dev, c.bytes, hipMemcpyDeviceToHost, ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, who);
-        any = true;
-    }
-    if (!any) return GNSSHIP_OK;
-    const hipError_t e = hipStreamSynchronize(ctx->stream);
-    return e == hipSuccess ? GNSSHIP_OK : hip_fail(ctx, e, who);
-}
-
-// A handle's device buffers: `count` elements at *ptr, zeroed on the stream where `zero`.
-struct TlmBuf {
-    void** ptr;
-    size_t bytes;
-    bool zero;
-};
-template <class T>
-static inline TlmBuf tlm_buf(T** ptr, size_t count, bool zero)
-{
-    return {reinterpret_cast<void**>(ptr), sizeof(T) * count, zero};
-}
-// every hipMalloc, then every hipMemsetAsync; stops at the first error (the caller destroys the handle, which frees)
-static inline hipError_t tlm_alloc(gnsship_ctx* ctx, std::initializer_list<TlmBuf> list)
-{
-    hipError_t e = hipSuccess;
-    for (const TlmBuf& b : list)
-        if (e == hipSuccess) e = hipMalloc(b.ptr, b.bytes);
-    for (const TlmBuf& b : list)
-        if (e == hipSuccess && b.zero) e = hipMemsetAsync(*b.ptr, 0, b.bytes, ctx->stream);
-    return e;
-}
-// what gnsship_<f>_destroy does ahead of `delete`: wait for the stream, free `owned` and the staging buffers
-static inline void tlm_release(TlmHost& h, std::initializer_list<void*> owned)
-{
-    (void)hipSetDevice(h.ctx->device);
-    (void)hipStreamSynchronize(h.ctx->stream);
-    for (void* p : owned)
-        if (p) (void)hipFree(p);
-    for (DevBuf* s : {&h.stage, &h.valid, &h.mask}) release(*s);
 }
 
 }  // namespace gnsship

@@ -413,10 +413,8 @@ hipError_t upload_hd_code(gnsship_trk* t, int job, const CodeDesc& cd)
 
 void release(gnsship_trk* t)
 {
-    void* ptrs[] = {t->params_dev, t->chans_dev, t->jobs_dev, t->chunks_dev, t->items_dev, t->anchors_dev, t->partials_dev, t->out_dev, t->hist_dev,
-        t->serial_dev};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    free_all({t->params_dev, t->chans_dev, t->jobs_dev, t->chunks_dev, t->items_dev, t->anchors_dev, t->partials_dev, t->out_dev, t->hist_dev,
+        t->serial_dev});
     for (DevBuf* b : {&t->rec_dev, &t->dump_dev, &t->ran_dev, &t->stage_dev, &t->trace_dev, &t->start_stage_dev}) release(*b);
     hd_plan_free(t->hd);
 }
@@ -441,8 +439,7 @@ extern "C" int gnsship_trk_last_plan(gnsship_trk* t, gnsship_trk_plan* plan)
 extern "C" int gnsship_trk_destroy(gnsship_trk* t)
 {
     if (!t) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(t->ctx->device);
-    (void)hipStreamSynchronize(t->ctx->stream);
+    quiesce(t->ctx);
     release(t);
     delete t;
     return GNSSHIP_OK;

@@ -118,9 +118,8 @@ struct gnsship_vit {
 extern "C" int gnsship_vit_destroy(gnsship_vit* v)
 {
     if (!v) return GNSSHIP_E_INVAL;
-    (void)hipSetDevice(v->ctx->device);
-    (void)hipStreamSynchronize(v->ctx->stream);
-    if (v->sections_dev) (void)hipFree(v->sections_dev);
+    quiesce(v->ctx);
+    free_all({v->sections_dev});
     for (DevBuf* b : {&v->channels_dev, &v->negate_dev, &v->bits_dev, &v->sym_dev}) release(*b);
     delete v;
     return GNSSHIP_OK;
@@ -130,9 +129,7 @@ static int vit_fill(gnsship_vit* v, int64_t first, int64_t n, const char* where)
 {
     gnsship_ctx* ctx = v->ctx;
     hipLaunchKernelGGL(vit_fill_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, ctx->stream, v->sections_dev + first, n, -kVitMaxLog);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, where);
-    return GNSSHIP_OK;
+    return launched(ctx, where);
 }
 
 extern "C" int gnsship_vit_create(gnsship_ctx* ctx, const gnsship_vit_conf* conf, int32_t max_channels, gnsship_vit** out)
@@ -188,11 +185,7 @@ extern "C" int gnsship_vit_state_get(gnsship_vit* v, int32_t channel, float* sec
     gnsship_ctx* ctx = v->ctx;
     if (channel < 0 || channel >= v->max_channels) return fail(ctx, GNSSHIP_E_INVAL, "gnsship_vit_state_get: channel out of range");
     if (int rc = set_device(ctx)) return rc;
-    hipError_t e = hipMemcpyAsync(section, v->sections_dev + static_cast<int64_t>(channel) * kVitStates, sizeof(float) * kVitStates,
-        hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_vit_state_get");
-    return GNSSHIP_OK;
+    return copy_out(ctx, {{section, v->sections_dev + static_cast<int64_t>(channel) * kVitStates, sizeof(float) * kVitStates}}, "gnsship_vit_state_get");
 }
 
 extern "C" int gnsship_vit_run(gnsship_vit* v, const float* symbols, int on_device, int32_t n_frames, const int32_t* channels,
@@ -222,16 +215,12 @@ extern "C" int gnsship_vit_run(gnsship_vit* v, const float* symbols, int on_devi
     if (int rc = reserve(ctx, v->channels_dev, sizeof(int32_t) * nf, "gnsship_vit_run", "buffers")) return rc;
     if (int rc = reserve(ctx, v->negate_dev, nf, "gnsship_vit_run", "buffers")) return rc;
     if (int rc = reserve(ctx, v->bits_dev, nf * LL, "gnsship_vit_run", "buffers")) return rc;
-    hipError_t e = hipSuccess;
     const float* src = symbols;
     if (!on_device) {
-        const size_t bytes = sizeof(float) * nf * v->frame;
-        if (int rc = reserve(ctx, v->sym_dev, bytes, "gnsship_vit_run", "stage")) return rc;
-        e = hipMemcpyAsync(v->sym_dev.dev, symbols, bytes, hipMemcpyHostToDevice, ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_vit_run(upload)");
+        if (int rc = stage(ctx, v->sym_dev, symbols, sizeof(float) * nf * v->frame, "gnsship_vit_run", "stage")) return rc;
         src = v->sym_dev.as<float>();
     }
-    e = hipMemcpyAsync(v->channels_dev.dev, channels, sizeof(int32_t) * nf, hipMemcpyHostToDevice, ctx->stream);
+    hipError_t e = hipMemcpyAsync(v->channels_dev.dev, channels, sizeof(int32_t) * nf, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess && negate) e = hipMemcpyAsync(v->negate_dev.dev, negate, nf, hipMemcpyHostToDevice, ctx->stream);
     if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_vit_run(upload)");
     VitArgs a = {};
@@ -255,12 +244,6 @@ extern "C" int gnsship_vit_run(gnsship_vit* v, const float* symbols, int on_devi
         hipLaunchKernelGGL(vit_decode_kernel<true>, dim3(blocks), dim3(kVitFramesPerWg * 64), lds, ctx->stream, a);
     else
         hipLaunchKernelGGL(vit_decode_kernel<false>, dim3(blocks), dim3(kVitFramesPerWg * 64), lds, ctx->stream, a);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_vit_run(launch)");
-    if (bits_host) {
-        e = hipMemcpyAsync(bits_host, a.bits, static_cast<size_t>(n_frames) * LL, hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) return hip_fail(ctx, e, "gnsship_vit_run(download)");
-    }
-    return GNSSHIP_OK;
+    if (int rc = launched(ctx, "gnsship_vit_run(launch)")) return rc;
+    return copy_out(ctx, {{bits_host, a.bits, nf * LL}}, "gnsship_vit_run(download)");
 }

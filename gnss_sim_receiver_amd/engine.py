@@ -188,10 +188,53 @@ class Comm:
             self.h = None
 
 
-class MultiCorrelatorRealCodes:
+class _Handle:
+    """What every handle class shares over the C ABI (gnsship_<block>_*): the context, the handle and its life cycle.
+    A subclass states its C prefix, sets ``ctx`` and opens the handle with _create in __init__, and makes every other
+    call through _call, which raises GnssHipError under the C function's name with the context's last error."""
+    _prefix = None  # "gnsship_trk"
+
+    def _call(self, name: str, *args):
+        name = f"{self._prefix}_{name}"
+        check(getattr(self.ctx.lib, name)(self.h, *args), name, self.ctx.h)
+
+    def _create(self, *args):
+        """gnsship_<block>_create(ctx, *args, &handle)"""
+        h = ctypes.c_void_p()
+        name = f"{self._prefix}_create"
+        check(getattr(self.ctx.lib, name)(self.ctx.h, *args, ctypes.byref(h)), name, self.ctx.h)
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.ctx.lib, f"{self._prefix}_destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            if self.h and self.ctx.h:  # a closed context has taken its handles with it
+                self.close()
+        except Exception:
+            pass
+
+
+def _if_input(sig, fmt):
+    """IF samples as the run calls take them: a host ndarray (CF32 / CI16 / CI8 by its dtype) or a DeviceBuffer (then
+    fmt, CF32 when None).  Returns (pointer, on_device, fmt, n_samples); a host pointer keeps its array alive."""
+    if isinstance(sig, DeviceBuffer):
+        ptr, on_dev, f = sig.ptr, 1, FMT_CF32 if fmt is None else fmt
+    else:
+        sig = np.ascontiguousarray(sig)
+        ptr, on_dev, f = sig.ctypes.data_as(ctypes.c_void_p), 0, sample_format(sig)
+    return ptr, on_dev, f, sig.nbytes // _FMT_BYTES[f] if f in _FMT_BYTES else None
+
+
+class MultiCorrelatorRealCodes(_Handle):
     """Mirror of Cpu_Multicorrelator_Real_Codes (cpu_multicorrelator_real_codes.h:37-61).  rotator: the
     volk_gnsssdr rotator variant its Carrier_wipeoff_multicorrelator_resampler runs (abi.ROTATOR_*;
     default AUTO = what the reference's dispatcher picks on this host)."""
+
+    _prefix = "gnsship_corr"
 
     def __init__(self, ctx: Context, rotator: int = abi.ROTATOR_AUTO):
         self.ctx = ctx
@@ -202,24 +245,20 @@ class MultiCorrelatorRealCodes:
         self._sig = None
 
     def init(self, max_signal_length_samples: int, n_correlators: int) -> bool:
-        h = ctypes.c_void_p()
-        check(self.ctx.lib.gnsship_corr_create(self.ctx.h, max_signal_length_samples, n_correlators, ctypes.byref(h)),
-              "gnsship_corr_create", self.ctx.h)
-        self.h = h
+        self._create(max_signal_length_samples, n_correlators)
         self.n_correlators = n_correlators
-        check(self.ctx.lib.gnsship_corr_set_rotator(self.h, self.rotator), "gnsship_corr_set_rotator", self.ctx.h)
+        self._call("set_rotator", self.rotator)
         return True
 
     def set_high_dynamics_resampler(self, use: bool):
-        check(self.ctx.lib.gnsship_corr_set_high_dynamics_resampler(self.h, int(use)), "set_high_dynamics_resampler", self.ctx.h)
+        self._call("set_high_dynamics_resampler", int(use))
 
     def set_local_code_and_taps(self, code_length_chips: int, local_code_in: np.ndarray, shifts_chips: np.ndarray) -> bool:
         code = np.ascontiguousarray(local_code_in[:code_length_chips], np.float32)
         shifts = np.ascontiguousarray(shifts_chips, np.float32)
         if len(shifts) < self.n_correlators:
             raise ValueError("need one shift per correlator")
-        check(self.ctx.lib.gnsship_corr_set_local_code_and_taps(self.h, code_length_chips, fptr(code), fptr(shifts)),
-              "gnsship_corr_set_local_code_and_taps", self.ctx.h)
+        self._call("set_local_code_and_taps", code_length_chips, fptr(code), fptr(shifts))
         return True
 
     def set_input_output_vectors(self, corr_out: np.ndarray, sig_in: np.ndarray) -> bool:
@@ -233,48 +272,35 @@ class MultiCorrelatorRealCodes:
         sig = np.ascontiguousarray(self._sig)
         fmt = sample_format(sig)
         tmp = np.zeros(2 * self.n_correlators, np.float32)
-        check(self.ctx.lib.gnsship_corr_run(self.h, sig.ctypes.data, fmt, 0, rem_carrier_phase_in_rad, phase_step_rad,
-                                            phase_rate_step_rad, rem_code_phase_chips, code_phase_step_chips,
-                                            code_phase_rate_step_chips, signal_length_samples, fptr(tmp)),
-              "gnsship_corr_run", self.ctx.h)
+        self._call("run", sig.ctypes.data, fmt, 0, rem_carrier_phase_in_rad, phase_step_rad, phase_rate_step_rad, rem_code_phase_chips,
+                   code_phase_step_chips, code_phase_rate_step_chips, signal_length_samples, fptr(tmp))
         self._out[: self.n_correlators] = tmp.view(np.complex64)
         return True
 
     def free(self) -> bool:
-        if self.h:
-            self.ctx.lib.gnsship_corr_destroy(self.h)
-            self.h = None
+        self.close()
         return True
 
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.free()
-        except Exception:
-            pass
 
-
-class CorrelatorBatch:
+class CorrelatorBatch(_Handle):
     """Batched multicorrelator: every row of a JOB_DTYPE array is one channel-epoch."""
+    _prefix = "gnsship_batch"
 
     def __init__(self, ctx: Context, max_jobs: int):
         self.ctx = ctx
-        h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_batch_create(ctx.h, max_jobs, ctypes.byref(h)), "gnsship_batch_create", ctx.h)
-        self.h = h
+        self._create(max_jobs)
         self.n_jobs = 0
 
     def set_jobs(self, jobs: np.ndarray, n_buffer_samples: int):
         jobs = np.ascontiguousarray(jobs, JOB_DTYPE)
-        check(self.ctx.lib.gnsship_batch_set_jobs(self.h, jobs.ctypes.data, len(jobs), n_buffer_samples), "gnsship_batch_set_jobs",
-              self.ctx.h)
+        self._call("set_jobs", jobs.ctypes.data, len(jobs), n_buffer_samples)
         self.n_jobs = len(jobs)
 
     def launch(self, samples: DeviceBuffer, fmt: int = FMT_CF32):
-        check(self.ctx.lib.gnsship_batch_launch(self.h, samples.ptr, fmt), "gnsship_batch_launch", self.ctx.h)
+        self._call("launch", samples.ptr, fmt)
 
     def launch_ptr(self, dev_ptr: int, fmt: int = FMT_CF32, stages: int = 3):
-        check(self.ctx.lib.gnsship_batch_launch_stages(self.h, dev_ptr, fmt, stages), "gnsship_batch_launch_stages", self.ctx.h)
+        self._call("launch_stages", dev_ptr, fmt, stages)
 
     def launch_pipelined(self, dev_ptr: int, fmt: int = FMT_CF32, next_batch: "CorrelatorBatch" = None,
                          next2: "CorrelatorBatch" = None):
@@ -284,24 +310,12 @@ class CorrelatorBatch:
         carry half a replay chain per batch per launch."""
         nh = next_batch.h if next_batch is not None else None
         n2 = next2.h if next2 is not None else None
-        check(self.ctx.lib.gnsship_batch_launch_pipelined2(self.h, dev_ptr, fmt, nh, n2), "gnsship_batch_launch_pipelined2", self.ctx.h)
+        self._call("launch_pipelined2", dev_ptr, fmt, nh, n2)
 
     def results(self) -> np.ndarray:
         out = np.zeros((self.n_jobs, 2 * MAX_TAPS), np.float32)
-        check(self.ctx.lib.gnsship_batch_results(self.h, fptr(out)), "gnsship_batch_results", self.ctx.h)
+        self._call("results", fptr(out))
         return out.view(np.complex64)
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.gnsship_batch_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.close()
-        except Exception:
-            pass
 
 
 def correlate_host(ctx: Context, samples: np.ndarray, jobs: np.ndarray, codes: list) -> np.ndarray:
@@ -330,8 +344,9 @@ class AcqLayout(NamedTuple):
     ct_rows: bool   # the rows run a kernel with a compile-time plan
 
 
-class PcpsAcquisition:
+class PcpsAcquisition(_Handle):
     """pcps_acquisition (pcps_acquisition.cc) over up to ``max_prns`` local codes at once."""
+    _prefix = "gnsship_acq"
 
     def __init__(self, ctx: Context, fs_in: int, fft_size: int, doppler_max: int, doppler_step: int, doppler_center: int = 0,
                  use_cfar: bool = True, samples_per_chip: int = None, samples_per_code: float = None, max_prns: int = 1,
@@ -359,67 +374,54 @@ class PcpsAcquisition:
         self.consumed = consumed_samples or fft_size
         self.code_len = fft_size // 2 if bit_transition_flag else self.consumed  # samples set_local_code reads
         self.row_len = fft_size // 2 if bit_transition_flag else fft_size       # grid row length
-        h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_acq_create(ctx.h, ctypes.byref(conf), ctypes.byref(h)), "gnsship_acq_create", ctx.h)
-        self.h = h
-        nb = ctypes.c_int()
-        check(ctx.lib.gnsship_acq_num_bins(self.h, ctypes.byref(nb)), "gnsship_acq_num_bins", ctx.h)
-        self.n_bins = nb.value
+        self._create(ctypes.byref(conf))
+        self._refresh_bins()
         self.fdma_channels = 0  # > 0: the grid is an FDMA grid (set_grid_fdma)
+
+    def _refresh_bins(self):
+        nb = ctypes.c_int()
+        self._call("num_bins", ctypes.byref(nb))
+        self.n_bins = nb.value
 
     @property
     def layout(self) -> AcqLayout:
         """The transform layout the handle chose at create (gnsship_acq_layout_get)."""
         lay = abi.AcqLayout()
-        check(self.ctx.lib.gnsship_acq_layout_get(self.h, ctypes.byref(lay)), "gnsship_acq_layout_get", self.ctx.h)
+        self._call("layout_get", ctypes.byref(lay))
         return AcqLayout(("lds", "four_step", "huge")[lay.kind], lay.P, lay.row_len, tuple(lay.radix[: lay.n_passes]), bool(lay.ct_rows))
 
     def set_grid(self, doppler_max: int, doppler_step: int, doppler_center: int = 0):
-        check(self.ctx.lib.gnsship_acq_set_grid(self.h, doppler_max, doppler_step, doppler_center), "gnsship_acq_set_grid", self.ctx.h)
-        nb = ctypes.c_int()
-        check(self.ctx.lib.gnsship_acq_num_bins(self.h, ctypes.byref(nb)), "gnsship_acq_num_bins", self.ctx.h)
-        self.n_bins = nb.value
+        self._call("set_grid", doppler_max, doppler_step, doppler_center)
+        self._refresh_bins()
         self.fdma_channels = 0
 
     def set_grid_step2(self, doppler_center_step_two: float, doppler_step2: float, num_doppler_bins_step2: int,
                        step_one_input_power: float):
         """update_grid_doppler_wipeoffs_step2 (pcps_acquisition.cc:305-312): make_2_steps' narrow grid."""
-        check(self.ctx.lib.gnsship_acq_set_grid_step2(self.h, doppler_center_step_two, doppler_step2, num_doppler_bins_step2,
-                                                      step_one_input_power), "gnsship_acq_set_grid_step2", self.ctx.h)
-        nb = ctypes.c_int()
-        check(self.ctx.lib.gnsship_acq_num_bins(self.h, ctypes.byref(nb)), "gnsship_acq_num_bins", self.ctx.h)
-        self.n_bins = nb.value
+        self._call("set_grid_step2", doppler_center_step_two, doppler_step2, num_doppler_bins_step2, step_one_input_power)
+        self._refresh_bins()
 
     def set_local_code(self, code: np.ndarray, prn_slot: int = 0):
         code = np.ascontiguousarray(code, np.complex64)
         if len(code) < self.code_len:
             raise ValueError(f"local code must have at least {self.code_len} samples")
         code = np.ascontiguousarray(code[: self.code_len])
-        check(self.ctx.lib.gnsship_acq_set_local_code(self.h, prn_slot, fptr(code.view(np.float32))), "gnsship_acq_set_local_code",
-              self.ctx.h)
+        self._call("set_local_code", prn_slot, fptr(code.view(np.float32)))
 
     def run(self, sig, n_prns: int = 1, want_grid: bool = False, fmt: int = None):
         """sig: host ndarray (CF32/CI16/CI8) or DeviceBuffer (then pass fmt)."""
         res = (abi.AcqResult * n_prns)()
         grid = np.zeros((n_prns, self.n_bins, self.row_len), np.float32) if want_grid else None
-        if isinstance(sig, DeviceBuffer):
-            ptr, on_dev, f = sig.ptr, 1, FMT_CF32 if fmt is None else fmt
-        else:
-            sig = np.ascontiguousarray(sig)
-            ptr, on_dev, f = sig.ctypes.data, 0, sample_format(sig)
-        check(self.ctx.lib.gnsship_acq_run(self.h, ptr, f, on_dev, n_prns, res, fptr(grid) if want_grid else None),
-              "gnsship_acq_run", self.ctx.h)
+        ptr, on_dev, f, _ = _if_input(sig, fmt)
+        self._call("run", ptr, f, on_dev, n_prns, res, fptr(grid) if want_grid else None)
         return list(res), grid
 
     def set_grid_fdma(self, doppler_max: int, doppler_step: int, doppler_center: int, bias_hz):
         """One Doppler grid per FDMA frequency channel (pcps_acquisition's d_doppler_bias, :211-229, :295-302):
         channel g's rows are built from bias_hz[g] + the grid's Doppler.  set_grid returns to the ordinary grid."""
         bias = np.ascontiguousarray(bias_hz, np.int32)
-        check(self.ctx.lib.gnsship_acq_set_grid_fdma(self.h, doppler_max, doppler_step, doppler_center, len(bias),
-                                                     bias.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))), "gnsship_acq_set_grid_fdma", self.ctx.h)
-        nb = ctypes.c_int()
-        check(self.ctx.lib.gnsship_acq_num_bins(self.h, ctypes.byref(nb)), "gnsship_acq_num_bins", self.ctx.h)
-        self.n_bins = nb.value
+        self._call("set_grid_fdma", doppler_max, doppler_step, doppler_center, len(bias), bias.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)))
+        self._refresh_bins()
         self.fdma_channels = len(bias)
 
     def run_fdma(self, sig, prn_slot: int = 0, want_grid: bool = False, fmt: int = None):
@@ -430,33 +432,27 @@ class PcpsAcquisition:
             raise ValueError("run_fdma needs set_grid_fdma first")
         res = (abi.AcqResult * nch)()
         grid = np.zeros((nch, self.n_bins, self.row_len), np.float32) if want_grid else None
-        if isinstance(sig, DeviceBuffer):
-            ptr, on_dev, f = sig.ptr, 1, FMT_CF32 if fmt is None else fmt
-        else:
-            sig = np.ascontiguousarray(sig)
-            ptr, on_dev, f = sig.ctypes.data, 0, sample_format(sig)
-        check(self.ctx.lib.gnsship_acq_run_fdma(self.h, ptr, f, on_dev, prn_slot, res, fptr(grid) if want_grid else None),
-              "gnsship_acq_run_fdma", self.ctx.h)
+        ptr, on_dev, f, _ = _if_input(sig, fmt)
+        self._call("run_fdma", ptr, f, on_dev, prn_slot, res, fptr(grid) if want_grid else None)
         return list(res), grid
 
-    def close(self):
-        if self.h:
-            self.ctx.lib.gnsship_acq_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.close()
-        except Exception:
-            pass
+def _ms_code_acquisition(ctx, fs_in, doppler_max, doppler_step, sampled_ms, code_rate_cps, code_length_chips, kw) -> PcpsAcquisition:
+    """The acquisition of a signal whose code lasts 1 ms: ms_per_code 1, code_length = floor(fs / codes per second)
+    samples and a search window of sampled_ms of them."""
+    code_length = int(np.floor(fs_in / (code_rate_cps / code_length_chips)))
+    return PcpsAcquisition(ctx, fs_in, sampled_ms * code_length, doppler_max, doppler_step, chip_rate=code_rate_cps, ms_per_code=1, **kw)
+
+
+def _vector_length(fs_in, code_rate_cps, code_length_chips) -> int:
+    """A tracking block's vector_length: round(fs / codes per second) samples."""
+    return int(round(fs_in / (code_rate_cps / code_length_chips)))
 
 
 def _glonass_pcps_acquisition(signal, ctx, fs_in, doppler_max, doppler_step, freq_channels, sampled_ms, kw):
     from . import codes
-    code_length = int(np.floor(fs_in / (codes.GLONASS_L1_CA_CODE_RATE_CPS / codes.GLONASS_L1_CA_CODE_LENGTH_CHIPS)))
-    acq = PcpsAcquisition(ctx, fs_in, sampled_ms * code_length, doppler_max, doppler_step, chip_rate=codes.GLONASS_L1_CA_CODE_RATE_CPS,
-                          ms_per_code=1, **kw)
+    acq = _ms_code_acquisition(ctx, fs_in, doppler_max, doppler_step, sampled_ms, codes.GLONASS_L1_CA_CODE_RATE_CPS,
+                               codes.GLONASS_L1_CA_CODE_LENGTH_CHIPS, kw)
     acq.freq_channels = [int(k) for k in freq_channels]
     # gnsship_acq_create has just built the ordinary grid's table and buffers; they are replaced here, once per handle
     # (a few ms of host table per grid).  Kept so: a handle is always runnable, and creation is not on the dwell path.
@@ -484,7 +480,7 @@ def glonass_l2_ca_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, d
 
 def _glonass_trk_conf(system: int, fs_in: float, kw) -> "abi.TrkConf":
     from . import codes
-    vl = int(round(fs_in / (codes.GLONASS_L1_CA_CODE_RATE_CPS / codes.GLONASS_L1_CA_CODE_LENGTH_CHIPS)))
+    vl = _vector_length(fs_in, codes.GLONASS_L1_CA_CODE_RATE_CPS, codes.GLONASS_L1_CA_CODE_LENGTH_CHIPS)
     base = dict(pll_bw_hz=50.0, dll_bw_hz=2.0, early_late_space_chips=0.5, max_carrier_lock_fail=50, rotator=abi.ROTATOR_GENERIC)
     base.update(kw)
     return abi.TrkConf.defaults(system, fs_in, vl, **base)
@@ -510,9 +506,7 @@ def gps_l5i_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, doppler
     codes.GPS_L5_OPT_ACQ_FS_SPS designs its resampler with acq_resampler_design(lib, fs, that rate)
     and passes the resampled rate here.  Other PcpsAcquisition arguments pass through."""
     from . import codes
-    code_length = int(np.floor(fs_in / (codes.GPS_L5I_CODE_RATE_CPS / codes.GPS_L5I_CODE_LENGTH_CHIPS)))
-    return PcpsAcquisition(ctx, fs_in, sampled_ms * code_length, doppler_max, doppler_step, chip_rate=codes.GPS_L5I_CODE_RATE_CPS,
-                           ms_per_code=1, **kw)
+    return _ms_code_acquisition(ctx, fs_in, doppler_max, doppler_step, sampled_ms, codes.GPS_L5I_CODE_RATE_CPS, codes.GPS_L5I_CODE_LENGTH_CHIPS, kw)
 
 
 def gps_l5_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
@@ -521,7 +515,7 @@ def gps_l5_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
     gnsship_trk_create), extend_correlation_symbols at least 1.  Tracking code: codes.gps_l5q_code_gen_float,
     data code (start's data_code_id): codes.gps_l5i_code_gen_float."""
     from . import codes
-    vl = int(round(fs_in / (codes.GPS_L5I_CODE_RATE_CPS / codes.GPS_L5I_CODE_LENGTH_CHIPS)))
+    vl = _vector_length(fs_in, codes.GPS_L5I_CODE_RATE_CPS, codes.GPS_L5I_CODE_LENGTH_CHIPS)
     c = abi.TrkConf.defaults(abi.SYS_GPS_L5, fs_in, vl, **kw)
     if c.extend_correlation_symbols < 1:
         c.extend_correlation_symbols = 1
@@ -534,9 +528,8 @@ def beidou_b3i_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, dopp
     reference passes an optimum acquisition rate of 100e6, so no resampler is ever designed.  The local
     code is codes.beidou_b3i_acquisition_code(prn, fs_in, sampled_ms)."""
     from . import codes
-    code_length = int(np.floor(fs_in / (codes.BEIDOU_B3I_CODE_RATE_CPS / codes.BEIDOU_B3I_CODE_LENGTH_CHIPS)))
-    return PcpsAcquisition(ctx, fs_in, sampled_ms * code_length, doppler_max, doppler_step, chip_rate=codes.BEIDOU_B3I_CODE_RATE_CPS,
-                           ms_per_code=1, **kw)
+    return _ms_code_acquisition(ctx, fs_in, doppler_max, doppler_step, sampled_ms, codes.BEIDOU_B3I_CODE_RATE_CPS,
+                                codes.BEIDOU_B3I_CODE_LENGTH_CHIPS, kw)
 
 
 def gps_l2_m_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, doppler_step: int, sampled_ms: int = 20, **kw) -> PcpsAcquisition:
@@ -557,7 +550,7 @@ def beidou_b3i_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
     round(fs / 1000), extend_correlation_symbols within [1, 20] (a GEO channel — start's prn in 1..5 or
     above 58 — is further capped at 2 by the engine).  Tracking code: codes.beidou_b3i_code_gen_float."""
     from . import codes
-    vl = int(round(fs_in / (codes.BEIDOU_B3I_CODE_RATE_CPS / codes.BEIDOU_B3I_CODE_LENGTH_CHIPS)))
+    vl = _vector_length(fs_in, codes.BEIDOU_B3I_CODE_RATE_CPS, codes.BEIDOU_B3I_CODE_LENGTH_CHIPS)
     c = abi.TrkConf.defaults(abi.SYS_BDS_B3I, fs_in, vl, **kw)
     c.extend_correlation_symbols = min(max(c.extend_correlation_symbols, 1), 20)
     c.track_pilot = 0
@@ -571,7 +564,7 @@ def gps_l2c_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
     configurations run the loops at pll_bw_hz = 2, dll_bw_hz = 0.25: Dll_Pll_Conf's defaults (35 / 2 Hz)
     are unstable at a 20 ms update interval.  Tracking code: codes.gps_l2c_m_code_gen_float."""
     from . import codes
-    vl = int(round(fs_in / (codes.GPS_L2_M_CODE_RATE_CPS / codes.GPS_L2_M_CODE_LENGTH_CHIPS)))
+    vl = _vector_length(fs_in, codes.GPS_L2_M_CODE_RATE_CPS, codes.GPS_L2_M_CODE_LENGTH_CHIPS)
     c = abi.TrkConf.defaults(abi.SYS_GPS_L2C, fs_in, vl, **kw)
     c.extend_correlation_symbols = 1
     c.track_pilot = 0
@@ -580,9 +573,8 @@ def gps_l2c_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
 
 def _e5_pcps_acquisition(ctx, fs_in, doppler_max, doppler_step, sampled_ms, kw):
     from . import codes
-    code_length = int(np.floor(fs_in / (codes.GALILEO_E5A_CODE_CHIP_RATE_CPS / codes.GALILEO_E5A_CODE_LENGTH_CHIPS)))
-    return PcpsAcquisition(ctx, fs_in, sampled_ms * code_length, doppler_max, doppler_step, chip_rate=codes.GALILEO_E5A_CODE_CHIP_RATE_CPS,
-                           ms_per_code=1, **kw)
+    return _ms_code_acquisition(ctx, fs_in, doppler_max, doppler_step, sampled_ms, codes.GALILEO_E5A_CODE_CHIP_RATE_CPS,
+                                codes.GALILEO_E5A_CODE_LENGTH_CHIPS, kw)
 
 
 def galileo_e5a_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, doppler_step: int, sampled_ms: int = 1,
@@ -612,7 +604,7 @@ def galileo_e5b_pcps_acquisition(ctx: Context, fs_in: int, doppler_max: int, dop
 
 def _e5_trk_conf(system: int, i_secondary_len: int, fs_in: float, kw) -> "abi.TrkConf":
     from . import codes
-    vl = int(round(fs_in / (codes.GALILEO_E5A_CODE_CHIP_RATE_CPS / codes.GALILEO_E5A_CODE_LENGTH_CHIPS)))
+    vl = _vector_length(fs_in, codes.GALILEO_E5A_CODE_CHIP_RATE_CPS, codes.GALILEO_E5A_CODE_LENGTH_CHIPS)
     kw.setdefault("track_pilot", 1)
     c = abi.TrkConf.defaults(system, fs_in, vl, **kw)
     c.extend_correlation_symbols = max(c.extend_correlation_symbols, 1)
@@ -636,39 +628,40 @@ def galileo_e5b_trk_conf(fs_in: float, **kw) -> "abi.TrkConf":
     return _e5_trk_conf(abi.SYS_GAL_E5B, 4, fs_in, kw)
 
 
+def _design_taps(fn, name: str, *args, refused: str = None) -> np.ndarray:
+    """The taps of a design function fn(*args, taps, taps_cap, &n_taps): one call without room for the size (an error
+    there reads `refused`, where given), then, when there are taps, one that fills them.  Only gnsship_acq_resampler_design
+    succeeds with no taps (no resampler needed); the low-pass designs have at least one."""
+    n = ctypes.c_int()
+    check(fn(*args, None, 0, ctypes.byref(n)), refused or name)
+    taps = np.zeros(n.value, np.float32)
+    if n.value:
+        check(fn(*args, fptr(taps), len(taps), ctypes.byref(n)), name)
+    return taps
+
+
 def firdes_low_pass(lib, gain: float, fs: float, cutoff: float, transition: float) -> np.ndarray:
     """gr::filter::firdes::low_pass (Hamming) as the library restates it."""
-    n = ctypes.c_int()
-    rc = lib.gnsship_firdes_low_pass(gain, fs, cutoff, transition, None, 0, ctypes.byref(n))
-    if rc != abi.OK:
-        raise abi.GnssHipError(rc, "gnsship_firdes_low_pass: bad arguments")
-    taps = np.zeros(n.value, np.float32)
-    check(lib.gnsship_firdes_low_pass(gain, fs, cutoff, transition, fptr(taps), len(taps), ctypes.byref(n)), "gnsship_firdes_low_pass")
-    return taps
+    return _design_taps(lib.gnsship_firdes_low_pass, "gnsship_firdes_low_pass", gain, fs, cutoff, transition,
+                        refused="gnsship_firdes_low_pass: bad arguments")
 
 
 def acq_resampler_design(lib, fs_in: int, opt_acq_fs: float):
     """gnss_flowgraph.cc:1070-1113: (decimation, taps); decimation 1 and no taps when not needed."""
-    d, n = ctypes.c_int(), ctypes.c_int()
-    check(lib.gnsship_acq_resampler_design(fs_in, opt_acq_fs, ctypes.byref(d), None, 0, ctypes.byref(n)), "gnsship_acq_resampler_design")
-    taps = np.zeros(n.value, np.float32)
-    if n.value:
-        check(lib.gnsship_acq_resampler_design(fs_in, opt_acq_fs, ctypes.byref(d), fptr(taps), len(taps), ctypes.byref(n)),
-              "gnsship_acq_resampler_design")
+    d = ctypes.c_int()
+    taps = _design_taps(lib.gnsship_acq_resampler_design, "gnsship_acq_resampler_design", fs_in, opt_acq_fs, ctypes.byref(d))
     return d.value, taps
 
 
-class AcqResampler:
+class AcqResampler(_Handle):
     """The acquisition resampler FIR (fir_filter_ccf(decimation, taps)) over a sample stream."""
+    _prefix = "gnsship_acq_resampler"
 
     def __init__(self, ctx: Context, taps: np.ndarray, decimation: int, max_in_samples: int):
         self.ctx = ctx
         self.taps = np.ascontiguousarray(taps, np.float32)
         self.decimation = decimation
-        h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_acq_resampler_create(ctx.h, fptr(self.taps), len(self.taps), decimation, max_in_samples, ctypes.byref(h)),
-              "gnsship_acq_resampler_create", ctx.h)
-        self.h = h
+        self._create(fptr(self.taps), len(self.taps), decimation, max_in_samples)
 
     @property
     def latency(self) -> int:
@@ -680,40 +673,29 @@ class AcqResampler:
         dev = ctypes.c_void_p()
         n_out = ctypes.c_int64()
         if on_device:
-            check(self.ctx.lib.gnsship_acq_resampler_run(self.h, x, fmt, 1, n_in, None, ctypes.byref(dev), ctypes.byref(n_out)),
-                  "gnsship_acq_resampler_run", self.ctx.h)
+            self._call("run", x, fmt, 1, n_in, None, ctypes.byref(dev), ctypes.byref(n_out))
             return dev.value, n_out.value
         fmt = sample_format(x) if fmt is None else fmt
         n = len(x) if x.dtype == np.complex64 else len(x) // 2
         out = np.zeros(n // self.decimation, np.complex64)
-        check(self.ctx.lib.gnsship_acq_resampler_run(self.h, x.ctypes.data, fmt, 0, n, fptr(out.view(np.float32)), ctypes.byref(dev),
-                                                      ctypes.byref(n_out)), "gnsship_acq_resampler_run", self.ctx.h)
+        self._call("run", x.ctypes.data, fmt, 0, n, fptr(out.view(np.float32)), ctypes.byref(dev), ctypes.byref(n_out))
         return out
 
     def reset(self):
-        check(self.ctx.lib.gnsship_acq_resampler_reset(self.h), "gnsship_acq_resampler_reset", self.ctx.h)
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.gnsship_acq_resampler_destroy(self.h)
-            self.h = None
+        self._call("reset")
 
 
 def cond_lowpass_taps(lib, fs: float, decimation: int, bw: float = 0.0, tw: float = 0.0) -> np.ndarray:
     """The Freq_Xlating_Fir_Filter adapter's filter_type=lowpass taps (freq_xlating_fir_filter.cc:99-106):
     firdes::low_pass(1, fs, bw, tw), bw = 0 → (fs / decimation) / 2, tw = 0 → bw / 10."""
-    n = ctypes.c_int()
-    rc = lib.gnsship_cond_lowpass_taps(fs, decimation, bw, tw, None, 0, ctypes.byref(n))
-    if rc != abi.OK:
-        raise abi.GnssHipError(rc, "gnsship_cond_lowpass_taps: bad arguments")
-    taps = np.zeros(n.value, np.float32)
-    check(lib.gnsship_cond_lowpass_taps(fs, decimation, bw, tw, fptr(taps), len(taps), ctypes.byref(n)), "gnsship_cond_lowpass_taps")
-    return taps
+    return _design_taps(lib.gnsship_cond_lowpass_taps, "gnsship_cond_lowpass_taps", fs, decimation, bw, tw,
+                        refused="gnsship_cond_lowpass_taps: bad arguments")
 
 
-class SignalConditioner:
+class SignalConditioner(_Handle):
     """The signal conditioner's frequency-translating FIR decimator (freq_xlating_fir_filter_ccf(decimation,
     taps, IF, fs) per band) over one sample stream.  bands: [(if_hz, decimation, taps), ...], up to 4."""
+    _prefix = "gnsship_cond"
 
     def __init__(self, ctx: Context, fs_in: float, bands, max_in_samples: int):
         self.ctx = ctx
@@ -722,9 +704,7 @@ class SignalConditioner:
         arr = (abi.CondBand * max(1, len(self.bands)))()
         for i, (f, d, t) in enumerate(self.bands):
             arr[i] = abi.CondBand(if_hz=f, decimation=d, taps=fptr(t), n_taps=len(t))
-        h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_cond_create(ctx.h, fs_in, arr, len(self.bands), max_in_samples, ctypes.byref(h)), "gnsship_cond_create", ctx.h)
-        self.h = h
+        self._create(fs_in, arr, len(self.bands), max_in_samples)
 
     @property
     def n_bands(self) -> int:
@@ -759,29 +739,17 @@ class SignalConditioner:
         if host:
             outs = [np.zeros(max(0, n_in // d), np.complex64) for _, d, _ in self.bands]
             hp = (abi._f32p * nb)(*[fptr(o.view(np.float32)) for o in outs])
-        check(self.ctx.lib.gnsship_cond_run(self.h, ptr, fmt, int(on_device), n_in, dst, hp, dev, n_out), "gnsship_cond_run", self.ctx.h)
+        self._call("run", ptr, fmt, int(on_device), n_in, dst, hp, dev, n_out)
         self.last_dev = [(dev[b], n_out[b]) for b in range(nb)]
         return outs if host else self.last_dev
 
     def reset(self, first_sample: int = 0):
-        check(self.ctx.lib.gnsship_cond_reset(self.h, first_sample), "gnsship_cond_reset", self.ctx.h)
+        self._call("reset", first_sample)
 
     def samples_in(self) -> int:
         n = ctypes.c_uint64()
-        check(self.ctx.lib.gnsship_cond_samples_in(self.h, ctypes.byref(n)), "gnsship_cond_samples_in", self.ctx.h)
+        self._call("samples_in", ctypes.byref(n))
         return n.value
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.gnsship_cond_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.close()
-        except Exception:
-            pass
 
 
 def mit_threshold(lib, pfa: float, length: int) -> float:
@@ -793,12 +761,13 @@ def mit_threshold(lib, pfa: float, length: int) -> float:
     return t.value
 
 
-class InterferenceMitigation:
+class InterferenceMitigation(_Handle):
     """Pulse blanking, notch or notch-lite filter (pulse_blanking_cc / notch_cc / notch_lite_cc) over one CF32
     stream.  kind: "pulse-blanking" | "notch" | "notch-lite" or abi.MIT_*; chain_form: "auto" | "serial" |
     "speculative" or abi.MIT_CHAIN_*.  A run returns the complete segments not yet emitted; the rest stays on
     the device."""
 
+    _prefix = "gnsship_mit"
     KINDS = {"pulse-blanking": abi.MIT_PULSE_BLANKING, "notch": abi.MIT_NOTCH, "notch-lite": abi.MIT_NOTCH_LITE}
     FORMS = {"auto": abi.MIT_CHAIN_AUTO, "serial": abi.MIT_CHAIN_SERIAL, "speculative": abi.MIT_CHAIN_SPECULATIVE}
 
@@ -815,9 +784,7 @@ class InterferenceMitigation:
                                 n_segments_est=n_segments_est, n_segments_reset=n_segments_reset, n_segments_coeff=n_segments_coeff,
                                 chain_form=form)
         self.max_in_samples = int(max_in_samples)
-        h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_mit_create(ctx.h, ctypes.byref(self.conf), self.max_in_samples, ctypes.byref(h)), "gnsship_mit_create", ctx.h)
-        self.h = h
+        self._create(ctypes.byref(self.conf), self.max_in_samples)
         self._pending = 0
 
     def run(self, x, on_device: bool = False, n_in: int = None, dev_dst=None, host: bool = None):
@@ -834,41 +801,29 @@ class InterferenceMitigation:
         out = np.zeros(max(0, self._pending + n_in), np.complex64) if host else None
         dev = ctypes.c_void_p()
         n_out = ctypes.c_int64()
-        check(self.ctx.lib.gnsship_mit_run(self.h, ptr, int(on_device), n_in, ctypes.c_void_p(dev_dst) if dev_dst else None,
-                                           fptr(out.view(np.float32)) if host and out.size else None, ctypes.byref(dev), ctypes.byref(n_out)),
-              "gnsship_mit_run", self.ctx.h)
+        self._call("run", ptr, int(on_device), n_in, ctypes.c_void_p(dev_dst) if dev_dst else None,
+                   fptr(out.view(np.float32)) if host and out.size else None, ctypes.byref(dev), ctypes.byref(n_out))
         self._pending += n_in - n_out.value
         self.last_dev = (dev.value, n_out.value)
         return out[:n_out.value] if host else self.last_dev
 
     def reset(self):
-        check(self.ctx.lib.gnsship_mit_reset(self.h), "gnsship_mit_reset", self.ctx.h)
+        self._call("reset")
         self._pending = 0
 
     def state(self) -> dict:
         st = abi.MitState()
-        check(self.ctx.lib.gnsship_mit_state_get(self.h, ctypes.byref(st)), "gnsship_mit_state_get", self.ctx.h)
+        self._call("state_get", ctypes.byref(st))
         return {name: getattr(st, name) for name, _ in abi.MitState._fields_}
 
-    def close(self):
-        if self.h:
-            self.ctx.lib.gnsship_mit_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.close()
-        except Exception:
-            pass
-
-
-class ViterbiDecoder:
+class ViterbiDecoder(_Handle):
     """The K = 7, rate-1/2 Viterbi decoder of the Galileo telemetry block with its de-interleaver and G2 flip
     (galileo_telemetry_decoder_gs.cc:342-371, viterbi_decoder.cc:47-120) for up to ``max_channels`` channels, one
     Viterbi_Decoder object per channel.  mode: "reference" (the decoder as written: first symbol of each pair only,
     metrics carried from frame to frame) | "full" (both symbols, every frame from state 0) or abi.VIT_MODE_*."""
 
+    _prefix = "gnsship_vit"
     MODES = {"reference": abi.VIT_MODE_REFERENCE, "full": abi.VIT_MODE_FULL}
 
     def __init__(self, ctx: Context, max_channels: int, data_length: int, interleaver_rows: int = 0, interleaver_cols: int = 0,
@@ -882,9 +837,7 @@ class ViterbiDecoder:
         self.max_channels = int(max_channels)
         self.data_length = int(data_length)
         self.frame_symbols = 2 * (self.data_length + 6)
-        h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_vit_create(ctx.h, ctypes.byref(self.conf), self.max_channels, ctypes.byref(h)), "gnsship_vit_create", ctx.h)
-        self.h = h
+        self._create(ctypes.byref(self.conf), self.max_channels)
 
     def run(self, symbols, channels, negate=None, on_device: bool = False, n_frames: int = None, bits_dev=None, host: bool = True):
         """Decode frames: a host float32 array [n_frames, frame_symbols] as received, or a device pointer with
@@ -908,34 +861,20 @@ class ViterbiDecoder:
                 raise ValueError("one negate flag per frame")
         out = np.zeros((n_frames, self.data_length), np.uint8) if host else None
         self._in_flight = (symbols, channels, negate)  # a run without a host copy returns before the stream has read them
-        check(self.ctx.lib.gnsship_vit_run(self.h, ptr, int(on_device), n_frames, channels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                                           negate.ctypes.data_as(u8p) if negate is not None else None,
-                                           out.ctypes.data_as(u8p) if host and out.size else None,
-                                           ctypes.c_void_p(bits_dev) if bits_dev else None),
-              "gnsship_vit_run", self.ctx.h)
+        self._call("run", ptr, int(on_device), n_frames, channels.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                   negate.ctypes.data_as(u8p) if negate is not None else None, out.ctypes.data_as(u8p) if host and out.size else None,
+                   ctypes.c_void_p(bits_dev) if bits_dev else None)
         return out
 
     def state(self, channel: int) -> np.ndarray:
         """The channel's 64 carried path metrics (d_prev_section)."""
         sec = np.zeros(64, np.float32)
-        check(self.ctx.lib.gnsship_vit_state_get(self.h, channel, fptr(sec)), "gnsship_vit_state_get", self.ctx.h)
+        self._call("state_get", channel, fptr(sec))
         return sec
 
     def reset_channel(self, channel: int):
         """A new Viterbi_Decoder object on this channel."""
-        check(self.ctx.lib.gnsship_vit_reset_channel(self.h, channel), "gnsship_vit_reset_channel", self.ctx.h)
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.gnsship_vit_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.close()
-        except Exception:
-            pass
+        self._call("reset_channel", channel)
 
 
 # (interleaver rows, interleaver columns, data length) of the Galileo page types: 8 rows each, frames of 240, 488
@@ -963,28 +902,19 @@ def galileo_cnav_page_decoder(ctx: Context, max_channels: int, mode="reference")
     return _galileo_page_decoder(ctx, max_channels, GALILEO_CNAV_PAGE, mode)
 
 
-class _TelemetryDecoder:
+class _TelemetryDecoder(_Handle):
     """What the five telemetry decoders share over the C ABI (gnsship_<family>_*, csrc/tlm_host.h): the handle's life
-    cycle, the three run calls and the device pointers.  A subclass states its C prefix, its result tuple and the name of
+    cycle (_Handle), the three run calls and the device pointers.  A subclass states its C prefix, its result tuple and the name of
     its per-run slot count, builds its configuration in __init__ and its host arrays in _new_result, and adds the calls
     only its family has."""
-    _prefix = None   # "gnsship_lnav"
     _result = None   # the run's NamedTuple; with tow_ms / sflags the family has a per-entry output stream
     _per_run = None  # "subframes_per_run": the attribute holding the record slots per channel of one run
     _state = None    # the ctypes state structure state() reads; a family whose state is a numpy record overrides state()
-    h = None
-
-    def _call(self, name: str, *args):
-        name = f"{self._prefix}_{name}"
-        check(getattr(self.ctx.lib, name)(self.h, *args), name, self.ctx.h)
 
     def _open(self, ctx: Context, conf, max_channels: int, max_rounds: int):
         self.ctx, self.conf = ctx, conf
         self.max_channels, self.max_rounds = int(max_channels), int(max_rounds)
-        h = ctypes.c_void_p()
-        name = f"{self._prefix}_create"
-        check(getattr(ctx.lib, name)(ctx.h, ctypes.byref(conf), self.max_channels, ctypes.byref(h)), name, ctx.h)
-        self.h = h
+        self._create(ctypes.byref(conf), self.max_channels)
         slots = ctypes.c_int32()
         self._call("outputs_device", *[None] * len(self._result._fields), ctypes.byref(slots))
         setattr(self, self._per_run, slots.value)
@@ -1055,18 +985,6 @@ class _TelemetryDecoder:
         st = self._state()
         self._call("state_get", channel, ctypes.byref(st))
         return st.as_dict()
-
-    def close(self):
-        if self.h:
-            getattr(self.ctx.lib, f"{self._prefix}_destroy")(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.close()
-        except Exception:
-            pass
 
 
 class TlmResult(NamedTuple):
@@ -1354,25 +1272,24 @@ def glonass_l2_ca_telemetry(ctx: Context, max_channels: int, max_rounds: int) ->
     return GlonassGnavTelemetryDecoder(ctx, max_channels, max_rounds, abi.GNAV_L2CA)
 
 
-class DllPllVemlTracking:
+class DllPllVemlTracking(_Handle):
     """dll_pll_veml_tracking (dll_pll_veml_tracking.cc) for up to ``max_channels`` channels, the
     per-epoch loop resident on the device: ``start_tracking`` → :meth:`start`, ``general_work``
     over an IF buffer → :meth:`run` (one record per channel-epoch, TRK_EPOCH_DTYPE)."""
+    _prefix = "gnsship_trk"
 
     def __init__(self, ctx: Context, conf: "abi.TrkConf", max_channels: int):
         self.ctx = ctx
         self.conf = conf
         self.max_channels = max_channels
-        h = ctypes.c_void_p()
-        check(ctx.lib.gnsship_trk_create(ctx.h, ctypes.byref(conf), max_channels, ctypes.byref(h)), "gnsship_trk_create", ctx.h)
-        self.h = h
+        self._create(ctypes.byref(conf), max_channels)
 
     def start(self, channel: int, code_id: int, acq_delay_samples: float, acq_doppler_hz: float, acq_samplestamp: int,
               first_sample: int, data_code_id: int = -1, prn: int = 0):
         a = abi.TrkStartArgs(code_id=code_id, data_code_id=data_code_id, acq_delay_samples=acq_delay_samples,
                              acq_doppler_hz=acq_doppler_hz, acq_samplestamp_samples=acq_samplestamp, first_sample=first_sample,
                              prn=prn)
-        check(self.ctx.lib.gnsship_trk_start(self.h, channel, ctypes.byref(a)), "gnsship_trk_start", self.ctx.h)
+        self._call("start", channel, ctypes.byref(a))
 
     def start_many(self, starts):
         """gnsship_trk_start_many: `starts` = [(channel, code_id, acq_delay_samples, acq_doppler_hz,
@@ -1389,19 +1306,18 @@ class DllPllVemlTracking:
             chans[i] = ch
             args[i] = abi.TrkStartArgs(code_id=code_id, data_code_id=data_code_id, acq_delay_samples=delay, acq_doppler_hz=dop,
                                        acq_samplestamp_samples=stamp, first_sample=first, prn=prn)
-        check(self.ctx.lib.gnsship_trk_start_many(self.h, n, chans, args), "gnsship_trk_start_many", self.ctx.h)
+        self._call("start_many", n, chans, args)
 
     def stop(self, channel: int):
-        check(self.ctx.lib.gnsship_trk_stop(self.h, channel), "gnsship_trk_stop", self.ctx.h)
+        self._call("stop", channel)
 
     def telemetry_event(self, channel: int, tlm_event: int = 1):
         """msg_handler_telemetry_to_trk (dll_pll_veml_tracking.cc:617-640): event 1 = telemetry fault."""
-        check(self.ctx.lib.gnsship_trk_telemetry_event(self.h, channel, tlm_event), "gnsship_trk_telemetry_event", self.ctx.h)
+        self._call("telemetry_event", channel, tlm_event)
 
     def channel_state(self, channel: int):
         st, nx = ctypes.c_int(), ctypes.c_uint64()
-        check(self.ctx.lib.gnsship_trk_channel_state(self.h, channel, ctypes.byref(st), ctypes.byref(nx)), "gnsship_trk_channel_state",
-              self.ctx.h)
+        self._call("channel_state", channel, ctypes.byref(st), ctypes.byref(nx))
         return st.value, nx.value
 
     def run(self, sig, buffer_first_sample: int, max_rounds: int, fmt: int = None, n_buffer_samples: int = None,
@@ -1413,33 +1329,26 @@ class DllPllVemlTracking:
         dmp = np.zeros((max_rounds, self.max_channels), abi.TRK_DUMP_DTYPE) if dump else None
         if dump and not records:
             raise ValueError("dump records need the epoch records (flags & 16 marks them)")
-        if isinstance(sig, DeviceBuffer):
-            ptr, on_dev, f = sig.ptr, 1, FMT_CF32 if fmt is None else fmt
-            n = n_buffer_samples if n_buffer_samples is not None else sig.nbytes // _FMT_BYTES[f]
-        else:
-            sig = np.ascontiguousarray(sig)
-            ptr, on_dev, f = sig.ctypes.data, 0, sample_format(sig)
-            n = sig.nbytes // _FMT_BYTES[f]
+        ptr, on_dev, f, n = _if_input(sig, fmt)
+        if on_dev and n_buffer_samples is not None:
+            n = n_buffer_samples
         done = ctypes.c_int()
-        check(self.ctx.lib.gnsship_trk_run_dump(self.h, ptr, f, on_dev, buffer_first_sample, n, max_rounds,
-                                                out.ctypes.data if records else None, dmp.ctypes.data if dump else None,
-                                                ctypes.byref(done)), "gnsship_trk_run_dump", self.ctx.h)
+        self._call("run_dump", ptr, f, on_dev, buffer_first_sample, n, max_rounds, out.ctypes.data if records else None,
+                   dmp.ctypes.data if dump else None, ctypes.byref(done))
         return (out, done.value, dmp) if dump else (out, done.value)
 
     def run_ptr(self, dev_ptr: int, fmt: int, buffer_first_sample: int, n_buffer_samples: int, max_rounds: int) -> int:
         """general_work over a device IF buffer given as a raw pointer (e.g. a torch tensor's data_ptr,
         or an offset into one), no records: returns the rounds run."""
         done = ctypes.c_int()
-        check(self.ctx.lib.gnsship_trk_run_dump(self.h, ctypes.c_void_p(dev_ptr), fmt, 1, buffer_first_sample, n_buffer_samples, max_rounds,
-                                                None, None, ctypes.byref(done)), "gnsship_trk_run_dump", self.ctx.h)
+        self._call("run_dump", ctypes.c_void_p(dev_ptr), fmt, 1, buffer_first_sample, n_buffer_samples, max_rounds, None, None, ctypes.byref(done))
         return done.value
 
     def launch_ptr(self, dev_ptr: int, fmt: int, buffer_first_sample: int, n_buffer_samples: int, max_rounds: int,
                    records: bool = False, dump: bool = False):
         """gnsship_trk_launch: enqueue the run on this engine's context stream and return at once
         (engines on other contexts of the same device run concurrently); :meth:`collect` waits."""
-        check(self.ctx.lib.gnsship_trk_launch(self.h, ctypes.c_void_p(dev_ptr), fmt, buffer_first_sample, n_buffer_samples, max_rounds,
-                                              int(records), int(dump)), "gnsship_trk_launch", self.ctx.h)
+        self._call("launch", ctypes.c_void_p(dev_ptr), fmt, buffer_first_sample, n_buffer_samples, max_rounds, int(records), int(dump))
         self._pending = (max_rounds, records, dump)
 
     def collect(self, out: np.ndarray = None):
@@ -1453,30 +1362,29 @@ class DllPllVemlTracking:
             out = np.zeros((max_rounds, self.max_channels), abi.TRK_EPOCH_DTYPE) if records else None
         dmp = np.zeros((max_rounds, self.max_channels), abi.TRK_DUMP_DTYPE) if dump else None
         done = ctypes.c_int()
-        check(self.ctx.lib.gnsship_trk_collect(self.h, out.ctypes.data if records else None, dmp.ctypes.data if dump else None,
-                                               ctypes.byref(done)), "gnsship_trk_collect", self.ctx.h)
+        self._call("collect", out.ctypes.data if records else None, dmp.ctypes.data if dump else None, ctypes.byref(done))
         return (out, done.value, dmp) if dump else (out, done.value)
 
     def set_trace(self, enable: bool = True):
         """gnsship_trk_set_trace: record every channel-epoch's correlator arguments and outputs."""
-        check(self.ctx.lib.gnsship_trk_set_trace(self.h, int(enable)), "gnsship_trk_set_trace", self.ctx.h)
+        self._call("set_trace", int(enable))
 
     def trace(self, max_rounds: int) -> np.ndarray:
         """The last run's trace, [max_rounds, max_channels] TRK_TRACE_DTYPE (max_rounds of that run)."""
         out = np.zeros((max_rounds, self.max_channels), abi.TRK_TRACE_DTYPE)
-        check(self.ctx.lib.gnsship_trk_trace_records(self.h, out.ctypes.data, out.size), "gnsship_trk_trace_records", self.ctx.h)
+        self._call("trace_records", out.ctypes.data, out.size)
         return out
 
     def last_engine(self) -> int:
         """gnsship_trk_last_engine: the kernel the last run / launch ran (abi.TRK_ENGINE_*)."""
         v = ctypes.c_int(0)
-        check(self.ctx.lib.gnsship_trk_last_engine(self.h, ctypes.byref(v)), "gnsship_trk_last_engine", self.ctx.h)
+        self._call("last_engine", ctypes.byref(v))
         return v.value
 
     def last_plan(self) -> dict:
         """gnsship_trk_last_plan: the variant the last run's launch function chose (abi.TrkPlan's members by name)."""
         p = abi.TrkPlan()
-        check(self.ctx.lib.gnsship_trk_last_plan(self.h, ctypes.byref(p)), "gnsship_trk_last_plan", self.ctx.h)
+        self._call("last_plan", ctypes.byref(p))
         return p.as_dict()
 
     def states(self) -> np.ndarray:
@@ -1502,15 +1410,3 @@ class DllPllVemlTracking:
                 f.write(rows.tobytes())
             paths.append(path)
         return paths
-
-    def close(self):
-        if self.h:
-            self.ctx.lib.gnsship_trk_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            if self.h and self.ctx.h:
-                self.close()
-        except Exception:
-            pass
